@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on its headline configuration (C2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over one resident batch: MPN forward -> gsp_wls_edge -> backward
 (/root/reference/dss2_run.py:138-142; optimizer excluded, gradient all-reduce included for N > 1).
 Workload at every N (weak scaling): CIGRE-14, B = 4096 graphs per GPU, MPN(8, 6, 2, H=128, L=4, K=2),
 dropout 0, fp32, synthetic states on the reference's CIGRE-14 parameter tables, random-init weights.
-Rank 0 prints ONE JSON line (contract in the task brief) with two extra objects:
+A plain run sets up, warms up (clock ramp + W steps), times EXACTLY K steps of the step replayed as a launch plan
+(one C call per step, graphs.PlannedStep; eager with --no-graph), writes the last step's outputs if --dump-outputs is
+given, and rank 0 prints ONE JSON line: metric, value (graphs/s), unit, higher_is_better, dtype, ms_per_step (one
+timed step).  --dump-outputs DIR: the loss, the model output and every parameter gradient of the last timed step as
+DIR/<name>.npy (float32; inputs and weights are seeded, so two builds can be compared output for output).
+--full adds everything else to the same line, each after the timed region:
+  ms_per_step_by_mode : the same step eager and as a replayed hipGraph, K timed steps each
   roofline     : the dominant kernel (fused MFMA GEMM + propagation over chains of hid->hid TAGConv
-                 layers), timed in situ with HIP events in an instrumented pass after the timed region
+                 layers), timed in situ with HIP events in an instrumented pass
+  ms_per_step_by_arithmetic_route, scatter_add, other_configs (the other BASELINE configurations)
   cpu_baseline : the CPU oracle (a port of the reference's PyTorch-eager path, dead dense Laplacian
-                 stripped) timed on this box's host cores on the same batch (N = 1 only)
+                 stripped) timed on the host's cores on the same batch (N = 1 only)
 """
 import argparse
 import contextlib
@@ -83,7 +90,7 @@ def capture_watchdog(result: dict, rank: int, world: int, timeout: float, leg: s
     """Dead-man timer of a replay leg (hipGraph capture / launch plan; every rank runs one).  If the leg does not answer within
     `timeout` seconds -- e.g. a collective that never completes inside a capture -- the process cannot be recovered (a hung HIP call
     holds the GPU), so it ends here, VISIBLY: rank 0 prints the run's FINAL JSON line = everything measured so far (value /
-    ms_per_step: the best leg that completed) + `"hang": {"leg", "timeout_s", "exit_status"}` and `legs[leg] = "hung"`, and every rank
+    ms_per_step stay null if the headline's own launch-plan leg hung) + `"hang": {"leg", "timeout_s", "exit_status"}` and `legs[leg] = "hung"`, and every rank
     leaves with exit status HANG_RC (3; DSS2_BENCH_HANG_RC) -- the measurement survives on stdout, the launcher reports the failure.
     Never a re-exec of this process (it has initialised the GPU).  Returns the started threading.Timer (cancel() it when the leg
     finishes)."""
@@ -141,6 +148,22 @@ def dry_run(args) -> int:
     if rank == 0:
         print(json.dumps(res), flush=True)
     return 0
+
+
+DUMP_MAX_ELEMENTS = 4 << 20      # per array (16 MB of float32); the model output of a larger --batch is written as a seeded row sample
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor as <path>/<name>.npy in float32.  An array above DUMP_MAX_ELEMENTS keeps a fixed, seeded
+    sample of its rows, in row order (the same rows for the same shape, so two builds still compare output for output)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMENTS:
+            keep = DUMP_MAX_ELEMENTS // max(a[0].numel(), 1)
+            a = a[torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(path, f"{name}.npy"), a.numpy())
 
 
 def flops_per_graph(n, e, hid, layers, khops, fn=8, fe=6, fo=2, blocks=1, fo_inner=None):
@@ -415,9 +438,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="graphs per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, model output and parameter gradients "
+                                                          "as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the eager and hipGraph legs, the roofline pass, the arithmetic routes, the scatter-add, the "
+                         "other configurations and the CPU baseline (the --no-* / *-seconds options below apply to these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-graph", action="store_true", help="time the eager step only (default: eager and hipGraph replay, best reported)")
-    ap.add_argument("--graph-timeout", type=float, default=90.0, help="seconds the hipGraph leg may take before the eager result is printed")
+    ap.add_argument("--no-graph", action="store_true", help="time the eager step (default: the launch plan; with --full also "
+                                                            "eager and hipGraph replay beside it)")
+    ap.add_argument("--graph-timeout", type=float, default=90.0, help="seconds a replay leg (the headline's launch plan up to its timed steps, which get this plus ten times their expected "
+                         "time; with --full the hipGraph leg and each arithmetic route) may go without answering before the line so far is printed "
+                         "and the run exits with status 3")
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="CPU time budget per thread count of the cpu_baseline thread sweep")
     ap.add_argument("--cpu-protocol-steps", type=int, default=50, help="timed steps of the cpu_baseline's protocol leg at the best thread count (10 warm-ups before them)")
     ap.add_argument("--no-routes", action="store_true", help="skip timing the step on the bf16x6 and fp32-MFMA routes beside the default one")
@@ -425,10 +456,6 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs block (C1, C3, C3', C5 shard, B=32768, driver line)")
     ap.add_argument("--no-train-epochs", action="store_true", help="skip the end-to-end training epochs in other_configs")
     ap.add_argument("--other-seconds", type=float, default=1.0, help="timed work per mode of every other_configs entry")
-    ap.add_argument("--min-window-seconds", type=float, default=5.0,
-                    help="repeat the K-step timed window until this much timed work has accumulated; the median window is "
-                         "reported (5 s per mode: the eager and the replay leg together keep the GPU busy >= 10 s in a row, so "
-                         "that an outside utilisation sampler sees the run)")
     ap.add_argument("--ramp-seconds", type=float, default=2.0,
                     help="untimed load before the W warm-up steps: a fresh MI355X needs ~1 s of sustained work to reach "
                          "its steady clocks (measured: the first ~100 steps of a process run 40 %% slower)")
@@ -437,6 +464,8 @@ def main():
                     help="launch / rendezvous path only (gloo on CPU, no GPU call): every rank joins the process group, one "
                          "all-reduce checks it, rank 0 prints a JSON line marked dry_run (tests/test_bench_launch_cpu.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python3 bench.py --gpus N` without a launcher: start one fresh child process per GPU through torch's own
@@ -482,11 +511,13 @@ def main():
     work_stream.wait_stream(torch.cuda.current_stream())
     torch.cuda.set_stream(work_stream)
     params = list(model.parameters())        # (walking the module tree every step costs the host ~70 us of a 0.58 ms step)
+    last_out = [None]        # the model output of the latest step (--dump-outputs); it also stays allocated for a recorded plan
 
     def step():
         for p in params:
             p.grad = None
         out = model(xin, ei, ein)
+        last_out[0] = out
         loss = pkg.gsp_wls_edge(input=xin, edge_input=ein, output=out, x_mean=stats[0], x_std=stats[1],
                                 edge_mean=stats[2], edge_std=stats[3], edge_index=ei, reg_coefs=REG,
                                 num_samples=None, node_param=npar, edge_param=epar, group=group)
@@ -514,56 +545,93 @@ def main():
                 break
         return n
 
-    def timed_windows(run):
-        """EXACTLY K steps between barrier + synchronize on both sides.  K steps of this workload can be as short as 12 ms,
-        a fragile sample, so the K-step window is repeated until >= --min-window-seconds of timed work has accumulated and
-        the MEDIAN window is reported (every window is bracketed the same way; its duration is the max over ranks)."""
-        out, last = [], None
-        while True:
-            sync()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                last = run()
-            sync()
-            dtw = time.perf_counter() - t0
-            if distributed:
-                tt = torch.tensor([dtw], dtype=torch.float64, device=dev)
-                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-                dtw = float(tt.item())
-            out.append(dtw)
-            go = sum(out) < args.min_window_seconds and len(out) < 2000
-            if distributed:
-                flag = torch.tensor([int(go)], dtype=torch.int32, device=dev)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                go = bool(flag.item())
-            if not go:
-                break
-        return out, last
-
-    ramp_steps = ramp(step)
-    for _ in range(args.warmup):
-        step()
-    windows, loss = timed_windows(step)
-    mode = "eager"
-    dt = sorted(windows)[len(windows) // 2]
-    ms = dt / args.steps * 1e3
-    value = args.batch * world / (dt / args.steps)
+    def timed_steps(run):
+        """EXACTLY --steps steps between barrier + synchronize on both sides; the duration is the max over ranks."""
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            last = run()
+        sync()
+        dtw = time.perf_counter() - t0
+        if distributed:
+            tt = torch.tensor([dtw], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dtw = float(tt.item())
+        return dtw, last
 
     result = {
-        "metric": "grid-samples/sec fwd+bwd (WLS loss), CIGRE-14 batch=4096, 1/2/4/8 GPU", "value": value, "unit": "graphs/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
+        "metric": "grid-samples/sec fwd+bwd (WLS loss), CIGRE-14 batch=4096, 1/2/4/8 GPU", "value": None, "unit": "graphs/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": DTYPE_BY_ROUTE[route_name(pkg)], "data": "synthetic",
         "config": {"workload": f"CIGRE-14 (15 buses, 14 closed branches) B={args.batch} graphs/GPU, "
                                f"MPN L={LAYERS} H={HID} K={KHOPS} dropout=0: forward + gsp_wls_edge + backward"
                                + (" + RCCL loss-sum and gradient all-reduce" if distributed else ""),
                    "graphs_per_gpu": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}",
-                   "loss": float(loss.item()), "clock_ramp_steps_before_warmup": ramp_steps,
-                   "timed_windows": len(windows), "window_ms_min_median_max": [min(windows) * 1e3, dt * 1e3, max(windows) * 1e3],
-                   "mode": mode, "ms_per_step_by_mode": {"eager": ms}, "ranks_seen": ranks_seen,
+                   "ranks_seen": ranks_seen,
                    "ranks_seen_source": ("SUM all-reduce of a ones tensor over RCCL at start-up" if distributed else "single process, no process group"),
                    "arithmetic_route": route_name(pkg)},
-        "legs": {"eager": "ok"},
+        "legs": {},
     }
+
+    # ---- the timed step: replayed as a launch plan (graphs.PlannedStep, include/dss2_hip.h "launch plans"): the library's own record of
+    # the step's launches re-issued from ONE C call per step -- real launches of the same kernels on the same stream, no Python between
+    # them, and it carries the step's vminmax launch (no cached batch constants).  At world > 1 the step's collectives (loss sums,
+    # gradient bucket) cut the plan into segments: one C call per segment, the collectives between them (graphs.plan_collective).  The
+    # eager step and its hipGraph replay time within a few percent of it on this GPU-bound step (--full times both beside it).  Eager with
+    # --no-graph, at world > 1 with DSS2_BENCH_DIST_PLAN=0, or if the plan cannot be recorded (config.launch_plan says why).
+    run, mode = step, "eager"
+    dist_plan = os.environ.get("DSS2_BENCH_DIST_PLAN", "1") != "0"
+    ptimer = None
+    if not args.no_graph and (world == 1 or dist_plan):
+        # the watchdog covers the recording, the clock ramp and the warm-up: a collective that never completes hangs there first
+        ptimer = capture_watchdog(result, rank, world, args.graph_timeout, leg="launch plan")
+        try:
+            # (verify: one replay must reproduce the recorded step's gradients bit for bit -- a launch the plan does not carry would show here)
+            planned = pkg.graphs.PlannedStep(step, stream=work_stream, verify=(lambda: [p.grad for p in params]) if world == 1 else None)
+            run, mode = planned.replay, "launch plan"
+            result["config"]["plan_launches"] = planned.n_launches
+            if world > 1:
+                result["config"]["plan_segments"] = len(planned.segments)
+        except Exception as exc:
+            result["config"]["launch_plan"] = f"failed: {type(exc).__name__}: {exc}"[:300]
+            result["legs"]["launch plan"] = "failed"
+    t_warm = time.perf_counter()
+    ramp_steps = ramp(run)
+    for _ in range(args.warmup):
+        run()
+    sync()
+    if ptimer is not None:
+        # the timed replays get a watchdog of their own, sized by the warm-up's pace: --graph-timeout plus ten times the K steps' expected time
+        ptimer.cancel()
+        per_step = (time.perf_counter() - t_warm) / max(ramp_steps + args.warmup, 1)
+        ptimer = capture_watchdog(result, rank, world, args.graph_timeout + 10.0 * args.steps * per_step, leg="launch plan")
+    dt, loss = timed_steps(run)
+    if ptimer is not None:
+        ptimer.cancel()
+    ms = dt / args.steps * 1e3
+    value = args.batch * world / (dt / args.steps)
+    result["legs"][mode] = "ok"
+    result.update(value=value, ms_per_step=ms)
+    result["config"].update(loss=float(loss.item()), clock_ramp_steps_before_warmup=ramp_steps,
+                            mode=("launch plan (dss2_plan_run)" if mode == "launch plan" else mode), ms_per_step_by_mode={mode: ms})
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "output": last_out[0],
+                                         **{f"grad.{n}": p.grad for n, p in model.named_parameters()}})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: every leg below runs after the timed region and adds to the same line
+    if mode != "eager":
+        for _ in range(args.warmup):
+            step()
+        edt, _ = timed_steps(step)
+        result["config"]["ms_per_step_by_mode"]["eager"] = edt / args.steps * 1e3
+        result["legs"]["eager"] = "ok"
 
     # ---- instrumented pass: EVERY rank runs it (the steps contain collectives); rank 0 reports
     # ---- roofline of the dominant kernel, timed in situ (instrumented pass, not the timed region).
@@ -745,13 +813,13 @@ def main():
                 r["held_clock_ghz"] = held_clock_ghz
                 r["frac_at_held_clock"] = r["frac"] * 2.4 / held_clock_ghz
                 r["held_clock_source"] = "s_memtime / s_memrealtime (100 MHz) over the life of workgroups 0, 256, 512, 768 of the last chain launch of the instrumented pass"
-    # ---- the SAME step replayed as a hipGraph (graphs.GraphedStep), timed the same way; the faster mode is reported.
+    # ---- the SAME step replayed as a hipGraph (graphs.GraphedStep), timed the same way, reported beside the headline.
     # Eager: 19 launches through the C ABI per step, ~0.41 ms of host work on a quiet box (hidden by the 0.58 ms of GPU work)
     # but up to 0.8 ms on a loaded host -- and two collectives more per step when distributed -- which then bounds the step.
     # Replay has no host work.  Distributed steps are captured WITH their RCCL collectives (capture_error_mode =
     # "thread_local": the process-group watchdog may touch HIP during the capture; tests/test_gpu_rccl.py).  A watchdog
     # timer (capture_watchdog) leaves with the eager result and exit code 0 if a capture or a replay ever hangs.
-    # At world > 1 rank 0 prints (and flushes) the EAGER line before the leg starts: whatever happens to a capture that
+    # At world > 1 rank 0 prints (and flushes) the line so far before the leg starts: whatever happens to a capture that
     # contains RCCL collectives on more than one rank (it has never run on hardware), the run has a valid
     # measurement on stdout.  If the leg completes, the final line follows and supersedes it.  DSS2_BENCH_DIST_GRAPH=0 skips
     # the leg at world > 1.
@@ -762,7 +830,7 @@ def main():
     run_graph_leg = not args.no_graph and (world == 1 or dist_graph)
     if world > 1 and rank == 0 and run_graph_leg:
         early = dict(result)
-        early["partial"] = "eager measurement, printed before the hipGraph leg; a later line (if any) supersedes it"
+        early["partial"] = "printed before the hipGraph leg; a later line (if any) supersedes it"
         print(json.dumps(early), flush=True)
     if run_graph_leg:
         timer = capture_watchdog(result, rank, world, args.graph_timeout, leg="hipGraph replay")
@@ -770,58 +838,16 @@ def main():
             graphed = pkg.graphs.GraphedStep(step, stream=work_stream, capture_error_mode="thread_local")
             for _ in range(max(args.warmup, 5)):
                 graphed.replay()
-            gw, _ = timed_windows(graphed.replay)
-            gdt = sorted(gw)[len(gw) // 2]
+            gdt, _ = timed_steps(graphed.replay)
             result["config"]["ms_per_step_by_mode"]["hipGraph replay"] = gdt / args.steps * 1e3
             result["legs"]["hipGraph replay"] = "ok"
-            if gdt < dt:
-                dt, ms, windows, mode = gdt, gdt / args.steps * 1e3, gw, "hipGraph replay"
-                value = args.batch * world / (dt / args.steps)
-                result.update(value=value, ms_per_step=ms)
-                result["config"].update(mode=mode, timed_windows=len(gw),
-                                        window_ms_min_median_max=[min(gw) * 1e3, gdt * 1e3, max(gw) * 1e3])
-        except Exception as exc:          # capture not possible on this stack: the eager numbers stand
+        except Exception as exc:          # capture not possible on this stack: the other legs' numbers stand
             result["config"]["hipgraph"] = f"failed: {type(exc).__name__}: {exc}"[:300]
             result["legs"]["hipGraph replay"] = "failed"
         timer.cancel()
     elif not args.no_graph:
         result["config"]["hipgraph"] = "skipped at world > 1 (opt in with DSS2_BENCH_DIST_GRAPH=1: a capture with RCCL inside can abort the process)"
         result["legs"]["hipGraph replay"] = "skipped"
-    # ---- and as a launch plan (graphs.PlannedStep, include/dss2_hip.h "launch plans"): the library's own record of the step's launches
-    # re-issued from ONE C call per step -- real launches of the same kernels on the same stream, no Python between them, and like the
-    # hipGraph replay it carries the step's vminmax launch (no cached batch constants).  At world > 1 the step's collectives (loss
-    # sums, gradient bucket) cut the plan into segments: one C call per segment, the collectives between them (graphs.plan_collective)
-    # -- no Python around the launches and no RCCL inside a capture.  Behind the same watchdog as the hipGraph leg; rank 0 first
-    # prints what it has (the hipGraph result, if that leg completed), so a hang here costs nothing.
-    dist_plan = os.environ.get("DSS2_BENCH_DIST_PLAN", "1") != "0"
-    if not args.no_graph and (world == 1 or dist_plan):
-        if world > 1 and rank == 0:
-            early = dict(result)
-            early["partial"] = "printed before the launch-plan leg; a later line (if any) supersedes it"
-            print(json.dumps(early), flush=True)
-        ptimer = capture_watchdog(result, rank, world, args.graph_timeout, leg="launch plan")
-        try:
-            # (verify: one replay must reproduce the recorded step's gradients bit for bit -- a launch the plan does not carry would show here)
-            planned = pkg.graphs.PlannedStep(step, stream=work_stream, verify=(lambda: [p.grad for p in params]) if world == 1 else None)
-            for _ in range(max(args.warmup, 5)):
-                planned.replay()
-            pw, _ = timed_windows(planned.replay)
-            pdt = sorted(pw)[len(pw) // 2]
-            result["config"]["ms_per_step_by_mode"]["launch plan"] = pdt / args.steps * 1e3
-            result["config"]["plan_launches"] = planned.n_launches
-            result["legs"]["launch plan"] = "ok"
-            if pdt < dt:
-                dt, ms, windows, mode = pdt, pdt / args.steps * 1e3, pw, "launch plan (dss2_plan_run)"
-                value = args.batch * world / (dt / args.steps)
-                result.update(value=value, ms_per_step=ms)
-                result["config"].update(mode=mode, timed_windows=len(pw),
-                                        window_ms_min_median_max=[min(pw) * 1e3, pdt * 1e3, max(pw) * 1e3])
-            if world > 1:
-                result["config"]["plan_segments"] = len(planned.segments)
-        except Exception as exc:
-            result["config"]["launch_plan"] = f"failed: {type(exc).__name__}: {exc}"[:300]
-            result["legs"]["launch plan"] = "failed"
-        ptimer.cancel()
 
     # ---- the same step on the two other arithmetic routes of the H -> H layers: the headline runs the products as
     # f16x3 (two fp16 pieces per operand, THREE 16-bit MFMAs per fp32 product, fp32 accumulate); beside it bf16x6 (SIX) and the true

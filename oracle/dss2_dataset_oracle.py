@@ -77,20 +77,26 @@ def measure_edges(pq_from: np.ndarray, gb: np.ndarray, meas_pflow: Sequence[int]
     return torch.concat([ea[:, 0:1], cov[:, 0:1], ea[:, 1:], cov[:, 1:], imp], axis=1)
 
 
-def masked_zscore(t: torch.Tensor, num_feat: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def masked_zscore(t: torch.Tensor, num_feat: int, stats=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """data.py:179-190: per-column mean / std over the NON-ZERO entries, z-score of those entries, zeros stay
-    zero; columns >= num_feat pass through.  Returns (normalised, mean[all cols], std[all cols])."""
+    zero; columns >= num_feat pass through.  Returns (normalised, mean[all cols], std[all cols]).
+    ``stats`` = (mean, std) of the first num_feat columns: normalise with these instead of the column statistics
+    (tests: a golden's statistics, whose fp32 column sums another torch build may round differently)."""
     mask = t != 0.0
     mean = torch.nan_to_num((t * mask).sum(dim=[0]) / mask.sum(dim=[0]))
     std = torch.nan_to_num(torch.sqrt(((t - mean) ** 2 * mask).sum(dim=[0]) / mask.sum(dim=[0])))
+    if stats is not None:
+        mean, std = mean.clone(), std.clone()
+        mean[:num_feat], std[:num_feat] = stats
     out = torch.nan_to_num((t - mean) * mask / std)
     out[:, num_feat:] = t[:, num_feat:]
     return out, mean, std
 
 
 def data_from_tables(nodes: np.ndarray, edges: np.ndarray, labels: np.ndarray, noise: Dict[str, float],
-                     meas_v: Sequence[int], meas_pflow: Sequence[int], z_nodes: np.ndarray, z_edges: np.ndarray):
-    """data.py:96-204 on raw tables (uniform sample shapes).
+                     meas_v: Sequence[int], meas_pflow: Sequence[int], z_nodes: np.ndarray, z_edges: np.ndarray, stats=None):
+    """data.py:96-204 on raw tables (uniform sample shapes).  ``stats``: optional dict of x_mean, x_std, edge_mean,
+    edge_std to normalise with (masked_zscore).
     nodes  [S, n, 7]  = (vm_pu, va_rad, p_mw, q_mvar, vn_kv, bool_slack, bool_zero_inj)
     edges  [S, e, 11] = (from_bus, to_bus, p_from_mw, q_from_mvar, G, B, Gs, Bs, closed, phase shift, imax or sn),
                         closed branches only, stored order
@@ -109,8 +115,8 @@ def data_from_tables(nodes: np.ndarray, edges: np.ndarray, labels: np.ndarray, n
         ys.append(torch.tensor(labels[i], dtype=torch.float32))
         eis.append(torch.tensor(edges[i, :, 0:2].astype(int), dtype=torch.long).t().contiguous())
     x_tensor, ea_tensor, y_tensor = torch.cat(xs, 0), torch.cat(eas, 0), torch.cat(ys, 0)
-    x_set, x_mean, x_std = masked_zscore(x_tensor, 8)
-    ea_set, e_mean, e_std = masked_zscore(ea_tensor, 6)
+    x_set, x_mean, x_std = masked_zscore(x_tensor, 8, None if stats is None else (stats["x_mean"], stats["x_std"]))
+    ea_set, e_mean, e_std = masked_zscore(ea_tensor, 6, None if stats is None else (stats["edge_mean"], stats["edge_std"]))
     return dict(x=x_set, edge_attr=ea_set, y=y_tensor, edge_index=eis, x_mean=x_mean[:8], x_std=x_std[:8],
                 edge_mean=e_mean[:6], edge_std=e_std[:6])   # data.py:205 returns the feature columns' statistics
 

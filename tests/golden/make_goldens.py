@@ -16,7 +16,8 @@ Fixtures written:
     tests/golden/case_<name>.npz        model / loss cases (weights, inputs, reference outputs)
     tests/golden/dataset64.npz          raw tables of 64 real CIGRE-14 samples, the standard-normal draws
                                         the reference consumed, and its data_from_pickles output on them
-                                        (python tests/golden/make_goldens.py dataset64 writes only this one)
+    tests/golden/cigre14_pickles64/     the reference's CIGRE-14 pickles cut to those 64 samples
+                                        (python tests/golden/make_goldens.py dataset64 writes only these two)
     tests/golden/case_mpn_{c2model,ober_h128,ober179_h128}.npz   the C2 model at the three tile heights
                                         (python tests/golden/make_goldens.py flagship)
 """
@@ -75,11 +76,12 @@ def real_cigre():
 
 
 def dataset64():
-    """data_from_pickles on the first 64 CIGRE-14 samples (pickles truncated into a temp folder), with the
-    raw tables and the standard-normal draws saved beside the reference's output."""
-    import tempfile
+    """data_from_pickles on the first 64 CIGRE-14 samples (pickles truncated into cigre14_pickles64/, the
+    fixture of dataset.read_pickles' test), with the raw tables and the standard-normal draws saved beside the
+    reference's output."""
     src = f"{REF}/data/cigre14/"
-    tmp = tempfile.mkdtemp(prefix="dss2_ds64_") + "/"
+    tmp = os.path.join(HERE, "cigre14_pickles64") + "/"
+    os.makedirs(tmp, exist_ok=True)
     tabs = {}
     for name in ["nodes", "edges", "labels"]:
         tabs[name] = pickle.load(open(src + name, "rb"))[:64]

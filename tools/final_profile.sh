@@ -7,10 +7,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/final; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/final_stats -o s -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs --no-routes --min-window-seconds 0.5 > $O/bench_under_rocprof.log 2>&1
-find /tmp/final_stats -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_bench_c2.csv \;
+rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/final_stats -o s -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs --no-routes > $O/bench_under_rocprof.log 2>&1
+find $TMPDIR/final_stats -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_bench_c2.csv \;
 cd $R
 bash tools/pmc_one.sh chain > $O/pmc_gemm_chain.txt 2>&1
 bash tools/pmc_one.sh wgrad3 > $O/pmc_wgrad_batched.txt 2>&1
