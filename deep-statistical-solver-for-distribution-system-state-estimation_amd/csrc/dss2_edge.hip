@@ -816,6 +816,12 @@ static bool edge_mfma_ok(int h, int nrb, int D, bool bwd = false) {
   return edge_mfma_lds(nrb * 32, D, h >> 5, true) <= (size_t)kMaxLdsBytes;
 }
 
+// the tile kernels of 32 / 64 / 96-row tiles run the bf16x6 forms of dss2_edge16.hip (by target, without U): what the edge phases of the
+// 64-row split-plane chain reproduce (dss2_gemm_chain_sp.hip)
+bool dss2::edge16_tile_route(int h, int nrb, int D, bool bwd) {
+  return edge_mfma_ok(h, nrb, D, bwd) && edge16_ok(h, nrb, D, bwd, false);
+}
+
 template <int NRB>
 static int launch_edge_mfma(const EdgeTileArgs& a, int grid, bool bwd, hipStream_t s) {
   const int nw = a.h >> 5;                  // one wave per 32-column group of the hidden layer (<= 8)

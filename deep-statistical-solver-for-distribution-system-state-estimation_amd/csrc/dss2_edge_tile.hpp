@@ -116,5 +116,7 @@ __device__ __forceinline__ void edge_build_ak(const EdgeStage& s, int k, int tid
 // recomputation.  edge16_ok: the shape is covered (h % 32 == 0, h <= 256, 32 / 64 / 96-row tiles, LDS).
 bool edge16_ok(int h, int nrb, int D, bool bwd, bool with_u);
 int launch_edge16(const EdgeTileArgs& a, int nrb, int grid, bool bwd, hipStream_t s);
+// the route dss2_edge_tile_fwd_paired / dss2_edge_tile_bwd take for nrb <= 3 without U is the bf16x6 one (dss2_edge.hip)
+bool edge16_tile_route(int h, int nrb, int D, bool bwd);
 
 }  // namespace dss2

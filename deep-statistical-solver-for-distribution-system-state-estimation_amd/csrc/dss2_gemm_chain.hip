@@ -89,6 +89,14 @@ extern "C" int dss2_gemm_prop_chain_head_wgrad_supported(int nrb, int nmat, int 
   return nrb == 2 && chain_row_split(nrb, a.ncg) == 1 && chain_sp_supported(a) ? 1 : 0;      // the 64-row split-plane chain (dss2_gemm_chain_sp.hip)
 }
 
+extern "C" int dss2_gemm_prop_chain_edge_supported(int nrb, int nmat, int kreal, int hout, int ell_width, int edge_width) {
+  using namespace dss2;
+  if (edge_width <= 0 || edge_width > 32 || !dss2_gemm_prop_chain_f16_supported(nrb, nmat, kreal, hout, ell_width)) return 0;
+  dss2_gemm_prop_args a = {};
+  a.b_format = 2; a.nrb = nrb; a.nmat = nmat; a.kreal = kreal; a.kpad = (kreal + 15) / 16 * 16; a.hout = hout; a.ncg = (hout + 31) / 32; a.ell_width = ell_width;
+  return chain_sp_edge_modes(a, edge_width);
+}
+
 static int dss2_gemm_prop_chain_head_launch(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream);
 extern "C" int dss2_gemm_prop_chain_head(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream) {
   if (!ap) { dss2::set_error("dss2_gemm_prop_chain_head: null argument"); return 2; }
@@ -114,6 +122,17 @@ static int dss2_gemm_prop_chain_head_launch(const dss2_gemm_prop_args* ap, const
   if (head->drop_id && !ap->drop_state) { set_error("gemm_prop_chain_head: drop_id without drop_state"); return 2; }
   if (head->wg_slab && (head->mode != 2 || !head->gate || !dss2_gemm_prop_chain_head_wgrad_supported(ap->nrb, ap->nmat, ap->kreal, ap->hout, ap->ell_width, head->nout))) {
     set_error("gemm_prop_chain_head: wg_slab needs mode 2, gate and a shape dss2_gemm_prop_chain_head_wgrad_supported accepts"); return 2;
+  }
+  const dss2_chain_edge& e = head->edge;
+  if (e.W1) {
+    if (ap->b_format != 2 || !(dss2_gemm_prop_chain_edge_supported(ap->nrb, ap->nmat, ap->kreal, ap->hout, ap->ell_width, e.width) & head->mode)) {
+      set_error("gemm_prop_chain_head: no edge phase for this shape (nrb=%d nmat=%d hid=%d ell=%d edge ell=%d b_format=%d mode=%d)",
+                ap->nrb, ap->nmat, ap->hout, ap->ell_width, e.width, ap->b_format, head->mode);
+      return 2;
+    }
+    if (!e.x || !e.ea || !e.b1 || !e.ell_ent || (head->mode == 1 && (!e.S || !al16(e.S))) || (head->mode == 2 && !e.slab)) {
+      set_error("gemm_prop_chain_head: the edge phase needs x, edge_attr, W1, b1, ell_ent and S (mode 1, 16-byte aligned) / slab (mode 2)"); return 2;
+    }
   }
   return chain_impl(ap, layers, n_layers, head, stream);
 }

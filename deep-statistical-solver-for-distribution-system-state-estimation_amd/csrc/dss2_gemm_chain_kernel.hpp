@@ -467,6 +467,7 @@ inline int launch_chain(const dss2_gemm_prop_args& a, const ChainTable& ct, hipS
 int launch_chain16(const dss2_gemm_prop_args& a, const ChainTable& ct, int rsplit, hipStream_t s);
 // 64-row tiles, one wave per column group: the tile kept in LDS as split bf16 planes (dss2_gemm_chain_sp.hip; DSS2_CHAIN_SP=0: off)
 bool chain_sp_supported(const dss2_gemm_prop_args& a);
+int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width);      // dss2_gemm_prop_chain_edge_supported's mask for a b_format-2 launch
 int launch_chain_sp(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, hipStream_t s);
 // 192-row tiles, six row blocks per wave (dss2_gemm_chain_sp6.hip)
 bool chain_sp6_supported(const dss2_gemm_prop_args& a);

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "dss2_gemm_chain_kernel.hpp"
+#include "dss2_edge16_tile.hpp"
 
 namespace dss2 {
 
@@ -77,6 +78,14 @@ constexpr int SP_HEAD_MAX = 4;      // nout
 // layer output (DPP), four LDS words, ONE more barrier per layer.  Errors of the size of fp32 arithmetic's own (dss2_wgrad16h.hip).
 // Layers gated by fp32 activations and X plane images: not in this form (the host routes them to MS = 1).
 typedef float f32x4_acc __attribute__((ext_vector_type(4)));
+
+// the edge kernels' arguments of this launch's tiles (dss2_chain_edge)
+__device__ __forceinline__ EdgeTileArgs edge_args(const dss2_gemm_prop_args& p, const dss2_chain_edge& e) {
+  EdgeTileArgs a{e.x, e.ldx, e.ea, e.ldea, e.W1, e.b1, nullptr, p.tile_start, reinterpret_cast<const int2*>(e.ell_ent), e.S, e.slab, nullptr, 0,
+                 p.hout, e.width, SP_TM, 0, p.ntiles};
+  return a;
+}
+
 template <int NMAT, int NW, int HM, int MS>
 __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_gemm_prop_args p, const ChainTable ct, const dss2_chain_head hd) {
   constexpr int TM = SP_TM;
@@ -89,6 +98,9 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
   const int tile = blockIdx.x;
   constexpr bool F16 = MS == 2;
   constexpr int NP = F16 ? 2 : 3;      // planes per stripe / per weight fragment group
+  // the edge phases (hd.edge, dss2_chain_edge): only the two instantiations the C2 shape runs carry them (a uniform branch on hd.edge.W1)
+  constexpr bool EDGE = F16 && NMAT == 3 && NW == 4 && HM != 0;
+  const bool eon = EDGE && hd.edge.W1 != nullptr;
   const uint64_t drop_seed = p.drop_state ? p.drop_state[0] : 0, drop_off = p.drop_state ? p.drop_state[1] : 0;
   const bool probe = ct.clock_probe != nullptr && (tile & 255) == 0 && tile < 1024;      // (uniform; diagnostic, see ChainTable)
   if (probe && tid == 0) {      // (written at once: nothing of the probe stays live across the kernel)
@@ -132,6 +144,45 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
       sp_store_split(xpl + (c >> 5) * (2 * SP_REGION) + r * SP_RS + (c & 31), v);
     }
   } else if constexpr (HM != 2) {
+    if (eon) {
+      // ---- edge phase, forward: the input tile S = sum_k relu(W1 [x_i | x_j | ea]_k + b1) computed here (dss2_edge16_tile.hpp: the
+      // arithmetic of edge16_fwd_kernel, the same bits) instead of read back from HBM.  Its images fill the planes' region, which is not
+      // live before the first GEMM; wave w owns hidden columns 32 w .. 32 w + 31 -- exactly its stripe of the planes below.
+      const EdgeTileArgs ep = edge_args(p, hd.edge);
+      E16Lds EL = e16_ptrs<2>(smem, ep.D, TM);
+      const E16W w = e16_weights(ep.W1, ep.b1, cg * 32 + c32, half);
+      edge_stage_part<2>(ep, EL.s, tile, TM, 0, ts, R, tid, nthreads);
+      sp_barrier();
+      e16_build<2>(EL, ep.D, tid, nthreads);
+      sp_barrier();
+      f32x16 sacc[2];
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) sacc[rb] = e16_fwd_rb<2>(EL, w, ep.D, rb, c32, half);
+      sp_barrier();      // every wave is done with the edge images: the region is the waves' own again
+      // accumulator layout (lane = column, rows acc_row) -> the wave's slot, row-major -> the row pieces of the staging below
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) slot0[(rb * 32 + acc_row(r, half)) * 32 + c32] = sacc[rb][r];
+      wave_lds_sync();
+      f32x4 sv[8];
+      float mx = 0.f;
+      char* sp = reinterpret_cast<char*>(ep.S + (size_t)(ts + r8) * ep.h + col0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int row = r8 + 8 * i;
+        sv[i] = row < R ? *reinterpret_cast<const f32x4*>(slot0 + row * 32 + cq) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if (row < R) *reinterpret_cast<f32x4*>(sp) = sv[i];      // S: conv 0's X for the weight gradients
+        sp += (size_t)ep.h * 32;
+        mx = absmax4(mx, sv[i]);
+      }
+      mx = wave_max(mx);
+      if (lane == 0) mxw[wave] = mx;
+      sp_barrier();      // (also: every lane has read its row pieces before the planes go over the slot)
+      ea = tile_exponent();
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sp_store_split_h(own_planes + (r8 + 8 * i) * SP_RS + cq, sv[i], ea);
+    } else {
     // the input tile waits in registers (TM kq / threads = kpad / (4 ncg) <= 8 row pieces per thread) while its maximum is formed
     f32x4 xin[8];
     float mx = 0.f;
@@ -153,6 +204,7 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
       const int idx = tid + j * nthreads;
       const int r = idx / kq, c = (idx - r * kq) << 2;
       if (idx < TM * kq) sp_store_split_h(xpl + (c >> 5) * (2 * SP_REGION) + r * SP_RS + (c & 31), xin[j], ea);
+    }
     }
   } else {
     // X[row][c] = gate(row, c) * sum_{m, o} ((P^T)^m G)[row][o] W_m[o][c]: every wave builds its own 32-column stripe.
@@ -650,7 +702,7 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
 #pragma unroll
         for (int i = 0; i < 8; ++i) U[i] += *reinterpret_cast<const f32x4*>(L.add_src + grow_of(i) * p.ld_add + col0);
       }
-      {
+      if (!(HM == 2 && eon && !keep)) {      // (the edge phase's dS stays on chip)
         char* yp = reinterpret_cast<char*>(L.Y + (size_t)(ts + rowv) * p.ldy + col0);      // one 64-bit product per layer, then a uniform stride
         const size_t ystep = (size_t)p.ldy * 32;                                           // 8 rows
 #pragma unroll
@@ -680,6 +732,13 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
         }
       }
       reinterpret_cast<uint32_t*>(L.y_bits)[((size_t)tile * ncg + cg) * 64 + lane] = word;
+    }
+    if constexpr (EDGE && HM == 2) {
+      if (eon && !keep) {      // conv 0's input gradient dS -> the wave's slot 0 (free after the hops), row-major; rows beyond the tile: 0
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          *reinterpret_cast<f32x4*>(slot0 + (rowv + 8 * i) * 32 + cq) = rowv + 8 * i < R ? U[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
     if (keep) {
       // (rows beyond the tile's R rows are NOT zeroed -- 32 selects per layer: their values are finite (bias-driven like any
@@ -797,6 +856,60 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
     CSTAMP(2 + li * 6 + 4);
     if (!keep) CSTAMP_RT(63);
   }
+  if constexpr (EDGE && HM == 2) {
+    if (eon) {
+      // ---- edge phase, backward (edge16_bwd_kernel's PRE path on this tile): dS, wave-private, from the slot into the accumulator
+      // layout (lane = hidden column, rows acc_row) and split into its bf16 planes once; per slot the recomputed pre-activation's gates
+      // mask the planes and dW1 += dZ_k^T A_k as bf16x6.  One dW1 | db1 slab per tile.
+      wave_lds_sync();
+      uint32_t gh[2][8], gm[2][8], gl[2][8];
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          split3_pair(slot0[(rb * 32 + acc_row(2 * j, half)) * 32 + c32], slot0[(rb * 32 + acc_row(2 * j + 1, half)) * 32 + c32], gh[rb][j], gm[rb][j], gl[rb][j]);
+      sp_barrier();      // every wave holds its dS: the region becomes the edge images
+      const EdgeTileArgs ep = edge_args(p, hd.edge);
+      constexpr int CS = e16_cs(TM);
+      E16Bwd B = e16_bwd_ptrs<2>(smem, ep.D, TM);
+      E16Lds EL;
+      EL.s = B.s; EL.xi = B.xi; EL.PI = B.PI; EL.PK = B.PK;
+      const E16W w = e16_weights(ep.W1, ep.b1, cg * 32 + c32, half);
+      const char* bcol = c32 < FN ? B.ATI + c32 * CS : B.ATK + ((c32 < FN + E16_ATN ? c32 : FN) - FN) * CS;
+      const int bps = c32 < FN ? FN * CS : E16_ATN * CS;
+      const bool bcol_ok = c32 < FN + E16_ATN;
+      f32x16 dWacc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dWacc[r] = 0.f;
+      edge_stage_part<2>(ep, B.s, tile, TM, 0, ts, R, tid, nthreads);
+      sp_barrier();
+      e16_bwd_build_tile<2>(B, tid, nthreads);
+      f32x16 ci[2];
+      for (int k = 0; k < ep.D; ++k) {
+        e16_bwd_build_slot<2>(B, k, tid, nthreads);
+        sp_barrier();
+        if (k == 0) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb) ci[rb] = e16_xterm<2>(EL, w, rb, c32, half);
+        }
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+          const f32x16 c = e16_z<2>(EL, w, 0, rb, c32, half, ci[rb]);
+          uint32_t mk[8];
+          e16_gate_masks(c, mk);
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+            const uint4 ah = {gh[rb][4 * st] & mk[4 * st], gh[rb][4 * st + 1] & mk[4 * st + 1], gh[rb][4 * st + 2] & mk[4 * st + 2], gh[rb][4 * st + 3] & mk[4 * st + 3]};
+            const uint4 am = {gm[rb][4 * st] & mk[4 * st], gm[rb][4 * st + 1] & mk[4 * st + 1], gm[rb][4 * st + 2] & mk[4 * st + 2], gm[rb][4 * st + 3] & mk[4 * st + 3]};
+            const uint4 al = {gl[rb][4 * st] & mk[4 * st], gl[rb][4 * st + 1] & mk[4 * st + 1], gl[rb][4 * st + 2] & mk[4 * st + 2], gl[rb][4 * st + 3] & mk[4 * st + 3]};
+            e16_dw_step<2>(ah, am, al, bcol, bps, bcol_ok, rb, st, half, dWacc);
+          }
+        }
+        sp_barrier();      // everyone is done with the slot's images
+      }
+      e16_store_slab(ep.slab + (size_t)tile * ((size_t)ep.h * FC + ep.h), ep.h, cg, c32, half, dWacc);
+    }
+  }
   if (probe && tid == 0) {
     unsigned long long* q = ct.clock_probe + (tile >> 8) * 4;
     q[2] = __builtin_amdgcn_s_memtime(); q[3] = __builtin_amdgcn_s_memrealtime();
@@ -811,6 +924,15 @@ bool chain_sp_supported(const dss2_gemm_prop_args& a) {
   if (a.b_format == 2 && (!f16on || (a.kpad & 31) != 0)) return false;      // the f16x3 form: 16x16x32 MFMAs only
   return on && (a.b_format == 1 || a.b_format == 2) && a.nrb == 2 && a.nmat >= 2 && a.nmat <= 3 && (a.kpad & 15) == 0 && a.kpad <= 32 * a.ncg &&
          a.ncg >= 3 && a.ncg <= 8 && chain_sp_lds_bytes(a.ncg, a.ell_width) <= (size_t)kMaxLdsBytes;
+}
+
+int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width) {
+  if (!(a.b_format == 2 && a.nrb == 2 && a.nmat == 3 && a.ncg == 4 && a.hout == 128 && a.kreal == 128 && chain_sp_supported(a))) return 0;
+  const size_t region = (size_t)a.ncg * SP_REGION * 4;      // the edge images live where the planes / Horner slots do
+  int m = 0;
+  if (edge16_tile_route(a.hout, 2, edge_width, false) && e16_lds_bytes(SP_TM, edge_width, SP_TM) <= region) m |= 1;
+  if (edge16_tile_route(a.hout, 2, edge_width, true) && e16_bwd_lds_bytes(SP_TM, edge_width, SP_TM) <= region) m |= 2;
+  return m;
 }
 
 template <int NMAT, int NW, int HM, int MS>

@@ -17,6 +17,10 @@ CHAIN_HEAD = _os.environ.get("DSS2_CHAIN_HEAD", "1") == "1"            # the nar
 # 4 us shorter; round 5: on, and bench.py counts the head's FLOPs in the launch it rides in).  DSS2_CHAIN_HEAD_FWD=0: its own launch.
 CHAIN_HEAD_WGRAD = _os.environ.get("DSS2_CHAIN_HEAD_WGRAD", "1") == "1"   # ... and the head's weight gradient in the same staging (round 5; 0 = its own launch)
 CHAIN_HEAD_FWD = _os.environ.get("DSS2_CHAIN_HEAD_FWD", "1") == "1"
+# ... and the edge MLP's first Linear inside the chains with the fused head, tile by tile (64-row f16x3 chains at hid 128): the forward chain
+# computes its input S instead of reading it back, the data-gradient chain runs the edge backward on conv 0's input gradient instead of
+# writing it (dss2_chain_edge).  0 = the two edge launches of their own.
+CHAIN_EDGE = _os.environ.get("DSS2_CHAIN_EDGE", "1") == "1"
 WGRAD_BATCH = _os.environ.get("DSS2_WGRAD_BATCH", "1") == "1"
 STACK_NODE = _os.environ.get("DSS2_STACK_NODE", "1") == "1"              # PFN / SkipPFN as ONE autograd node (_PFNFn)
 DX_MERGE = _os.environ.get("DSS2_DX_MERGE", "1") == "1"                  # dx of the edge MLP as ONE K = 2 hid GEMM

@@ -33,7 +33,7 @@ from .topology import Topology, get_topology
 _F32 = torch.float32
 
 from . import flags as FL
-from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
+from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
 from .plans import (_DESC_DTYPE, _FoldPlan, _MatView, _PackPlan, _SG_DTYPE, _as_view, _pack_table, _sg, _sg_table, _small_gemm)
 
 
@@ -586,8 +586,17 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
     n_chain = L - 1 if (L - 1 >= 2 and chain_supported(topo, nmat, hid, False, bool(plan.fwd16))) else 0
     use16 = bool(n_chain) and bool(plan.fwd16) and chain16_supported(topo, nmat, hid, False)
     gw = chain_gate_words(topo, nmat, hid) if use16 else 0      # (inside autograd.Function.forward grad mode is off: always written; 1/32 of a layer output)
-    S, h = _edge_aggr_forward(topo, x, ldx, ea, ldea, W1, b1, b2, plan.fwd[0], hid, hid, mod.dim_featn, mod.dim_feate,
-                              second_linear=fold is None, need_dx=need_dx)
+    # the narrow last layer inside the same launch (the tile is still in the waves' registers): dss2_gemm_prop_chain_head
+    head_fused = bool(n_chain and FL.CHAIN_HEAD_FWD and use16 and n_chain == L - 1 and n_chain <= FL.CHAIN_MAX and not glob and is_narrow(nmat, mod.dim_out)
+                      and chain_head_supported(topo, nmat, hid, mod.dim_out, False))
+    # ... and the edge MLP's first Linear in its staging (dss2_chain_edge, mode 1): the chain computes S itself and writes it for the backward
+    edge_fused = (head_fused and fold is not None and plan.f16 and stack is None and not need_dx
+                  and chain_edge_supported(topo, nmat, hid, False))
+    if edge_fused:
+        S = h = torch.empty(topo.N, hid, dtype=_F32, device=dev)
+    else:
+        S, h = _edge_aggr_forward(topo, x, ldx, ea, ldea, W1, b1, b2, plan.fwd[0], hid, hid, mod.dim_featn, mod.dim_feate,
+                                  second_linear=fold is None, need_dx=need_dx)
     if fold is not None:
         h = S            # conv 0 consumes the aggregated hidden directly
     acts = [h]
@@ -617,14 +626,13 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
             if gw:
                 act_bits[len(acts)] = layers[-1]["y_bits"] = torch.empty(topo.ntiles * gw, dtype=torch.int64, device=dev)
             acts.append(out_l)
-        # the narrow last layer inside the same launch (the tile is still in the waves' registers): dss2_gemm_prop_chain_head
-        head_fused = (FL.CHAIN_HEAD_FWD and use16 and n_chain == L - 1 and n_chain <= FL.CHAIN_MAX and not glob and is_narrow(nmat, mod.dim_out)
-                      and chain_head_supported(topo, nmat, hid, mod.dim_out, False))
         head = None
         if head_fused:
             y_head = torch.empty(topo.N, mod.dim_out, dtype=_F32, device=dev)
             head = dict(W=list(conv_ps[L - 1][1:1 + nmat]), nout=mod.dim_out, Y=y_head, bias=conv_ps[L - 1][0],
                         add_src=(x if mod.skip else None), add_ld=ldx)
+            if edge_fused:
+                head["edge"] = dict(x=x, ldx=ldx, ea=ea, ldea=ldea, W1=W1, b1=b1, S=S)
         gemm_prop_chain(topo, h, hid, nmat, layers, pre_rowscale=(topo.deg_pows if fold is not None else None),
                         drop=((snap, p) if snap is not None else None), b_format=(2 if (use16 and plan.f16) else int(use16)), head=head)
         h = acts[-1]
@@ -680,6 +688,7 @@ def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=
     deferred = []
     l_start = L - 1
     dS = None
+    edge_slab = None           # (the edge MLP's backward inside the data-gradient chain: its per-tile dW1 | db1 slabs)
     # slab reductions recorded in ``pending`` run in ONE launch at the end (chained path; always inside a stack)
     fold_late = False
     if L >= 3 and FL.WGRAD_BATCH and chain_supported(topo, nmat, hid, True, bool(plan.bwd16)):
@@ -696,6 +705,10 @@ def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=
                       and (topo.nrb <= 2 or all(act_bits.get(l_) is not None for l_ in range(1, L - 1))))
         head = None
         head_wg = None
+        # the edge MLP's backward behind the chain's last layer (dss2_chain_edge, mode 2): conv 0's input gradient never leaves the chip,
+        # one dW1 | db1 slab per tile
+        edge_fused = (head_fused and fold is not None and use16 and plan.f16 and not in_stack and not need_dx
+                      and chain_edge_supported(topo, nmat, hid, True))
         if head_fused:
             # ... and the head's weight gradient from the same staging (it holds the hop results and the head's input rows): one slab
             # per tile, summed with the step's other slabs; elsewhere the narrow weight-gradient launch re-reads the activation
@@ -712,6 +725,9 @@ def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=
             head = dict(W=list(ps[4 + l * (nmat + 1) + 1:4 + (l + 1) * (nmat + 1)]), nout=mod.dim_out, G=g, gate=acts[l], Xout=g_in,
                         drop_id=(dr[2] if dr is not None else 0), wg_slab=(head_wg[0] if head_wg is not None else None),
                         wg_stride=(head_wg[3] if head_wg is not None else 0))
+            if edge_fused:
+                edge_slab = torch.empty(topo.ntiles * (hid * (2 * fn + fe) + hid), dtype=_F32, device=dev)
+                head["edge"] = dict(x=x, ldx=ldx, ea=ea, ldea=ldea, W1=W1, b1=b1, slab=edge_slab)
             g = g_in
         else:
             g = _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, mod.dim_out, flat[offs[2 + l]:offs[3 + l]],
@@ -730,6 +746,9 @@ def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=
                         drop=((snap, p_drop) if snap is not None else None), b_format=(2 if (use16 and plan.f16) else int(use16)), head=head)
         if head_wg is not None:
             _reduce(head_wg[0], 0, topo.ntiles, head_wg[3], head_wg[2], head_wg[1], pending)
+        if edge_slab is not None:
+            e_stride = hid * (2 * fn + fe) + hid
+            _reduce(edge_slab, 0, topo.ntiles, e_stride, flat[offs[0]:offs[1]], e_stride, pending)
         d_in = layers[-1]["Y"]                  # gradient w.r.t. conv 0's input: dS (folded) or dx0
         # The folded conv 0 joins the batched launch of the plain layers (round 4; FL.WGRAD_JOIN_FOLDED=False: its own launch).
         # Round 3 kept it apart because three layers x 85 workgroups leave a 13-vs-12-tile tail at C2; measured now, the
@@ -788,10 +807,13 @@ def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=
             wgrad(topo, chunk[0][1], hid, chunk[0][2], hid, nmat, out, pending=pending)
         else:
             wgrad_batched(topo, [c[1] for c in chunk], hid, [c[2] for c in chunk], hid, nmat, out, pending=pending)
-    dx = _edge_aggr_backward(topo, g, x, ldx, ea, ldea, W1, b1, S, plan.bwd[0], hid, hid, fn, fe,
-                             flat[offs[0]:offs[1]], flat[offs[1]:offs[2]], need_dx,
-                             pack_dx=tuple(plan.bwd[1 + L:4 + L]), dS=(dS if fold is not None else None),
-                             pending=pending, dx_add=(gout if (need_dx and mod.skip) else None))
+    if edge_slab is not None:      # (done inside the data-gradient chain; no input gradient asked for)
+        dx = None
+    else:
+        dx = _edge_aggr_backward(topo, g, x, ldx, ea, ldea, W1, b1, S, plan.bwd[0], hid, hid, fn, fe,
+                                 flat[offs[0]:offs[1]], flat[offs[1]:offs[2]], need_dx,
+                                 pack_dx=tuple(plan.bwd[1 + L:4 + L]), dS=(dS if fold is not None else None),
+                                 pending=pending, dx_add=(gout if (need_dx and mod.skip) else None))
     if not in_stack:
         # all slab reductions of the block in one launch, then the chain rule of the fold (it needs the reduced gfold)
         if fold_late:

@@ -169,6 +169,16 @@ def chain_head_supported(topo: Topology, nmat: int, hid: int, nout: int, transpo
         _lib.lib().dss2_gemm_prop_chain_head_supported(topo.nrb, nmat, hid, hid, ell, nout) & (2 if transposed else 1))
 
 
+def chain_edge_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
+    """True when the edge MLP's first Linear can run as a phase of the chain with the fused head (dss2_chain_edge): forward = the chain
+    computes its input S, transposed = the data-gradient chain runs the edge backward on conv 0's input gradient.  64-row tiles, f16x3,
+    hid 128, the bf16x6 tile edge kernels.  flags.CHAIN_EDGE = False: the edge launches of their own."""
+    if not (FL.CHAIN_EDGE and FL.EDGE_TILE_KERNELS and topo.ell_ent_tiles is not None and topo.ell_tiles is not None and topo.ellT_tiles is not None):
+        return False
+    ell = topo.ellT if transposed else topo.ell
+    return bool(_lib.lib().dss2_gemm_prop_chain_edge_supported(topo.nrb, nmat, hid, hid, ell, topo.ell) & (2 if transposed else 1))
+
+
 def chain_head_wgrad_supported(topo: Topology, nmat: int, hid: int, nout: int) -> bool:
     """True when the data-gradient chain with the fused head (mode 2) can also form the head's weight gradient in its staging
     (dss2_chain_head.wg_slab, round 5): 64-, 96- and 192-row tiles, nout <= 2.  flags.CHAIN_HEAD_WGRAD = False: the narrow weight-gradient launch."""
@@ -251,6 +261,12 @@ def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: i
         hd.drop_id = int(head.get("drop_id", 0)) if drop is not None else 0
         hd.wg_slab = _ptr(head.get("wg_slab"))      # (optional: the head's weight gradient, one slab per tile; chain_head_wgrad_supported)
         hd.pad = int(head.get("wg_stride", 0))      # (stride of those slabs in floats)
+    edge = head.get("edge")      # (optional: dss2_chain_edge; chain_edge_supported)
+    if edge is not None:
+        e = hd.edge
+        e.x, e.ldx, e.ea, e.ldea = edge["x"].data_ptr(), int(edge["ldx"]), edge["ea"].data_ptr(), int(edge["ldea"])
+        e.W1, e.b1, e.ell_ent, e.width = edge["W1"].data_ptr(), edge["b1"].data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell
+        e.S, e.slab = _ptr(edge.get("S")), _ptr(edge.get("slab"))
     _lib.check(_lib.lib().dss2_gemm_prop_chain_head(C.byref(a), C.addressof(tab), len(layers), C.byref(hd), _stream(dev_t)),
                "dss2_gemm_prop_chain_head")
 

@@ -325,6 +325,24 @@ int dss2_gemm_prop_chain(const dss2_gemm_prop_args* args_host, const dss2_chain_
  *   X = (gate > 0) * dropout(drop_id) * sum_m (P^T)^m G W_m with G[N][nout] the gradient w.r.t. the head's output, gate the
  *   head's input activation; X is also written to Xout (the weight-gradient kernels read it); args.X is ignored.
  * W[m]: the head's weights [nout][hid] row-major, m < nmat.  nout <= 4.  Same tiles / ELL slices as the chain. */
+/* The edge MLP's first Linear (the bf16x6 tile kernels of dss2_edge_tile_fwd / dss2_edge_tile_bwd, by target, without U) as a phase
+ * of the chain with the fused head, tile by tile (where dss2_gemm_prop_chain_edge_supported says so):
+ *   mode 1: the chain's input tile is S = sum over the incoming edges of relu(W1 [x_i | x_j | edge_attr] + b1), computed in the
+ *     launch's staging instead of read from args.X; S [N][hid] is still written (row-major, ld = hid).
+ *   mode 2: the last layer's output (conv 0's input gradient dS) is NOT written to its Y; the edge MLP's backward runs on it in the
+ *     same launch and writes ONE slab per tile to `slab`: [ntiles][hid * 22 + hid] floats = [dW1 ([hid][22]) | db1], to be summed
+ *     over the tiles (dss2_reduce_slabs*).
+ * x [N][8] (ldx), edge_attr [E][6] (ldea), W1 [hid][22], b1 [hid], ell_ent: the forward topology's per-tile ELL table of the edge
+ * kernels ({other node, eid | flip << 31}, ell_width = width). */
+typedef struct dss2_chain_edge {
+  const float* x; const float* ea; const float* W1; const float* b1;
+  const void* ell_ent;
+  float* S;       /* mode 1 */
+  float* slab;    /* mode 2 */
+  int64_t ldx, ldea;
+  int32_t width, pad;
+} dss2_chain_edge;
+
 typedef struct dss2_chain_head {
   const float* W[4];
   const float* bias; const float* add_src; float* Y;      /* mode 1 */
@@ -336,6 +354,7 @@ typedef struct dss2_chain_head {
                      * (dss2_reduce_slabs*); `pad` > 0: the stride between the tiles' slabs in floats (a multiple of 4 lets the reduction use
                      * 16-byte lanes).  Needs gate (the head's input rows) and nout <= 2 on 64-, 96- or 192-row tiles
                      * (dss2_gemm_prop_chain_head_wgrad_supported); NULL: not computed */
+  dss2_chain_edge edge;   /* optional (W1 == NULL: off): the edge MLP's first Linear inside this launch, see dss2_chain_edge */
 } dss2_chain_head;
 int dss2_gemm_prop_chain_head(const dss2_gemm_prop_args* args_host, const dss2_chain_layer* layers_host, int n_layers,
                               const dss2_chain_head* head_host, void* stream);
@@ -344,6 +363,10 @@ int dss2_gemm_prop_chain_head(const dss2_gemm_prop_args* args_host, const dss2_c
 int dss2_gemm_prop_chain_head_supported(int nrb, int nmat, int kreal, int hout, int ell_width, int nout);
 /* != 0: a mode-2 launch of this shape also forms the head's weight gradient (dss2_chain_head.wg_slab) */
 int dss2_gemm_prop_chain_head_wgrad_supported(int nrb, int nmat, int kreal, int hout, int ell_width, int nout);
+/* mask of the edge phases (dss2_chain_edge) a launch of this shape runs: bit 0 = mode 1 (forward; ell_width = the forward ELL's),
+ * bit 1 = mode 2 (backward; ell_width = the transposed ELL's); edge_width = the edge kernels' ELL width.  64-row tiles, nmat = 3,
+ * hid = 128 (four column groups), f16x3 weights (b_format 2), and edge kernels that would run their bf16x6 form; 0 otherwise. */
+int dss2_gemm_prop_chain_edge_supported(int nrb, int nmat, int kreal, int hout, int ell_width, int edge_width);
 int dss2_gemm_prop_chain_supported(int nrb, int nmat, int kreal, int hout, int ell_width);
 /* != 0: the chain can also run with args.b_format = 1 -- weights packed as bf16x3 fragments, the tile GEMM as six
  * v_mfma_f32_32x32x16_bf16 per fp32 product term set (h/m/l splits of both operands, fp32 accumulation): fp32-accurate
