@@ -1,0 +1,418 @@
+"""GATv2 and the reference's default model, ``GAT_DSSE`` (/root/reference/networks.py:113-156), on the HIP kernels of
+csrc/dss2_gat.hip.
+
+    GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
+              edge_dim=None, fill_value='mean', bias=True, share_weights=False)     PyG's layer, same parameter names
+    GAT_DSSE(dim_feat, dim_dense, dim_out, num_layers, edge_dim, heads=1, concat=True, slope=0.2, self_loops=True,
+             dropout=0., nonlin='leaky_relu', model='gat')                          the reference's signature and attributes
+
+``GAT_DSSE.model`` is a look-alike of PyG's ``Sequential`` with children ``module_{i}``: conv k is ``module_{2k}``, the shared
+nonlinearity sits at every ``module_{2k+1}``, the two Linears follow; so the ``state_dict`` keys are the reference's.  Its
+forward is ONE autograd node (``_GATFn``): one launch per conv forward (the head Linears fused into the last one), per layer
+one fused backward launch (source pass of layer l + target pass of layer l - 1), one batched weight-gradient launch and one
+slab reduction.  Every launch goes through the library, so the step records into launch plans and hipGraphs.
+
+The semantics are PyG 2.3-2.6's ``GATv2Conv`` / ``softmax`` / ``add_self_loops`` / ``Sequential`` (torch_geometric is not a
+dependency; they are pinned by tests/golden/gat_known_answers.json and the fp64 restatement tests/gat_oracle.py).  Not
+provided (ValueError): heads > 1, attention dropout > 0, fill_value other than 'mean', bipartite (tuple) inputs,
+return_attention_weights.  No gradient with respect to edge_attr; no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .ops import _require_gpu, _rows
+from .topology import get_topology
+
+_F32 = torch.float32
+MAX_CHANNELS = 32        # conv input / output channels and the head's input width (lane group of 8 / 16 / 32 lanes)
+MAX_EDGE_DIM = 16
+MAX_DENSE = 32           # head widths dim_dense and dim_out
+_MAX_SLABS = 256
+_NONLIN = {"none": 0, "leaky_relu": 1, "relu": 2, "tanh": 3}
+
+
+def _glorot(t: torch.Tensor) -> None:
+    a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
+    with torch.no_grad():
+        t.uniform_(-a, a)
+
+
+def _fan_in_uniform(t: torch.Tensor, fan_in: int) -> None:
+    b = 1.0 / math.sqrt(fan_in) if fan_in > 0 else 0.0
+    with torch.no_grad():
+        t.uniform_(-b, b)
+
+
+def _check_width(name: str, v: int, limit: int) -> None:
+    if not isinstance(v, int) or v < 1 or v > limit:
+        raise ValueError(f"{name} = {v}: the GAT kernels take 1 <= {name} <= {limit}")
+
+
+class GATv2Conv(nn.Module):
+    """PyG ``GATv2Conv`` with ``heads = 1`` on the HIP kernels.  ``state_dict`` keys: ``att [1, 1, C]``, ``bias [C]``,
+    ``lin_l.{weight, bias}``, ``lin_r.{weight, bias}`` (the same module as lin_l with share_weights), ``lin_edge.weight``
+    (with edge_dim).  Edges are used as given (not doubled); with add_self_loops the input's self loops are dropped and one per
+    node is added with the mean of its incoming edges' attributes (0 without any)."""
+
+    def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
+                 dropout: float = 0.0, add_self_loops: bool = True, edge_dim: Optional[int] = None, fill_value="mean",
+                 bias: bool = True, share_weights: bool = False, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("GATv2Conv: bipartite (tuple) in_channels are not supported")
+        if heads != 1:
+            raise ValueError(f"GATv2Conv: heads = {heads}; only heads = 1 is supported")
+        if dropout > 0:
+            raise ValueError(f"GATv2Conv: attention dropout = {dropout}; only dropout = 0 is supported")
+        if not (isinstance(fill_value, str) and fill_value == "mean"):
+            raise ValueError(f"GATv2Conv: fill_value = {fill_value!r}; only 'mean' is supported")
+        _check_width("in_channels", in_channels, MAX_CHANNELS)
+        _check_width("out_channels", out_channels, MAX_CHANNELS)
+        if edge_dim is not None:
+            _check_width("edge_dim", edge_dim, MAX_EDGE_DIM)
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout, self.add_self_loops = float(negative_slope), float(dropout), bool(add_self_loops)
+        self.edge_dim, self.fill_value, self.share_weights = edge_dim, fill_value, bool(share_weights)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(heads * out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = self.lin_l if share_weights else nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False) if edge_dim is not None else None
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        """GATv2Conv.reset_parameters: glorot weights and att, Linear biases U(+-1/sqrt(in)), conv bias zeros."""
+        for lin in ([self.lin_l] if self.share_weights else [self.lin_l, self.lin_r]):
+            _glorot(lin.weight)
+            if lin.bias is not None:
+                _fan_in_uniform(lin.bias, self.in_channels)
+        if self.lin_edge is not None:
+            _glorot(self.lin_edge.weight)
+        _glorot(self.att)
+        if self.bias is not None:
+            with torch.no_grad():
+                self.bias.zero_()
+
+    def _slots(self) -> List[Optional[torch.Tensor]]:
+        """The 7 kernel slots (att, bias, W_l, b_l, W_r, b_r, W_e) in the slab's column order."""
+        return [self.att, self.bias, self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, self.lin_r.bias,
+                None if self.lin_edge is None else self.lin_edge.weight]
+
+    def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None):
+        if isinstance(x, (tuple, list)):
+            raise ValueError("GATv2Conv: bipartite (tuple) inputs are not supported")
+        if return_attention_weights:
+            raise ValueError("GATv2Conv: return_attention_weights is not supported")
+        if self.lin_edge is None:
+            edge_attr = None
+        elif edge_attr is None:
+            raise ValueError("GATv2Conv: edge_dim is set, so forward needs edge_attr")
+        return run_gat([self], None, "none", x, edge_index, edge_attr)
+
+
+class GATSequential(nn.Module):
+    """Stand-in for PyG's ``Sequential('x, edge_index, edge_attr', [...])`` as GAT_DSSE builds it: children ``module_{i}`` in
+    the list's order (the naming is PyG's and not pinned by a test against PyG itself).  ``forward`` runs the fused route."""
+
+    def __init__(self, modules: Sequence[nn.Module], convs: Sequence[GATv2Conv], head: Sequence[nn.Linear], nonlin: str):
+        super().__init__()
+        for i, m in enumerate(modules):
+            self.add_module(f"module_{i}", m)
+        self.__dict__["_convs"], self.__dict__["_head"], self.__dict__["_nonlin"] = list(convs), list(head), nonlin
+
+    def forward(self, x, edge_index, edge_attr):
+        return run_gat(self._convs, self._head, self._nonlin, x, edge_index, edge_attr)
+
+
+class GAT_DSSE(nn.Module):
+    """/root/reference/networks.py:113-156: ``num_layers - 1`` GATv2Conv(dim_feat -> dim_feat) layers, each followed by the
+    (shared) nonlinearity, then Linear(dim_feat, dim_dense) and Linear(dim_dense, dim_out)."""
+
+    def __init__(self, dim_feat, dim_dense, dim_out, num_layers, edge_dim, heads=1, concat=True, slope=0.2, self_loops=True,
+                 dropout=0., nonlin="leaky_relu", model="gat"):
+        super().__init__()
+        self.dim_out = dim_out
+        self.num_layers = num_layers
+        self.dim_feat = dim_feat
+        self.dim_dense = dim_dense
+        self.edge_dim = edge_dim
+        self.dim_hidden = dim_feat
+        self.channels = dim_feat
+        self.heads = heads
+        self.concat = concat
+        self.slope = slope
+        self.dropout = dropout
+        self.loop = self_loops
+        if nonlin == "relu":
+            self.nonlin = nn.ReLU()
+        elif nonlin == "tanh":
+            self.nonlin = nn.Tanh()
+        elif nonlin == "leaky_relu":
+            self.nonlin = nn.LeakyReLU()
+        else:
+            raise ValueError("invalid activation type")
+        if model != "gat":
+            raise ValueError("invalid model type")
+        if num_layers < 1:
+            raise ValueError(f"num_layers = {num_layers}: at least 1 (the two Linears)")
+        _check_width("dim_feat", dim_feat, MAX_CHANNELS)
+        _check_width("dim_dense", dim_dense, MAX_DENSE)
+        _check_width("dim_out", dim_out, MAX_DENSE)
+        layers, convs = [], []
+        for _ in range(num_layers - 1):
+            conv = GATv2Conv(self.channels, self.channels, heads=heads, concat=concat, negative_slope=slope, dropout=dropout,
+                             add_self_loops=self_loops, edge_dim=edge_dim)
+            convs.append(conv)
+            layers += [conv, self.nonlin]
+        head = [nn.Linear(self.dim_hidden, dim_dense), nn.Linear(dim_dense, dim_out)]
+        self.model = GATSequential(layers + head, convs, head, nonlin)
+
+    def forward(self, x, edge_index, edge_attr):
+        return self.model(x, edge_index, edge_attr)
+
+
+# ------------------------------------------------------------------------------------------
+# the fused route
+# ------------------------------------------------------------------------------------------
+class _Spec:
+    """Dimensions, slab layout and launch geometry of one conv stack (+ head)."""
+
+    def __init__(self, convs, head, nonlin, n_nodes):
+        self.convs, self.head = convs, head
+        self.nonlin = _NONLIN[nonlin]
+        c0 = convs[0] if convs else None
+        self.ed = (c0.edge_dim or 0) if c0 is not None else 0
+        self.loops = int(c0.add_self_loops) if c0 is not None else 1
+        self.slope = float(c0.negative_slope) if c0 is not None else 0.2
+        for cv in convs:
+            if (cv.edge_dim or 0) != self.ed or int(cv.add_self_loops) != self.loops or float(cv.negative_slope) != self.slope:
+                raise ValueError("GAT stack: every conv must share edge_dim, add_self_loops and negative_slope")
+        widths = [w for cv in convs for w in (cv.in_channels, cv.out_channels)]
+        if head:
+            widths.append(head[0].in_features)
+            if head[0].out_features > MAX_DENSE or head[1].out_features > MAX_DENSE or head[1].in_features != head[0].out_features:
+                raise ValueError(f"GAT head: widths up to {MAX_DENSE}")
+        if max(widths) > MAX_CHANNELS:
+            raise ValueError(f"GAT: channel width {max(widths)} above the limit {MAX_CHANNELS}")
+        self.group = 8 if max(widths) <= 8 else (16 if max(widths) <= 16 else 32)
+        self.offs, off = [], 0
+        for cv in convs:
+            self.offs.append(off)
+            co, ci = cv.out_channels, cv.in_channels
+            off += 4 * co + 2 * co * ci + co * self.ed
+        self.head_off = off
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            off += d * c + d + o * d + o
+        self.total = off
+        self.n_slabs = max(1, min(_MAX_SLABS, -(-n_nodes // (256 // self.group))))
+
+
+def _slots(convs, head) -> List[Optional[torch.Tensor]]:
+    ps = []
+    for cv in convs:
+        ps += cv._slots()
+    if head:
+        ps += [head[0].weight, head[0].bias, head[1].weight, head[1].bias]
+    return ps
+
+
+def run_gat(convs, head, nonlin, x, edge_index, edge_attr):
+    _require_gpu(x, edge_index, edge_attr)
+    if edge_attr is not None:
+        from .networks import _no_edge_attr_grad
+        _no_edge_attr_grad(edge_attr)
+    if x.dim() != 2:
+        raise ValueError("x must be [N, C]")
+    topo = get_topology(edge_index, x.size(0), double=False)
+    topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
+    spec = _Spec(convs, head, nonlin, x.size(0))
+    need = convs[0].in_channels if convs else head[0].in_features
+    if x.size(1) != need:
+        raise ValueError(f"x has {x.size(1)} columns, the model takes {need}")
+    if spec.ed:
+        if edge_attr is None or edge_attr.dim() != 2 or edge_attr.size(1) != spec.ed or edge_attr.size(0) != edge_index.size(1):
+            raise ValueError(f"edge_attr must be [E, {spec.ed}]")
+    else:
+        edge_attr = None
+    return _GATFn.apply(x, edge_attr, topo, spec, *_slots(convs, head))
+
+
+def _graph(topo, spec, ea, ldea, slab=None):
+    g = _lib.GatGraph()
+    g.rowptr, g.col, g.ent = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
+    g.rowptrT, g.colT, g.entT = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr()
+    g.ea, g.ldea = (ea.data_ptr() if ea is not None else None), ldea
+    g.n_nodes, g.ed, g.add_self_loops, g.slope, g.nonlin = topo.N, spec.ed, spec.loops, spec.slope, spec.nonlin
+    g.slab, g.n_slabs, g.slab_len = (slab.data_ptr() if slab is not None else None), spec.n_slabs, spec.total
+    return g
+
+
+def _conv(d, cv, ps7, h, ldh, st, off):
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d.att, d.bias, d.Wl, d.bl, d.Wr, d.br, d.We = (p(t) for t in ps7)
+    d.h, d.ldh = h.data_ptr(), ldh
+    d.y, d.m, d.s = st["y"].data_ptr(), st["ms"].data_ptr(), st["ms"].data_ptr() + 4 * st["ms"].size(1)
+    for k in ("dxl", "dxr", "dedge", "dself"):
+        if k in st:
+            setattr(d, k, st[k].data_ptr())
+    d.cin, d.cout, d.slab_off = cv.in_channels, cv.out_channels, off
+
+
+def _head(d, hd, hps, st):
+    d.W1, d.b1, d.W2, d.b2 = (t.data_ptr() for t in hps)
+    d.c, d.dense, d.nout = hd[0].in_features, hd[0].out_features, hd[1].out_features
+    d.z1 = st["z1"].data_ptr()
+
+
+class _GATFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ea, topo, spec, *ps):
+        L = _lib.lib()
+        N, dev = topo.N, x.device
+        x, ldx = _rows(x)
+        ldea = 0
+        if ea is not None:
+            ea, ldea = _rows(ea)
+        sm = _lib.stream_ptr(dev)
+        convs, head = spec.convs, spec.head
+        n = len(convs)
+        states, hs = [], []
+        h, ldh = x, ldx
+        for l, cv in enumerate(convs):
+            st = {"y": torch.empty(N, cv.out_channels, dtype=_F32, device=dev), "ms": torch.empty(2, N, dtype=_F32, device=dev)}
+            states.append(st)
+            hs.append((h, ldh))
+            h, ldh = st["y"], cv.out_channels
+        hst, out = {}, None
+        if head:
+            hst["z1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
+            out = torch.empty(N, head[1].out_features, dtype=_F32, device=dev)
+        g = _graph(topo, spec, ea, ldea)
+        for l, cv in enumerate(convs):
+            a = _lib.GatArgs()
+            a.g, a.group, a.has_lo = g, spec.group, 1
+            _conv(a.lo, cv, ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
+            if head and l == n - 1:
+                a.has_head = 1
+                _head(a.head, head, ps[7 * n:7 * n + 4], hst)
+                a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
+            _lib.check(L.dss2_gat_forward(C.byref(a), sm), "dss2_gat_forward")
+        if n == 0:
+            a = _lib.GatArgs()
+            a.g, a.group, a.has_head = g, spec.group, 1
+            _head(a.head, head, ps[0:4], hst)
+            a.head.hin, a.head.ldhin = x.data_ptr(), ldx
+            a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
+            _lib.check(L.dss2_gat_forward(C.byref(a), sm), "dss2_gat_forward")
+        if out is None:
+            out = states[-1]["y"]
+        # internal buffers live on ctx (never handed out, except the last conv's y of a head-less stack, whose backward does
+        # not read it: the standalone layer has no nonlinearity)
+        ctx.save_for_backward(x, ea)      # (autograd's version check covers the inputs the backward reads)
+        ctx.st = (topo, spec, ldx, ldea, states, hs, hst, ps)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, ea = ctx.saved_tensors
+        topo, spec, ldx, ldea, states, hs, hst, ps = ctx.st
+        L = _lib.lib()
+        N, dev, E = topo.N, gout.device, topo.E
+        sm = _lib.stream_ptr(dev)
+        gout, ldgo = _rows(gout)
+        convs, head = spec.convs, spec.head
+        n = len(convs)
+        need_dx = ctx.needs_input_grad[0]
+        slab = torch.empty(spec.n_slabs, spec.total, dtype=_F32, device=dev)
+        flat = torch.empty(spec.total, dtype=_F32, device=dev)
+        cmax = max([cv.out_channels for cv in convs] or [1])
+        pp = [(torch.empty(E, cmax, dtype=_F32, device=dev), torch.empty(N, cmax, dtype=_F32, device=dev)) for _ in range(2 if n > 1 else 1)]
+        for l, cv in enumerate(convs):
+            st = states[l]
+            st["dxl"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
+            st["dxr"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
+            st["dedge"], st["dself"] = pp[l % len(pp)]
+        cin0 = convs[0].in_channels if n else head[0].in_features
+        dx = torch.empty(N, cin0, dtype=_F32, device=dev) if need_dx else None
+        if head:
+            hst["dz1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
+        g = _graph(topo, spec, ea, ldea, slab)
+
+        def conv_into(d, l):
+            _conv(d, convs[l], ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
+
+        # launch 1: head backward (or the output gradient) + target pass of the last conv
+        a = _lib.GatArgs()
+        a.g, a.group = g, spec.group
+        if head:
+            a.has_head = 1
+            _head(a.head, head, ps[7 * n:7 * n + 4], hst)
+            a.head.gout, a.head.ldgo, a.head.dz1 = gout.data_ptr(), ldgo, hst["dz1"].data_ptr()
+        else:
+            a.gy, a.ldgy = gout.data_ptr(), ldgo
+        if n:
+            a.has_lo = 1
+            conv_into(a.lo, n - 1)
+        else:
+            a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
+        _lib.check(L.dss2_gat_backward(C.byref(a), sm), "dss2_gat_backward")
+        # source pass of conv l fused with the target pass of conv l - 1; the last one writes dx
+        for l in range(n - 1, -1, -1):
+            a = _lib.GatArgs()
+            a.g, a.group, a.has_up = g, spec.group, 1
+            conv_into(a.up, l)
+            if l > 0:
+                a.has_lo = 1
+                conv_into(a.lo, l - 1)
+            else:
+                a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
+            _lib.check(L.dss2_gat_backward(C.byref(a), sm), "dss2_gat_backward")
+        # outer-product weight gradients of every layer, then ONE fixed-order reduction of the slab
+        jobs = []
+        for l, cv in enumerate(convs):
+            co, ci, off = cv.out_channels, cv.in_channels, spec.offs[l]
+            h, ldh = hs[l]
+            jobs.append((states[l]["dxl"], co, h, ldh, co, ci, off + 2 * co))
+            jobs.append((states[l]["dxr"], co, h, ldh, co, ci, off + 3 * co + co * ci))
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            hin, ldhin = (states[-1]["y"], c) if n else (x, ldx)
+            jobs.append((hst["dz1"], d, hin, ldhin, d, c, spec.head_off))
+            jobs.append((gout, ldgo, hst["z1"], d, o, d, spec.head_off + d * c + d))
+        for j0 in range(0, len(jobs), _lib.GAT_MAX_JOBS):
+            w = _lib.GatWgradArgs()
+            chunk = jobs[j0:j0 + _lib.GAT_MAX_JOBS]
+            for jd, (Gm, ldg, Xm, ldxm, gw, xw, col) in zip(w.jobs, chunk):
+                jd.G, jd.ldg, jd.X, jd.ldx, jd.gw, jd.xw, jd.col = Gm.data_ptr(), ldg, Xm.data_ptr(), ldxm, gw, xw, col
+            w.slab, w.n_nodes, w.n_slabs, w.slab_len, w.n_jobs = slab.data_ptr(), N, spec.n_slabs, spec.total, len(chunk)
+            _lib.check(L.dss2_gat_wgrad(C.byref(w), sm), "dss2_gat_wgrad")
+        rd = (_lib.ReduceDesc * 1)()
+        rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
+        _lib.check(L.dss2_reduce_slabs_multi(rd, 1, sm), "dss2_reduce_slabs_multi")
+        grads = []
+        for l, cv in enumerate(convs):
+            co, ci, ed, off = cv.out_channels, cv.in_channels, spec.ed, spec.offs[l]
+            sizes = [co, co, co * ci, co, co * ci, co, co * ed]
+            parts, o = [], off
+            for sz in sizes:
+                parts.append(flat[o:o + sz])
+                o += sz
+            for t, gpart in zip(ps[7 * l:7 * l + 7], parts):
+                grads.append(None if t is None else gpart.view(t.shape))
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            hoff = spec.head_off
+            grads += [flat[hoff:hoff + d * c].view(d, c), flat[hoff + d * c:hoff + d * c + d],
+                      flat[hoff + d * c + d:hoff + d * c + d + o * d].view(o, d), flat[hoff + d * c + d + o * d:spec.total]]
+        return (dx, None, None, None, *grads)

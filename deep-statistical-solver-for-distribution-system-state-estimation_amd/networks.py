@@ -1003,3 +1003,7 @@ class SkipPFN(PFN):
     """/root/reference/networks.py:365-388: SkipMPN blocks, last one a plain MPN."""
 
     inner = SkipMPN
+
+
+# the reference driver's default model (networks.py:113-156), defined in gat.py on its own kernels
+from .gat import GATv2Conv, GAT_DSSE  # noqa: E402,F401

@@ -737,6 +737,62 @@ int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, in
                           float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev,
                           uint32_t* counter, void* stream);
 
+/* ---- GATv2 (PyG GATv2Conv, heads = 1) and the GAT_DSSE model (reference networks.py:113-156), csrc/dss2_gat.hip ------------ *
+ * Graph: the Topology of the edge list AS GIVEN (no doubling): CSR by target (rowptr / col = source / ent = stored edge id) and by  *
+ * source (rowptrT / colT = target / entT).  add_self_loops != 0: entries with source == target are skipped and one self loop per   *
+ * node is added whose edge term is the mean over the remaining incoming edges (fill_value 'mean'; 0 without any).  Lane group of   *
+ * `group` (8 / 16 / 32) lanes per node: every channel count <= group, edge_dim <= 16, head dense / out widths <= 32.  The grid is   *
+ * n_slabs workgroups; every launch that produces weight-gradient partials writes its columns of ALL n_slabs rows of `slab`       *
+ * ([n_slabs][slab_len]); one dss2_reduce_slabs(_multi) over the whole slab gives the flat gradient.  Slab columns of a conv at    *
+ * slab_off: att[cout], bias[cout], lin_l.weight[cout][cin], lin_l.bias[cout], lin_r.weight[cout][cin], lin_r.bias[cout],         *
+ * lin_edge.weight[cout][ed] (its parameter order); of the head: W1[dense][c], b1[dense], W2[nout][dense], b2[nout].              */
+typedef struct dss2_gat_graph {
+  const int32_t* rowptr; const int32_t* col; const int32_t* ent;
+  const int32_t* rowptrT; const int32_t* colT; const int32_t* entT;
+  const float* ea; int64_t ldea;           /* edge attributes [E][ed] (leading dimension ldea); NULL when ed == 0 */
+  int64_t n_nodes; int32_t ed; int32_t add_self_loops;
+  float slope;                             /* attention LeakyReLU slope (negative_slope) */
+  int32_t nonlin;                          /* after every conv: 0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh */
+  float* slab; int32_t n_slabs; int32_t slab_len;
+} dss2_gat_graph;
+typedef struct dss2_gat_conv {
+  const float* att; const float* bias; const float* Wl; const float* bl; const float* Wr; const float* br; const float* We;  /* bias, bl, br, We may be NULL */
+  const float* h; int64_t ldh;             /* layer input [N][cin] */
+  float* y; float* m; float* s;            /* forward: output after the nonlinearity [N][cout]; per-target softmax max / sum [N] */
+  float* dxl; float* dxr;                  /* backward: d x_l, d x_r [N][cout] (kept for dss2_gat_wgrad) */
+  float* dedge; float* dself;              /* backward: per-edge [E][cout] / self-loop [N][cout] d x_l contributions */
+  int32_t cin; int32_t cout; int32_t slab_off; int32_t pad_;
+} dss2_gat_conv;
+typedef struct dss2_gat_head {             /* Linear(c, dense) -> Linear(dense, nout) on the last conv's output (or on hin) */
+  const float* W1; const float* b1; const float* W2; const float* b2;
+  const float* hin; int64_t ldhin;         /* head input when the launch has no conv (num_layers = 1) */
+  float* z1; float* out; int64_t ldo;      /* forward: hidden [N][dense], output [N][nout] */
+  const float* gout; int64_t ldgo; float* dz1;   /* backward: output gradient, hidden gradient [N][dense] */
+  int32_t c; int32_t dense; int32_t nout; int32_t pad_;
+} dss2_gat_head;
+typedef struct dss2_gat_args {
+  dss2_gat_graph g;
+  dss2_gat_conv up;                        /* backward: the layer whose SOURCE pass this launch runs (has_up) */
+  dss2_gat_conv lo;                        /* the layer whose TARGET pass this launch runs (has_lo): forward, or backward */
+  dss2_gat_head head;
+  int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
+  const float* gy; int64_t ldgy;           /* backward without head / up: gradient of lo's output */
+  float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */
+} dss2_gat_args;
+/* forward: lo's target pass (online softmax, nonlinearity fused), then the head when has_head */
+int dss2_gat_forward(const dss2_gat_args* args_host, void* stream);
+/* backward: (head backward | up's source pass | gy), then lo's target pass, or the input gradient into dh */
+int dss2_gat_backward(const dss2_gat_args* args_host, void* stream);
+#define DSS2_GAT_MAX_JOBS 16
+typedef struct dss2_gat_wgrad_job {        /* slab[s][col + o * xw + k] = sum_n G[n][o] X[n][k], then [col + gw * xw + o] = sum_n G[n][o] */
+  const float* G; int64_t ldg; const float* X; int64_t ldx; int32_t gw; int32_t xw; int32_t col; int32_t pad_;
+} dss2_gat_wgrad_job;
+typedef struct dss2_gat_wgrad_args {      /* node chunk s of ceil(N / n_slabs) rows -> slab row s */
+  dss2_gat_wgrad_job jobs[DSS2_GAT_MAX_JOBS];
+  float* slab; int64_t n_nodes; int32_t n_slabs; int32_t slab_len; int32_t n_jobs; int32_t pad_;
+} dss2_gat_wgrad_args;
+int dss2_gat_wgrad(const dss2_gat_wgrad_args* args_host, void* stream);
+
 /* LDS bytes a dss2_gemm_prop / dss2_wgrad launch will request (host-side helper; lets the
  * caller reject configurations that do not fit the 160 KiB LDS before launching). */
 size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width);
