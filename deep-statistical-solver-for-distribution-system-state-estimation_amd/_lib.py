@@ -196,6 +196,25 @@ class GatWgradArgs(C.Structure):
                 ("slab_len", C.c_int32), ("n_jobs", C.c_int32), ("pad_", C.c_int32)]
 
 
+class GineGraph(C.Structure):
+    _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("rowptrT", C.c_void_p), ("colT", C.c_void_p),
+                ("entT", C.c_void_p), ("ea", C.c_void_p), ("ldea", C.c_int64), ("n_nodes", C.c_int64), ("ed", C.c_int32),
+                ("nonlin", C.c_int32), ("slab", C.c_void_p), ("n_slabs", C.c_int32), ("slab_len", C.c_int32),
+                ("nslab", C.c_void_p), ("nslab_len", C.c_int32), ("pad_", C.c_int32)]
+
+
+class GineConv(C.Structure):
+    _fields_ = [("eps", C.c_void_p), ("Wn", C.c_void_p), ("bn", C.c_void_p), ("We", C.c_void_p), ("be", C.c_void_p),
+                ("h", C.c_void_p), ("ldh", C.c_int64), ("y", C.c_void_p), ("z", C.c_void_p), ("dz", C.c_void_p),
+                ("cin", C.c_int32), ("cout", C.c_int32), ("slab_off", C.c_int32), ("nn_off", C.c_int32)]
+
+
+class GineArgs(C.Structure):
+    _fields_ = [("g", GineGraph), ("up", GineConv), ("lo", GineConv), ("head", GatHead), ("has_up", C.c_int32),
+                ("has_lo", C.c_int32), ("has_head", C.c_int32), ("group", C.c_int32), ("gy", C.c_void_p), ("ldgy", C.c_int64),
+                ("dh", C.c_void_p), ("dh_cols", C.c_int32), ("pad_", C.c_int32)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "dss2_last_error": (C.c_char_p, []),
@@ -306,6 +325,8 @@ _SIGNATURES = {
     "dss2_gat_forward": (C.c_int, [C.POINTER(GatArgs), C.c_void_p]),
     "dss2_gat_backward": (C.c_int, [C.POINTER(GatArgs), C.c_void_p]),
     "dss2_gat_wgrad": (C.c_int, [C.POINTER(GatWgradArgs), C.c_void_p]),
+    "dss2_gine_forward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
+    "dss2_gine_backward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,0 +1,352 @@
+// GINE (PyG GINEConv with nn = one Linear) and the GINE_DSSE model on gfx950: forward, backward and weight gradients.
+//
+// Lane mapping as in dss2_gat.hip: one lane group of G (8 / 16 / 32) lanes per node, lane c owns channel c; a 256-thread
+// workgroup holds 256 / G nodes at a time and walks the nodes with a grid stride (the grid is the slab count, so every workgroup
+// writes exactly one slab row).  fp32 VALU throughout.  Weights are staged in LDS with padded rows (33 / 17 floats).
+//
+// One layer, j = edge_index[0] the source and i = edge_index[1] the target, edges as given (no doubling, no self loops added):
+//     m_e   = h_j + W_e ea_e + b_e                 (without lin: h_j + ea_e)
+//     z_i   = sum_{e: j->i} relu(m_e) + (1 + eps) h_i
+//     y_i   = phi(W_nn z_i + b_nn)                  eps read from device memory, so replays follow a trained eps
+// Backward, per conv l, with dh the gradient of its output:
+//     dv = dh * phi'(y)     dz = W_nn^T dv           (node-local: the "local step")
+//     dh_in[j] = (1 + eps) dz_j + sum_{e: j->i} [relu open at m_e] dz_i      (the "source pass", CSR by source)
+// The source pass of conv l recomputes m_e with the forward's own function, so every ReLU gate is the forward's bit for bit; it
+// also forms d W_e / d b_e (each edge has one source, so each edge is visited once).  The local step of conv l - 1 (or dx) runs
+// in the same launch.  The local step forms d eps and the shared nn's partial d W_nn = dv z^T, d b_nn = dv; those go to the
+// workgroup's row of a second slab, [n_slabs][n_convs][nn_len], which dss2_reduce_slabs_multi sums as n_slabs * n_convs rows in
+// a fixed order.  No float atomics.
+#include "dss2_common.hpp"
+
+#include <math.h>
+
+using namespace dss2;
+
+namespace {
+
+constexpr int GMAX = 32, EDMAX = 16, DMAX = 32, NT = 256;
+
+struct ConvSm {
+  float Wn[GMAX][GMAX + 1], We[GMAX][EDMAX + 1];
+  float bn[GMAX], be[GMAX];
+};
+struct HeadSm {
+  float W1[DMAX][GMAX + 1], W2[DMAX][DMAX + 1], b1[DMAX], b2[DMAX];
+};
+
+__device__ void stage_conv(ConvSm& s, const dss2_gine_conv& p, int ed) {
+  for (int t = threadIdx.x; t < GMAX * GMAX; t += NT) {
+    const int r = t / GMAX, k = t % GMAX;
+    s.Wn[r][k] = (r < p.cout && k < p.cin) ? p.Wn[r * p.cin + k] : 0.f;
+  }
+  for (int t = threadIdx.x; t < GMAX * EDMAX; t += NT) {
+    const int r = t / EDMAX, k = t % EDMAX;
+    s.We[r][k] = (r < p.cin && k < ed && p.We) ? p.We[r * ed + k] : 0.f;
+  }
+  for (int t = threadIdx.x; t < GMAX; t += NT) {
+    s.bn[t] = t < p.cout ? p.bn[t] : 0.f;
+    s.be[t] = (t < p.cin && p.be) ? p.be[t] : 0.f;
+  }
+}
+
+__device__ void stage_head(HeadSm& s, const dss2_gat_head& p) {
+  for (int t = threadIdx.x; t < DMAX * GMAX; t += NT) {
+    const int d = t / GMAX, c = t % GMAX;
+    s.W1[d][c] = (d < p.dense && c < p.c) ? p.W1[d * p.c + c] : 0.f;
+  }
+  for (int t = threadIdx.x; t < DMAX * DMAX; t += NT) {
+    const int o = t / DMAX, d = t % DMAX;
+    s.W2[o][d] = (o < p.nout && d < p.dense) ? p.W2[o * p.dense + d] : 0.f;
+  }
+  for (int t = threadIdx.x; t < DMAX; t += NT) {
+    s.b1[t] = t < p.dense ? p.b1[t] : 0.f;
+    s.b2[t] = t < p.nout ? p.b2[t] : 0.f;
+  }
+}
+
+// the model's nonlinearity: 0 none (standalone GINEConv), 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh
+__device__ __forceinline__ float act(float v, int mode) {
+  if (mode == 1) return v > 0.f ? v : 0.01f * v;
+  if (mode == 2) return relu_nan(v);
+  if (mode == 3) return tanhf(v);
+  return v;
+}
+// its derivative from the saved OUTPUT, with torch's gates: leaky_relu_backward (input > 0; y > 0 <=> v > 0, NaN takes the
+// slope), threshold_backward on the ReLU's result (y <= 0 closes, NaN passes), tanh_backward (1 - y^2)
+__device__ __forceinline__ float act_grad(float y, int mode) {
+  if (mode == 1) return y > 0.f ? 1.f : 0.01f;
+  if (mode == 2) return relu_open(y) ? 1.f : 0.f;
+  if (mode == 3) return 1.f - y * y;
+  return 1.f;
+}
+
+// the message m_e of lane c before the ReLU.  The forward and the source pass both call this, so the gates agree bit for bit.
+__device__ __forceinline__ float message(const ConvSm& s, const dss2_gine_graph& g, int c, float hj, int64_t e, int cin) {
+  const float* er = g.ea + e * g.ldea;
+  float v;
+  if (g.ed) {
+    v = s.be[c];
+    for (int k = 0; k < g.ed; ++k) v = fmaf(s.We[c][k], er[k], v);
+  } else {
+    v = c < cin ? er[c] : 0.f;
+  }
+  return hj + v;
+}
+
+// lane-group fixed-order sum of red[g * G + ch][k] over the NT / G groups
+template <int G>
+__device__ __forceinline__ float group_sum(const float (*red)[GMAX + 1], int ch, int k) {
+  float v = 0.f;
+  for (int g = 0; g < NT / G; ++g) v += red[g * G + ch][k];
+  return v;
+}
+
+// ---- forward: one GINE layer (nonlinearity fused) and / or the two head Linears -------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(NT) void gine_fwd_kernel(const dss2_gine_args a) {
+  __shared__ ConvSm cs;
+  __shared__ HeadSm hs;
+  if (a.has_lo) stage_conv(cs, a.lo, a.g.ed);
+  if (a.has_head) stage_head(hs, a.head);
+  __syncthreads();
+  const int c = threadIdx.x % G, grp = threadIdx.x / G;
+  const int64_t n = a.g.n_nodes, stride = (int64_t)gridDim.x * (NT / G);
+  const float ope = a.has_lo ? 1.f + a.lo.eps[0] : 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * (NT / G) + grp; i < n; i += stride) {
+    float y = 0.f;
+    if (a.has_lo) {
+      const dss2_gine_conv& p = a.lo;
+      const bool in = c < p.cin;
+      float agg = 0.f;
+      const int r0 = a.g.rowptr[i], r1 = a.g.rowptr[i + 1];
+      for (int q = r0; q < r1; ++q) {
+        const int64_t j = a.g.col[q], e = a.g.ent[q] & 0x7fffffff;
+        const float hj = in ? p.h[j * p.ldh + c] : 0.f;
+        agg += relu_nan(message(cs, a.g, c, hj, e, p.cin));
+      }
+      const float hi = in ? p.h[i * p.ldh + c] : 0.f;
+      const float z = in ? agg + ope * hi : 0.f;
+      if (in) p.z[i * p.cin + c] = z;
+      float v = cs.bn[c];
+#pragma unroll
+      for (int k = 0; k < G; ++k) v = fmaf(cs.Wn[c][k], __shfl(z, k, G), v);
+      y = act(v, a.g.nonlin);
+      if (c < p.cout) p.y[i * p.cout + c] = y;
+    } else if (a.has_head) {
+      y = c < a.head.c ? a.head.hin[i * a.head.ldhin + c] : 0.f;
+    }
+    if (a.has_head) {
+      const dss2_gat_head& hp = a.head;
+      float z1[DMAX / G];
+#pragma unroll
+      for (int u = 0; u < DMAX / G; ++u) z1[u] = hs.b1[u * G + c];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const float yk = __shfl(y, k, G);
+#pragma unroll
+        for (int u = 0; u < DMAX / G; ++u) z1[u] = fmaf(hs.W1[u * G + c][k], yk, z1[u]);
+      }
+      float o[DMAX / G];
+#pragma unroll
+      for (int u = 0; u < DMAX / G; ++u) {
+        o[u] = hs.b2[u * G + c];
+        if (u * G + c < hp.dense) hp.z1[i * hp.dense + u * G + c] = z1[u];
+      }
+#pragma unroll
+      for (int v = 0; v < DMAX / G; ++v)
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+          const float zd = __shfl(z1[v], k, G);
+#pragma unroll
+          for (int u = 0; u < DMAX / G; ++u) o[u] = fmaf(hs.W2[u * G + c][v * G + k], zd, o[u]);
+        }
+#pragma unroll
+      for (int u = 0; u < DMAX / G; ++u)
+        if (u * G + c < hp.nout) hp.out[i * hp.ldo + u * G + c] = o[u];
+    }
+  }
+}
+
+// ---- backward: [head backward | source pass of conv `up` | gy], then [local step of conv `lo`] or the input gradient ---------------
+template <int G>
+__global__ __launch_bounds__(NT) void gine_bwd_kernel(const dss2_gine_args a) {
+  __shared__ ConvSm us, ls;
+  __shared__ HeadSm hs;
+  __shared__ float red[NT][GMAX + 1];
+  if (a.has_up) stage_conv(us, a.up, a.g.ed);
+  if (a.has_lo) stage_conv(ls, a.lo, a.g.ed);
+  if (a.has_head) stage_head(hs, a.head);
+  __syncthreads();
+  const int c = threadIdx.x % G, grp = threadIdx.x / G;
+  const int64_t n = a.g.n_nodes, stride = (int64_t)gridDim.x * (NT / G);
+  const int ed = a.g.ed, nl = a.g.nonlin;
+  const float ope_up = a.has_up ? 1.f + a.up.eps[0] : 0.f;
+  float g_we[EDMAX], g_be = 0.f;     // up: d W_e row c, d b_e[c]
+  float g_wn[G], g_bn = 0.f, g_eps = 0.f;   // lo: d W_nn row c, d b_nn[c], lane c's share of d eps
+#pragma unroll
+  for (int k = 0; k < EDMAX; ++k) g_we[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < G; ++k) g_wn[k] = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * (NT / G) + grp; i < n; i += stride) {
+    float gy = 0.f;   // gradient of lo's output (or of the model input) at channel c
+    if (a.has_head) {
+      const dss2_gat_head& hp = a.head;
+      float dz[DMAX / G];
+#pragma unroll
+      for (int u = 0; u < DMAX / G; ++u) dz[u] = 0.f;
+      for (int o = 0; o < hp.nout; ++o) {
+        const float go = hp.gout[i * hp.ldgo + o];
+#pragma unroll
+        for (int u = 0; u < DMAX / G; ++u) dz[u] = fmaf(hs.W2[o][u * G + c], go, dz[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < DMAX / G; ++u) {
+        if (u * G + c < hp.dense) hp.dz1[i * hp.dense + u * G + c] = dz[u];
+#pragma unroll
+        for (int k = 0; k < G; ++k) gy = fmaf(hs.W1[u * G + k][c], __shfl(dz[u], k, G), gy);
+      }
+    } else if (a.has_up) {
+      const dss2_gine_conv& p = a.up;
+      const bool in = c < p.cin;
+      const float hj = in ? p.h[i * p.ldh + c] : 0.f;
+      const float dzj = in ? p.dz[i * p.cin + c] : 0.f;
+      float acc = 0.f;
+      const int r0 = a.g.rowptrT[i], r1 = a.g.rowptrT[i + 1];
+      for (int q = r0; q < r1; ++q) {
+        const int64_t t = a.g.colT[q], e = a.g.entT[q] & 0x7fffffff;
+        const float m = message(us, a.g, c, hj, e, p.cin);
+        const float d = (in && relu_open(m)) ? p.dz[t * p.cin + c] : 0.f;
+        acc += d;
+        if (ed) {
+          const float* er = a.g.ea + e * a.g.ldea;
+          g_be += d;
+#pragma unroll
+          for (int k = 0; k < EDMAX; ++k)
+            if (k < ed) g_we[k] = fmaf(d, er[k], g_we[k]);
+        }
+      }
+      gy = fmaf(ope_up, dzj, acc);
+    } else {
+      gy = c < a.lo.cout ? a.gy[i * a.ldgy + c] : 0.f;
+    }
+    if (!a.has_lo) {
+      if (a.dh && c < a.dh_cols) a.dh[i * a.dh_cols + c] = gy;
+      continue;
+    }
+    // local step of conv lo for node i
+    const dss2_gine_conv& p = a.lo;
+    const float dv = c < p.cout ? gy * act_grad(p.y[i * p.cout + c], nl) : 0.f;
+    const float zc = c < p.cin ? p.z[i * p.cin + c] : 0.f;
+    float dz = 0.f;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      dz = fmaf(ls.Wn[k][c], __shfl(dv, k, G), dz);
+      g_wn[k] = fmaf(dv, __shfl(zc, k, G), g_wn[k]);
+    }
+    g_bn += dv;
+    if (c < p.cin) {
+      p.dz[i * p.cin + c] = dz;
+      g_eps = fmaf(dz, p.h[i * p.ldh + c], g_eps);
+    }
+  }
+  // this workgroup's partials -> its slab rows (fixed order over the lane groups)
+  float* row = a.g.slab + (int64_t)blockIdx.x * a.g.slab_len;
+  if (a.has_up && ed) {
+    const dss2_gine_conv& p = a.up;
+#pragma unroll
+    for (int k = 0; k < EDMAX; ++k) red[threadIdx.x][k] = g_we[k];
+    red[threadIdx.x][EDMAX] = g_be;
+    __syncthreads();
+    // columns at slab_off: eps[1], lin.weight[cin][ed], lin.bias[cin]; this launch owns the lin part
+    for (int t = threadIdx.x; t < p.cin * (ed + 1); t += NT) {
+      const int ch = t < p.cin * ed ? t / ed : t - p.cin * ed, k = t < p.cin * ed ? t % ed : EDMAX;
+      row[p.slab_off + 1 + t] = group_sum<G>(red, ch, k);
+    }
+    __syncthreads();
+  }
+  if (a.has_lo) {
+    const dss2_gine_conv& p = a.lo;
+#pragma unroll
+    for (int k = 0; k < G; ++k) red[threadIdx.x][k] = g_wn[k];
+    red[threadIdx.x][G] = g_bn;
+    __syncthreads();
+    float* nrow = a.g.nslab + (int64_t)blockIdx.x * a.g.nslab_len + p.nn_off;
+    for (int t = threadIdx.x; t < p.cout * (p.cin + 1); t += NT) {
+      const int ch = t < p.cout * p.cin ? t / p.cin : t - p.cout * p.cin, k = t < p.cout * p.cin ? t % p.cin : G;
+      nrow[t] = group_sum<G>(red, ch, k);
+    }
+    __syncthreads();
+    red[threadIdx.x][0] = g_eps;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float v = 0.f;
+      for (int g = 0; g < NT / G; ++g)
+        for (int ch = 0; ch < G; ++ch) v += red[g * G + ch][0];
+      row[p.slab_off] = v;
+    }
+  }
+}
+
+int check_conv(const dss2_gine_conv& p, const dss2_gine_args& a, const char* what) {
+  if (p.cin < 1 || p.cout < 1 || p.cin > a.group || p.cout > a.group) {
+    set_error("%s: channels %d -> %d exceed the lane group %d (limit %d)", what, p.cin, p.cout, a.group, GMAX); return 2;
+  }
+  if (!p.eps || !p.Wn || !p.bn || !p.h || (a.g.ed && (!p.We || !p.be))) { set_error("%s: a conv pointer is missing", what); return 2; }
+  return 0;
+}
+
+int check_args(const dss2_gine_args& a, const char* what) {
+  if (a.g.n_nodes <= 0 || a.g.n_slabs <= 0) { set_error("%s: empty batch / no slabs", what); return 2; }
+  if (a.g.ed < 0 || a.g.ed > EDMAX) { set_error("%s: edge_dim %d outside [0, %d]", what, a.g.ed, EDMAX); return 2; }
+  if (a.group != 8 && a.group != 16 && a.group != 32) { set_error("%s: lane group %d (8, 16 or 32)", what, a.group); return 2; }
+  if (a.has_up)
+    if (int rc = check_conv(a.up, a, what)) return rc;
+  if (a.has_lo)
+    if (int rc = check_conv(a.lo, a, what)) return rc;
+  if (a.has_head && (a.head.c < 1 || a.head.c > a.group || a.head.dense < 1 || a.head.dense > DMAX || a.head.nout < 1 || a.head.nout > DMAX)) {
+    set_error("%s: head %d -> %d -> %d outside the limits (C <= lane group, dense, out <= %d)", what, a.head.c, a.head.dense, a.head.nout, DMAX);
+    return 2;
+  }
+  if (a.has_head && a.has_up) { set_error("%s: head and source pass in one launch", what); return 2; }
+  return 0;
+}
+
+}  // namespace
+
+static int dss2_gine_forward_launch(const dss2_gine_args* ap, void* stream) {
+  const dss2_gine_args& a = *ap;
+  if (int rc = check_args(a, "dss2_gine_forward")) return rc;
+  if (!a.has_lo && !a.has_head) { set_error("dss2_gine_forward: nothing to do"); return 2; }
+  if (a.has_up) { set_error("dss2_gine_forward: no source pass in the forward"); return 2; }
+  const dim3 grid((unsigned)a.g.n_slabs);
+  hipStream_t s = as_stream(stream);
+  if (a.group == 8) hipLaunchKernelGGL(gine_fwd_kernel<8>, grid, dim3(NT), 0, s, a);
+  else if (a.group == 16) hipLaunchKernelGGL(gine_fwd_kernel<16>, grid, dim3(NT), 0, s, a);
+  else hipLaunchKernelGGL(gine_fwd_kernel<32>, grid, dim3(NT), 0, s, a);
+  return check_launch("dss2_gine_forward");
+}
+
+static int dss2_gine_backward_launch(const dss2_gine_args* ap, void* stream) {
+  const dss2_gine_args& a = *ap;
+  if (int rc = check_args(a, "dss2_gine_backward")) return rc;
+  if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gine_backward: no output gradient"); return 2; }
+  if (!a.g.slab || (a.has_lo && !a.g.nslab)) { set_error("dss2_gine_backward: no slab"); return 2; }
+  const dim3 grid((unsigned)a.g.n_slabs);
+  hipStream_t s = as_stream(stream);
+  if (a.group == 8) hipLaunchKernelGGL(gine_bwd_kernel<8>, grid, dim3(NT), 0, s, a);
+  else if (a.group == 16) hipLaunchKernelGGL(gine_bwd_kernel<16>, grid, dim3(NT), 0, s, a);
+  else hipLaunchKernelGGL(gine_bwd_kernel<32>, grid, dim3(NT), 0, s, a);
+  return check_launch("dss2_gine_backward");
+}
+
+extern "C" int dss2_gine_forward(const dss2_gine_args* ap, void* stream) {
+  if (!ap) { set_error("dss2_gine_forward: null argument"); return 2; }
+  DSS2_RECORD([a = *ap](void* s_) { return dss2_gine_forward_launch(&a, s_); });
+  return dss2_gine_forward_launch(ap, stream);
+}
+
+extern "C" int dss2_gine_backward(const dss2_gine_args* ap, void* stream) {
+  if (!ap) { set_error("dss2_gine_backward: null argument"); return 2; }
+  DSS2_RECORD([a = *ap](void* s_) { return dss2_gine_backward_launch(&a, s_); });
+  return dss2_gine_backward_launch(ap, stream);
+}

@@ -1,0 +1,407 @@
+"""GINE and the reference's GIN model, ``GINE_DSSE`` (/root/reference/networks.py:71-111), on the HIP kernels of
+csrc/dss2_gine.hip.
+
+    GINEConv(nn, eps=0., train_eps=False, edge_dim=None)          PyG's layer, same parameter names; nn must be a torch.nn.Linear
+    GINE_DSSE(dim_feat, dim_dense, dim_out, num_layers, edge_dim, nn='mlp', nonlin='leaky_relu', eps=0., train_eps=False,
+              model='gine')                                        the reference's signature and attributes
+
+One layer (j = edge_index[0] the source, i = edge_index[1] the target, edges as given: no doubling, no self loops added or
+removed, duplicates kept):  out_i = nn(sum_{e: j->i} relu(h_j + lin(ea_e)) + (1 + eps) h_i).  Without edge_dim the message is
+relu(h_j + ea_e) and edge_attr must be [E, nn.in_features] (PyG's rule).
+
+``GINE_DSSE`` builds ONE ``Linear(dim_feat, dim_feat)`` (``self.nn``) and hands the same object to every conv, as the reference
+does: ``state_dict()`` lists it once per owner (``nn.*`` and ``model.module_{2k}.nn.*``), ``parameters()`` once, and its gradient is
+the sum over the layers.  ``model`` is a look-alike of PyG's ``Sequential`` with children ``module_{i}`` (as in gat.py).  Its
+forward is ONE autograd node (``_GINEFn``): one launch per conv forward (the head Linears fused into the last one), one fused
+backward launch per conv (source pass of conv l + node-local step of conv l - 1), one launch for the head's weight gradients and
+one fixed-order slab reduction.  Every launch goes through the library, so the step records into launch plans and hipGraphs.
+
+One intended deviation: the reference's constructor argument ``nn='mlp'`` shadows ``torch.nn``, so its ``nonlin='relu'`` and
+``nonlin='tanh'`` raise (``'mlp'.ReLU()``); here they build ``torch.nn.ReLU`` / ``torch.nn.Tanh`` as the argument names say.  The
+default ``leaky_relu`` is the reference's model exactly.
+
+Not provided (ValueError): an ``nn`` other than one Linear, bipartite (tuple) inputs, a missing edge_attr, widths over the limits.
+No gradient with respect to edge_attr; no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .gat import _NONLIN, _head, _MAX_SLABS
+from .ops import _require_gpu, _rows
+from .topology import get_topology
+
+_F32 = torch.float32
+MAX_CHANNELS = 32        # nn's input / output width and the head's input width (lane group of 8 / 16 / 32 lanes)
+MAX_EDGE_DIM = 16
+MAX_DENSE = 32           # head widths dim_dense and dim_out
+
+
+def _check_width(name: str, v: int, limit: int) -> None:
+    if not isinstance(v, int) or v < 1 or v > limit:
+        raise ValueError(f"{name} = {v}: the GINE kernels take 1 <= {name} <= {limit}")
+
+
+class GINEConv(nn.Module):
+    """PyG ``GINEConv`` with ``nn`` one ``torch.nn.Linear`` on the HIP kernels.  ``state_dict`` keys in PyG's order: ``eps [1]``
+    (a buffer, or a Parameter with train_eps), ``nn.{weight, bias}``, ``lin.{weight [in, edge_dim], bias [in]}`` (with edge_dim)."""
+
+    def __init__(self, nn: torch.nn.Module, eps: float = 0.0, train_eps: bool = False, edge_dim: Optional[int] = None, **kwargs):
+        super().__init__()
+        if type(nn) is not torch.nn.Linear:
+            raise ValueError(f"GINEConv: nn must be one torch.nn.Linear (got {type(nn).__name__}); other modules are not supported")
+        _check_width("nn.in_features", nn.in_features, MAX_CHANNELS)
+        _check_width("nn.out_features", nn.out_features, MAX_CHANNELS)
+        if nn.bias is None:
+            raise ValueError("GINEConv: nn must have a bias")
+        if edge_dim is not None:
+            _check_width("edge_dim", edge_dim, MAX_EDGE_DIM)
+        self.nn = nn
+        self.initial_eps = eps
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("eps", torch.empty(1))
+        self.edge_dim = edge_dim
+        self.lin = torch.nn.Linear(edge_dim, nn.in_features) if edge_dim is not None else None
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        """PyG: reset(nn), eps = initial_eps, lin.reset_parameters() (PyG's Linear initialises as torch's)."""
+        self.nn.reset_parameters()
+        with torch.no_grad():
+            self.eps.fill_(self.initial_eps)
+        if self.lin is not None:
+            self.lin.reset_parameters()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None):
+        if isinstance(x, (tuple, list)):
+            raise ValueError("GINEConv: bipartite (tuple) inputs are not supported")
+        if size is not None:
+            raise ValueError("GINEConv: size (bipartite graphs) is not supported")
+        if edge_attr is None:
+            raise ValueError("GINEConv: forward needs edge_attr")
+        return run_gine([self], None, "none", x, edge_index, edge_attr)
+
+
+class GINESequential(nn.Module):
+    """Stand-in for PyG's ``Sequential('x, edge_index, edge_attr', [...])`` as GINE_DSSE builds it: children ``module_{i}`` in
+    the list's order.  ``forward`` runs the fused route."""
+
+    def __init__(self, modules: Sequence[nn.Module], convs: Sequence[GINEConv], head: Sequence[nn.Linear], nonlin: str):
+        super().__init__()
+        for i, m in enumerate(modules):
+            self.add_module(f"module_{i}", m)
+        self.__dict__["_convs"], self.__dict__["_head"], self.__dict__["_nonlin"] = list(convs), list(head), nonlin
+
+    def forward(self, x, edge_index, edge_attr):
+        return run_gine(self._convs, self._head, self._nonlin, x, edge_index, edge_attr)
+
+
+class GINE_DSSE(nn.Module):
+    """/root/reference/networks.py:71-111: ``num_layers - 1`` GINEConv layers sharing ONE Linear(dim_feat, dim_feat), each
+    followed by the (shared) nonlinearity, then Linear(dim_feat, dim_dense) and Linear(dim_dense, dim_out)."""
+
+    def __init__(self, dim_feat, dim_dense, dim_out, num_layers, edge_dim, nn="mlp", nonlin="leaky_relu", eps=0., train_eps=False,
+                 model="gine"):
+        super().__init__()
+        self.dim_out = dim_out
+        self.num_layers = num_layers
+        self.dim_feat = dim_feat
+        self.dim_dense = dim_dense
+        self.eps = eps
+        self.train_eps = train_eps
+        self.edge_dim = edge_dim
+        self.dim_hidden = dim_feat
+        _check_width("dim_feat", dim_feat, MAX_CHANNELS)
+        _check_width("dim_dense", dim_dense, MAX_DENSE)
+        _check_width("dim_out", dim_out, MAX_DENSE)
+        if edge_dim is not None:
+            _check_width("edge_dim", edge_dim, MAX_EDGE_DIM)
+        if num_layers < 1:
+            raise ValueError(f"num_layers = {num_layers}: at least 1 (the two Linears)")
+        if nn == "mlp":
+            self.nn = torch.nn.Linear(in_features=self.dim_feat, out_features=self.dim_hidden)
+        else:
+            raise ValueError("invalid nn type")
+        # (the reference calls nn.ReLU() / nn.Tanh() on the string argument here; see the module docstring)
+        if nonlin == "relu":
+            self.nonlin = torch.nn.ReLU()
+        elif nonlin == "tanh":
+            self.nonlin = torch.nn.Tanh()
+        elif nonlin == "leaky_relu":
+            self.nonlin = torch.nn.LeakyReLU()
+        else:
+            raise ValueError("invalid activation type")
+        if model != "gine":
+            raise ValueError("invalid model type")
+        layers, convs = [], []
+        for _ in range(num_layers - 1):
+            conv = GINEConv(nn=self.nn, eps=self.eps, train_eps=self.train_eps, edge_dim=self.edge_dim)
+            convs.append(conv)
+            layers += [conv, self.nonlin]
+        head = [torch.nn.Linear(self.dim_hidden, self.dim_dense), torch.nn.Linear(self.dim_dense, self.dim_out)]
+        self.model = GINESequential(layers + head, convs, head, nonlin)
+
+    def forward(self, x, edge_index, edge_attr):
+        return self.model(x, edge_index, edge_attr)
+
+
+# ------------------------------------------------------------------------------------------
+# the fused route
+# ------------------------------------------------------------------------------------------
+def _up4(v: int) -> int:
+    return (v + 3) // 4 * 4
+
+
+class _Spec:
+    """Dimensions, slab layout and launch geometry of one conv stack (+ head)."""
+
+    def __init__(self, convs, head, nonlin, n_nodes):
+        self.convs, self.head = convs, head
+        self.nonlin = _NONLIN[nonlin]
+        self.nn = convs[0].nn if convs else None
+        self.ed = (convs[0].edge_dim or 0) if convs else 0
+        for cv in convs:
+            if cv.nn is not self.nn:
+                raise ValueError("GINE stack: every conv must share the one nn Linear")
+            if (cv.edge_dim or 0) != self.ed:
+                raise ValueError("GINE stack: every conv must have the same edge_dim")
+        self.cin = self.nn.in_features if convs else 0
+        self.cout = self.nn.out_features if convs else 0
+        if len(convs) > 1 and self.cin != self.cout:
+            raise ValueError("GINE stack: a shared nn between layers needs in_features == out_features")
+        widths = [self.cin, self.cout] if convs else []
+        if head:
+            widths.append(head[0].in_features)
+            if head[0].out_features > MAX_DENSE or head[1].out_features > MAX_DENSE or head[1].in_features != head[0].out_features:
+                raise ValueError(f"GINE head: widths up to {MAX_DENSE}")
+            if convs and head[0].in_features != self.cout:
+                raise ValueError("GINE head: its input width must be the convs' output width")
+        if max(widths) > MAX_CHANNELS:
+            raise ValueError(f"GINE: channel width {max(widths)} above the limit {MAX_CHANNELS}")
+        self.group = 8 if max(widths) <= 8 else (16 if max(widths) <= 16 else 32)
+        # main slab row: per conv eps[1] (+ lin.weight [cin][ed], lin.bias [cin]), then the head; the shared nn's per-conv partials
+        # go to a second slab [n_slabs][n_convs][nn_len]
+        self.offs, off = [], 0
+        for _ in convs:
+            self.offs.append(off)
+            off += 1 + (self.cin * self.ed + self.cin if self.ed else 0)
+        self.head_off = off
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            off += d * c + d + o * d + o
+        self.total = off
+        self.nn_len = self.cout * self.cin + self.cout
+        self.n_slabs = max(1, min(_MAX_SLABS, -(-n_nodes // (256 // self.group))))
+
+
+class _NoEdges:
+    """The CSR of an edge-less batch (Topology refuses E = 0; every GINE layer is then nn((1 + eps) h))."""
+
+    def __init__(self, n, dev):
+        self.N, self.E = n, 0
+        self.rowptr = self.rowptrT = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        self.col = self.ent = self.colT = self.entT = self.rowptr
+
+
+def _slots(convs, head) -> List[Optional[torch.Tensor]]:
+    """[nn.weight, nn.bias] (when there is a conv), per conv [eps, lin.weight, lin.bias], the head's four."""
+    ps = []
+    if convs:
+        ps += [convs[0].nn.weight, convs[0].nn.bias]
+    for cv in convs:
+        ps += [cv.eps, None if cv.lin is None else cv.lin.weight, None if cv.lin is None else cv.lin.bias]
+    if head:
+        ps += [head[0].weight, head[0].bias, head[1].weight, head[1].bias]
+    return ps
+
+
+def run_gine(convs, head, nonlin, x, edge_index, edge_attr):
+    _require_gpu(x, edge_index, edge_attr, *[cv.eps for cv in convs])
+    if convs:
+        from .networks import _no_edge_attr_grad
+        if edge_attr is None:
+            raise ValueError("GINE: forward needs edge_attr")
+        _no_edge_attr_grad(edge_attr)
+    if x.dim() != 2:
+        raise ValueError("x must be [N, C]")
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError("edge_index must be [2, E]")
+    if edge_index.size(1) == 0:
+        topo = _NoEdges(x.size(0), x.device)
+    else:
+        topo = get_topology(edge_index, x.size(0), double=False)
+        topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
+    spec = _Spec(convs, head, nonlin, x.size(0))
+    need = spec.cin if convs else head[0].in_features
+    if x.size(1) != need:
+        raise ValueError(f"x has {x.size(1)} columns, the model takes {need}")
+    if convs:
+        w = spec.ed if spec.ed else spec.cin
+        if edge_attr.dim() != 2 or edge_attr.size(1) != w or edge_attr.size(0) != edge_index.size(1):
+            raise ValueError(f"edge_attr must be [E, {w}]" + ("" if spec.ed else " (without edge_dim: [E, nn.in_features])"))
+    else:
+        edge_attr = None
+    return _GINEFn.apply(x, edge_attr, topo, spec, *_slots(convs, head))
+
+
+def _graph(topo, spec, ea, ldea, slab=None, nslab=None):
+    g = _lib.GineGraph()
+    g.rowptr, g.col, g.ent = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
+    g.rowptrT, g.colT, g.entT = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr()
+    g.ea, g.ldea = (ea.data_ptr() if ea is not None else None), ldea
+    g.n_nodes, g.ed, g.nonlin = topo.N, spec.ed, spec.nonlin
+    g.slab, g.n_slabs, g.slab_len = (slab.data_ptr() if slab is not None else None), spec.n_slabs, spec.total
+    g.nslab, g.nslab_len = (nslab.data_ptr() if nslab is not None else None), spec.nn_len * len(spec.convs)
+    return g
+
+
+def _conv(d, spec, ps, l, h, ldh, st, dz=None):
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d.Wn, d.bn = p(ps[0]), p(ps[1])
+    d.eps, d.We, d.be = (p(t) for t in ps[2 + 3 * l:5 + 3 * l])
+    d.h, d.ldh = h.data_ptr(), ldh
+    d.y, d.z = st["y"].data_ptr(), st["z"].data_ptr()
+    d.dz = p(dz)
+    d.cin, d.cout, d.slab_off, d.nn_off = spec.cin, spec.cout, spec.offs[l], l * spec.nn_len
+
+
+class _GINEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ea, topo, spec, *ps):
+        L = _lib.lib()
+        N, dev = topo.N, x.device
+        x, ldx = _rows(x)
+        ldea = 0
+        if ea is not None:
+            ea, ldea = _rows(ea)
+        sm = _lib.stream_ptr(dev)
+        convs, head = spec.convs, spec.head
+        n = len(convs)
+        hps = ps[2 + 3 * n:] if n else ps
+        states, hs = [], []
+        h, ldh = x, ldx
+        for _ in range(n):
+            st = {"y": torch.empty(N, spec.cout, dtype=_F32, device=dev), "z": torch.empty(N, spec.cin, dtype=_F32, device=dev)}
+            states.append(st)
+            hs.append((h, ldh))
+            h, ldh = st["y"], spec.cout
+        hst, out = {}, None
+        if head:
+            hst["z1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
+            out = torch.empty(N, head[1].out_features, dtype=_F32, device=dev)
+        g = _graph(topo, spec, ea, ldea)
+        for l in range(n):
+            a = _lib.GineArgs()
+            a.g, a.group, a.has_lo = g, spec.group, 1
+            _conv(a.lo, spec, ps, l, hs[l][0], hs[l][1], states[l])
+            if head and l == n - 1:
+                a.has_head = 1
+                _head(a.head, head, hps, hst)
+                a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
+            _lib.check(L.dss2_gine_forward(C.byref(a), sm), "dss2_gine_forward")
+        if n == 0:
+            a = _lib.GineArgs()
+            a.g, a.group, a.has_head = g, spec.group, 1
+            _head(a.head, head, hps, hst)
+            a.head.hin, a.head.ldhin = x.data_ptr(), ldx
+            a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
+            _lib.check(L.dss2_gine_forward(C.byref(a), sm), "dss2_gine_forward")
+        if out is None:
+            out = states[-1]["y"]
+        # internal buffers live on ctx (never handed out, except the last conv's y of a head-less stack, whose backward does
+        # not read it: the standalone layer has no nonlinearity)
+        ctx.save_for_backward(x, ea)
+        ctx.st = (topo, spec, ldx, ldea, states, hs, hst, ps)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, ea = ctx.saved_tensors
+        topo, spec, ldx, ldea, states, hs, hst, ps = ctx.st
+        L = _lib.lib()
+        N, dev = topo.N, gout.device
+        sm = _lib.stream_ptr(dev)
+        gout, ldgo = _rows(gout)
+        convs, head = spec.convs, spec.head
+        n = len(convs)
+        hps = ps[2 + 3 * n:] if n else ps
+        need_dx = ctx.needs_input_grad[0]
+        main = _up4(spec.n_slabs * spec.total)
+        buf = torch.empty(main + spec.n_slabs * n * spec.nn_len, dtype=_F32, device=dev)
+        slab, nslab = buf[:main], buf[main:]
+        flat = torch.empty(_up4(spec.total) + spec.nn_len, dtype=_F32, device=dev)
+        fnn = flat[_up4(spec.total):]
+        dzs = [torch.empty(N, spec.cin, dtype=_F32, device=dev) for _ in range(min(n, 2))]
+        cin0 = spec.cin if n else head[0].in_features
+        dx = torch.empty(N, cin0, dtype=_F32, device=dev) if need_dx else None
+        if head:
+            hst["dz1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
+        g = _graph(topo, spec, ea, ldea, slab, nslab)
+
+        def conv_into(d, l):
+            _conv(d, spec, ps, l, hs[l][0], hs[l][1], states[l], dzs[l % 2])
+
+        # launch 1: head backward (or the output gradient) + the node-local step of the last conv
+        a = _lib.GineArgs()
+        a.g, a.group = g, spec.group
+        if head:
+            a.has_head = 1
+            _head(a.head, head, hps, hst)
+            a.head.gout, a.head.ldgo, a.head.dz1 = gout.data_ptr(), ldgo, hst["dz1"].data_ptr()
+        else:
+            a.gy, a.ldgy = gout.data_ptr(), ldgo
+        if n:
+            a.has_lo = 1
+            conv_into(a.lo, n - 1)
+        else:
+            a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
+        _lib.check(L.dss2_gine_backward(C.byref(a), sm), "dss2_gine_backward")
+        # source pass of conv l fused with the node-local step of conv l - 1; the last one writes dx
+        for l in range(n - 1, -1, -1):
+            a = _lib.GineArgs()
+            a.g, a.group, a.has_up = g, spec.group, 1
+            conv_into(a.up, l)
+            if l > 0:
+                a.has_lo = 1
+                conv_into(a.lo, l - 1)
+            else:
+                a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
+            _lib.check(L.dss2_gine_backward(C.byref(a), sm), "dss2_gine_backward")
+        # the head's outer-product weight gradients, then ONE fixed-order reduction of both slabs
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            hin, ldhin = (states[-1]["y"], c) if n else (x, ldx)
+            w = _lib.GatWgradArgs()
+            jobs = [(hst["dz1"], d, hin, ldhin, d, c, spec.head_off), (gout, ldgo, hst["z1"], d, o, d, spec.head_off + d * c + d)]
+            for jd, (Gm, ldg, Xm, ldxm, gw, xw, col) in zip(w.jobs, jobs):
+                jd.G, jd.ldg, jd.X, jd.ldx, jd.gw, jd.xw, jd.col = Gm.data_ptr(), ldg, Xm.data_ptr(), ldxm, gw, xw, col
+            w.slab, w.n_nodes, w.n_slabs, w.slab_len, w.n_jobs = slab.data_ptr(), N, spec.n_slabs, spec.total, len(jobs)
+            _lib.check(L.dss2_gat_wgrad(C.byref(w), sm), "dss2_gat_wgrad")
+        rd = (_lib.ReduceDesc * 2)()
+        rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
+        if n:
+            rd[1].slab, rd[1].out, rd[1].stride, rd[1].len = nslab.data_ptr(), fnn.data_ptr(), spec.nn_len, spec.nn_len
+            rd[1].n_slabs = spec.n_slabs * n
+        _lib.check(L.dss2_reduce_slabs_multi(rd, 2 if n else 1, sm), "dss2_reduce_slabs_multi")
+        grads = []
+        if n:
+            ci, co = spec.cin, spec.cout
+            grads += [fnn[:co * ci].view(co, ci), fnn[co * ci:co * ci + co]]
+            for l in range(n):
+                off, ed = spec.offs[l], spec.ed
+                grads.append(flat[off:off + 1])
+                grads += [flat[off + 1:off + 1 + ci * ed].view(ci, ed), flat[off + 1 + ci * ed:off + 1 + ci * ed + ci]] if ed else [None, None]
+        if head:
+            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
+            hoff = spec.head_off
+            grads += [flat[hoff:hoff + d * c].view(d, c), flat[hoff + d * c:hoff + d * c + d],
+                      flat[hoff + d * c + d:hoff + d * c + d + o * d].view(o, d), flat[hoff + d * c + d + o * d:spec.total]]
+        grads = [gr if ctx.needs_input_grad[4 + k] else None for k, gr in enumerate(grads)]
+        return (dx, None, None, None, *grads)

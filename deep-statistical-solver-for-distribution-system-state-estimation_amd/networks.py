@@ -1007,3 +1007,5 @@ class SkipPFN(PFN):
 
 # the reference driver's default model (networks.py:113-156), defined in gat.py on its own kernels
 from .gat import GATv2Conv, GAT_DSSE  # noqa: E402,F401
+# the reference's GIN model (networks.py:71-111), defined in gine.py on its own kernels
+from .gine import GINEConv, GINE_DSSE  # noqa: E402,F401

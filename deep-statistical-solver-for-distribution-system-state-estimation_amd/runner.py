@@ -4,7 +4,7 @@ Reproduces the training loop (dss2_run.py:131-147) and the per-epoch evaluation
 (dss2_run.py:165-224) with the reference's knobs as arguments and its defaults:
 feature slicing ``x[:, :8] / edge_attr[:, :6] / x[:, 8:] / edge_attr[:, 6:]`` (:138,140),
 ``reg_coefs`` (:104-112), Adamax lr 3e-3 (:91-92), batch_size 64, the hyper-parameter dict (:72-82).
-The model: the driver's default ``GAT_DSSE`` (:85-86, ``--model GAT_DSSE``) or the MPN / SkipMPN / PFN / SkipPFN line (:88).
+The model: the driver's default ``GAT_DSSE`` (:85-86, ``--model GAT_DSSE``), the GIN model ``GINE_DSSE`` (same line, ``--model GINE_DSSE``) or the MPN / SkipMPN / PFN / SkipPFN line (:88).
 Data: either a folder in the reference's layout (``--data-folder``: ``dataset.data_from_pickles`` ->
 shuffle -> 0.9 split -> ``dataset.DataLoader``, dss2_run.py:56-69, measurement model / z-score / collation
 on the device) or synthetic batches from ``synthetic.make_batch`` (same layout), collated once and kept
@@ -34,6 +34,9 @@ def build_model(name: str, hp: Dict) -> torch.nn.Module:
     if name == "GAT_DSSE":     # dss2_run.py:86
         return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], heads=hp["heads"],
                    num_layers=hp["gnn_layers"], edge_dim=hp["dim_lines"])
+    if name == "GINE_DSSE":    # dss2_run.py:86 with the GIN model (no heads argument)
+        return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], num_layers=hp["gnn_layers"],
+                   edge_dim=hp["dim_lines"])
     a = (hp["dim_nodes"], hp["dim_lines"], hp["dim_out"], hp["dim_hid"], hp["gnn_layers"], hp["K"], hp["dropout_rate"])
     return cls(*a, hp["L"]) if name in ("PFN", "SkipPFN") else cls(*a)
 
@@ -278,7 +281,7 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", default="cigre14", choices=["cigre14", "cigre14_reswitched", "ober_sub", "ober179"])
-    ap.add_argument("--model", default="SkipPFN", choices=["MPN", "SkipMPN", "PFN", "SkipPFN", "GAT_DSSE"])
+    ap.add_argument("--model", default="SkipPFN", choices=["MPN", "SkipMPN", "PFN", "SkipPFN", "GAT_DSSE", "GINE_DSSE"])
     ap.add_argument("--graphs", type=int, default=720)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=600)

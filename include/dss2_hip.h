@@ -793,6 +793,44 @@ typedef struct dss2_gat_wgrad_args {      /* node chunk s of ceil(N / n_slabs) r
 } dss2_gat_wgrad_args;
 int dss2_gat_wgrad(const dss2_gat_wgrad_args* args_host, void* stream);
 
+/* ---- GINE (PyG GINEConv, nn = one Linear) and the GINE_DSSE model (reference networks.py:71-111), csrc/dss2_gine.hip -------- *
+ * Graph: the Topology of the edge list AS GIVEN (no doubling, no self loops added or removed), CSR by target and by source as for  *
+ * GAT.  Lane group of `group` (8 / 16 / 32) lanes per node: cin, cout <= group, ed <= 16, head widths <= 32.  The grid is n_slabs *
+ * workgroups.  Slab columns of a conv at slab_off: eps[1], lin.weight[cin][ed], lin.bias[cin] (ed > 0 only); of the head at its    *
+ * offset: W1[dense][c], b1[dense], W2[nout][dense], b2[nout].  The nn Linear's partials go to nslab ([n_slabs][nslab_len], conv k   *
+ * at nn_off: weight[cout][cin], bias[cout]); with nn_off = k * nn_len the n_slabs * n_convs rows of nn_len reduce to its gradient.  */
+typedef struct dss2_gine_graph {
+  const int32_t* rowptr; const int32_t* col; const int32_t* ent;
+  const int32_t* rowptrT; const int32_t* colT; const int32_t* entT;
+  const float* ea; int64_t ldea;           /* edge attributes [E][ed], or [E][cin] when ed == 0 (no lin: m = h_j + ea) */
+  int64_t n_nodes; int32_t ed;
+  int32_t nonlin;                          /* after every conv: 0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh */
+  float* slab; int32_t n_slabs; int32_t slab_len;
+  float* nslab; int32_t nslab_len; int32_t pad_;
+} dss2_gine_graph;
+typedef struct dss2_gine_conv {
+  const float* eps;                        /* [1], read on the device */
+  const float* Wn; const float* bn;        /* nn: Linear(cin, cout) */
+  const float* We; const float* be;        /* lin: Linear(ed, cin); NULL when ed == 0 */
+  const float* h; int64_t ldh;             /* layer input [N][cin] */
+  float* y; float* z;                      /* forward: output after the nonlinearity [N][cout]; nn's input [N][cin] */
+  float* dz;                               /* backward: gradient of nn's input [N][cin] */
+  int32_t cin; int32_t cout; int32_t slab_off; int32_t nn_off;
+} dss2_gine_conv;
+typedef struct dss2_gine_args {
+  dss2_gine_graph g;
+  dss2_gine_conv up;                       /* backward: the conv whose SOURCE pass this launch runs (has_up) */
+  dss2_gine_conv lo;                       /* forward: the conv; backward: the conv whose node-local step this launch runs */
+  dss2_gat_head head;                      /* the two head Linears (the GAT head's descriptor) */
+  int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
+  const float* gy; int64_t ldgy;           /* backward without head / up: gradient of lo's output */
+  float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */
+} dss2_gine_args;
+/* forward: lo's aggregation, nn and nonlinearity, then the head when has_head (or the head alone on head.hin) */
+int dss2_gine_forward(const dss2_gine_args* args_host, void* stream);
+/* backward: (head backward | up's source pass | gy), then lo's node-local step, or the input gradient into dh */
+int dss2_gine_backward(const dss2_gine_args* args_host, void* stream);
+
 /* LDS bytes a dss2_gemm_prop / dss2_wgrad launch will request (host-side helper; lets the
  * caller reject configurations that do not fit the 160 KiB LDS before launching). */
 size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width);
