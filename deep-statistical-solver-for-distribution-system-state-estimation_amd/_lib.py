@@ -156,6 +156,26 @@ class StackArgs(C.Structure):
                 ("n_nodes", C.c_int64)]
 
 
+class LanegroupHead(C.Structure):
+    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p), ("hin", C.c_void_p),
+                ("ldhin", C.c_int64), ("z1", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("gout", C.c_void_p),
+                ("ldgo", C.c_int64), ("dz1", C.c_void_p), ("c", C.c_int32), ("dense", C.c_int32), ("nout", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+LANEGROUP_WGRAD_MAX_JOBS = 16
+
+
+class LanegroupWgradJob(C.Structure):
+    _fields_ = [("G", C.c_void_p), ("ldg", C.c_int64), ("X", C.c_void_p), ("ldx", C.c_int64), ("gw", C.c_int32),
+                ("xw", C.c_int32), ("col", C.c_int32), ("pad_", C.c_int32)]
+
+
+class LanegroupWgradArgs(C.Structure):
+    _fields_ = [("jobs", LanegroupWgradJob * LANEGROUP_WGRAD_MAX_JOBS), ("slab", C.c_void_p), ("n_nodes", C.c_int64),
+                ("n_slabs", C.c_int32), ("slab_len", C.c_int32), ("n_jobs", C.c_int32), ("pad_", C.c_int32)]
+
+
 class GatGraph(C.Structure):
     _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("rowptrT", C.c_void_p), ("colT", C.c_void_p),
                 ("entT", C.c_void_p), ("ea", C.c_void_p), ("ldea", C.c_int64), ("n_nodes", C.c_int64), ("ed", C.c_int32),
@@ -170,30 +190,10 @@ class GatConv(C.Structure):
                 ("dself", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32), ("slab_off", C.c_int32), ("pad_", C.c_int32)]
 
 
-class GatHead(C.Structure):
-    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p), ("hin", C.c_void_p),
-                ("ldhin", C.c_int64), ("z1", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("gout", C.c_void_p),
-                ("ldgo", C.c_int64), ("dz1", C.c_void_p), ("c", C.c_int32), ("dense", C.c_int32), ("nout", C.c_int32),
-                ("pad_", C.c_int32)]
-
-
 class GatArgs(C.Structure):
-    _fields_ = [("g", GatGraph), ("up", GatConv), ("lo", GatConv), ("head", GatHead), ("has_up", C.c_int32),
+    _fields_ = [("g", GatGraph), ("up", GatConv), ("lo", GatConv), ("head", LanegroupHead), ("has_up", C.c_int32),
                 ("has_lo", C.c_int32), ("has_head", C.c_int32), ("group", C.c_int32), ("gy", C.c_void_p), ("ldgy", C.c_int64),
                 ("dh", C.c_void_p), ("dh_cols", C.c_int32), ("pad_", C.c_int32)]
-
-
-GAT_MAX_JOBS = 16
-
-
-class GatWgradJob(C.Structure):
-    _fields_ = [("G", C.c_void_p), ("ldg", C.c_int64), ("X", C.c_void_p), ("ldx", C.c_int64), ("gw", C.c_int32),
-                ("xw", C.c_int32), ("col", C.c_int32), ("pad_", C.c_int32)]
-
-
-class GatWgradArgs(C.Structure):
-    _fields_ = [("jobs", GatWgradJob * GAT_MAX_JOBS), ("slab", C.c_void_p), ("n_nodes", C.c_int64), ("n_slabs", C.c_int32),
-                ("slab_len", C.c_int32), ("n_jobs", C.c_int32), ("pad_", C.c_int32)]
 
 
 class GineGraph(C.Structure):
@@ -210,7 +210,7 @@ class GineConv(C.Structure):
 
 
 class GineArgs(C.Structure):
-    _fields_ = [("g", GineGraph), ("up", GineConv), ("lo", GineConv), ("head", GatHead), ("has_up", C.c_int32),
+    _fields_ = [("g", GineGraph), ("up", GineConv), ("lo", GineConv), ("head", LanegroupHead), ("has_up", C.c_int32),
                 ("has_lo", C.c_int32), ("has_head", C.c_int32), ("group", C.c_int32), ("gy", C.c_void_p), ("ldgy", C.c_int64),
                 ("dh", C.c_void_p), ("dh_cols", C.c_int32), ("pad_", C.c_int32)]
 
@@ -324,7 +324,7 @@ _SIGNATURES = {
     "dss2_wgrad_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dss2_gat_forward": (C.c_int, [C.POINTER(GatArgs), C.c_void_p]),
     "dss2_gat_backward": (C.c_int, [C.POINTER(GatArgs), C.c_void_p]),
-    "dss2_gat_wgrad": (C.c_int, [C.POINTER(GatWgradArgs), C.c_void_p]),
+    "dss2_lanegroup_wgrad": (C.c_int, [C.POINTER(LanegroupWgradArgs), C.c_void_p]),
     "dss2_gine_forward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
     "dss2_gine_backward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
 }

@@ -1,9 +1,7 @@
-// GATv2 (PyG GATv2Conv, heads = 1) and the GAT_DSSE model on gfx950: forward, backward and weight gradients.
+// GATv2 (PyG GATv2Conv, heads = 1) and the GAT_DSSE model on gfx950: forward and backward.
 //
-// Lane mapping: one lane group of G (8 / 16 / 32) lanes per node, lane c owns channel c; a 256-thread workgroup holds 256 / G
-// nodes at a time and walks the nodes with a grid stride (the grid is the slab count, so every workgroup writes exactly one slab
-// row).  fp32 VALU throughout: at C = 8 there is no matrix work worth the MFMA.  The weights of the one or two layers a launch
-// touches are staged in LDS (rows padded to 33 / 17 floats: lane c reading row c hits bank c).
+// Lane mapping, the head Linears and the nonlinearity: dss2_lanegroup.hpp.  The weights of the one or two layers a launch touches
+// are staged in LDS.
 //
 // Per target i (CSR by target of the edge list as given; with add_self_loops the input's self loops are skipped and one self
 // loop whose edge term is the MEAN of the non-loop incoming edges' terms -- lin_edge is linear, so that is lin_edge of the mean
@@ -13,24 +11,18 @@
 // The backward is two node-parallel passes per layer: a per-target pass (softmax backward, d att, d bias, d W_e, d x_r and the
 // per-edge d x_l contributions) and a per-source pass over the CSR by source that sums those into d x_l and forms
 // d h = W_l^T d x_l + W_r^T d x_r.  The source pass of layer l and the target pass of layer l - 1 run in ONE launch.  The
-// outer-product weight gradients (lin_l, lin_r, the head) are one batched launch over all layers at the end.  Every
-// weight-gradient partial goes to the workgroup's slab row; dss2_reduce_slabs_multi sums them in a fixed order: no float atomics.
-#include "dss2_common.hpp"
-
-#include <math.h>
+// outer-product weight gradients (lin_l, lin_r, the head) are one batched dss2_lanegroup_wgrad launch over all layers at the end.
+// Every weight-gradient partial goes to the workgroup's slab row; dss2_reduce_slabs_multi sums them in a fixed order: no float
+// atomics.
+#include "dss2_lanegroup.hpp"
 
 using namespace dss2;
 
 namespace {
 
-constexpr int GMAX = 32, EDMAX = 16, DMAX = 32, NT = 256;
-
 struct ConvSm {
   float Wl[GMAX][GMAX + 1], Wr[GMAX][GMAX + 1], We[GMAX][EDMAX + 1];
   float bl[GMAX], br[GMAX], att[GMAX], bias[GMAX];
-};
-struct HeadSm {
-  float W1[DMAX][GMAX + 1], W2[DMAX][DMAX + 1], b1[DMAX], b2[DMAX];
 };
 
 __device__ void stage_conv(ConvSm& s, const dss2_gat_conv& p, int ed) {
@@ -53,41 +45,11 @@ __device__ void stage_conv(ConvSm& s, const dss2_gat_conv& p, int ed) {
   }
 }
 
-__device__ void stage_head(HeadSm& s, const dss2_gat_head& p) {
-  for (int t = threadIdx.x; t < DMAX * GMAX; t += NT) {
-    const int d = t / GMAX, c = t % GMAX;
-    s.W1[d][c] = (d < p.dense && c < p.c) ? p.W1[d * p.c + c] : 0.f;
-  }
-  for (int t = threadIdx.x; t < DMAX * DMAX; t += NT) {
-    const int o = t / DMAX, d = t % DMAX;
-    s.W2[o][d] = (o < p.nout && d < p.dense) ? p.W2[o * p.dense + d] : 0.f;
-  }
-  for (int t = threadIdx.x; t < DMAX; t += NT) {
-    s.b1[t] = t < p.dense ? p.b1[t] : 0.f;
-    s.b2[t] = t < p.nout ? p.b2[t] : 0.f;
-  }
-}
-
 template <int G>
 __device__ __forceinline__ float gsum(float v) {
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
   return v;
-}
-
-// the model's nonlinearity: 0 none (standalone GATv2Conv), 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh
-__device__ __forceinline__ float act(float v, int mode) {
-  if (mode == 1) return v > 0.f ? v : 0.01f * v;
-  if (mode == 2) return relu_nan(v);
-  if (mode == 3) return tanhf(v);
-  return v;
-}
-// its derivative from the saved OUTPUT (LeakyReLU / ReLU: y > 0 <=> v > 0, torch's gates at v = 0 included; Tanh: 1 - y^2)
-__device__ __forceinline__ float act_grad(float y, int mode) {
-  if (mode == 1) return y > 0.f ? 1.f : 0.01f;
-  if (mode == 2) return y > 0.f ? 1.f : 0.f;
-  if (mode == 3) return 1.f - y * y;
-  return 1.f;
 }
 
 // x_l[j][c] (or x_r) of lane c: b[c] + sum_k W[c][k] h[j][k]
@@ -157,35 +119,7 @@ __global__ __launch_bounds__(NT) void gat_fwd_kernel(const dss2_gat_args a) {
     } else if (a.has_head) {
       y = c < a.head.c ? a.head.hin[i * a.head.ldhin + c] : 0.f;
     }
-    if (a.has_head) {
-      const dss2_gat_head& hp = a.head;
-      float z1[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) z1[u] = hs.b1[u * G + c];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const float yk = __shfl(y, k, G);
-#pragma unroll
-        for (int u = 0; u < DMAX / G; ++u) z1[u] = fmaf(hs.W1[u * G + c][k], yk, z1[u]);
-      }
-      float o[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) {
-        o[u] = hs.b2[u * G + c];
-        if (u * G + c < hp.dense) hp.z1[i * hp.dense + u * G + c] = z1[u];
-      }
-#pragma unroll
-      for (int v = 0; v < DMAX / G; ++v)
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-          const float zd = __shfl(z1[v], k, G);
-#pragma unroll
-          for (int u = 0; u < DMAX / G; ++u) o[u] = fmaf(hs.W2[u * G + c][v * G + k], zd, o[u]);
-        }
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u)
-        if (u * G + c < hp.nout) hp.out[i * hp.ldo + u * G + c] = o[u];
-    }
+    if (a.has_head) head_forward<G>(hs, a.head, i, c, y);
   }
 }
 
@@ -209,21 +143,7 @@ __global__ __launch_bounds__(NT) void gat_bwd_kernel(const dss2_gat_args a) {
   for (int64_t i = (int64_t)blockIdx.x * (NT / G) + grp; i < n; i += stride) {
     float gy = 0.f;   // gradient of the output of layer lo (or of the model input) at channel c
     if (a.has_head) {
-      const dss2_gat_head& hp = a.head;
-      float dz[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) dz[u] = 0.f;
-      for (int o = 0; o < hp.nout; ++o) {
-        const float go = hp.gout[i * hp.ldgo + o];
-#pragma unroll
-        for (int u = 0; u < DMAX / G; ++u) dz[u] = fmaf(hs.W2[o][u * G + c], go, dz[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) {
-        if (u * G + c < hp.dense) hp.dz1[i * hp.dense + u * G + c] = dz[u];
-#pragma unroll
-        for (int k = 0; k < G; ++k) gy = fmaf(hs.W1[u * G + k][c], __shfl(dz[u], k, G), gy);
-      }
+      gy = head_backward<G>(hs, a.head, i, c);
     } else if (a.has_up) {
       const dss2_gat_conv& p = a.up;
       float dxl = (loops && c < p.cout) ? p.dself[i * p.cout + c] : 0.f;
@@ -323,46 +243,17 @@ __global__ __launch_bounds__(NT) void gat_bwd_kernel(const dss2_gat_args a) {
     float* dst;
     if (t < 2 * p.cout) { k = t / p.cout; ch = t % p.cout; dst = row + t; }
     else { const int u = t - 2 * p.cout; ch = u / ed; k = 2 + u % ed; dst = row + 4 * p.cout + 2 * p.cout * p.cin + u; }
-    float v = 0.f;
-    for (int g = 0; g < NT / G; ++g) v += red[g * G + ch][k];
-    *dst = v;
-  }
-}
-
-// ---- outer-product weight gradients: slab[s][col + o * xw + k] = sum_{n in chunk s} Gm[n][o] X[n][k], then the column sums of Gm
-__global__ __launch_bounds__(NT) void gat_wgrad_kernel(const dss2_gat_wgrad_args a) {
-  const dss2_gat_wgrad_job& jb = a.jobs[blockIdx.y];
-  const int64_t chunk = (a.n_nodes + gridDim.x - 1) / gridDim.x;
-  const int64_t n0 = (int64_t)blockIdx.x * chunk, n1 = n0 + chunk < a.n_nodes ? n0 + chunk : a.n_nodes;
-  const int nw = jb.gw * jb.xw;
-  float* row = a.slab + (int64_t)blockIdx.x * a.slab_len + jb.col;
-  for (int t = threadIdx.x; t < nw + jb.gw; t += NT) {
-    float v = 0.f;
-    if (t < nw) {
-      const int o = t / jb.xw, k = t % jb.xw;
-      for (int64_t n = n0; n < n1; ++n) v = fmaf(jb.G[n * jb.ldg + o], jb.X[n * jb.ldx + k], v);
-    } else {
-      const int o = t - nw;
-      for (int64_t n = n0; n < n1; ++n) v += jb.G[n * jb.ldg + o];
-    }
-    row[t] = v;
+    *dst = group_sum<G>(red, ch, k);
   }
 }
 
 int check_args(const dss2_gat_args& a, const char* what) {
-  if (a.g.n_nodes <= 0 || a.g.n_slabs <= 0) { set_error("%s: empty batch / no slabs", what); return 2; }
-  if (a.g.ed < 0 || a.g.ed > EDMAX) { set_error("%s: edge_dim %d outside [0, %d]", what, a.g.ed, EDMAX); return 2; }
-  if (a.group != 8 && a.group != 16 && a.group != 32) { set_error("%s: lane group %d (8, 16 or 32)", what, a.group); return 2; }
+  if (int rc = check_lanegroup_args(a, what)) return rc;
   const dss2_gat_conv* cv[2] = {a.has_up ? &a.up : nullptr, a.has_lo ? &a.lo : nullptr};
   for (const dss2_gat_conv* p : cv)
     if (p && (p->cin < 1 || p->cout < 1 || p->cin > a.group || p->cout > a.group)) {
       set_error("%s: channels %d -> %d exceed the lane group %d (limit %d)", what, p->cin, p->cout, a.group, GMAX); return 2;
     }
-  if (a.has_head && (a.head.c < 1 || a.head.c > a.group || a.head.dense < 1 || a.head.dense > DMAX || a.head.nout < 1 || a.head.nout > DMAX)) {
-    set_error("%s: head %d -> %d -> %d outside the limits (C <= lane group, dense, out <= %d)", what, a.head.c, a.head.dense, a.head.nout, DMAX);
-    return 2;
-  }
-  if (a.has_head && a.has_up) { set_error("%s: head and source pass in one launch", what); return 2; }
   return 0;
 }
 
@@ -372,50 +263,20 @@ static int dss2_gat_forward_launch(const dss2_gat_args* ap, void* stream) {
   const dss2_gat_args& a = *ap;
   if (int rc = check_args(a, "dss2_gat_forward")) return rc;
   if (!a.has_lo && !a.has_head) { set_error("dss2_gat_forward: nothing to do"); return 2; }
-  const dim3 grid((unsigned)a.g.n_slabs);
-  hipStream_t s = as_stream(stream);
-  if (a.group == 8) hipLaunchKernelGGL(gat_fwd_kernel<8>, grid, dim3(NT), 0, s, a);
-  else if (a.group == 16) hipLaunchKernelGGL(gat_fwd_kernel<16>, grid, dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL(gat_fwd_kernel<32>, grid, dim3(NT), 0, s, a);
-  return check_launch("dss2_gat_forward");
+  return launch_group(gat_fwd_kernel<8>, gat_fwd_kernel<16>, gat_fwd_kernel<32>, a, stream, "dss2_gat_forward");
 }
 
 static int dss2_gat_backward_launch(const dss2_gat_args* ap, void* stream) {
   const dss2_gat_args& a = *ap;
   if (int rc = check_args(a, "dss2_gat_backward")) return rc;
   if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gat_backward: no output gradient"); return 2; }
-  const dim3 grid((unsigned)a.g.n_slabs);
-  hipStream_t s = as_stream(stream);
-  if (a.group == 8) hipLaunchKernelGGL(gat_bwd_kernel<8>, grid, dim3(NT), 0, s, a);
-  else if (a.group == 16) hipLaunchKernelGGL(gat_bwd_kernel<16>, grid, dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL(gat_bwd_kernel<32>, grid, dim3(NT), 0, s, a);
-  return check_launch("dss2_gat_backward");
-}
-
-static int dss2_gat_wgrad_launch(const dss2_gat_wgrad_args* ap, void* stream) {
-  const dss2_gat_wgrad_args& a = *ap;
-  if (a.n_jobs < 1 || a.n_jobs > DSS2_GAT_MAX_JOBS || a.n_slabs < 1 || a.n_nodes < 1) {
-    set_error("dss2_gat_wgrad: %d jobs (1..%d), %d slabs", a.n_jobs, DSS2_GAT_MAX_JOBS, a.n_slabs);
-    return 2;
-  }
-  hipLaunchKernelGGL(gat_wgrad_kernel, dim3((unsigned)a.n_slabs, (unsigned)a.n_jobs), dim3(NT), 0, as_stream(stream), a);
-  return check_launch("dss2_gat_wgrad");
+  return launch_group(gat_bwd_kernel<8>, gat_bwd_kernel<16>, gat_bwd_kernel<32>, a, stream, "dss2_gat_backward");
 }
 
 extern "C" int dss2_gat_forward(const dss2_gat_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_gat_forward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gat_forward_launch(&a, s_); });
-  return dss2_gat_forward_launch(ap, stream);
+  return run_entry(dss2_gat_forward_launch, ap, stream, "dss2_gat_forward");
 }
 
 extern "C" int dss2_gat_backward(const dss2_gat_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_gat_backward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gat_backward_launch(&a, s_); });
-  return dss2_gat_backward_launch(ap, stream);
-}
-
-extern "C" int dss2_gat_wgrad(const dss2_gat_wgrad_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_gat_wgrad: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gat_wgrad_launch(&a, s_); });
-  return dss2_gat_wgrad_launch(ap, stream);
+  return run_entry(dss2_gat_backward_launch, ap, stream, "dss2_gat_backward");
 }

@@ -1,8 +1,6 @@
-// GINE (PyG GINEConv with nn = one Linear) and the GINE_DSSE model on gfx950: forward, backward and weight gradients.
+// GINE (PyG GINEConv with nn = one Linear) and the GINE_DSSE model on gfx950: forward and backward.
 //
-// Lane mapping as in dss2_gat.hip: one lane group of G (8 / 16 / 32) lanes per node, lane c owns channel c; a 256-thread
-// workgroup holds 256 / G nodes at a time and walks the nodes with a grid stride (the grid is the slab count, so every workgroup
-// writes exactly one slab row).  fp32 VALU throughout.  Weights are staged in LDS with padded rows (33 / 17 floats).
+// Lane mapping, the head Linears and the nonlinearity: dss2_lanegroup.hpp.  The head's weight gradient is dss2_lanegroup_wgrad.
 //
 // One layer, j = edge_index[0] the source and i = edge_index[1] the target, edges as given (no doubling, no self loops added):
 //     m_e   = h_j + W_e ea_e + b_e                 (without lin: h_j + ea_e)
@@ -16,22 +14,15 @@
 // in the same launch.  The local step forms d eps and the shared nn's partial d W_nn = dv z^T, d b_nn = dv; those go to the
 // workgroup's row of a second slab, [n_slabs][n_convs][nn_len], which dss2_reduce_slabs_multi sums as n_slabs * n_convs rows in
 // a fixed order.  No float atomics.
-#include "dss2_common.hpp"
-
-#include <math.h>
+#include "dss2_lanegroup.hpp"
 
 using namespace dss2;
 
 namespace {
 
-constexpr int GMAX = 32, EDMAX = 16, DMAX = 32, NT = 256;
-
 struct ConvSm {
   float Wn[GMAX][GMAX + 1], We[GMAX][EDMAX + 1];
   float bn[GMAX], be[GMAX];
-};
-struct HeadSm {
-  float W1[DMAX][GMAX + 1], W2[DMAX][DMAX + 1], b1[DMAX], b2[DMAX];
 };
 
 __device__ void stage_conv(ConvSm& s, const dss2_gine_conv& p, int ed) {
@@ -49,37 +40,6 @@ __device__ void stage_conv(ConvSm& s, const dss2_gine_conv& p, int ed) {
   }
 }
 
-__device__ void stage_head(HeadSm& s, const dss2_gat_head& p) {
-  for (int t = threadIdx.x; t < DMAX * GMAX; t += NT) {
-    const int d = t / GMAX, c = t % GMAX;
-    s.W1[d][c] = (d < p.dense && c < p.c) ? p.W1[d * p.c + c] : 0.f;
-  }
-  for (int t = threadIdx.x; t < DMAX * DMAX; t += NT) {
-    const int o = t / DMAX, d = t % DMAX;
-    s.W2[o][d] = (o < p.nout && d < p.dense) ? p.W2[o * p.dense + d] : 0.f;
-  }
-  for (int t = threadIdx.x; t < DMAX; t += NT) {
-    s.b1[t] = t < p.dense ? p.b1[t] : 0.f;
-    s.b2[t] = t < p.nout ? p.b2[t] : 0.f;
-  }
-}
-
-// the model's nonlinearity: 0 none (standalone GINEConv), 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh
-__device__ __forceinline__ float act(float v, int mode) {
-  if (mode == 1) return v > 0.f ? v : 0.01f * v;
-  if (mode == 2) return relu_nan(v);
-  if (mode == 3) return tanhf(v);
-  return v;
-}
-// its derivative from the saved OUTPUT, with torch's gates: leaky_relu_backward (input > 0; y > 0 <=> v > 0, NaN takes the
-// slope), threshold_backward on the ReLU's result (y <= 0 closes, NaN passes), tanh_backward (1 - y^2)
-__device__ __forceinline__ float act_grad(float y, int mode) {
-  if (mode == 1) return y > 0.f ? 1.f : 0.01f;
-  if (mode == 2) return relu_open(y) ? 1.f : 0.f;
-  if (mode == 3) return 1.f - y * y;
-  return 1.f;
-}
-
 // the message m_e of lane c before the ReLU.  The forward and the source pass both call this, so the gates agree bit for bit.
 __device__ __forceinline__ float message(const ConvSm& s, const dss2_gine_graph& g, int c, float hj, int64_t e, int cin) {
   const float* er = g.ea + e * g.ldea;
@@ -91,14 +51,6 @@ __device__ __forceinline__ float message(const ConvSm& s, const dss2_gine_graph&
     v = c < cin ? er[c] : 0.f;
   }
   return hj + v;
-}
-
-// lane-group fixed-order sum of red[g * G + ch][k] over the NT / G groups
-template <int G>
-__device__ __forceinline__ float group_sum(const float (*red)[GMAX + 1], int ch, int k) {
-  float v = 0.f;
-  for (int g = 0; g < NT / G; ++g) v += red[g * G + ch][k];
-  return v;
 }
 
 // ---- forward: one GINE layer (nonlinearity fused) and / or the two head Linears -------------------------------------------------
@@ -135,35 +87,7 @@ __global__ __launch_bounds__(NT) void gine_fwd_kernel(const dss2_gine_args a) {
     } else if (a.has_head) {
       y = c < a.head.c ? a.head.hin[i * a.head.ldhin + c] : 0.f;
     }
-    if (a.has_head) {
-      const dss2_gat_head& hp = a.head;
-      float z1[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) z1[u] = hs.b1[u * G + c];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const float yk = __shfl(y, k, G);
-#pragma unroll
-        for (int u = 0; u < DMAX / G; ++u) z1[u] = fmaf(hs.W1[u * G + c][k], yk, z1[u]);
-      }
-      float o[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) {
-        o[u] = hs.b2[u * G + c];
-        if (u * G + c < hp.dense) hp.z1[i * hp.dense + u * G + c] = z1[u];
-      }
-#pragma unroll
-      for (int v = 0; v < DMAX / G; ++v)
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-          const float zd = __shfl(z1[v], k, G);
-#pragma unroll
-          for (int u = 0; u < DMAX / G; ++u) o[u] = fmaf(hs.W2[u * G + c][v * G + k], zd, o[u]);
-        }
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u)
-        if (u * G + c < hp.nout) hp.out[i * hp.ldo + u * G + c] = o[u];
-    }
+    if (a.has_head) head_forward<G>(hs, a.head, i, c, y);
   }
 }
 
@@ -190,21 +114,7 @@ __global__ __launch_bounds__(NT) void gine_bwd_kernel(const dss2_gine_args a) {
   for (int64_t i = (int64_t)blockIdx.x * (NT / G) + grp; i < n; i += stride) {
     float gy = 0.f;   // gradient of lo's output (or of the model input) at channel c
     if (a.has_head) {
-      const dss2_gat_head& hp = a.head;
-      float dz[DMAX / G];
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) dz[u] = 0.f;
-      for (int o = 0; o < hp.nout; ++o) {
-        const float go = hp.gout[i * hp.ldgo + o];
-#pragma unroll
-        for (int u = 0; u < DMAX / G; ++u) dz[u] = fmaf(hs.W2[o][u * G + c], go, dz[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < DMAX / G; ++u) {
-        if (u * G + c < hp.dense) hp.dz1[i * hp.dense + u * G + c] = dz[u];
-#pragma unroll
-        for (int k = 0; k < G; ++k) gy = fmaf(hs.W1[u * G + k][c], __shfl(dz[u], k, G), gy);
-      }
+      gy = head_backward<G>(hs, a.head, i, c);
     } else if (a.has_up) {
       const dss2_gine_conv& p = a.up;
       const bool in = c < p.cin;
@@ -296,18 +206,11 @@ int check_conv(const dss2_gine_conv& p, const dss2_gine_args& a, const char* wha
 }
 
 int check_args(const dss2_gine_args& a, const char* what) {
-  if (a.g.n_nodes <= 0 || a.g.n_slabs <= 0) { set_error("%s: empty batch / no slabs", what); return 2; }
-  if (a.g.ed < 0 || a.g.ed > EDMAX) { set_error("%s: edge_dim %d outside [0, %d]", what, a.g.ed, EDMAX); return 2; }
-  if (a.group != 8 && a.group != 16 && a.group != 32) { set_error("%s: lane group %d (8, 16 or 32)", what, a.group); return 2; }
+  if (int rc = check_lanegroup_args(a, what)) return rc;
   if (a.has_up)
     if (int rc = check_conv(a.up, a, what)) return rc;
   if (a.has_lo)
     if (int rc = check_conv(a.lo, a, what)) return rc;
-  if (a.has_head && (a.head.c < 1 || a.head.c > a.group || a.head.dense < 1 || a.head.dense > DMAX || a.head.nout < 1 || a.head.nout > DMAX)) {
-    set_error("%s: head %d -> %d -> %d outside the limits (C <= lane group, dense, out <= %d)", what, a.head.c, a.head.dense, a.head.nout, DMAX);
-    return 2;
-  }
-  if (a.has_head && a.has_up) { set_error("%s: head and source pass in one launch", what); return 2; }
   return 0;
 }
 
@@ -318,12 +221,7 @@ static int dss2_gine_forward_launch(const dss2_gine_args* ap, void* stream) {
   if (int rc = check_args(a, "dss2_gine_forward")) return rc;
   if (!a.has_lo && !a.has_head) { set_error("dss2_gine_forward: nothing to do"); return 2; }
   if (a.has_up) { set_error("dss2_gine_forward: no source pass in the forward"); return 2; }
-  const dim3 grid((unsigned)a.g.n_slabs);
-  hipStream_t s = as_stream(stream);
-  if (a.group == 8) hipLaunchKernelGGL(gine_fwd_kernel<8>, grid, dim3(NT), 0, s, a);
-  else if (a.group == 16) hipLaunchKernelGGL(gine_fwd_kernel<16>, grid, dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL(gine_fwd_kernel<32>, grid, dim3(NT), 0, s, a);
-  return check_launch("dss2_gine_forward");
+  return launch_group(gine_fwd_kernel<8>, gine_fwd_kernel<16>, gine_fwd_kernel<32>, a, stream, "dss2_gine_forward");
 }
 
 static int dss2_gine_backward_launch(const dss2_gine_args* ap, void* stream) {
@@ -331,22 +229,13 @@ static int dss2_gine_backward_launch(const dss2_gine_args* ap, void* stream) {
   if (int rc = check_args(a, "dss2_gine_backward")) return rc;
   if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gine_backward: no output gradient"); return 2; }
   if (!a.g.slab || (a.has_lo && !a.g.nslab)) { set_error("dss2_gine_backward: no slab"); return 2; }
-  const dim3 grid((unsigned)a.g.n_slabs);
-  hipStream_t s = as_stream(stream);
-  if (a.group == 8) hipLaunchKernelGGL(gine_bwd_kernel<8>, grid, dim3(NT), 0, s, a);
-  else if (a.group == 16) hipLaunchKernelGGL(gine_bwd_kernel<16>, grid, dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL(gine_bwd_kernel<32>, grid, dim3(NT), 0, s, a);
-  return check_launch("dss2_gine_backward");
+  return launch_group(gine_bwd_kernel<8>, gine_bwd_kernel<16>, gine_bwd_kernel<32>, a, stream, "dss2_gine_backward");
 }
 
 extern "C" int dss2_gine_forward(const dss2_gine_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_gine_forward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gine_forward_launch(&a, s_); });
-  return dss2_gine_forward_launch(ap, stream);
+  return run_entry(dss2_gine_forward_launch, ap, stream, "dss2_gine_forward");
 }
 
 extern "C" int dss2_gine_backward(const dss2_gine_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_gine_backward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gine_backward_launch(&a, s_); });
-  return dss2_gine_backward_launch(ap, stream);
+  return run_entry(dss2_gine_backward_launch, ap, stream, "dss2_gine_backward");
 }

@@ -6,11 +6,12 @@ csrc/dss2_gat.hip.
     GAT_DSSE(dim_feat, dim_dense, dim_out, num_layers, edge_dim, heads=1, concat=True, slope=0.2, self_loops=True,
              dropout=0., nonlin='leaky_relu', model='gat')                          the reference's signature and attributes
 
-``GAT_DSSE.model`` is a look-alike of PyG's ``Sequential`` with children ``module_{i}``: conv k is ``module_{2k}``, the shared
-nonlinearity sits at every ``module_{2k+1}``, the two Linears follow; so the ``state_dict`` keys are the reference's.  Its
-forward is ONE autograd node (``_GATFn``): one launch per conv forward (the head Linears fused into the last one), per layer
-one fused backward launch (source pass of layer l + target pass of layer l - 1), one batched weight-gradient launch and one
-slab reduction.  Every launch goes through the library, so the step records into launch plans and hipGraphs.
+``GAT_DSSE.model`` is a look-alike of PyG's ``Sequential`` (``lanegroup.Sequential``) with children ``module_{i}``: conv k is
+``module_{2k}``, the shared nonlinearity sits at every ``module_{2k+1}``, the two Linears follow; so the ``state_dict`` keys are
+the reference's.  Its forward is ONE autograd node (``_GATFn``) on the launch schedule of lanegroup.py: one launch per conv
+forward (the head Linears fused into the last one), per layer one fused backward launch (source pass of layer l + target pass of
+layer l - 1), one batched weight-gradient launch and one slab reduction.  Every launch goes through the library, so the step
+records into launch plans and hipGraphs.
 
 The semantics are PyG 2.3-2.6's ``GATv2Conv`` / ``softmax`` / ``add_self_loops`` / ``Sequential`` (torch_geometric is not a
 dependency; they are pinned by tests/golden/gat_known_answers.json and the fp64 restatement tests/gat_oracle.py).  Not
@@ -19,23 +20,19 @@ return_attention_weights.  No gradient with respect to edge_attr; no CPU path.
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 import math
-from typing import List, Optional, Sequence
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, lanegroup
+from .lanegroup import MAX_CHANNELS, MAX_DENSE, MAX_EDGE_DIM
 from .ops import _require_gpu, _rows
 from .topology import get_topology
 
 _F32 = torch.float32
-MAX_CHANNELS = 32        # conv input / output channels and the head's input width (lane group of 8 / 16 / 32 lanes)
-MAX_EDGE_DIM = 16
-MAX_DENSE = 32           # head widths dim_dense and dim_out
-_MAX_SLABS = 256
-_NONLIN = {"none": 0, "leaky_relu": 1, "relu": 2, "tanh": 3}
 
 
 def _glorot(t: torch.Tensor) -> None:
@@ -50,9 +47,7 @@ def _fan_in_uniform(t: torch.Tensor, fan_in: int) -> None:
         t.uniform_(-b, b)
 
 
-def _check_width(name: str, v: int, limit: int) -> None:
-    if not isinstance(v, int) or v < 1 or v > limit:
-        raise ValueError(f"{name} = {v}: the GAT kernels take 1 <= {name} <= {limit}")
+_check_width = functools.partial(lanegroup.check_width, "GAT")
 
 
 class GATv2Conv(nn.Module):
@@ -120,20 +115,6 @@ class GATv2Conv(nn.Module):
         return run_gat([self], None, "none", x, edge_index, edge_attr)
 
 
-class GATSequential(nn.Module):
-    """Stand-in for PyG's ``Sequential('x, edge_index, edge_attr', [...])`` as GAT_DSSE builds it: children ``module_{i}`` in
-    the list's order (the naming is PyG's and not pinned by a test against PyG itself).  ``forward`` runs the fused route."""
-
-    def __init__(self, modules: Sequence[nn.Module], convs: Sequence[GATv2Conv], head: Sequence[nn.Linear], nonlin: str):
-        super().__init__()
-        for i, m in enumerate(modules):
-            self.add_module(f"module_{i}", m)
-        self.__dict__["_convs"], self.__dict__["_head"], self.__dict__["_nonlin"] = list(convs), list(head), nonlin
-
-    def forward(self, x, edge_index, edge_attr):
-        return run_gat(self._convs, self._head, self._nonlin, x, edge_index, edge_attr)
-
-
 class GAT_DSSE(nn.Module):
     """/root/reference/networks.py:113-156: ``num_layers - 1`` GATv2Conv(dim_feat -> dim_feat) layers, each followed by the
     (shared) nonlinearity, then Linear(dim_feat, dim_dense) and Linear(dim_dense, dim_out)."""
@@ -153,14 +134,7 @@ class GAT_DSSE(nn.Module):
         self.slope = slope
         self.dropout = dropout
         self.loop = self_loops
-        if nonlin == "relu":
-            self.nonlin = nn.ReLU()
-        elif nonlin == "tanh":
-            self.nonlin = nn.Tanh()
-        elif nonlin == "leaky_relu":
-            self.nonlin = nn.LeakyReLU()
-        else:
-            raise ValueError("invalid activation type")
+        self.nonlin = lanegroup.nonlin_module(nonlin)
         if model != "gat":
             raise ValueError("invalid model type")
         if num_layers < 1:
@@ -175,7 +149,7 @@ class GAT_DSSE(nn.Module):
             convs.append(conv)
             layers += [conv, self.nonlin]
         head = [nn.Linear(self.dim_hidden, dim_dense), nn.Linear(dim_dense, dim_out)]
-        self.model = GATSequential(layers + head, convs, head, nonlin)
+        self.model = lanegroup.Sequential(layers + head, convs, head, nonlin, run_gat)
 
     def forward(self, x, edge_index, edge_attr):
         return self.model(x, edge_index, edge_attr)
@@ -184,12 +158,10 @@ class GAT_DSSE(nn.Module):
 # ------------------------------------------------------------------------------------------
 # the fused route
 # ------------------------------------------------------------------------------------------
-class _Spec:
+class _Spec(lanegroup.Spec):
     """Dimensions, slab layout and launch geometry of one conv stack (+ head)."""
 
     def __init__(self, convs, head, nonlin, n_nodes):
-        self.convs, self.head = convs, head
-        self.nonlin = _NONLIN[nonlin]
         c0 = convs[0] if convs else None
         self.ed = (c0.edge_dim or 0) if c0 is not None else 0
         self.loops = int(c0.add_self_loops) if c0 is not None else 1
@@ -198,24 +170,8 @@ class _Spec:
             if (cv.edge_dim or 0) != self.ed or int(cv.add_self_loops) != self.loops or float(cv.negative_slope) != self.slope:
                 raise ValueError("GAT stack: every conv must share edge_dim, add_self_loops and negative_slope")
         widths = [w for cv in convs for w in (cv.in_channels, cv.out_channels)]
-        if head:
-            widths.append(head[0].in_features)
-            if head[0].out_features > MAX_DENSE or head[1].out_features > MAX_DENSE or head[1].in_features != head[0].out_features:
-                raise ValueError(f"GAT head: widths up to {MAX_DENSE}")
-        if max(widths) > MAX_CHANNELS:
-            raise ValueError(f"GAT: channel width {max(widths)} above the limit {MAX_CHANNELS}")
-        self.group = 8 if max(widths) <= 8 else (16 if max(widths) <= 16 else 32)
-        self.offs, off = [], 0
-        for cv in convs:
-            self.offs.append(off)
-            co, ci = cv.out_channels, cv.in_channels
-            off += 4 * co + 2 * co * ci + co * self.ed
-        self.head_off = off
-        if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            off += d * c + d + o * d + o
-        self.total = off
-        self.n_slabs = max(1, min(_MAX_SLABS, -(-n_nodes // (256 // self.group))))
+        cols = [4 * cv.out_channels + 2 * cv.out_channels * cv.in_channels + cv.out_channels * self.ed for cv in convs]
+        super().__init__("GAT", convs, head, nonlin, n_nodes, widths, cols)
 
 
 def _slots(convs, head) -> List[Optional[torch.Tensor]]:
@@ -269,24 +225,15 @@ def _conv(d, cv, ps7, h, ldh, st, off):
     d.cin, d.cout, d.slab_off = cv.in_channels, cv.out_channels, off
 
 
-def _head(d, hd, hps, st):
-    d.W1, d.b1, d.W2, d.b2 = (t.data_ptr() for t in hps)
-    d.c, d.dense, d.nout = hd[0].in_features, hd[0].out_features, hd[1].out_features
-    d.z1 = st["z1"].data_ptr()
-
-
 class _GATFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ea, topo, spec, *ps):
-        L = _lib.lib()
         N, dev = topo.N, x.device
         x, ldx = _rows(x)
         ldea = 0
         if ea is not None:
             ea, ldea = _rows(ea)
-        sm = _lib.stream_ptr(dev)
-        convs, head = spec.convs, spec.head
-        n = len(convs)
+        convs, n = spec.convs, len(spec.convs)
         states, hs = [], []
         h, ldh = x, ldx
         for l, cv in enumerate(convs):
@@ -294,27 +241,12 @@ class _GATFn(torch.autograd.Function):
             states.append(st)
             hs.append((h, ldh))
             h, ldh = st["y"], cv.out_channels
-        hst, out = {}, None
-        if head:
-            hst["z1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
-            out = torch.empty(N, head[1].out_features, dtype=_F32, device=dev)
-        g = _graph(topo, spec, ea, ldea)
-        for l, cv in enumerate(convs):
-            a = _lib.GatArgs()
-            a.g, a.group, a.has_lo = g, spec.group, 1
-            _conv(a.lo, cv, ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
-            if head and l == n - 1:
-                a.has_head = 1
-                _head(a.head, head, ps[7 * n:7 * n + 4], hst)
-                a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-            _lib.check(L.dss2_gat_forward(C.byref(a), sm), "dss2_gat_forward")
-        if n == 0:
-            a = _lib.GatArgs()
-            a.g, a.group, a.has_head = g, spec.group, 1
-            _head(a.head, head, ps[0:4], hst)
-            a.head.hin, a.head.ldhin = x.data_ptr(), ldx
-            a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-            _lib.check(L.dss2_gat_forward(C.byref(a), sm), "dss2_gat_forward")
+
+        def conv_into(d, l):
+            _conv(d, convs[l], ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
+
+        hst, out = lanegroup.forward(spec, _graph(topo, spec, ea, ldea), _lib.GatArgs, "dss2_gat_forward", conv_into, x, ldx,
+                                     ps[7 * n:])
         if out is None:
             out = states[-1]["y"]
         # internal buffers live on ctx (never handed out, except the last conv's y of a head-less stack, whose backward does
@@ -327,13 +259,10 @@ class _GATFn(torch.autograd.Function):
     def backward(ctx, gout):
         x, ea = ctx.saved_tensors
         topo, spec, ldx, ldea, states, hs, hst, ps = ctx.st
-        L = _lib.lib()
         N, dev, E = topo.N, gout.device, topo.E
-        sm = _lib.stream_ptr(dev)
         gout, ldgo = _rows(gout)
         convs, head = spec.convs, spec.head
         n = len(convs)
-        need_dx = ctx.needs_input_grad[0]
         slab = torch.empty(spec.n_slabs, spec.total, dtype=_F32, device=dev)
         flat = torch.empty(spec.total, dtype=_F32, device=dev)
         cmax = max([cv.out_channels for cv in convs] or [1])
@@ -343,41 +272,15 @@ class _GATFn(torch.autograd.Function):
             st["dxl"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
             st["dxr"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
             st["dedge"], st["dself"] = pp[l % len(pp)]
-        cin0 = convs[0].in_channels if n else head[0].in_features
-        dx = torch.empty(N, cin0, dtype=_F32, device=dev) if need_dx else None
-        if head:
-            hst["dz1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
-        g = _graph(topo, spec, ea, ldea, slab)
+        dx = torch.empty(N, x.size(1), dtype=_F32, device=dev) if ctx.needs_input_grad[0] else None
 
         def conv_into(d, l):
             _conv(d, convs[l], ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
 
-        # launch 1: head backward (or the output gradient) + target pass of the last conv
-        a = _lib.GatArgs()
-        a.g, a.group = g, spec.group
-        if head:
-            a.has_head = 1
-            _head(a.head, head, ps[7 * n:7 * n + 4], hst)
-            a.head.gout, a.head.ldgo, a.head.dz1 = gout.data_ptr(), ldgo, hst["dz1"].data_ptr()
-        else:
-            a.gy, a.ldgy = gout.data_ptr(), ldgo
-        if n:
-            a.has_lo = 1
-            conv_into(a.lo, n - 1)
-        else:
-            a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
-        _lib.check(L.dss2_gat_backward(C.byref(a), sm), "dss2_gat_backward")
-        # source pass of conv l fused with the target pass of conv l - 1; the last one writes dx
-        for l in range(n - 1, -1, -1):
-            a = _lib.GatArgs()
-            a.g, a.group, a.has_up = g, spec.group, 1
-            conv_into(a.up, l)
-            if l > 0:
-                a.has_lo = 1
-                conv_into(a.lo, l - 1)
-            else:
-                a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
-            _lib.check(L.dss2_gat_backward(C.byref(a), sm), "dss2_gat_backward")
+        # head backward (or the output gradient) + target pass of the last conv, then per conv l its source pass fused with the
+        # target pass of conv l - 1; the last one writes dx
+        lanegroup.backward(spec, _graph(topo, spec, ea, ldea, slab), _lib.GatArgs, "dss2_gat_backward", conv_into, gout, ldgo,
+                           ps[7 * n:], hst, dx)
         # outer-product weight gradients of every layer, then ONE fixed-order reduction of the slab
         jobs = []
         for l, cv in enumerate(convs):
@@ -386,20 +289,11 @@ class _GATFn(torch.autograd.Function):
             jobs.append((states[l]["dxl"], co, h, ldh, co, ci, off + 2 * co))
             jobs.append((states[l]["dxr"], co, h, ldh, co, ci, off + 3 * co + co * ci))
         if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            hin, ldhin = (states[-1]["y"], c) if n else (x, ldx)
-            jobs.append((hst["dz1"], d, hin, ldhin, d, c, spec.head_off))
-            jobs.append((gout, ldgo, hst["z1"], d, o, d, spec.head_off + d * c + d))
-        for j0 in range(0, len(jobs), _lib.GAT_MAX_JOBS):
-            w = _lib.GatWgradArgs()
-            chunk = jobs[j0:j0 + _lib.GAT_MAX_JOBS]
-            for jd, (Gm, ldg, Xm, ldxm, gw, xw, col) in zip(w.jobs, chunk):
-                jd.G, jd.ldg, jd.X, jd.ldx, jd.gw, jd.xw, jd.col = Gm.data_ptr(), ldg, Xm.data_ptr(), ldxm, gw, xw, col
-            w.slab, w.n_nodes, w.n_slabs, w.slab_len, w.n_jobs = slab.data_ptr(), N, spec.n_slabs, spec.total, len(chunk)
-            _lib.check(L.dss2_gat_wgrad(C.byref(w), sm), "dss2_gat_wgrad")
+            jobs += lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo)
+        lanegroup.wgrad(jobs, slab, spec, N, dev)
         rd = (_lib.ReduceDesc * 1)()
         rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
-        _lib.check(L.dss2_reduce_slabs_multi(rd, 1, sm), "dss2_reduce_slabs_multi")
+        _lib.check(_lib.lib().dss2_reduce_slabs_multi(rd, 1, _lib.stream_ptr(dev)), "dss2_reduce_slabs_multi")
         grads = []
         for l, cv in enumerate(convs):
             co, ci, ed, off = cv.out_channels, cv.in_channels, spec.ed, spec.offs[l]
@@ -410,9 +304,5 @@ class _GATFn(torch.autograd.Function):
                 o += sz
             for t, gpart in zip(ps[7 * l:7 * l + 7], parts):
                 grads.append(None if t is None else gpart.view(t.shape))
-        if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            hoff = spec.head_off
-            grads += [flat[hoff:hoff + d * c].view(d, c), flat[hoff + d * c:hoff + d * c + d],
-                      flat[hoff + d * c + d:hoff + d * c + d + o * d].view(o, d), flat[hoff + d * c + d + o * d:spec.total]]
-        return (dx, None, None, None, *grads)
+        grads += lanegroup.head_grads(spec, flat)
+        return lanegroup.backward_result(ctx, dx, grads)

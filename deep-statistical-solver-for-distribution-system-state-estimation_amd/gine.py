@@ -11,10 +11,10 @@ relu(h_j + ea_e) and edge_attr must be [E, nn.in_features] (PyG's rule).
 
 ``GINE_DSSE`` builds ONE ``Linear(dim_feat, dim_feat)`` (``self.nn``) and hands the same object to every conv, as the reference
 does: ``state_dict()`` lists it once per owner (``nn.*`` and ``model.module_{2k}.nn.*``), ``parameters()`` once, and its gradient is
-the sum over the layers.  ``model`` is a look-alike of PyG's ``Sequential`` with children ``module_{i}`` (as in gat.py).  Its
-forward is ONE autograd node (``_GINEFn``): one launch per conv forward (the head Linears fused into the last one), one fused
-backward launch per conv (source pass of conv l + node-local step of conv l - 1), one launch for the head's weight gradients and
-one fixed-order slab reduction.  Every launch goes through the library, so the step records into launch plans and hipGraphs.
+the sum over the layers.  ``model`` is ``lanegroup.Sequential`` with children ``module_{i}`` (as in gat.py).  Its forward is
+ONE autograd node (``_GINEFn``) on the launch schedule of lanegroup.py: one launch per conv forward (the head Linears fused into
+the last one), one fused backward launch per conv (source pass of conv l + node-local step of conv l - 1), one launch for the
+head's weight gradients and one fixed-order slab reduction.  Every launch goes through the library, so the step records into launch plans and hipGraphs.
 
 One intended deviation: the reference's constructor argument ``nn='mlp'`` shadows ``torch.nn``, so its ``nonlin='relu'`` and
 ``nonlin='tanh'`` raise (``'mlp'.ReLU()``); here they build ``torch.nn.ReLU`` / ``torch.nn.Tanh`` as the argument names say.  The
@@ -25,26 +25,19 @@ No gradient with respect to edge_attr; no CPU path.
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import List, Optional, Sequence
+import functools
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .gat import _NONLIN, _head, _MAX_SLABS
+from . import _lib, lanegroup
+from .lanegroup import MAX_CHANNELS, MAX_DENSE, MAX_EDGE_DIM
 from .ops import _require_gpu, _rows
 from .topology import get_topology
 
 _F32 = torch.float32
-MAX_CHANNELS = 32        # nn's input / output width and the head's input width (lane group of 8 / 16 / 32 lanes)
-MAX_EDGE_DIM = 16
-MAX_DENSE = 32           # head widths dim_dense and dim_out
-
-
-def _check_width(name: str, v: int, limit: int) -> None:
-    if not isinstance(v, int) or v < 1 or v > limit:
-        raise ValueError(f"{name} = {v}: the GINE kernels take 1 <= {name} <= {limit}")
+_check_width = functools.partial(lanegroup.check_width, "GINE")
 
 
 class GINEConv(nn.Module):
@@ -89,20 +82,6 @@ class GINEConv(nn.Module):
         return run_gine([self], None, "none", x, edge_index, edge_attr)
 
 
-class GINESequential(nn.Module):
-    """Stand-in for PyG's ``Sequential('x, edge_index, edge_attr', [...])`` as GINE_DSSE builds it: children ``module_{i}`` in
-    the list's order.  ``forward`` runs the fused route."""
-
-    def __init__(self, modules: Sequence[nn.Module], convs: Sequence[GINEConv], head: Sequence[nn.Linear], nonlin: str):
-        super().__init__()
-        for i, m in enumerate(modules):
-            self.add_module(f"module_{i}", m)
-        self.__dict__["_convs"], self.__dict__["_head"], self.__dict__["_nonlin"] = list(convs), list(head), nonlin
-
-    def forward(self, x, edge_index, edge_attr):
-        return run_gine(self._convs, self._head, self._nonlin, x, edge_index, edge_attr)
-
-
 class GINE_DSSE(nn.Module):
     """/root/reference/networks.py:71-111: ``num_layers - 1`` GINEConv layers sharing ONE Linear(dim_feat, dim_feat), each
     followed by the (shared) nonlinearity, then Linear(dim_feat, dim_dense) and Linear(dim_dense, dim_out)."""
@@ -130,14 +109,7 @@ class GINE_DSSE(nn.Module):
         else:
             raise ValueError("invalid nn type")
         # (the reference calls nn.ReLU() / nn.Tanh() on the string argument here; see the module docstring)
-        if nonlin == "relu":
-            self.nonlin = torch.nn.ReLU()
-        elif nonlin == "tanh":
-            self.nonlin = torch.nn.Tanh()
-        elif nonlin == "leaky_relu":
-            self.nonlin = torch.nn.LeakyReLU()
-        else:
-            raise ValueError("invalid activation type")
+        self.nonlin = lanegroup.nonlin_module(nonlin)
         if model != "gine":
             raise ValueError("invalid model type")
         layers, convs = [], []
@@ -146,7 +118,7 @@ class GINE_DSSE(nn.Module):
             convs.append(conv)
             layers += [conv, self.nonlin]
         head = [torch.nn.Linear(self.dim_hidden, self.dim_dense), torch.nn.Linear(self.dim_dense, self.dim_out)]
-        self.model = GINESequential(layers + head, convs, head, nonlin)
+        self.model = lanegroup.Sequential(layers + head, convs, head, nonlin, run_gine)
 
     def forward(self, x, edge_index, edge_attr):
         return self.model(x, edge_index, edge_attr)
@@ -159,12 +131,10 @@ def _up4(v: int) -> int:
     return (v + 3) // 4 * 4
 
 
-class _Spec:
+class _Spec(lanegroup.Spec):
     """Dimensions, slab layout and launch geometry of one conv stack (+ head)."""
 
     def __init__(self, convs, head, nonlin, n_nodes):
-        self.convs, self.head = convs, head
-        self.nonlin = _NONLIN[nonlin]
         self.nn = convs[0].nn if convs else None
         self.ed = (convs[0].edge_dim or 0) if convs else 0
         for cv in convs:
@@ -176,29 +146,13 @@ class _Spec:
         self.cout = self.nn.out_features if convs else 0
         if len(convs) > 1 and self.cin != self.cout:
             raise ValueError("GINE stack: a shared nn between layers needs in_features == out_features")
-        widths = [self.cin, self.cout] if convs else []
-        if head:
-            widths.append(head[0].in_features)
-            if head[0].out_features > MAX_DENSE or head[1].out_features > MAX_DENSE or head[1].in_features != head[0].out_features:
-                raise ValueError(f"GINE head: widths up to {MAX_DENSE}")
-            if convs and head[0].in_features != self.cout:
-                raise ValueError("GINE head: its input width must be the convs' output width")
-        if max(widths) > MAX_CHANNELS:
-            raise ValueError(f"GINE: channel width {max(widths)} above the limit {MAX_CHANNELS}")
-        self.group = 8 if max(widths) <= 8 else (16 if max(widths) <= 16 else 32)
+        if convs and head and head[0].in_features != self.cout:
+            raise ValueError("GINE head: its input width must be the convs' output width")
         # main slab row: per conv eps[1] (+ lin.weight [cin][ed], lin.bias [cin]), then the head; the shared nn's per-conv partials
         # go to a second slab [n_slabs][n_convs][nn_len]
-        self.offs, off = [], 0
-        for _ in convs:
-            self.offs.append(off)
-            off += 1 + (self.cin * self.ed + self.cin if self.ed else 0)
-        self.head_off = off
-        if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            off += d * c + d + o * d + o
-        self.total = off
+        cols = [1 + (self.cin * self.ed + self.cin if self.ed else 0)] * len(convs)
+        super().__init__("GINE", convs, head, nonlin, n_nodes, [self.cin, self.cout] if convs else [], cols)
         self.nn_len = self.cout * self.cin + self.cout
-        self.n_slabs = max(1, min(_MAX_SLABS, -(-n_nodes // (256 // self.group))))
 
 
 class _NoEdges:
@@ -275,16 +229,12 @@ def _conv(d, spec, ps, l, h, ldh, st, dz=None):
 class _GINEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ea, topo, spec, *ps):
-        L = _lib.lib()
         N, dev = topo.N, x.device
         x, ldx = _rows(x)
         ldea = 0
         if ea is not None:
             ea, ldea = _rows(ea)
-        sm = _lib.stream_ptr(dev)
-        convs, head = spec.convs, spec.head
-        n = len(convs)
-        hps = ps[2 + 3 * n:] if n else ps
+        n = len(spec.convs)
         states, hs = [], []
         h, ldh = x, ldx
         for _ in range(n):
@@ -292,27 +242,12 @@ class _GINEFn(torch.autograd.Function):
             states.append(st)
             hs.append((h, ldh))
             h, ldh = st["y"], spec.cout
-        hst, out = {}, None
-        if head:
-            hst["z1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
-            out = torch.empty(N, head[1].out_features, dtype=_F32, device=dev)
-        g = _graph(topo, spec, ea, ldea)
-        for l in range(n):
-            a = _lib.GineArgs()
-            a.g, a.group, a.has_lo = g, spec.group, 1
-            _conv(a.lo, spec, ps, l, hs[l][0], hs[l][1], states[l])
-            if head and l == n - 1:
-                a.has_head = 1
-                _head(a.head, head, hps, hst)
-                a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-            _lib.check(L.dss2_gine_forward(C.byref(a), sm), "dss2_gine_forward")
-        if n == 0:
-            a = _lib.GineArgs()
-            a.g, a.group, a.has_head = g, spec.group, 1
-            _head(a.head, head, hps, hst)
-            a.head.hin, a.head.ldhin = x.data_ptr(), ldx
-            a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-            _lib.check(L.dss2_gine_forward(C.byref(a), sm), "dss2_gine_forward")
+
+        def conv_into(d, l):
+            _conv(d, spec, ps, l, hs[l][0], hs[l][1], states[l])
+
+        hst, out = lanegroup.forward(spec, _graph(topo, spec, ea, ldea), _lib.GineArgs, "dss2_gine_forward", conv_into, x, ldx,
+                                     ps[2 + 3 * n:] if n else ps)
         if out is None:
             out = states[-1]["y"]
         # internal buffers live on ctx (never handed out, except the last conv's y of a head-less stack, whose backward does
@@ -325,71 +260,33 @@ class _GINEFn(torch.autograd.Function):
     def backward(ctx, gout):
         x, ea = ctx.saved_tensors
         topo, spec, ldx, ldea, states, hs, hst, ps = ctx.st
-        L = _lib.lib()
         N, dev = topo.N, gout.device
-        sm = _lib.stream_ptr(dev)
         gout, ldgo = _rows(gout)
-        convs, head = spec.convs, spec.head
-        n = len(convs)
-        hps = ps[2 + 3 * n:] if n else ps
-        need_dx = ctx.needs_input_grad[0]
+        head, n = spec.head, len(spec.convs)
         main = _up4(spec.n_slabs * spec.total)
         buf = torch.empty(main + spec.n_slabs * n * spec.nn_len, dtype=_F32, device=dev)
         slab, nslab = buf[:main], buf[main:]
         flat = torch.empty(_up4(spec.total) + spec.nn_len, dtype=_F32, device=dev)
         fnn = flat[_up4(spec.total):]
         dzs = [torch.empty(N, spec.cin, dtype=_F32, device=dev) for _ in range(min(n, 2))]
-        cin0 = spec.cin if n else head[0].in_features
-        dx = torch.empty(N, cin0, dtype=_F32, device=dev) if need_dx else None
-        if head:
-            hst["dz1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
-        g = _graph(topo, spec, ea, ldea, slab, nslab)
+        dx = torch.empty(N, x.size(1), dtype=_F32, device=dev) if ctx.needs_input_grad[0] else None
 
         def conv_into(d, l):
             _conv(d, spec, ps, l, hs[l][0], hs[l][1], states[l], dzs[l % 2])
 
-        # launch 1: head backward (or the output gradient) + the node-local step of the last conv
-        a = _lib.GineArgs()
-        a.g, a.group = g, spec.group
-        if head:
-            a.has_head = 1
-            _head(a.head, head, hps, hst)
-            a.head.gout, a.head.ldgo, a.head.dz1 = gout.data_ptr(), ldgo, hst["dz1"].data_ptr()
-        else:
-            a.gy, a.ldgy = gout.data_ptr(), ldgo
-        if n:
-            a.has_lo = 1
-            conv_into(a.lo, n - 1)
-        else:
-            a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
-        _lib.check(L.dss2_gine_backward(C.byref(a), sm), "dss2_gine_backward")
-        # source pass of conv l fused with the node-local step of conv l - 1; the last one writes dx
-        for l in range(n - 1, -1, -1):
-            a = _lib.GineArgs()
-            a.g, a.group, a.has_up = g, spec.group, 1
-            conv_into(a.up, l)
-            if l > 0:
-                a.has_lo = 1
-                conv_into(a.lo, l - 1)
-            else:
-                a.dh, a.dh_cols = (dx.data_ptr() if dx is not None else None), cin0
-            _lib.check(L.dss2_gine_backward(C.byref(a), sm), "dss2_gine_backward")
+        # head backward (or the output gradient) + the node-local step of the last conv, then per conv l its source pass fused
+        # with the node-local step of conv l - 1; the last one writes dx
+        lanegroup.backward(spec, _graph(topo, spec, ea, ldea, slab, nslab), _lib.GineArgs, "dss2_gine_backward", conv_into, gout,
+                           ldgo, ps[2 + 3 * n:] if n else ps, hst, dx)
         # the head's outer-product weight gradients, then ONE fixed-order reduction of both slabs
         if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            hin, ldhin = (states[-1]["y"], c) if n else (x, ldx)
-            w = _lib.GatWgradArgs()
-            jobs = [(hst["dz1"], d, hin, ldhin, d, c, spec.head_off), (gout, ldgo, hst["z1"], d, o, d, spec.head_off + d * c + d)]
-            for jd, (Gm, ldg, Xm, ldxm, gw, xw, col) in zip(w.jobs, jobs):
-                jd.G, jd.ldg, jd.X, jd.ldx, jd.gw, jd.xw, jd.col = Gm.data_ptr(), ldg, Xm.data_ptr(), ldxm, gw, xw, col
-            w.slab, w.n_nodes, w.n_slabs, w.slab_len, w.n_jobs = slab.data_ptr(), N, spec.n_slabs, spec.total, len(jobs)
-            _lib.check(L.dss2_gat_wgrad(C.byref(w), sm), "dss2_gat_wgrad")
+            lanegroup.wgrad(lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo), slab, spec, N, dev)
         rd = (_lib.ReduceDesc * 2)()
         rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
         if n:
             rd[1].slab, rd[1].out, rd[1].stride, rd[1].len = nslab.data_ptr(), fnn.data_ptr(), spec.nn_len, spec.nn_len
             rd[1].n_slabs = spec.n_slabs * n
-        _lib.check(L.dss2_reduce_slabs_multi(rd, 2 if n else 1, sm), "dss2_reduce_slabs_multi")
+        _lib.check(_lib.lib().dss2_reduce_slabs_multi(rd, 2 if n else 1, _lib.stream_ptr(dev)), "dss2_reduce_slabs_multi")
         grads = []
         if n:
             ci, co = spec.cin, spec.cout
@@ -398,10 +295,5 @@ class _GINEFn(torch.autograd.Function):
                 off, ed = spec.offs[l], spec.ed
                 grads.append(flat[off:off + 1])
                 grads += [flat[off + 1:off + 1 + ci * ed].view(ci, ed), flat[off + 1 + ci * ed:off + 1 + ci * ed + ci]] if ed else [None, None]
-        if head:
-            c, d, o = head[0].in_features, head[0].out_features, head[1].out_features
-            hoff = spec.head_off
-            grads += [flat[hoff:hoff + d * c].view(d, c), flat[hoff + d * c:hoff + d * c + d],
-                      flat[hoff + d * c + d:hoff + d * c + d + o * d].view(o, d), flat[hoff + d * c + d + o * d:spec.total]]
-        grads = [gr if ctx.needs_input_grad[4 + k] else None for k, gr in enumerate(grads)]
-        return (dx, None, None, None, *grads)
+        grads += lanegroup.head_grads(spec, flat)
+        return lanegroup.backward_result(ctx, dx, grads)

@@ -737,6 +737,25 @@ int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, in
                           float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev,
                           uint32_t* counter, void* stream);
 
+/* ---- shared by the lane-group models GAT_DSSE and GINE_DSSE: the head Linears and the outer-product weight gradients ------- *
+ * The head runs inside each model's launches (csrc/dss2_lanegroup.hpp); dss2_lanegroup_wgrad is csrc/dss2_lanegroup.hip.         */
+typedef struct dss2_lanegroup_head {       /* Linear(c, dense) -> Linear(dense, nout) on the last conv's output (or on hin) */
+  const float* W1; const float* b1; const float* W2; const float* b2;
+  const float* hin; int64_t ldhin;         /* head input when the launch has no conv (num_layers = 1) */
+  float* z1; float* out; int64_t ldo;      /* forward: hidden [N][dense], output [N][nout] */
+  const float* gout; int64_t ldgo; float* dz1;   /* backward: output gradient, hidden gradient [N][dense] */
+  int32_t c; int32_t dense; int32_t nout; int32_t pad_;
+} dss2_lanegroup_head;
+#define DSS2_LANEGROUP_WGRAD_MAX_JOBS 16
+typedef struct dss2_lanegroup_wgrad_job {  /* slab[s][col + o * xw + k] = sum_n G[n][o] X[n][k], then [col + gw * xw + o] = sum_n G[n][o] */
+  const float* G; int64_t ldg; const float* X; int64_t ldx; int32_t gw; int32_t xw; int32_t col; int32_t pad_;
+} dss2_lanegroup_wgrad_job;
+typedef struct dss2_lanegroup_wgrad_args { /* node chunk s of ceil(N / n_slabs) rows -> slab row s */
+  dss2_lanegroup_wgrad_job jobs[DSS2_LANEGROUP_WGRAD_MAX_JOBS];
+  float* slab; int64_t n_nodes; int32_t n_slabs; int32_t slab_len; int32_t n_jobs; int32_t pad_;
+} dss2_lanegroup_wgrad_args;
+int dss2_lanegroup_wgrad(const dss2_lanegroup_wgrad_args* args_host, void* stream);
+
 /* ---- GATv2 (PyG GATv2Conv, heads = 1) and the GAT_DSSE model (reference networks.py:113-156), csrc/dss2_gat.hip ------------ *
  * Graph: the Topology of the edge list AS GIVEN (no doubling): CSR by target (rowptr / col = source / ent = stored edge id) and by  *
  * source (rowptrT / colT = target / entT).  add_self_loops != 0: entries with source == target are skipped and one self loop per   *
@@ -759,22 +778,15 @@ typedef struct dss2_gat_conv {
   const float* att; const float* bias; const float* Wl; const float* bl; const float* Wr; const float* br; const float* We;  /* bias, bl, br, We may be NULL */
   const float* h; int64_t ldh;             /* layer input [N][cin] */
   float* y; float* m; float* s;            /* forward: output after the nonlinearity [N][cout]; per-target softmax max / sum [N] */
-  float* dxl; float* dxr;                  /* backward: d x_l, d x_r [N][cout] (kept for dss2_gat_wgrad) */
+  float* dxl; float* dxr;                  /* backward: d x_l, d x_r [N][cout] (kept for dss2_lanegroup_wgrad) */
   float* dedge; float* dself;              /* backward: per-edge [E][cout] / self-loop [N][cout] d x_l contributions */
   int32_t cin; int32_t cout; int32_t slab_off; int32_t pad_;
 } dss2_gat_conv;
-typedef struct dss2_gat_head {             /* Linear(c, dense) -> Linear(dense, nout) on the last conv's output (or on hin) */
-  const float* W1; const float* b1; const float* W2; const float* b2;
-  const float* hin; int64_t ldhin;         /* head input when the launch has no conv (num_layers = 1) */
-  float* z1; float* out; int64_t ldo;      /* forward: hidden [N][dense], output [N][nout] */
-  const float* gout; int64_t ldgo; float* dz1;   /* backward: output gradient, hidden gradient [N][dense] */
-  int32_t c; int32_t dense; int32_t nout; int32_t pad_;
-} dss2_gat_head;
 typedef struct dss2_gat_args {
   dss2_gat_graph g;
   dss2_gat_conv up;                        /* backward: the layer whose SOURCE pass this launch runs (has_up) */
   dss2_gat_conv lo;                        /* the layer whose TARGET pass this launch runs (has_lo): forward, or backward */
-  dss2_gat_head head;
+  dss2_lanegroup_head head;
   int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
   const float* gy; int64_t ldgy;           /* backward without head / up: gradient of lo's output */
   float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */
@@ -783,15 +795,6 @@ typedef struct dss2_gat_args {
 int dss2_gat_forward(const dss2_gat_args* args_host, void* stream);
 /* backward: (head backward | up's source pass | gy), then lo's target pass, or the input gradient into dh */
 int dss2_gat_backward(const dss2_gat_args* args_host, void* stream);
-#define DSS2_GAT_MAX_JOBS 16
-typedef struct dss2_gat_wgrad_job {        /* slab[s][col + o * xw + k] = sum_n G[n][o] X[n][k], then [col + gw * xw + o] = sum_n G[n][o] */
-  const float* G; int64_t ldg; const float* X; int64_t ldx; int32_t gw; int32_t xw; int32_t col; int32_t pad_;
-} dss2_gat_wgrad_job;
-typedef struct dss2_gat_wgrad_args {      /* node chunk s of ceil(N / n_slabs) rows -> slab row s */
-  dss2_gat_wgrad_job jobs[DSS2_GAT_MAX_JOBS];
-  float* slab; int64_t n_nodes; int32_t n_slabs; int32_t slab_len; int32_t n_jobs; int32_t pad_;
-} dss2_gat_wgrad_args;
-int dss2_gat_wgrad(const dss2_gat_wgrad_args* args_host, void* stream);
 
 /* ---- GINE (PyG GINEConv, nn = one Linear) and the GINE_DSSE model (reference networks.py:71-111), csrc/dss2_gine.hip -------- *
  * Graph: the Topology of the edge list AS GIVEN (no doubling, no self loops added or removed), CSR by target and by source as for  *
@@ -821,7 +824,7 @@ typedef struct dss2_gine_args {
   dss2_gine_graph g;
   dss2_gine_conv up;                       /* backward: the conv whose SOURCE pass this launch runs (has_up) */
   dss2_gine_conv lo;                       /* forward: the conv; backward: the conv whose node-local step this launch runs */
-  dss2_gat_head head;                      /* the two head Linears (the GAT head's descriptor) */
+  dss2_lanegroup_head head;                /* the two head Linears */
   int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
   const float* gy; int64_t ldgy;           /* backward without head / up: gradient of lo's output */
   float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */

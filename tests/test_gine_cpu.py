@@ -181,11 +181,18 @@ def test_runner_builds_the_driver_line_and_the_cli_accepts_it(pkg):
 
 
 def test_struct_layouts_match_the_header_sizes(pkg):
-    """ctypes mirrors of the GINE structs: same sizes and field offsets as the C compiler's layout (probe compiled with gcc)."""
+    """ctypes mirrors of the lane-group structs (GINE, GAT and the shared head / wgrad): same sizes and field offsets as the C
+    compiler's layout (probe compiled with gcc)."""
     L = pkg._lib
     fields = {"dss2_gine_graph": (L.GineGraph, ["ea", "n_nodes", "slab", "nslab", "nslab_len"]),
               "dss2_gine_conv": (L.GineConv, ["eps", "h", "ldh", "dz", "cin", "nn_off"]),
-              "dss2_gine_args": (L.GineArgs, ["up", "lo", "head", "has_up", "group", "gy", "dh", "dh_cols"])}
+              "dss2_gine_args": (L.GineArgs, ["up", "lo", "head", "has_up", "group", "gy", "dh", "dh_cols"]),
+              "dss2_gat_graph": (L.GatGraph, ["ea", "ldea", "n_nodes", "add_self_loops", "slope", "nonlin", "slab", "slab_len"]),
+              "dss2_gat_conv": (L.GatConv, ["We", "h", "ldh", "y", "s", "dxl", "dself", "cin", "slab_off"]),
+              "dss2_gat_args": (L.GatArgs, ["up", "lo", "head", "has_up", "group", "gy", "dh", "dh_cols"]),
+              "dss2_lanegroup_head": (L.LanegroupHead, ["hin", "ldhin", "z1", "ldo", "gout", "dz1", "c", "nout"]),
+              "dss2_lanegroup_wgrad_job": (L.LanegroupWgradJob, ["ldg", "X", "ldx", "gw", "col"]),
+              "dss2_lanegroup_wgrad_args": (L.LanegroupWgradArgs, ["jobs", "slab", "n_nodes", "n_slabs", "n_jobs"])}
     lines = []
     for cname, (_, fs) in fields.items():
         lines.append(f'printf("%zu\\n", sizeof({cname}));')
@@ -201,3 +208,4 @@ def test_struct_layouts_match_the_header_sizes(pkg):
         want += [getattr(cls, f).offset for f in fs]
     assert got == want
     assert "dss2_gine_forward" in L.EXPORTED_SYMBOLS and "dss2_gine_backward" in L.EXPORTED_SYMBOLS
+    assert "dss2_lanegroup_wgrad" in L.EXPORTED_SYMBOLS
