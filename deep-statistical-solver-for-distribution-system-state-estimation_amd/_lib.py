@@ -215,6 +215,30 @@ class GineArgs(C.Structure):
                 ("dh", C.c_void_p), ("dh_cols", C.c_int32), ("pad_", C.c_int32)]
 
 
+GNN_GCN2, GNN_FA, GNN_TAG = 1, 2, 3
+GNN_MAX_K = 4
+
+
+class GnnGraph(C.Structure):
+    _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("rowptrT", C.c_void_p), ("colT", C.c_void_p),
+                ("entT", C.c_void_p), ("dis", C.c_void_p), ("n_nodes", C.c_int64), ("ed", C.c_int32), ("loops", C.c_int32),
+                ("nonlin", C.c_int32), ("pad_", C.c_int32), ("slab", C.c_void_p), ("n_slabs", C.c_int32), ("slab_len", C.c_int32)]
+
+
+class GnnConv(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("K", C.c_int32), ("W", C.c_void_p * (GNN_MAX_K + 1)), ("bias", C.c_void_p),
+                ("h", C.c_void_p), ("ldh", C.c_int64), ("x0", C.c_void_p), ("ldx0", C.c_int64), ("param", C.c_float),
+                ("c", C.c_int32), ("y", C.c_void_p), ("u", C.c_void_p), ("d", C.c_void_p), ("se", C.c_void_p), ("sn", C.c_void_p),
+                ("part", C.c_void_p), ("slab_off", C.c_int32), ("pad_", C.c_int32)]
+
+
+class GnnArgs(C.Structure):
+    _fields_ = [("g", GnnGraph), ("up", GnnConv), ("lo", GnnConv), ("head", LanegroupHead), ("has_up", C.c_int32),
+                ("has_lo", C.c_int32), ("has_head", C.c_int32), ("group", C.c_int32), ("hop", C.c_int32), ("dx0_first", C.c_int32),
+                ("rin", C.c_void_p), ("rout", C.c_void_p), ("gy", C.c_void_p), ("ldgy", C.c_int64), ("dh", C.c_void_p),
+                ("dh_cols", C.c_int32), ("pad_", C.c_int32), ("dx0", C.c_void_p)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "dss2_last_error": (C.c_char_p, []),
@@ -327,6 +351,9 @@ _SIGNATURES = {
     "dss2_lanegroup_wgrad": (C.c_int, [C.POINTER(LanegroupWgradArgs), C.c_void_p]),
     "dss2_gine_forward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
     "dss2_gine_backward": (C.c_int, [C.POINTER(GineArgs), C.c_void_p]),
+    "dss2_gnn_forward": (C.c_int, [C.POINTER(GnnArgs), C.c_void_p]),
+    "dss2_gnn_backward": (C.c_int, [C.POINTER(GnnArgs), C.c_void_p]),
+    "dss2_gnn_dis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

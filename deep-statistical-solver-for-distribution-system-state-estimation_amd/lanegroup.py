@@ -62,6 +62,14 @@ class Sequential(nn.Module):
         return self._run(self._convs, self._head, self._nonlin, x, edge_index, edge_attr)
 
 
+class SequentialX0(Sequential):
+    """``Sequential('x, x_0, edge_index', [...])`` as ``gnn_dsse`` builds it: the same children and naming, called with the
+    model input ``x_0`` beside ``x``; ``forward`` runs ``run(convs, head, nonlin, x, x_0, edge_index)``."""
+
+    def forward(self, x, x_0, edge_index):
+        return self._run(self._convs, self._head, self._nonlin, x, x_0, edge_index)
+
+
 def head_dims(head):
     """(c, dense, nout) of the two head Linears."""
     return head[0].in_features, head[0].out_features, head[1].out_features

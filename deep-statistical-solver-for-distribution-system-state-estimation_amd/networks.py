@@ -305,16 +305,21 @@ class MessagePassing(nn.Module):
 
 class TAGConv(nn.Module):
     """PyG TAGConv(in, out, K, bias=True, normalize=True) on the fused HIP kernel.
-    state_dict keys: ``bias``, ``lins.k.weight`` (k = 0..K)."""
+    state_dict keys: ``bias`` (not with bias=False), ``lins.k.weight`` (k = 0..K).  bias=False runs on gnn.py's kernels
+    (in == out <= 32, K <= 4); normalize=False is taken only inside gnn_dsse (ValueError standalone)."""
 
-    def __init__(self, in_channels: int, out_channels: int, K: int = 3):
+    def __init__(self, in_channels: int, out_channels: int, K: int = 3, bias: bool = True, normalize: bool = True):
         super().__init__()
         if K < 0:
             raise ValueError("TAGConv: K >= 0")
         # K <= 3: the fused tile GEMM + Horner kernels (templated on K + 1 <= 4 matrices); K > 3: ONE plain tile GEMM
         # X [W_0 | .. | W_K]^T and K propagation hops in global memory (the path of graphs beyond the LDS-resident tiles)
         self.in_channels, self.out_channels, self.K = in_channels, out_channels, K
-        self.bias = nn.Parameter(torch.zeros(out_channels))
+        self.normalize = normalize
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
         self.lins = nn.ModuleList([nn.Linear(in_channels, out_channels, bias=False) for _ in range(K + 1)])
         self._plan = None
 
@@ -322,6 +327,11 @@ class TAGConv(nn.Module):
         return [l.weight for l in self.lins]
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        if not self.normalize:
+            raise ValueError("TAGConv: normalize=False is supported only inside gnn_dsse(model='tagcn')")
+        if self.bias is None:
+            from .gnn import run_gnn
+            return run_gnn([self], None, "none", x, x, edge_index)
         _require_gpu(x, edge_index)
         topo = get_topology_asis(edge_index, x.size(0))
         return _TAGConvFn.apply(x, topo, self, self.bias, *self._weights())
@@ -1009,3 +1019,5 @@ class SkipPFN(PFN):
 from .gat import GATv2Conv, GAT_DSSE  # noqa: E402,F401
 # the reference's GIN model (networks.py:71-111), defined in gine.py on its own kernels
 from .gine import GINEConv, GINE_DSSE  # noqa: E402,F401
+# the reference's GCN2 / FA / TAG model (networks.py:11-69), defined in gnn.py on its own kernels
+from .gnn import GCN2Conv, FAConv, gnn_dsse  # noqa: E402,F401

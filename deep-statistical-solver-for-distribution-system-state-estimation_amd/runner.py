@@ -29,8 +29,11 @@ REG_COEFS = {"mu_v": 1e-1, "mu_theta": 1e-1, "lam_v": 1e-4, "lam_p": 1e-8, "lam_
 HYPER = {"dim_nodes": 8, "dim_lines": 6, "dim_out": 2, "dim_hid": 32, "gnn_layers": 8, "K": 2, "dropout_rate": 0.3, "L": 5, "heads": 1}
 
 
-def build_model(name: str, hp: Dict) -> torch.nn.Module:
+def build_model(name: str, hp: Dict, gnn_model: str = "gcn2") -> torch.nn.Module:
     cls = getattr(networks, name)
+    if name == "gnn_dsse":     # dss2_run.py:86 with the third model family; cached=False so a short last batch works
+        return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], num_layers=hp["gnn_layers"],
+                   K=hp["K"], model=gnn_model, cached=False)
     if name == "GAT_DSSE":     # dss2_run.py:86
         return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], heads=hp["heads"],
                    num_layers=hp["gnn_layers"], edge_dim=hp["dim_lines"])
@@ -39,6 +42,13 @@ def build_model(name: str, hp: Dict) -> torch.nn.Module:
                    edge_dim=hp["dim_lines"])
     a = (hp["dim_nodes"], hp["dim_lines"], hp["dim_out"], hp["dim_hid"], hp["gnn_layers"], hp["K"], hp["dropout_rate"])
     return cls(*a, hp["L"]) if name in ("PFN", "SkipPFN") else cls(*a)
+
+
+def run_model(model, x, ei, ea):
+    """The model's forward on a batch: gnn_dsse takes (x, edge_index), every other model (x, edge_index, edge_attr)."""
+    if isinstance(model, networks.gnn_dsse):
+        return model(x, ei)
+    return model(x, ei, ea)
 
 
 def make_loaders(case: str, n_graphs: int, batch_size: int, device, seed: int = 0, split: float = 0.9):
@@ -71,7 +81,7 @@ def train_epoch(model, opt, loader, stats, reg_coefs, group=None) -> float:
     for data in loader:                                              # dss2_run.py:134-144
         opt.zero_grad()
         x, ei, ea, _, num_graphs = _fields(data)
-        out = model(x[:, :8], ei, ea[:, :6])
+        out = run_model(model, x[:, :8], ei, ea[:, :6])
         loss = dss2_data.gsp_wls_edge(input=x[:, :8], edge_input=ea[:, :6], output=out, x_mean=stats[0], x_std=stats[1],
                                       edge_mean=stats[2], edge_std=stats[3], edge_index=ei, reg_coefs=reg_coefs,
                                       num_samples=num_graphs, node_param=x[:, 8:], edge_param=ea[:, 6:], group=group)
@@ -105,7 +115,7 @@ class GraphedTrainer:
         def step_fn():
             for p in params:
                 p.grad = None
-            out = model(sx[:, :8], sei, sea[:, :6])
+            out = run_model(model, sx[:, :8], sei, sea[:, :6])
             loss = dss2_data.gsp_wls_edge(input=sx[:, :8], edge_input=sea[:, :6], output=out, x_mean=st[0], x_std=st[1],
                                           edge_mean=st[2], edge_std=st[3], edge_index=sei, reg_coefs=reg, num_samples=None,
                                           node_param=sx[:, 8:], edge_param=sea[:, 6:], group=group)
@@ -224,7 +234,7 @@ class EpochTrainer:
             ds.collate_into(descs, ids, nb, cursor=cursor, advance=True)
             for p in params:
                 p.grad = None
-            out = model(sx[:, :8], ei, sea[:, :6])
+            out = run_model(model, sx[:, :8], ei, sea[:, :6])
             loss = dss2_data.gsp_wls_edge(input=sx[:, :8], edge_input=sea[:, :6], output=out, x_mean=st[0], x_std=st[1],
                                           edge_mean=st[2], edge_std=st[3], edge_index=ei, reg_coefs=reg, num_samples=None,
                                           node_param=sx[:, 8:], edge_param=sea[:, 6:], group=group)
@@ -271,7 +281,7 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
     n = 0
     for data in loader:
         x, ei, ea, y, _ = _fields(data)
-        out = model(x[:, :8], ei, ea[:, :6])
+        out = run_model(model, x[:, :8], ei, ea[:, :6])
         dss2_data.eval_batch(out, y, x, ei, ea, stats[0], stats[1], acc)
         n += 1
     vals = (acc / max(n, 1)).cpu().tolist()
@@ -281,7 +291,8 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", default="cigre14", choices=["cigre14", "cigre14_reswitched", "ober_sub", "ober179"])
-    ap.add_argument("--model", default="SkipPFN", choices=["MPN", "SkipMPN", "PFN", "SkipPFN", "GAT_DSSE", "GINE_DSSE"])
+    ap.add_argument("--model", default="SkipPFN", choices=["MPN", "SkipMPN", "PFN", "SkipPFN", "GAT_DSSE", "GINE_DSSE"] + ["gnn_dsse"])
+    ap.add_argument("--gnn-model", default="gcn2", choices=["gcn2", "fagcn", "tagcn"], help="gnn_dsse's conv kind")
     ap.add_argument("--graphs", type=int, default=720)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=600)
@@ -313,7 +324,7 @@ def main(argv=None):
         stats = tuple(stats)
     else:
         train_loader, test_loader, stats = make_loaders(a.case, a.graphs, a.batch_size, dev, a.seed)
-    model = build_model(a.model, hp).to(dev)
+    model = build_model(a.model, hp, gnn_model=a.gnn_model).to(dev)
     single_topology = (not a.data_folder) or bool(getattr(train_loader.dataset, "shared_topology", False))
     use_graph = (a.graph == 1) or (a.graph == -1 and single_topology and hp["dim_out"] == 2)
     opt = FusedAdamax(model.parameters(), lr=a.lr, capturable=use_graph)

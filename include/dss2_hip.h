@@ -834,6 +834,66 @@ int dss2_gine_forward(const dss2_gine_args* args_host, void* stream);
 /* backward: (head backward | up's source pass | gy), then lo's node-local step, or the input gradient into dh */
 int dss2_gine_backward(const dss2_gine_args* args_host, void* stream);
 
+/* ---- gnn_dsse (reference networks.py:11-69): PyG GCN2Conv, FAConv and TAGConv, csrc/dss2_gnn.hip ------------------------- *
+ * Graph: the Topology of the edge list AS GIVEN, CSR by target and by source as for GAT, and dis[N], gcn_norm's deg^-1/2 built  *
+ * once per structure by dss2_gnn_dis.  Edge weight w_e = dis[src] dis[dst].  loops != 0 (add_remaining_self_loops): entries with *
+ * src == dst are skipped and every node with dis != 0 gets one loop of weight dis^2.  Every conv maps c -> c channels, c <= group *
+ * (8 / 16 / 32); TAG K <= DSS2_GNN_MAX_K; head widths <= 32.  The grid is n_slabs workgroups; every launch that produces weight-   *
+ * gradient partials writes its columns of ALL n_slabs rows of `slab`.  Slab columns of a conv at slab_off (its parameter order):   *
+ *   GCN2  weight1[c][c] (, weight2[c][c]) -- written by its local step                                                            *
+ *   FA    att_l.weight[c] (written by its source pass), att_r.weight[c] (by its local step)                                       *
+ *   TAG   bias[c], lins.k.weight[c][c] for k = 0..K -- written by its local step (bias columns written even without a bias)       *
+ * of the head at its offset: W1[dense][c], b1[dense], W2[nout][dense], b2[nout].                                                  */
+#define DSS2_GNN_GCN2 1
+#define DSS2_GNN_FA 2
+#define DSS2_GNN_TAG 3
+#define DSS2_GNN_MAX_K 4
+typedef struct dss2_gnn_graph {
+  const int32_t* rowptr; const int32_t* col; const int32_t* ent;
+  const int32_t* rowptrT; const int32_t* colT; const int32_t* entT;
+  const float* dis;                        /* [n_nodes] */
+  int64_t n_nodes; int32_t ed;             /* ed: 0 (no edge attributes; the shared lane-group checks read it) */
+  int32_t loops;
+  int32_t nonlin;                          /* after every conv: 0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 Tanh */
+  int32_t pad_;
+  float* slab; int32_t n_slabs; int32_t slab_len;
+} dss2_gnn_graph;
+typedef struct dss2_gnn_conv {
+  int32_t kind; int32_t K;                 /* DSS2_GNN_*; K: TAG's hop count */
+  const float* W[DSS2_GNN_MAX_K + 1];      /* GCN2: weight1, weight2 (NULL: shared); FA: att_l, att_r [c]; TAG: lins.k.weight [c][c] */
+  const float* bias;                       /* TAG bias [c] or NULL */
+  const float* h; int64_t ldh;             /* conv input [N][c] */
+  const float* x0; int64_t ldx0;           /* the model input x_0 [N][c] (GCN2, FA) */
+  float param;                             /* GCN2 alpha, FA eps */
+  int32_t c;
+  float* y;                                /* forward: output after the nonlinearity [N][c] */
+  float* u;                                /* forward: GCN2 the product's input [N][c]; TAG P^k h for k = 1..K [K][N][c] */
+  float* d;                                /* backward: GCN2 du [N][c]; FA dv [N][c]; TAG g_k = dv W_k [K + 1][N][c] */
+  float* se; float* sn;                    /* backward, FA: s_e per edge [E], s of the added loop per node [N] */
+  float* part;                             /* backward, FA: the node-local part of the input gradient [N][c] */
+  int32_t slab_off; int32_t pad_;
+} dss2_gnn_conv;
+typedef struct dss2_gnn_args {
+  dss2_gnn_graph g;
+  dss2_gnn_conv up;                        /* backward: the conv whose SOURCE pass / adjoint hop this launch runs (has_up) */
+  dss2_gnn_conv lo;                        /* forward: the conv; backward: the conv whose node-local step this launch runs */
+  dss2_lanegroup_head head;                /* the two head Linears */
+  int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
+  int32_t hop; int32_t dx0_first;          /* TAG: forward hop 1..K (0 when K = 0), backward adjoint hop K - 1..0 */
+  const float* rin; float* rout;           /* TAG backward: r of hop + 1 (g_K for the first hop; NULL when K = 0), r of hop > 0 */
+  const float* gy; int64_t ldgy;           /* backward without head / up: gradient of lo's output */
+  float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */
+  float* dx0;                              /* backward: with lo, the x_0-path gradient [N][c] (written when dx0_first, else added);
+                                              without lo, added into dh (NULL: not) */
+} dss2_gnn_args;
+/* forward: lo's hop / aggregation, product and nonlinearity, then the head when has_head (or the head alone on head.hin) */
+int dss2_gnn_forward(const dss2_gnn_args* args_host, void* stream);
+/* backward: (head backward | up's source pass or adjoint hop | gy), then lo's local step, or the input gradient into dh */
+int dss2_gnn_backward(const dss2_gnn_args* args_host, void* stream);
+/* dis[i] = deg_i^-1/2 (0 when deg_i = 0) over the CSR by target: mode 0 all ones (normalize = False), 1 every entry counts,
+ * 2 entries with col == i dropped and one loop added (add_remaining_self_loops) */
+int dss2_gnn_dis(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int mode, float* dis, void* stream);
+
 /* LDS bytes a dss2_gemm_prop / dss2_wgrad launch will request (host-side helper; lets the
  * caller reject configurations that do not fit the 160 KiB LDS before launching). */
 size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width);

@@ -60,9 +60,20 @@ def count_launches(fn):
     return n, r
 
 
+def describe(name):
+    """The constructor call runner.build_model makes for a --models entry."""
+    base, _, kind = name.partition(":")
+    if base in ("GINE_DSSE", "GAT_DSSE"):
+        return f"{base}(8, 32, 2, 8, 6)"
+    if base == "gnn_dsse":
+        return f"gnn_dsse(8, 32, 2, 8, K=2, model='{kind or 'gcn2'}', cached=False)"
+    return base
+
+
 def model_and_opt(name, capturable, seed=0):
     torch.manual_seed(seed)
-    m = pkg.runner.build_model(name, pkg.runner.HYPER).to(DEV)
+    base, _, kind = name.partition(":")       # gnn_dsse:gcn2 / gnn_dsse:fagcn / gnn_dsse:tagcn
+    m = pkg.runner.build_model(base, pkg.runner.HYPER, gnn_model=kind or "gcn2").to(DEV)
     return m, pkg.FusedAdamax(m.parameters(), lr=3e-3, capturable=capturable)
 
 
@@ -86,11 +97,11 @@ def bench(name, grid, B, steps, warmup):
 
     m, o = model_and_opt(name, False)
     res["eager_ms"] = timed(lambda: pkg.runner.train_epoch(m, o, [batch], st, REG), steps, warmup)
-    out = m(x[:, :8], ei, ea[:, :6])
+    out = pkg.runner.run_model(m, x[:, :8], ei, ea[:, :6])
     g = torch.ones_like(out)
     out.backward(g)
     torch.cuda.synchronize()
-    res["launches_forward"], out = count_launches(lambda: m(x[:, :8], ei, ea[:, :6]))
+    res["launches_forward"], out = count_launches(lambda: pkg.runner.run_model(m, x[:, :8], ei, ea[:, :6]))
     res["launches_backward"], _ = count_launches(lambda: out.backward(g))
 
     m, o = model_and_opt(name, True)
@@ -113,7 +124,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--models", default="GINE_DSSE,GAT_DSSE")
     a = ap.parse_args()
-    print(json.dumps({"device": torch.cuda.get_device_name(0), "models": "GINE_DSSE(8, 32, 2, 8, 6), GAT_DSSE(8, 32, 2, 8, 6)",
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "models": ", ".join(describe(m) for m in a.models.split(",")),
                       "steps": a.steps, "warmup": a.warmup, "repeats": 5, "statistic": "median of per-step means"}), flush=True)
     for cfg in a.configs.split(","):
         grid, B = cfg.split(":")
