@@ -17,6 +17,18 @@
 // launch geometry: same inputs, same bits.  Inf / NaN inputs give Inf / NaN outputs as they should (the maxima ignore NaN).
 // LDS: 2 x 8 KB fp32 G / P G + 24 KB planes of G, P G, P^2 G + 16 KB planes of X + ELL = 58 KB, two workgroups per CU.
 // 36 MFMAs per tile and wave instead of 72, 7 VALU per split pair instead of 11.
+//
+// The hops on the matrix pipe (HM = true, the default; args.mfma_bf16 bit 16 set = the gathered fp32 form, DSS2_WGRAD_HOPS_MFMA=0).
+// A hop P Z of a 32-row tile contracts over the tile's rows like dW itself, so the transposed planes of Z ARE its B operand: 8 consecutive
+// rows of one column per lane, the 16-byte chunk the MFMA phase reads.  P of the tile is built per tile as two fp16 planes [row][32 k]
+// (4 KB, zero-filled, the ELL entries scattered into it; entries of one row that name the same node are summed first, the lowest slot
+// writes), scaled by 2^(14 - hb): a weight is at most the propagation's gain <= 2^hb, so the planes cannot overflow, and the lo piece of
+// a weight down to 2^(hb - 28) of that bound stays a normal fp16 (unscaled, the lo piece of every weight below 2^-3 would be subnormal).
+// Per wave a hop is 2 blocks of v_mfma_f32_16x16x32_f16 x 3 (lo hi + hi lo + hi hi, one k-step); the accumulator holds 4 consecutive
+// rows of one column, 8 bytes per plane of the output image.  P's scale is taken out before the split, so the planes of P Z hold
+// 2^(14 - hb - Eg) P Z exactly as in the gathered form: |P Z| <= gain |Z| and |P^2 Z| <= gain^2 |Z| <= 2^hb max |G|, which is what hb was
+// made for -- the hop outputs stay below 2^15.  Hop 2 reads hop 1's SPLIT result (22 bits), not its fp32 value.
+// LDS: 24 KB + 16 KB planes + 4 KB P = 44 KB; no fp32 images, no ELL slice.
 // Built without packed fp32 VALU ops like the other MFMA-beside-VALU translation units (build.sh).
 #include <stdlib.h>
 
@@ -60,7 +72,27 @@ __device__ __forceinline__ void store_planes_h(char* img, int off0, const f32x4 
   }
 }
 
-template <int NMAT, bool RS2>
+// lane j of a 16-lane MFMA row <-> column of the workgroup's 64 that wave wv's hop blocks own.  Bits 3 and 4 of the column (the image's
+// swizzle key) run over the four 4-lane sets in the order 0, 2, 3, 1: the four 16-lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...)
+// then meet 16 different 16-byte slots, and the 16 lanes of a ds_write_b64 group 8 of the 8 possible bank sets (2-way, 8 LDS cycles
+// against the store's own 6; 16 consecutive columns are 4-way).
+__device__ __forceinline__ int hop_col(int j, int wv) {
+  const int j2 = (j >> 2) & 1, j3 = (j >> 3) & 1;
+  return (j & 3) + 4 * (wv & 1) + 8 * (j2 ^ j3) + 16 * j3 + 32 * (wv >> 1);
+}
+// lane ^ M within groups of 8 lanes (M = 1 .. 7): quad_perm, row_half_mirror (lane ^ 7), or both
+template <int M>
+__device__ __forceinline__ int xor8(int v) {
+  constexpr int QP[4] = {0xE4, 0xB1, 0x4E, 0x1B};      // quad_perm of lane ^ 0 .. 3
+  if constexpr (M < 4) return __builtin_amdgcn_update_dpp(0, v, QP[M], 0xf, 0xf, true);
+  else {
+    const int y = __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);      // row_half_mirror
+    if constexpr (M == 7) return y;
+    else return __builtin_amdgcn_update_dpp(0, y, QP[7 ^ M], 0xf, 0xf, true);
+  }
+}
+
+template <int NMAT, bool RS2, bool HM>
 __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_args p, int nibg, const WgradBatch wb, int hb) {
   constexpr int TM = W16H_TM, ZC = W16H_ZC, XW = W16H_XW, NT = W16H_NT, LDZF = W16H_LDZF;
   const float* __restrict__ Gp = wb.n > 0 ? wb.G[blockIdx.z] : p.G;
@@ -68,12 +100,13 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
   float* __restrict__ slabp = wb.n > 0 ? wb.slab[blockIdx.z] : p.slab;
   const float* __restrict__ rs2 = RS2 ? (wb.n > 0 ? wb.rowscale2[blockIdx.z] : p.rowscale2) : nullptr;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Zf0 = smem;
+  float* Zf0 = smem;                                              // (HM: no fp32 images)
   float* Zf1 = Zf0 + TM * LDZF;
-  char* ZT = reinterpret_cast<char*>(Zf1 + TM * LDZF);          // [NMAT][2 planes][ZC columns][64 B]
+  char* ZT = reinterpret_cast<char*>(smem) + (HM ? 0 : 2 * TM * LDZF * 4);      // [NMAT][2 planes][ZC columns][64 B]
   char* XT = ZT + NMAT * 2 * ZC * 64;                             // [2 planes][XW columns][64 B]
   int2* ell = reinterpret_cast<int2*>(XT + 2 * XW * 64);         // [D][TM]
-  float* mxp = reinterpret_cast<float*>(ell + W16H_DMAX * TM);   // [2][4 waves]: max |X|, max |G| of the tile in the registers
+  char* PT = XT + 2 * XW * 64;                                    // HM, in the ELL slice's place: [2 planes][TM rows][64 B], P[row][k] like a column of ZT
+  float* mxp = reinterpret_cast<float*>(XT + 2 * XW * 64 + (HM ? 2 * TM * 64 : W16H_DMAX * TM * 8));   // [2][4 waves]: max |X|, max |G| of the tile in the registers
   const int D = p.ell_width;
 
   const int tid = threadIdx.x;
@@ -89,7 +122,14 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
   const int cg = tid & 15, rp = (tid >> 4) ^ ((tid & 1) << 1);
   const int g_off0 = tph_off(4 * cg, 2 * rp);
   const int x_off0[2] = {tph_off(4 * cg, 2 * rp), tph_off(64 + 4 * cg, 2 * rp)};
-  const uint32_t g_goff = (uint32_t)((2 * rp) * p.ldg + 4 * cg) * 4u;
+  // HM: the ELL entry (slot pk, row prow) of this thread -- a row's slots sit in 8 neighbouring lanes --, and the hop's fragment offsets
+  const int pk = tid & 7, prow = tid >> 3;
+  const int pkc = pk < D ? pk : D - 1;
+  const int hj = lane & 15, hg = lane >> 4;
+  const int hc = hop_col(hj, wv);
+  const int hop_b = hc * 64 + ((hg ^ tph_key(hc)) << 4);                                  // B fragment: rows 8 hg .. 8 hg + 7 of column hc
+  const int hop_a[2] = {tph_off(hj, 8 * hg), tph_off(16 + hj, 8 * hg)};                   // A fragments: P[16 rb + hj][8 hg ..]
+  const int hop_d[2] = {tph_off(hc, 4 * hg), tph_off(hc, 16 + 4 * hg)};                   // results: rows 16 rb + 4 hg .. + 3 of column hc
 
   f32x16 acc[2][NMAT];
 #pragma unroll
@@ -136,7 +176,58 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
 #endif
       if constexpr (RS2) prs[u] = *reinterpret_cast<const f32x3*>(rsb + (size_t)(ts + rr) * 4);
     }
-    pel = tid < D * TM ? (reinterpret_cast<const int2*>(p.ell_tiles) + (size_t)tile * D * TM)[tid] : make_int2(tid & (TM - 1), 0);
+    if constexpr (HM) pel = (reinterpret_cast<const int2*>(p.ell_tiles) + (size_t)tile * D * TM)[pkc * TM + prow];      // (slots beyond D: slot D - 1, weight masked below)
+    else pel = tid < D * TM ? (reinterpret_cast<const int2*>(p.ell_tiles) + (size_t)tile * D * TM)[tid] : make_int2(tid & (TM - 1), 0);
+  };
+  // P of the tile into its (zero-filled) planes.  Slots of one row that name the same node (parallel branches) are summed; the lowest
+  // such slot writes, so the image does not depend on the order the lanes arrive in.  An entry of weight 0 -- an empty slot is
+  // {own row, 0} -- writes nothing and joins nothing: it gets an index of its own.  Slots pk ^ m >= D are empty, so ELL slices of
+  // width <= 4 look at three neighbours only, and the sums are formed only where a wave has a repeated index at all (uniform).
+  auto scatter_p = [&]() {
+    const float w = pk < D ? __int_as_float(pel.y) : 0.f;
+    const int idx = w != 0.f ? (pel.x & (TM - 1)) : TM + pk;
+    const int wi = __float_as_int(w);
+    bool s1 = xor8<1>(idx) == idx, s2 = xor8<2>(idx) == idx, s3 = xor8<3>(idx) == idx;
+    bool s4 = false, s5 = false, s6 = false, s7 = false;
+    if (D > 4) { s4 = xor8<4>(idx) == idx; s5 = xor8<5>(idx) == idx; s6 = xor8<6>(idx) == idx; s7 = xor8<7>(idx) == idx; }
+    float tot = w;
+    bool lose = false;
+    if (__builtin_amdgcn_ballot_w64(s1 || s2 || s3 || s4 || s5 || s6 || s7) != 0) {
+      tot += s1 ? __int_as_float(xor8<1>(wi)) : 0.f; lose = lose || (s1 && (pk ^ 1) < pk);
+      tot += s2 ? __int_as_float(xor8<2>(wi)) : 0.f; lose = lose || (s2 && (pk ^ 2) < pk);
+      tot += s3 ? __int_as_float(xor8<3>(wi)) : 0.f; lose = lose || (s3 && (pk ^ 3) < pk);
+      if (D > 4) {
+        tot += s4 ? __int_as_float(xor8<4>(wi)) : 0.f; lose = lose || (s4 && (pk ^ 4) < pk);
+        tot += s5 ? __int_as_float(xor8<5>(wi)) : 0.f; lose = lose || (s5 && (pk ^ 5) < pk);
+        tot += s6 ? __int_as_float(xor8<6>(wi)) : 0.f; lose = lose || (s6 && (pk ^ 6) < pk);
+        tot += s7 ? __int_as_float(xor8<7>(wi)) : 0.f; lose = lose || (s7 && (pk ^ 7) < pk);
+      }
+    }
+    if (!lose && tot != 0.f) {
+      uint32_t h, l;
+      split2_pair(tot * pow2f(14 - hb), 0.f, h, l);
+      char* dst = PT + tph_off(prow, idx & (TM - 1));
+      *reinterpret_cast<uint16_t*>(dst) = (uint16_t)h;
+      *reinterpret_cast<uint16_t*>(dst + TM * 64) = (uint16_t)l;
+    }
+  };
+  // one hop on the matrix pipe: planes of P Z <- P (planes of Z), both scaled by 2^ez
+  auto hop = [&](const char* src, char* dst) {
+    const f16x8 zh = *reinterpret_cast<const f16x8*>(src + hop_b), zl = *reinterpret_cast<const f16x8*>(src + ZC * 64 + hop_b);
+    const float s = pow2f(hb - 14);      // P's scale out again
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+      const f16x8 ph = *reinterpret_cast<const f16x8*>(PT + hop_a[rb]), pl = *reinterpret_cast<const f16x8*>(PT + TM * 64 + hop_a[rb]);
+      f32x4 c = {0.f, 0.f, 0.f, 0.f};
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(pl, zh, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, zl, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, zh, c, 0, 0, 0);
+      uint2 h, l;
+      split2_pair(c[0] * s, c[1] * s, h.x, l.x);
+      split2_pair(c[2] * s, c[3] * s, h.y, l.y);
+      *reinterpret_cast<uint2*>(dst + hop_d[rb]) = h;
+      *reinterpret_cast<uint2*>(dst + ZC * 64 + hop_d[rb]) = l;
+    }
   };
   // the maxima of the tile whose rows wait in px / pg: one partial per wave, read by everybody after the next barrier
   auto publish_max = [&]() {
@@ -182,6 +273,7 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
     publish_max();
     if (slice + p.n_split < p.ntiles) { ts_n = p.tile_start[slice + p.n_split]; R_n = p.tile_start[slice + p.n_split + 1] - ts_n; }
   }
+  if constexpr (HM) *reinterpret_cast<f32x4*>(PT + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   for (int tile = slice; tile < p.ntiles; tile += p.n_split) {
     const int next = tile + p.n_split;
@@ -216,10 +308,13 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
 #pragma unroll
     for (int i = 0; i < 2; ++i) store_planes_h<XW>(XT, x_off0[i], px[2 * i], px[2 * i + 1], sxe);
 #endif
+    if constexpr (!HM) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) *reinterpret_cast<f32x4*>(Zf0 + (2 * rp + u) * LDZF + 4 * cg) = pg[u];
+      for (int u = 0; u < 2; ++u) *reinterpret_cast<f32x4*>(Zf0 + (2 * rp + u) * LDZF + 4 * cg) = pg[u];
+    }
     store_planes_h<ZC>(ZT, g_off0, pg[0], pg[1], sze);
-    if (tid < ((D + 3) & ~3) * TM) ell[tid] = pel;
+    if constexpr (HM) scatter_p();
+    else if (tid < ((D + 3) & ~3) * TM) ell[tid] = pel;
     bsum += pg[0] + pg[1];
     if constexpr (RS2) {
       if (rs2) {
@@ -240,16 +335,19 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
 #else
     if (NMAT > 1) {
 #endif
-      prop(Zf0, NMAT > 2 ? Zf1 : nullptr, ZT + 2 * ZC * 64, sze);
+      if constexpr (HM) hop(ZT, ZT + 2 * ZC * 64);
+      else prop(Zf0, NMAT > 2 ? Zf1 : nullptr, ZT + 2 * ZC * 64, sze);
       HSTAMP(5);
       if (NMAT > 2) {
         __syncthreads();
         HSTAMP(6);
-        prop(Zf1, nullptr, ZT + 2 * 2 * ZC * 64, sze);
+        if constexpr (HM) hop(ZT + 2 * ZC * 64, ZT + 2 * 2 * ZC * 64);
+        else prop(Zf1, nullptr, ZT + 2 * 2 * ZC * 64, sze);
         HSTAMP(7);
       }
       __syncthreads();
       HSTAMP(8);
+      if constexpr (HM) *reinterpret_cast<f32x4*>(PT + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};      // (every wave's hops have read P; the next tile's entries land behind the tile's last barrier)
     }
     // ---- MFMA phase: 2 steps of 16 rows; lo hi + hi lo + hi hi, smallest terms first
 #ifdef DSS2_ABLATE_MFMA      // (diagnostic: no matrix instructions)
@@ -337,8 +435,9 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
   }
 }
 
-size_t wgrad16h_lds_bytes(int nmat, int ell_width) {
-  const size_t b = 2 * (size_t)W16H_TM * W16H_LDZF * 4 + (size_t)nmat * 2 * W16H_ZC * 64 + 2 * (size_t)W16H_XW * 64 + (size_t)W16H_DMAX * W16H_TM * 8 + 32;
+size_t wgrad16h_lds_bytes(int nmat, int ell_width, bool hops_mfma) {
+  const size_t planes = (size_t)nmat * 2 * W16H_ZC * 64 + 2 * (size_t)W16H_XW * 64;
+  const size_t b = hops_mfma ? planes + 2 * (size_t)W16H_TM * 64 + 32 : 2 * (size_t)W16H_TM * W16H_LDZF * 4 + planes + (size_t)W16H_DMAX * W16H_TM * 8 + 32;
   const size_t red = (size_t)(1 + nmat) * W16H_NT * 16;
   (void)ell_width;
   return b > red ? b : red;
@@ -351,14 +450,14 @@ bool wgrad16h_covers(const dss2_wgrad_args& a) {
          a.hout > 32 && (a.hout & 3) == 0 && (a.hin & 3) == 0;
 }
 
-template <int NMAT, bool RS2>
+template <int NMAT, bool RS2, bool HM>
 static int launch16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16h_kernel<NMAT, RS2>;
+  auto kern = wgrad16h_kernel<NMAT, RS2, HM>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(f16x3, 32 rows)")) return 1;
   const int nobg = (a.hout + W16H_ZC - 1) / W16H_ZC, nibg = (a.hin + W16H_XW - 1) / W16H_XW;
   const int hb = (a.mfma_bf16 >> 8) & 255;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16H_NT), wgrad16h_lds_bytes(a.nmat, a.ell_width), stream, a, nibg, wb, hb);
+  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16H_NT), wgrad16h_lds_bytes(a.nmat, a.ell_width, HM), stream, a, nibg, wb, hb);
   return check_launch("wgrad(f16x3, 32 rows)");
 }
 
@@ -371,8 +470,12 @@ int launch_wgrad16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBat
     rs2 = rs2 || wb.rowscale2[l] != nullptr;
   }
   if (((a.mfma_bf16 >> 8) & 255) > 10) { set_error("wgrad(f16x3): %d headroom bits for the propagation leave no precision", (a.mfma_bf16 >> 8) & 255); return 2; }
-  if (a.nmat == 2) return rs2 ? launch16h<2, true>(a, stream, wb) : launch16h<2, false>(a, stream, wb);
-  if (a.nmat == 3) return rs2 ? launch16h<3, true>(a, stream, wb) : launch16h<3, false>(a, stream, wb);
+  // the hops as f16x3 products unless the caller asks for the gathered fp32 form (bit 16; flags.WGRAD_HOPS_MFMA = 0)
+  const bool hm = !((a.mfma_bf16 >> 16) & 1);
+  if (a.nmat == 2) return rs2 ? (hm ? launch16h<2, true, true>(a, stream, wb) : launch16h<2, true, false>(a, stream, wb))
+                              : (hm ? launch16h<2, false, true>(a, stream, wb) : launch16h<2, false, false>(a, stream, wb));
+  if (a.nmat == 3) return rs2 ? (hm ? launch16h<3, true, true>(a, stream, wb) : launch16h<3, true, false>(a, stream, wb))
+                              : (hm ? launch16h<3, false, true>(a, stream, wb) : launch16h<3, false, false>(a, stream, wb));
   set_error("wgrad(f16x3): unsupported nmat=%d", a.nmat);
   return 2;
 }

@@ -29,6 +29,8 @@ FOLD_W2 = _os.environ.get("DSS2_FOLD_W2", "1") == "1"   # 0 = run the edge MLP's
 # ... and on 32-row tiles as f16x3: two fp16 pieces per operand after a power-of-two scale, three MFMAs per product instead of six
 # (csrc/dss2_wgrad16h.hip, round 5; errors of the size of fp32 arithmetic itself).  0 = bf16x6 there too.
 WGRAD_F16 = _os.environ.get("DSS2_WGRAD_F16", "1") == "1"
+# ... with its two propagation hops as f16x3 products on the matrix pipe (P of a tile as fp16 planes in LDS).  0 = the hops as fp32 gathers.
+WGRAD_HOPS_MFMA = _os.environ.get("DSS2_WGRAD_HOPS_MFMA", "1") == "1"
 # 1 = the loss's batch sums are finished by the last workgroup of the partials launch at every batch size (no finish launch; bitwise the
 # same sums).  Off above 16 workgroups: at C2 the 240 arrivals on one counter word (~12 ns each) and the last workgroup's round trip cost
 # what the 4.65 us finish launch costs -- A/B on one box 0.4047 / 0.4017 ms fused against 0.4022 / 0.3979 (end of round 5)

@@ -311,7 +311,7 @@ def _wgrad_mode(ts, nmat: int, b16: int, hinted: bool = False) -> int:
             w = ts.ellT_tiles[..., 1].contiguous().view(torch.float32)      # [tiles][width][rows]: the entries' weights
             gain = max(float(w.abs().sum(dim=1).max()), 1.0)
         hb = cache[nmat] = max(0, int(math.ceil(math.log2(gain) * (nmat - 1) - 1e-6)))
-    return (2 | (hb << 8)) if hb <= 10 else b16
+    return (2 | (hb << 8) | (0 if FL.WGRAD_HOPS_MFMA else 1 << 16)) if hb <= 10 else b16      # (bit 16: the 32-row kernel's hops as fp32 gathers)
 
 
 def wgrad(topo: Topology, G: torch.Tensor, hout: int, X: torch.Tensor, hin: int, nmat: int, out_flat: torch.Tensor,

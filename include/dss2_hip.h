@@ -449,7 +449,9 @@ typedef struct dss2_wgrad_args {
                                          * covers the shape (32-, 96- and 192-row tiles with ELL *
                                          * slices), bits 8..15 = headroom bits for the gain of   *
                                          * the propagation hops, ceil(log2(max row sum of        *
-                                         * |P^T|^K)); elsewhere the bf16x6 / fp32 kernels        */
+                                         * |P^T|^K)); elsewhere the bf16x6 / fp32 kernels.       *
+                                         * Bit 16 set: the 32-row f16x3 kernel forms its hops as *
+                                         * fp32 gathers (clear: f16x3 products, P as fp16 planes)*/
 } dss2_wgrad_args;
 
 int dss2_wgrad(const dss2_wgrad_args* args_host, void* stream);
