@@ -247,30 +247,26 @@ __global__ __launch_bounds__(NT) void gat_bwd_kernel(const dss2_gat_args a) {
   }
 }
 
-int check_args(const dss2_gat_args& a, const char* what) {
+int check_args(const dss2_gat_args& a, bool forward, const char* what) {
   if (int rc = check_lanegroup_args(a, what)) return rc;
   const dss2_gat_conv* cv[2] = {a.has_up ? &a.up : nullptr, a.has_lo ? &a.lo : nullptr};
   for (const dss2_gat_conv* p : cv)
     if (p && (p->cin < 1 || p->cout < 1 || p->cin > a.group || p->cout > a.group)) {
       set_error("%s: channels %d -> %d exceed the lane group %d (limit %d)", what, p->cin, p->cout, a.group, GMAX); return 2;
     }
-  return 0;
+  return check_pass_args(a, forward, what);
 }
 
 }  // namespace
 
 static int dss2_gat_forward_launch(const dss2_gat_args* ap, void* stream) {
-  const dss2_gat_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gat_forward")) return rc;
-  if (!a.has_lo && !a.has_head) { set_error("dss2_gat_forward: nothing to do"); return 2; }
-  return launch_group(gat_fwd_kernel<8>, gat_fwd_kernel<16>, gat_fwd_kernel<32>, a, stream, "dss2_gat_forward");
+  if (int rc = check_args(*ap, true, "dss2_gat_forward")) return rc;
+  return launch_group(gat_fwd_kernel<8>, gat_fwd_kernel<16>, gat_fwd_kernel<32>, *ap, stream, "dss2_gat_forward");
 }
 
 static int dss2_gat_backward_launch(const dss2_gat_args* ap, void* stream) {
-  const dss2_gat_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gat_backward")) return rc;
-  if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gat_backward: no output gradient"); return 2; }
-  return launch_group(gat_bwd_kernel<8>, gat_bwd_kernel<16>, gat_bwd_kernel<32>, a, stream, "dss2_gat_backward");
+  if (int rc = check_args(*ap, false, "dss2_gat_backward")) return rc;
+  return launch_group(gat_bwd_kernel<8>, gat_bwd_kernel<16>, gat_bwd_kernel<32>, *ap, stream, "dss2_gat_backward");
 }
 
 extern "C" int dss2_gat_forward(const dss2_gat_args* ap, void* stream) {

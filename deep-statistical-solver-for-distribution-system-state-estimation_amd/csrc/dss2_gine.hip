@@ -205,30 +205,26 @@ int check_conv(const dss2_gine_conv& p, const dss2_gine_args& a, const char* wha
   return 0;
 }
 
-int check_args(const dss2_gine_args& a, const char* what) {
+int check_args(const dss2_gine_args& a, bool forward, const char* what) {
   if (int rc = check_lanegroup_args(a, what)) return rc;
   if (a.has_up)
     if (int rc = check_conv(a.up, a, what)) return rc;
   if (a.has_lo)
     if (int rc = check_conv(a.lo, a, what)) return rc;
-  return 0;
+  return check_pass_args(a, forward, what);
 }
 
 }  // namespace
 
 static int dss2_gine_forward_launch(const dss2_gine_args* ap, void* stream) {
-  const dss2_gine_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gine_forward")) return rc;
-  if (!a.has_lo && !a.has_head) { set_error("dss2_gine_forward: nothing to do"); return 2; }
-  if (a.has_up) { set_error("dss2_gine_forward: no source pass in the forward"); return 2; }
-  return launch_group(gine_fwd_kernel<8>, gine_fwd_kernel<16>, gine_fwd_kernel<32>, a, stream, "dss2_gine_forward");
+  if (int rc = check_args(*ap, true, "dss2_gine_forward")) return rc;
+  return launch_group(gine_fwd_kernel<8>, gine_fwd_kernel<16>, gine_fwd_kernel<32>, *ap, stream, "dss2_gine_forward");
 }
 
 static int dss2_gine_backward_launch(const dss2_gine_args* ap, void* stream) {
   const dss2_gine_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gine_backward")) return rc;
-  if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gine_backward: no output gradient"); return 2; }
-  if (!a.g.slab || (a.has_lo && !a.g.nslab)) { set_error("dss2_gine_backward: no slab"); return 2; }
+  if (int rc = check_args(a, false, "dss2_gine_backward")) return rc;
+  if (a.has_lo && !a.g.nslab) { set_error("dss2_gine_backward: no slab"); return 2; }
   return launch_group(gine_bwd_kernel<8>, gine_bwd_kernel<16>, gine_bwd_kernel<32>, a, stream, "dss2_gine_backward");
 }
 

@@ -359,7 +359,7 @@ int check_conv(const dss2_gnn_conv& p, const dss2_gnn_args& a, const char* what)
   return 0;
 }
 
-int check_args(const dss2_gnn_args& a, const char* what) {
+int check_args(const dss2_gnn_args& a, bool forward, const char* what) {
   if (int rc = check_lanegroup_args(a, what)) return rc;
   if ((a.has_lo || a.has_up) && (!a.g.dis || !a.g.rowptr || !a.g.rowptrT)) { set_error("%s: graph pointer missing", what); return 2; }
   if (a.has_up)
@@ -367,16 +367,14 @@ int check_args(const dss2_gnn_args& a, const char* what) {
   if (a.has_lo)
     if (int rc = check_conv(a.lo, a, what)) return rc;
   if (a.has_up && a.has_lo && a.up.c != a.lo.c) { set_error("%s: convs of different widths", what); return 2; }
-  return 0;
+  return check_pass_args(a, forward, what);
 }
 
 }  // namespace
 
 static int dss2_gnn_forward_launch(const dss2_gnn_args* ap, void* stream) {
   const dss2_gnn_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gnn_forward")) return rc;
-  if (!a.has_lo && !a.has_head) { set_error("dss2_gnn_forward: nothing to do"); return 2; }
-  if (a.has_up) { set_error("dss2_gnn_forward: no source pass in the forward"); return 2; }
+  if (int rc = check_args(a, true, "dss2_gnn_forward")) return rc;
   if (a.has_lo) {
     const bool tag = a.lo.kind == DSS2_GNN_TAG;
     if (tag ? (a.hop < (a.lo.K ? 1 : 0) || a.hop > a.lo.K) : a.hop != 0) { set_error("dss2_gnn_forward: hop %d", a.hop); return 2; }
@@ -387,9 +385,7 @@ static int dss2_gnn_forward_launch(const dss2_gnn_args* ap, void* stream) {
 
 static int dss2_gnn_backward_launch(const dss2_gnn_args* ap, void* stream) {
   const dss2_gnn_args& a = *ap;
-  if (int rc = check_args(a, "dss2_gnn_backward")) return rc;
-  if (!a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("dss2_gnn_backward: no output gradient"); return 2; }
-  if (!a.g.slab) { set_error("dss2_gnn_backward: no slab"); return 2; }
+  if (int rc = check_args(a, false, "dss2_gnn_backward")) return rc;
   if (a.has_up) {
     const dss2_gnn_conv& u = a.up;
     if (!u.d) { set_error("dss2_gnn_backward: the source pass has no gradient buffer"); return 2; }

@@ -1,4 +1,4 @@
-// The lane-group core shared by the GAT (dss2_gat.hip) and GINE (dss2_gine.hip) kernels.
+// The lane-group core shared by the GAT (dss2_gat.hip), GINE (dss2_gine.hip) and gnn_dsse (dss2_gnn.hip) kernels.
 //
 // Lane mapping: one lane group of G (8 / 16 / 32) lanes per node, lane c owns channel c; a 256-thread workgroup holds 256 / G
 // nodes at a time and walks the nodes with a grid stride (the grid is the slab count, so every workgroup writes exactly one slab
@@ -6,7 +6,7 @@
 // 33 / 17 floats (lane c reading row c hits bank c).
 //
 // Here: the two head Linears (LDS staging, the fused forward and backward of one node), the model nonlinearity and its gradient,
-// the fixed-order lane-group sum of a workgroup's partials, the argument checks both models share, the group dispatch and the
+// the fixed-order lane-group sum of a workgroup's partials, the argument checks the models share, the group dispatch and the
 // body of an extern "C" entry point.  The head's outer-product weight gradient is dss2_lanegroup_wgrad (dss2_lanegroup.hip).
 // Nothing here knows which model calls it; the conv staging, the message, the softmax and the slab columns stay in the model files.
 #pragma once
@@ -113,7 +113,7 @@ __device__ __forceinline__ float group_sum(const float (*red)[W], int ch, int k)
   return v;
 }
 
-// the checks of a lane-group model's args (dss2_gat_args / dss2_gine_args) that do not depend on the model: graph sizes, edge
+// the checks of a lane-group model's args (dss2_gat_args / _gine_args / _gnn_args) that do not depend on the model: graph sizes, edge
 // width, lane group, head widths, and no head next to a source pass.  The model checks its convs.
 template <class Args>
 inline int check_lanegroup_args(const Args& a, const char* what) {
@@ -125,6 +125,17 @@ inline int check_lanegroup_args(const Args& a, const char* what) {
     return 2;
   }
   if (a.has_head && a.has_up) { set_error("%s: head and source pass in one launch", what); return 2; }
+  return 0;
+}
+
+// what a forward (something to run, no source pass) and a backward launch (an output gradient, a slab) need in every model;
+// what is the entry point's name
+template <class Args>
+inline int check_pass_args(const Args& a, bool forward, const char* what) {
+  if (forward && !a.has_lo && !a.has_head) { set_error("%s: nothing to do", what); return 2; }
+  if (forward && a.has_up) { set_error("%s: no source pass in the forward", what); return 2; }
+  if (!forward && !a.has_head && !a.has_up && (!a.has_lo || !a.gy)) { set_error("%s: no output gradient", what); return 2; }
+  if (!forward && !a.g.slab) { set_error("%s: no slab", what); return 2; }
   return 0;
 }
 

@@ -29,16 +29,11 @@ import torch.nn as nn
 
 from . import _lib, lanegroup
 from .lanegroup import MAX_CHANNELS, MAX_DENSE, MAX_EDGE_DIM
-from .ops import _require_gpu, _rows
+from .lanegroup import glorot as _glorot
+from .ops import _ptr, _require_gpu, _rows
 from .topology import get_topology
 
 _F32 = torch.float32
-
-
-def _glorot(t: torch.Tensor) -> None:
-    a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
-    with torch.no_grad():
-        t.uniform_(-a, a)
 
 
 def _fan_in_uniform(t: torch.Tensor, fan_in: int) -> None:
@@ -188,14 +183,11 @@ def run_gat(convs, head, nonlin, x, edge_index, edge_attr):
     if edge_attr is not None:
         from .networks import _no_edge_attr_grad
         _no_edge_attr_grad(edge_attr)
-    if x.dim() != 2:
-        raise ValueError("x must be [N, C]")
+    lanegroup.check_x(x)
     topo = get_topology(edge_index, x.size(0), double=False)
     topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
     spec = _Spec(convs, head, nonlin, x.size(0))
-    need = convs[0].in_channels if convs else head[0].in_features
-    if x.size(1) != need:
-        raise ValueError(f"x has {x.size(1)} columns, the model takes {need}")
+    lanegroup.check_columns(x, spec)
     if spec.ed:
         if edge_attr is None or edge_attr.dim() != 2 or edge_attr.size(1) != spec.ed or edge_attr.size(0) != edge_index.size(1):
             raise ValueError(f"edge_attr must be [E, {spec.ed}]")
@@ -206,17 +198,15 @@ def run_gat(convs, head, nonlin, x, edge_index, edge_attr):
 
 def _graph(topo, spec, ea, ldea, slab=None):
     g = _lib.GatGraph()
-    g.rowptr, g.col, g.ent = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
-    g.rowptrT, g.colT, g.entT = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr()
-    g.ea, g.ldea = (ea.data_ptr() if ea is not None else None), ldea
+    lanegroup.fill_csr(g, topo)
+    g.ea, g.ldea = _ptr(ea), ldea
     g.n_nodes, g.ed, g.add_self_loops, g.slope, g.nonlin = topo.N, spec.ed, spec.loops, spec.slope, spec.nonlin
-    g.slab, g.n_slabs, g.slab_len = (slab.data_ptr() if slab is not None else None), spec.n_slabs, spec.total
+    g.slab, g.n_slabs, g.slab_len = _ptr(slab), spec.n_slabs, spec.total
     return g
 
 
 def _conv(d, cv, ps7, h, ldh, st, off):
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    d.att, d.bias, d.Wl, d.bl, d.Wr, d.br, d.We = (p(t) for t in ps7)
+    d.att, d.bias, d.Wl, d.bl, d.Wr, d.br, d.We = (_ptr(t) for t in ps7)
     d.h, d.ldh = h.data_ptr(), ldh
     d.y, d.m, d.s = st["y"].data_ptr(), st["ms"].data_ptr(), st["ms"].data_ptr() + 4 * st["ms"].size(1)
     for k in ("dxl", "dxr", "dedge", "dself"):
@@ -234,13 +224,8 @@ class _GATFn(torch.autograd.Function):
         if ea is not None:
             ea, ldea = _rows(ea)
         convs, n = spec.convs, len(spec.convs)
-        states, hs = [], []
-        h, ldh = x, ldx
-        for l, cv in enumerate(convs):
-            st = {"y": torch.empty(N, cv.out_channels, dtype=_F32, device=dev), "ms": torch.empty(2, N, dtype=_F32, device=dev)}
-            states.append(st)
-            hs.append((h, ldh))
-            h, ldh = st["y"], cv.out_channels
+        states, hs = lanegroup.state_chain(x, ldx, [cv.out_channels for cv in convs],
+                                           lambda l: {"ms": torch.empty(2, N, dtype=_F32, device=dev)})
 
         def conv_into(d, l):
             _conv(d, convs[l], ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
@@ -291,9 +276,7 @@ class _GATFn(torch.autograd.Function):
         if head:
             jobs += lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo)
         lanegroup.wgrad(jobs, slab, spec, N, dev)
-        rd = (_lib.ReduceDesc * 1)()
-        rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
-        _lib.check(_lib.lib().dss2_reduce_slabs_multi(rd, 1, _lib.stream_ptr(dev)), "dss2_reduce_slabs_multi")
+        lanegroup.reduce_slabs([(slab, flat, spec.total, spec.total, spec.n_slabs)], dev)
         grads = []
         for l, cv in enumerate(convs):
             co, ci, ed, off = cv.out_channels, cv.in_channels, spec.ed, spec.offs[l]

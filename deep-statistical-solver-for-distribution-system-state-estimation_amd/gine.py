@@ -33,7 +33,7 @@ import torch.nn as nn
 
 from . import _lib, lanegroup
 from .lanegroup import MAX_CHANNELS, MAX_DENSE, MAX_EDGE_DIM
-from .ops import _require_gpu, _rows
+from .ops import _ptr, _require_gpu, _rows
 from .topology import get_topology
 
 _F32 = torch.float32
@@ -155,15 +155,6 @@ class _Spec(lanegroup.Spec):
         self.nn_len = self.cout * self.cin + self.cout
 
 
-class _NoEdges:
-    """The CSR of an edge-less batch (Topology refuses E = 0; every GINE layer is then nn((1 + eps) h))."""
-
-    def __init__(self, n, dev):
-        self.N, self.E = n, 0
-        self.rowptr = self.rowptrT = torch.zeros(n + 1, dtype=torch.int32, device=dev)
-        self.col = self.ent = self.colT = self.entT = self.rowptr
-
-
 def _slots(convs, head) -> List[Optional[torch.Tensor]]:
     """[nn.weight, nn.bias] (when there is a conv), per conv [eps, lin.weight, lin.bias], the head's four."""
     ps = []
@@ -183,19 +174,14 @@ def run_gine(convs, head, nonlin, x, edge_index, edge_attr):
         if edge_attr is None:
             raise ValueError("GINE: forward needs edge_attr")
         _no_edge_attr_grad(edge_attr)
-    if x.dim() != 2:
-        raise ValueError("x must be [N, C]")
-    if edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise ValueError("edge_index must be [2, E]")
+    lanegroup.check_x(x, edge_index)
     if edge_index.size(1) == 0:
-        topo = _NoEdges(x.size(0), x.device)
+        topo = lanegroup.NoEdges(x.size(0), x.device)       # every GINE layer is then nn((1 + eps) h)
     else:
         topo = get_topology(edge_index, x.size(0), double=False)
         topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
     spec = _Spec(convs, head, nonlin, x.size(0))
-    need = spec.cin if convs else head[0].in_features
-    if x.size(1) != need:
-        raise ValueError(f"x has {x.size(1)} columns, the model takes {need}")
+    lanegroup.check_columns(x, spec)
     if convs:
         w = spec.ed if spec.ed else spec.cin
         if edge_attr.dim() != 2 or edge_attr.size(1) != w or edge_attr.size(0) != edge_index.size(1):
@@ -207,22 +193,20 @@ def run_gine(convs, head, nonlin, x, edge_index, edge_attr):
 
 def _graph(topo, spec, ea, ldea, slab=None, nslab=None):
     g = _lib.GineGraph()
-    g.rowptr, g.col, g.ent = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
-    g.rowptrT, g.colT, g.entT = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr()
-    g.ea, g.ldea = (ea.data_ptr() if ea is not None else None), ldea
+    lanegroup.fill_csr(g, topo)
+    g.ea, g.ldea = _ptr(ea), ldea
     g.n_nodes, g.ed, g.nonlin = topo.N, spec.ed, spec.nonlin
-    g.slab, g.n_slabs, g.slab_len = (slab.data_ptr() if slab is not None else None), spec.n_slabs, spec.total
-    g.nslab, g.nslab_len = (nslab.data_ptr() if nslab is not None else None), spec.nn_len * len(spec.convs)
+    g.slab, g.n_slabs, g.slab_len = _ptr(slab), spec.n_slabs, spec.total
+    g.nslab, g.nslab_len = _ptr(nslab), spec.nn_len * len(spec.convs)
     return g
 
 
 def _conv(d, spec, ps, l, h, ldh, st, dz=None):
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    d.Wn, d.bn = p(ps[0]), p(ps[1])
-    d.eps, d.We, d.be = (p(t) for t in ps[2 + 3 * l:5 + 3 * l])
+    d.Wn, d.bn = _ptr(ps[0]), _ptr(ps[1])
+    d.eps, d.We, d.be = (_ptr(t) for t in ps[2 + 3 * l:5 + 3 * l])
     d.h, d.ldh = h.data_ptr(), ldh
     d.y, d.z = st["y"].data_ptr(), st["z"].data_ptr()
-    d.dz = p(dz)
+    d.dz = _ptr(dz)
     d.cin, d.cout, d.slab_off, d.nn_off = spec.cin, spec.cout, spec.offs[l], l * spec.nn_len
 
 
@@ -235,13 +219,7 @@ class _GINEFn(torch.autograd.Function):
         if ea is not None:
             ea, ldea = _rows(ea)
         n = len(spec.convs)
-        states, hs = [], []
-        h, ldh = x, ldx
-        for _ in range(n):
-            st = {"y": torch.empty(N, spec.cout, dtype=_F32, device=dev), "z": torch.empty(N, spec.cin, dtype=_F32, device=dev)}
-            states.append(st)
-            hs.append((h, ldh))
-            h, ldh = st["y"], spec.cout
+        states, hs = lanegroup.state_chain(x, ldx, [spec.cout] * n, lambda l: {"z": torch.empty(N, spec.cin, dtype=_F32, device=dev)})
 
         def conv_into(d, l):
             _conv(d, spec, ps, l, hs[l][0], hs[l][1], states[l])
@@ -281,12 +259,10 @@ class _GINEFn(torch.autograd.Function):
         # the head's outer-product weight gradients, then ONE fixed-order reduction of both slabs
         if head:
             lanegroup.wgrad(lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo), slab, spec, N, dev)
-        rd = (_lib.ReduceDesc * 2)()
-        rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
+        descs = [(slab, flat, spec.total, spec.total, spec.n_slabs)]
         if n:
-            rd[1].slab, rd[1].out, rd[1].stride, rd[1].len = nslab.data_ptr(), fnn.data_ptr(), spec.nn_len, spec.nn_len
-            rd[1].n_slabs = spec.n_slabs * n
-        _lib.check(_lib.lib().dss2_reduce_slabs_multi(rd, 2 if n else 1, _lib.stream_ptr(dev)), "dss2_reduce_slabs_multi")
+            descs.append((nslab, fnn, spec.nn_len, spec.nn_len, spec.n_slabs * n))
+        lanegroup.reduce_slabs(descs, dev)
         grads = []
         if n:
             ci, co = spec.cin, spec.cout

@@ -15,7 +15,7 @@ w_e = deg_j^-1/2 deg_i^-1/2.  TAGConv uses it without self loops; normalize=Fals
     TAG    out = sum_{k=0..K} (P^k h) @ lins[k].weight^T + bias
 
 ``gnn_dsse.model`` is ``lanegroup.SequentialX0`` with children ``module_{i}``; its forward is ONE autograd node on the launch
-schedule below, every launch through the library (so the step records into launch plans and hipGraphs):
+schedule of lanegroup.py, every launch through the library (so the step records into launch plans and hipGraphs):
 
     forward    GCN2 / FA: one launch per conv; TAG: K per conv (hops 1..K-1 write P^k h, hop K forms the sum); the head Linears
                run in the last launch
@@ -33,9 +33,7 @@ outside [0, N).  No bipartite inputs.
 """
 from __future__ import annotations
 
-import ctypes
 import functools
-import math
 from typing import Optional
 
 import torch
@@ -43,19 +41,13 @@ import torch.nn as nn
 
 from . import _lib, lanegroup
 from .lanegroup import MAX_CHANNELS, MAX_DENSE
-from .ops import _rows
+from .lanegroup import glorot as _glorot
+from .ops import _ptr, _rows
 from .topology import get_topology
 
 _F32 = torch.float32
 MAX_K = _lib.GNN_MAX_K
 _check_width = functools.partial(lanegroup.check_width, "gnn_dsse")
-
-
-def _glorot(t: torch.Tensor) -> None:
-    """PyG's glorot: uniform(-a, a), a = sqrt(6 / (fan_in + fan_out)) over the last two dimensions."""
-    a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
-    with torch.no_grad():
-        t.uniform_(-a, a)
 
 
 class _CachedStructure:
@@ -194,22 +186,13 @@ class gnn_dsse(nn.Module):
 # ------------------------------------------------------------------------------------------
 # structure: CSR by target and by source, gcn_norm's deg^-1/2
 # ------------------------------------------------------------------------------------------
-class _NoEdges:
-    """The CSR of an edge-less batch (Topology refuses E = 0)."""
-
-    def __init__(self, n, dev):
-        self.N, self.E2 = n, 0
-        self.rowptr = self.rowptrT = torch.zeros(n + 1, dtype=torch.int32, device=dev)
-        self.col = self.ent = self.colT = self.entT = self.rowptr
-
-
 class _Structure:
     """One structure with its deg^-1/2 for one mode (0 weight 1, 1 gcn_norm, 2 gcn_norm with remaining self loops).  ``ref_n``:
     the node count its entries reference (every node with loops, else the largest node id + 1)."""
 
     def __init__(self, topo, dis, mode, ref_n):
         self.topo, self.dis, self.mode, self.ref_n = topo, dis, mode, ref_n
-        self.N, self.E = topo.N, topo.E2
+        self.N, self.E = topo.N, topo.E      # (the structure is built with double=False: the edges as given)
         self.rowptr, self.col, self.ent = topo.rowptr, topo.col, topo.ent
         self.rowptrT, self.colT, self.entT = topo.rowptrT, topo.colT, topo.entT
         self.loops = int(mode == 2)
@@ -220,14 +203,12 @@ _NO_EDGES = {}
 
 
 def _structure(edge_index, n, mode):
-    if edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise ValueError("edge_index must be [2, E]")
     dev = edge_index.device
     if edge_index.size(1) == 0:
         key = (dev.index, n)
         topo = _NO_EDGES.get(key)
         if topo is None:
-            topo = _NO_EDGES[key] = _NoEdges(n, dev)
+            topo = _NO_EDGES[key] = lanegroup.NoEdges(n, dev)
     else:
         topo = get_topology(edge_index, n, double=False)
         topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
@@ -334,6 +315,9 @@ class _Spec(lanegroup.Spec):
         CC = C * C
         cols = {_lib.GNN_GCN2: CC * (1 if self.shared else 2), _lib.GNN_FA: 2 * C, _lib.GNN_TAG: C + (self.K + 1) * CC}.get(self.kind, 0)
         self.n_ps = {_lib.GNN_GCN2: 2, _lib.GNN_FA: 2, _lib.GNN_TAG: self.K + 2}.get(self.kind, 0)
+        # TAG: hops 1..K-1 write P^k h and hop K forms the sum; the adjoint runs r_k = g_k + P^T r_{k+1} for k = K-1..0
+        self.fwd_hops = tuple(range(1, self.K + 1)) or (0,)
+        self.bwd_hops = tuple(range(self.K - 1, -1, -1)) or (0,)
         super().__init__("gnn_dsse", convs, head, nonlin, n_nodes, [C] if convs else [], [cols] * len(convs))
 
 
@@ -344,19 +328,14 @@ def _check_inputs(x, x_0, edge_index, params):
     for t in (x, x_0, *params):
         if t is not None and t.dtype != _F32:
             raise ValueError(f"gnn_dsse: the kernels compute in float32; got {t.dtype}")
-    if x.dim() != 2:
-        raise ValueError("x must be [N, C]")
-    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
-        raise ValueError("edge_index must be an int64 tensor [2, E]")
+    lanegroup.check_x(x, edge_index, int64=True)
 
 
 def run_gnn(convs, head, nonlin, x, x_0, edge_index):
     ps = [t for cv in convs for t in _conv_params(cv, _kind(cv))]
     _check_inputs(x, x_0, edge_index, [t for t in ps if t is not None])
     spec = _Spec(convs, head, nonlin, x.size(0))
-    need = spec.c if convs else head[0].in_features
-    if x.size(1) != need:
-        raise ValueError(f"x has {x.size(1)} columns, the model takes {need}")
+    lanegroup.check_columns(x, spec)
     if x_0 is x or spec.kind == _lib.GNN_TAG or not convs:
         x0 = None          # the x_0 path goes into x's gradient inside the kernels (TAG and the head have none)
     else:
@@ -382,16 +361,11 @@ def run_gnn(convs, head, nonlin, x, x_0, edge_index):
 def _graph(st, spec, N, slab=None):
     g = _lib.GnnGraph()
     if st is not None:
-        g.rowptr, g.col, g.ent = st.rowptr.data_ptr(), st.col.data_ptr(), st.ent.data_ptr()
-        g.rowptrT, g.colT, g.entT = st.rowptrT.data_ptr(), st.colT.data_ptr(), st.entT.data_ptr()
+        lanegroup.fill_csr(g, st)
         g.dis, g.loops = st.dis.data_ptr(), st.loops
     g.n_nodes, g.nonlin = N, spec.nonlin
-    g.slab, g.n_slabs, g.slab_len = (slab.data_ptr() if slab is not None else None), spec.n_slabs, spec.total
+    g.slab, g.n_slabs, g.slab_len = _ptr(slab), spec.n_slabs, spec.total
     return g
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 class _GnnFn(torch.autograd.Function):
@@ -405,59 +379,36 @@ class _GnnFn(torch.autograd.Function):
         else:
             x0, ldx0 = x, ldx
         cps, hps = ps[:n * spec.n_ps], ps[n * spec.n_ps:]
-        states, hs = [], []
-        h, ldh = x, ldx
-        for _ in range(n):
-            s = {"y": torch.empty(N, C, dtype=_F32, device=dev)}
+
+        def extra(l):
             if spec.kind == _lib.GNN_GCN2:
-                s["u"] = torch.empty(N, C, dtype=_F32, device=dev)
-            elif spec.kind == _lib.GNN_TAG and K:
-                s["u"] = torch.empty(K, N, C, dtype=_F32, device=dev)
-            states.append(s)
-            hs.append((h, ldh))
-            h, ldh = s["y"], C
+                return {"u": torch.empty(N, C, dtype=_F32, device=dev)}
+            if spec.kind == _lib.GNN_TAG and K:
+                return {"u": torch.empty(K, N, C, dtype=_F32, device=dev)}
+            return {}
+
+        states, hs = lanegroup.state_chain(x, ldx, [C] * n, extra)
 
         def conv_into(d, l, bufs=None):
             d.kind, d.K, d.c, d.slab_off = spec.kind, K, C, spec.offs[l]
             w = cps[l * spec.n_ps:(l + 1) * spec.n_ps]
             if spec.kind == _lib.GNN_TAG:
-                d.bias = _p(w[0])
+                d.bias = _ptr(w[0])
                 for m in range(K + 1):
-                    d.W[m] = _p(w[1 + m])
+                    d.W[m] = _ptr(w[1 + m])
             else:
-                d.W[0], d.W[1] = _p(w[0]), _p(w[1])
+                d.W[0], d.W[1] = _ptr(w[0]), _ptr(w[1])
             d.h, d.ldh = hs[l][0].data_ptr(), hs[l][1]
             d.x0, d.ldx0 = x0.data_ptr(), ldx0
             d.param = spec.params[l]
-            d.y, d.u = states[l]["y"].data_ptr(), _p(states[l].get("u"))
+            d.y, d.u = states[l]["y"].data_ptr(), _ptr(states[l].get("u"))
             if bufs is not None:
-                d.d, d.se, d.sn, d.part = (_p(bufs.get(k)) for k in ("d", "se", "sn", "part"))
+                d.d, d.se, d.sn, d.part = (_ptr(bufs.get(k)) for k in ("d", "se", "sn", "part"))
 
-        L, sm, head = _lib.lib(), _lib.stream_ptr(dev), spec.head
-        g = _graph(st, spec, N)
-        hst, out = {}, None
-        if head:
-            _, d_, o_ = lanegroup.head_dims(head)
-            hst["z1"] = torch.empty(N, d_, dtype=_F32, device=dev)
-            out = torch.empty(N, o_, dtype=_F32, device=dev)
-        hops = list(range(1, K + 1)) if (spec.kind == _lib.GNN_TAG and K) else [0]
-        for l in range(n):
-            for hop in hops:
-                a = _lib.GnnArgs()
-                a.g, a.group, a.has_lo, a.hop = g, spec.group, 1, hop
-                conv_into(a.lo, l)
-                if head and l == n - 1 and hop == hops[-1]:
-                    a.has_head = 1
-                    lanegroup._head_into(a.head, head, hps, hst)
-                    a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-                _lib.check(L.dss2_gnn_forward(ctypes.byref(a), sm), "dss2_gnn_forward")
-        if n == 0:
-            a = _lib.GnnArgs()
-            a.g, a.group, a.has_head = g, spec.group, 1
-            lanegroup._head_into(a.head, head, hps, hst)
-            a.head.hin, a.head.ldhin = x.data_ptr(), ldx
-            a.head.out, a.head.ldo = out.data_ptr(), out.stride(0)
-            _lib.check(L.dss2_gnn_forward(ctypes.byref(a), sm), "dss2_gnn_forward")
+        def hook(a, l, hop):
+            a.hop = hop
+
+        hst, out = lanegroup.forward(spec, _graph(st, spec, N), _lib.GnnArgs, "dss2_gnn_forward", conv_into, x, ldx, hps, hook)
         if out is None:
             out = states[-1]["y"]
         ctx.save_for_backward(x, x0)
@@ -467,13 +418,11 @@ class _GnnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, x0 = ctx.saved_tensors
-        st, spec, ldx, states, hps, hst, conv_into, sep_x0 = ctx.st
+        st, spec, ldx, states, hps, hst, conv_fwd, sep_x0 = ctx.st
         N, dev, C, K, n, head = x.size(0), gout.device, spec.c, spec.K, len(spec.convs), spec.head
         gout, ldgo = _rows(gout)
-        L, sm = _lib.lib(), _lib.stream_ptr(dev)
         slab = torch.empty(spec.n_slabs * spec.total, dtype=_F32, device=dev)
         flat = torch.empty(spec.total, dtype=_F32, device=dev)
-        g = _graph(st, spec, N, slab)
         need_dx = ctx.needs_input_grad[0]
         dx = torch.empty(N, x.size(1), dtype=_F32, device=dev) if need_dx else None
         need_x0 = sep_x0 and ctx.needs_input_grad[1]
@@ -495,48 +444,27 @@ class _GnnFn(torch.autograd.Function):
             bufs.append(b)
         rbuf = [torch.empty(N, C, dtype=_F32, device=dev) for _ in range(2)] if (spec.kind == _lib.GNN_TAG and K > 1) else None
 
-        # head backward (or the output gradient) + the local step of the last conv
-        a = _lib.GnnArgs()
-        a.g, a.group = g, spec.group
-        if head:
-            hst["dz1"] = torch.empty(N, head[0].out_features, dtype=_F32, device=dev)
-            a.has_head = 1
-            lanegroup._head_into(a.head, head, hps, hst)
-            a.head.gout, a.head.ldgo, a.head.dz1 = gout.data_ptr(), ldgo, hst["dz1"].data_ptr()
-        else:
-            a.gy, a.ldgy = gout.data_ptr(), ldgo
-        if n:
-            a.has_lo, a.dx0_first, a.dx0 = 1, 1, _p(dx0)
-            conv_into(a.lo, n - 1, bufs[(n - 1) % 2])
-        else:
-            a.dh, a.dh_cols = _p(dx), head[0].in_features
-        _lib.check(L.dss2_gnn_backward(ctypes.byref(a), sm), "dss2_gnn_backward")
-        # per conv: its source pass (TAG: K adjoint hops, r_k = g_k + P^T r_{k+1}) with the local step of the conv before
-        hops = list(range(K - 1, -1, -1)) if (spec.kind == _lib.GNN_TAG and K) else [0]
-        NC = N * C
-        for l in range(n - 1, -1, -1):
-            b = bufs[l % 2]
-            for hop in hops:
-                a = _lib.GnnArgs()
-                a.g, a.group, a.has_up, a.hop = g, spec.group, 1, hop
-                conv_into(a.up, l, b)
-                if spec.kind == _lib.GNN_TAG and K:
-                    a.rin = b["d"].data_ptr() + 4 * K * NC if hop == K - 1 else rbuf[(hop + 1) % 2].data_ptr()
-                    a.rout = rbuf[hop % 2].data_ptr() if hop > 0 else None
-                if hop == 0:
-                    if l > 0:
-                        a.has_lo, a.dx0 = 1, _p(dx0)
-                        conv_into(a.lo, l - 1, bufs[(l - 1) % 2])
-                    else:
-                        a.dh, a.dh_cols = _p(dx), C
-                        a.dx0 = _p(dx0) if fused_x0 else None
-                _lib.check(L.dss2_gnn_backward(ctypes.byref(a), sm), "dss2_gnn_backward")
+        def conv_into(d, l):
+            conv_fwd(d, l, bufs[l % 2])
+
+        def hook(a, l, hop):
+            a.hop = hop
+            if l == n:                  # the first launch: with a conv, its local step starts the x_0 gradient
+                if n:
+                    a.dx0_first, a.dx0 = 1, _ptr(dx0)
+                return
+            if spec.kind == _lib.GNN_TAG and K:
+                a.rin = bufs[l % 2]["d"].data_ptr() + 4 * K * N * C if hop == K - 1 else rbuf[(hop + 1) % 2].data_ptr()
+                a.rout = rbuf[hop % 2].data_ptr() if hop > 0 else None
+            if hop == 0 and (l > 0 or fused_x0):        # the local step of conv l - 1 adds to it; conv 0's folds it into dx
+                a.dx0 = _ptr(dx0)
+
+        lanegroup.backward(spec, _graph(st, spec, N, slab), _lib.GnnArgs, "dss2_gnn_backward", conv_into, gout, ldgo, hps, hst, dx,
+                           hook)
         # the head's outer-product weight gradients, then ONE fixed-order reduction
         if head:
             lanegroup.wgrad(lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo), slab, spec, N, dev)
-        rd = (_lib.ReduceDesc * 1)()
-        rd[0].slab, rd[0].out, rd[0].stride, rd[0].len, rd[0].n_slabs = slab.data_ptr(), flat.data_ptr(), spec.total, spec.total, spec.n_slabs
-        _lib.check(L.dss2_reduce_slabs_multi(rd, 1, sm), "dss2_reduce_slabs_multi")
+        lanegroup.reduce_slabs([(slab, flat, spec.total, spec.total, spec.n_slabs)], dev)
         grads, CC = [], C * C
         for l in range(n):
             o = spec.offs[l]
@@ -548,5 +476,4 @@ class _GnnFn(torch.autograd.Function):
                 grads.append(flat[o:o + C] if spec.convs[l].bias is not None else None)
                 grads += [flat[o + C + m * CC:o + C + (m + 1) * CC].view(C, C) for m in range(K + 1)]
         grads += lanegroup.head_grads(spec, flat)
-        grads = [gr if ctx.needs_input_grad[4 + k] else None for k, gr in enumerate(grads)]
-        return (dx, dx0 if need_x0 else None, None, None, *grads)
+        return lanegroup.backward_result(ctx, dx, grads, dx0 if need_x0 else None)
