@@ -5,7 +5,7 @@ Drop-in modules ``networks`` (EdgeAggregation, TAGConv, MPN, SkipMPN, PFN, SkipP
 path BASELINE.json names; everything below them is hand-written HIP in libdss2_hip.so.
 """
 from . import _lib, flags, synthetic, topology  # noqa: F401
-from . import ops, plans  # noqa: F401
+from . import ops, plans, route  # noqa: F401
 from . import networks, data, parallel, graphs, optim, dataset  # noqa: F401
 from .optim import FusedAdamax  # noqa: F401
 from . import runner, multi  # noqa: F401

@@ -1,7 +1,10 @@
-"""Module-level switches of the hot path, in ONE place (environment defaults).
+"""Module-level switches of the hot path (environment defaults).  All of them live here except the two of the
+whole-stack kernels, ``stack.STACK_KERNEL`` / ``stack.STACK_NRB`` (``DSS2_STACK_KERNEL``, ``DSS2_STACK_NRB``), which stay attributes of
+``stack.py`` next to the route they switch.
 
-``ops.py``, ``plans.py`` and ``networks.py`` read them at call time as ``flags.<NAME>``, so a test or a tool flips a code path
-inside one process with ``pkg.flags.<NAME> = value`` (and restores it afterwards)."""
+``ops.py``, ``plans.py``, ``route.py`` and ``networks.py`` read them at call time as ``flags.<NAME>``, so a test or a tool flips a code
+path inside one process with ``pkg.flags.<NAME> = value`` (and restores it afterwards).  An MPN block reads them ONCE per forward call
+(``route.block_route``): a flag flipped between two calls takes effect at the next forward, not between a forward and its own backward."""
 import os as _os
 
 EDGE_TILE_KERNELS = _os.environ.get("DSS2_EDGE_TILE", "1") == "1"       # 0 = row-per-wave CSR kernels

@@ -27,32 +27,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .networks import (_F32, _DESC_DTYPE, _MPNFn, _PackPlan, _MatView, _ncg, _require_gpu, _round8, _rows, _stream,
-                       MPN, TAGConv, dropout_snapshot, gemm_prop, is_narrow, wgrad, _reduce, _tagconv_forward,
-                       _tagconv_backward, _tagconv_forward_global, _tagconv_backward_global, use_global_path)
+from .networks import (_F32, _DESC_DTYPE, _MPNFn, _PackPlan, _ncg, _require_gpu, _round8, _rows, _stream, MPN, TAGConv,
+                       _gate, _post_spec, _reduce, _run_tagconv, gemm_prop, wgrad)
 from .topology import Topology, get_topology
-
-
-def _post_spec(mod, dev):
-    """(relu, snapshot or None, p) of the 'dropout then ReLU' that follows a layer inside a Multi* stack."""
-    post = getattr(mod, "_post", None)
-    if not post:
-        return False, None, 0.0
-    p = float(post)
-    if post is True:
-        p = 0.0
-    snap = dropout_snapshot(mod, dev) if p > 0.0 else None
-    mod._last_dropout = (snap, p)
-    return True, snap, p
-
-
-def _gate(g: torch.Tensor, y: torch.Tensor, snap, p: float) -> torch.Tensor:
-    out = torch.empty_like(y)
-    g = g.contiguous()
-    _lib.check(_lib.lib().dss2_gate_grad(g.data_ptr(), y.data_ptr(), out.data_ptr(), y.size(0), y.size(1),
-                                         (snap.data_ptr() if snap is not None else None), 1, float(p), 1, _stream(y)),
-               "dss2_gate_grad")
-    return out
 
 
 class _StackedPack:
@@ -105,7 +82,7 @@ class _EdgeAggrGeneralFn(torch.autograd.Function):
         _lib.check(L.dss2_edge_combine_fwd(AB.data_ptr(), 2 * h, ea.data_ptr(), ldea, w1c, W1.stride(0), b1.data_ptr(),
                                            topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), S.data_ptr(), N, h, fe,
                                            _stream(S)), "dss2_edge_combine_fwd")
-        relu, snap, p = _post_spec(mod, dev)
+        relu, snap, p = _post_spec(mod, mod._post, dev)
         y = torch.empty(N, ho, dtype=_F32, device=dev)
         # second Linear after the (linear) aggregation: sum_e (W2 h_e + b2) = W2 S + deg b2, then dropout + ReLU if inside a stack
         gemm_prop(topo, S, h, h, p2.fwd[0], 1, ho, y, bias=b2, rowscale=topo.deg, relu=relu,
@@ -182,49 +159,6 @@ class EdgeAggregationGeneral(nn.Module):
     def forward(self, x, edge_index, edge_attr):
         _require_gpu(x, edge_index, edge_attr)
         return self.run(x, edge_attr, get_topology(edge_index, x.size(0), double=False))
-
-
-class _TAGConvPostFn(torch.autograd.Function):
-    """TAGConv followed (inside a Multi* stack) by dropout + ReLU, fused into the layer's epilogue."""
-
-    @staticmethod
-    def forward(ctx, x, topo, mod, bias, *ws):
-        x = x.contiguous()
-        hin, hout, nmat = mod.in_channels, mod.out_channels, mod.K + 1
-        glob = use_global_path(topo, nmat)
-        if mod._plan is None or mod._plan.device != x.device or mod._plan.stacked != glob:
-            mod._plan = _PackPlan([list(ws)], x.device, stacked=glob)
-        plan = mod._plan
-        ctx.ver = plan.refresh()
-        if not glob:
-            topo.lds_check(nmat, _round8(hin), _ncg(hout))
-        relu, snap, p = _post_spec(mod, x.device)
-        out = (_tagconv_forward_global if glob else _tagconv_forward)(topo, x, plan.fwd[0], bias, nmat, hin, hout, relu=relu,
-                               drop=((snap, p, 1) if snap is not None else None))
-        ctx.save_for_backward(x, out if relu else None)       # (see _EdgeAggrGeneralFn: an un-gated output may be modified in place)
-        ctx.meta = (topo, mod, relu, snap, p, glob)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        x, y = ctx.saved_tensors
-        topo, mod, relu, snap, p, glob = ctx.meta
-        plan = mod._plan
-        if plan.version != ctx.ver:
-            plan.refresh()
-        hin, hout, nmat = mod.in_channels, mod.out_channels, mod.K + 1
-        g = _gate(gout, y, snap, p) if relu else gout.contiguous()
-        flat = torch.empty(nmat * hout * hin + hout, dtype=_F32, device=g.device)
-        if plan.stacked != glob:
-            raise RuntimeError("the module's weight layouts changed between forward and backward")
-        dh = (_tagconv_backward_global if glob else _tagconv_backward)(
-            topo, g, x, plan.bwd[0], nmat, hin, hout, flat, need_dh=ctx.needs_input_grad[0])
-        gw = [flat[m * hout * hin:(m + 1) * hout * hin].view(hout, hin) for m in range(nmat)]
-        return (dh, None, None, flat[nmat * hout * hin:], *gw)
-
-
-def _run_tagconv(conv: TAGConv, x, topo):
-    return _TAGConvPostFn.apply(x, topo, conv, conv.bias, *[l.weight for l in conv.lins])
 
 
 class _MaskEmbdFn(torch.autograd.Function):

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os as _os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,6 +35,7 @@ _F32 = torch.float32
 from . import flags as FL
 from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
 from .plans import (_DESC_DTYPE, _FoldPlan, _MatView, _PackPlan, _SG_DTYPE, _as_view, _pack_table, _sg, _sg_table, _small_gemm)
+from .route import BlockRoute, block_route, use_global_path
 
 
 # ------------------------------------------------------------------------------------------
@@ -334,12 +335,35 @@ class TAGConv(nn.Module):
             return run_gnn([self], None, "none", x, x, edge_index)
         _require_gpu(x, edge_index)
         topo = get_topology_asis(edge_index, x.size(0))
-        return _TAGConvFn.apply(x, topo, self, self.bias, *self._weights())
+        return _TAGConvFn.apply(x, topo, self, None, self.bias, *self._weights())
+
+
+def _post_spec(mod, post, dev):
+    """(relu, snapshot or None, p) of the 'dropout, then ReLU' that follows a layer inside a per-layer stack (``post``: None / False =
+    nothing follows, True = ReLU, a rate = dropout then ReLU)."""
+    if not post:
+        return False, None, 0.0
+    p = 0.0 if post is True else float(post)
+    snap = dropout_snapshot(mod, dev) if p > 0.0 else None
+    mod._last_dropout = (snap, p)
+    return True, snap, p
+
+
+def _gate(g: torch.Tensor, y: torch.Tensor, snap, p: float) -> torch.Tensor:
+    out = torch.empty_like(y)
+    g = g.contiguous()
+    _lib.check(_lib.lib().dss2_gate_grad(g.data_ptr(), y.data_ptr(), out.data_ptr(), y.size(0), y.size(1),
+                                         (snap.data_ptr() if snap is not None else None), 1, float(p), 1, _stream(y)),
+               "dss2_gate_grad")
+    return out
 
 
 class _TAGConvFn(torch.autograd.Function):
+    """One TAGConv as an autograd node.  ``post`` (see _post_spec): the "dropout, then ReLU" that follows it inside a Multi* stack
+    or the general-width MPN loop, fused into the layer's epilogue; its gradient is one dss2_gate_grad launch."""
+
     @staticmethod
-    def forward(ctx, x, topo, mod, bias, *ws):
+    def forward(ctx, x, topo, mod, post, bias, *ws):
         x = x.contiguous()
         hin, hout, nmat = mod.in_channels, mod.out_channels, mod.K + 1
         glob = use_global_path(topo, nmat)
@@ -349,27 +373,36 @@ class _TAGConvFn(torch.autograd.Function):
         ctx.ver = plan.refresh()
         if not glob:
             topo.lds_check(nmat, _round8(hin), _ncg(hout))
-        out = (_tagconv_forward_global if glob else _tagconv_forward)(topo, x, plan.fwd[0], bias, nmat, hin, hout)
-        ctx.save_for_backward(x)
-        ctx.topo, ctx.mod, ctx.glob = topo, mod, glob
+        relu, snap, p = _post_spec(mod, post, x.device)
+        out = (_tagconv_forward_global if glob else _tagconv_forward)(topo, x, plan.fwd[0], bias, nmat, hin, hout, relu=relu,
+                                                                      drop=((snap, p, 1) if snap is not None else None))
+        # (an un-gated output is not saved: gsp_wls_edge masks the model output IN PLACE, data.py:413, and a saved tensor must
+        #  not change under autograd)
+        ctx.save_for_backward(x, out if relu else None)
+        ctx.meta = (topo, mod, relu, snap, p, glob)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        (x,) = ctx.saved_tensors
-        mod, topo, plan = ctx.mod, ctx.topo, ctx.mod._plan
+        x, y = ctx.saved_tensors
+        topo, mod, relu, snap, p, glob = ctx.meta
+        plan = mod._plan
         if plan.version != ctx.ver:
             plan.refresh()
         hin, hout, nmat = mod.in_channels, mod.out_channels, mod.K + 1
-        g = gout.contiguous()
+        g = _gate(gout, y, snap, p) if relu else gout.contiguous()
         flat = torch.empty(nmat * hout * hin + hout, dtype=_F32, device=g.device)
-        if plan.stacked != ctx.glob:
+        if plan.stacked != glob:
             raise RuntimeError("the module's weight layouts changed between forward and backward")
-        dh = (_tagconv_backward_global if ctx.glob else _tagconv_backward)(
+        dh = (_tagconv_backward_global if glob else _tagconv_backward)(
             topo, g, x, plan.bwd[0], nmat, hin, hout, flat, need_dh=ctx.needs_input_grad[0])
         gw = [flat[m * hout * hin:(m + 1) * hout * hin].view(hout, hin) for m in range(nmat)]
-        gb = flat[nmat * hout * hin:]
-        return (dh, None, None, gb, *gw)
+        return (dh, None, None, None, flat[nmat * hout * hin:], *gw)
+
+
+def _run_tagconv(conv: TAGConv, x, topo):
+    """``conv`` inside a per-layer stack (MultiMPN, MPN._forward_general), which has set ``conv._post``."""
+    return _TAGConvFn.apply(x, topo, conv, conv._post, conv.bias, *conv._weights())
 
 
 class EdgeAggregation(MessagePassing):
@@ -447,15 +480,21 @@ def _no_edge_attr_grad(edge_attr: torch.Tensor) -> None:
                                   "of the reference's training loop, dss2_run.py:138); detach() it")
 
 
-def use_global_path(topo: Topology, nmat: int) -> bool:
-    """A TAGConv runs as ONE plain tile GEMM + K propagation hops in global memory when the graphs exceed the LDS-resident
-    tiles (> 192 nodes) or when K > 3 (the fused tile kernels are instantiated for K + 1 <= 4 matrices)."""
-    return bool(topo.global_only or nmat > 4)
-
-
 def get_topology_asis(edge_index: torch.Tensor, num_nodes: int) -> Topology:
     """Topology of an edge list used exactly as given (standalone EdgeAggregation / TAGConv / propagate)."""
     return get_topology(edge_index, num_nodes, double=False)
+
+
+class _FlatLayout(NamedTuple):
+    offs: List[int]        # segment l of the flat buffer is [offs[l], offs[l + 1])
+    sizes: List[int]       # the pieces in storage order ...
+    shapes: list           # ... their matrix shapes (None: a vector) ...
+    order: List[int]       # ... and the order of MPN._params() over them
+
+    def views(self, flat: torch.Tensor) -> List[torch.Tensor]:
+        """Parameter gradients as views into ``flat``, in the order of MPN._params(): one split call for all pieces."""
+        parts = flat.split(self.sizes)
+        return [parts[i] if self.shapes[i] is None else parts[i].view(self.shapes[i]) for i in self.order]
 
 
 class MPN(nn.Module):
@@ -496,22 +535,31 @@ class MPN(nn.Module):
             ps.extend(l.weight for l in c.lins)
         return ps
 
+    def _layout(self) -> "_FlatLayout":
+        """The block's flat gradient buffer, described once (the dimensions are fixed at construction): segments [W1 | b1],
+        [W2 | b2], [conv l: W_0 .. W_K | bias], and the pieces that become the views returned to autograd."""
+        lay = self.__dict__.get("_flat_layout")
+        if lay is None:
+            hid, nc, nmat, L = self.dim_hid, 2 * self.dim_featn + self.dim_feate, self.K + 1, self.n_gnn_layers
+            pieces = [(hid * nc, (hid, nc)), (hid, None), (hid * hid, (hid, hid)), (hid, None)]      # W1, b1, W2, b2
+            order, offs = [0, 1, 2, 3], [0, hid * nc + hid, hid * nc + hid + hid * hid + hid]
+            for l in range(L):
+                hout = self.dim_out if l == L - 1 else hid
+                base = len(pieces)
+                pieces += [(hout * hid, (hout, hid))] * nmat + [(hout, None)]                       # stored [W_0..W_K | bias]
+                order += [base + nmat] + list(range(base, base + nmat))                              # _params(): bias first
+                offs.append(offs[-1] + nmat * hout * hid + hout)
+            lay = self.__dict__["_flat_layout"] = _FlatLayout(offs, [sz for sz, _ in pieces], [sh for _, sh in pieces], order)
+        return lay
+
     def _flat_offsets(self):
-        """Element offsets of [W1|b1], [W2|b2], [conv l: W_0..W_K | bias] in the flat gradient buffer (a list of ints;
-        the model's dimensions are fixed at construction, so it is computed once)."""
-        cached = self.__dict__.get("_flat_offs")
-        if cached is not None:
-            return cached
-        hid, fn, fe, nmat, L = self.dim_hid, self.dim_featn, self.dim_feate, self.K + 1, self.n_gnn_layers
-        sizes = [hid * (2 * fn + fe) + hid, hid * hid + hid]
-        for l in range(L):
-            hout = self.dim_out if l == L - 1 else hid
-            sizes.append(nmat * hout * hid + hout)
-        offs = [0]
-        for s_ in sizes:
-            offs.append(offs[-1] + s_)
-        self.__dict__["_flat_offs"] = offs
-        return offs
+        """Element offsets of the segments of the flat gradient buffer (a list of ints)."""
+        return self._layout().offs
+
+    def _conv_params(self, ps):
+        """``ps`` (the order of _params()) -> per conv (bias, W_0 .. W_K)."""
+        n = self.K + 2
+        return [ps[4 + l * n: 4 + (l + 1) * n] for l in range(self.n_gnn_layers)]
 
     def forward(self, x, edge_index, edge_attr):
         _require_gpu(x, edge_index, edge_attr)
@@ -529,7 +577,7 @@ class MPN(nn.Module):
         """networks.py:260-273 for input widths other than (8, 6) (or dim_hid > 256): the same layer loop out of the
         per-layer autograd nodes of multi.py -- general edge aggregation, TAGConv with the fused "dropout, then ReLU"
         epilogue -- instead of the fused block.  Correct for every width the kernels take; not the tuned path."""
-        from .multi import _EdgeAggrGeneralFn, _check_general_dims, _run_tagconv
+        from .multi import _EdgeAggrGeneralFn, _check_general_dims
         ea_mod = self.edge_aggr
         _check_general_dims(ea_mod)
         lin1, lin2 = ea_mod.edge_aggr[0], ea_mod.edge_aggr[2]
@@ -548,61 +596,61 @@ class SkipMPN(MPN):
     skip = True
 
 
-def _ensure_plans(mod, topo, dev, ps):
-    """(pack plan, fold plan or None, global-memory mode) of an MPN block, created on first use / when the mode changes."""
+def _ensure_plans(mod, topo, dev, ps, rt: BlockRoute):
+    """(pack plan, fold plan or None) of an MPN block in the weight space of route ``rt``, created on first use / when that changes."""
     L, nmat, hid = mod.n_gnn_layers, mod.K + 1, mod.dim_hid
     W1, b1, W2, b2 = ps[0:4]
-    conv_ps = [ps[4 + l * (nmat + 1): 4 + (l + 1) * (nmat + 1)] for l in range(L)]   # (bias, W_0..W_K)
-    hout0 = mod.dim_out if L == 1 else hid
-    glob = use_global_path(topo, nmat)       # graphs beyond the LDS-resident tiles, or K > 3: plain GEMMs + propagation hops in global memory
-    fold_on = FL.FOLD_W2 and not is_narrow(nmat, hout0) and not glob
-    b16 = tuple(range(1, L)) if (FL.CHAIN_BF16 and not glob and hid % 4 == 0 and hid <= 256 and not is_narrow(nmat, hid) and L >= 2
-                                 and (L >= 3 or gemm16_supported(topo, nmat, hid, False))) else ()
-    # ... as f16x3 where both chains of the block have the form (64-row tiles; csrc/dss2_gemm_chain_sp.hip MS = 2) and the backward takes
-    # the chained route
-    f16 = bool(b16 and L >= 3 and FL.WGRAD_BATCH and chain_f16_supported(topo, nmat, hid))
-    if (mod._plan is None or mod._plan.device != dev or (mod._fold is not None) != fold_on or mod._plan.stacked != glob
-            or tuple(sorted(mod._plan.fwd16)) != b16 or mod._plan.f16 != f16):
+    conv_ps = mod._conv_params(ps)
+    if (mod._plan is None or mod._plan.device != dev or not _plans_match(mod, rt)):
         offs = mod._flat_offsets()
-        mod._fold = _FoldPlan(W2, b2, conv_ps[0][1:], dev, int(offs[1]), int(offs[2])) if fold_on else None
+        mod._fold = _FoldPlan(W2, b2, conv_ps[0][1:], dev, int(offs[1]), int(offs[2])) if rt.fold else None
         conv_groups = [list(cp[1:]) for cp in conv_ps]
-        if fold_on:   # conv 0 is packed from the folded weights
-            conv_groups[0] = [_MatView(mod._fold.Wf[m], hout0, hid, hid, 0, dep=True) for m in range(nmat)]
-        mod._plan = _PackPlan([[W2]] + conv_groups + _dx_views(W1, hid, mod.dim_featn, mod.dim_feate), dev, stacked=glob,
-                              stacked_groups=(L + 3,), bf16_groups=b16, f16=f16)
+        if rt.fold:   # conv 0 is packed from the folded weights
+            conv_groups[0] = [_MatView(mod._fold.Wf[m], conv_ps[0][1].shape[0], hid, hid, 0, dep=True) for m in range(nmat)]
+        mod._plan = _PackPlan([[W2]] + conv_groups + _dx_views(W1, hid, mod.dim_featn, mod.dim_feate), dev, stacked=rt.glob,
+                              stacked_groups=(L + 3,), bf16_groups=rt.b16, f16=rt.f16)
     if mod._fold is not None:
         mod._fold.params = (W2, b2, list(conv_ps[0][1:]))
-    return mod._plan, mod._fold, glob
+    return mod._plan, mod._fold
+
+
+def _plans_match(mod, rt: BlockRoute) -> bool:
+    """The module's plans are those of route ``rt`` (a forward on another topology or under other flags rebuilds them)."""
+    plan = mod._plan
+    return ((mod._fold is not None) == rt.fold and plan.stacked == rt.glob and tuple(sorted(plan.fwd16)) == rt.b16
+            and plan.f16 == rt.f16)
+
+
+class _BlockMeta(NamedTuple):
+    """What one forward call of a block hands to its backward besides the saved tensors."""
+    route: BlockRoute
+    ldx: int
+    ldea: int
+    n_acts: int
+    drop: tuple          # (snapshot or None, p, first mask id of the block)
+    ver: int             # version of the pack plan the forward ran on
+    act_bits: dict       # index into the activations -> sign-bit words of that activation (route.gw > 0)
 
 
 def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
-    """One MPN block forward on raw tensors.  ``stack`` (a _StackRun, PFN / SkipPFN): the weight packing, the fold and the
-    dropout snapshot were already done for all blocks of the stack in one launch each.
-    Returns (out, tensors to keep for backward, meta)."""
+    """One MPN block forward on raw tensors.  ``stack`` (a _StackRun, PFN / SkipPFN): the routes were computed and the weight
+    packing, the fold and the dropout snapshot done for all blocks of the stack, in one launch each.
+    Returns (out, tensors to keep for backward, _BlockMeta)."""
     x, ldx = _rows(x)
     ea, ldea = _rows(ea)
     dev = x.device
     L, nmat, hid = mod.n_gnn_layers, mod.K + 1, mod.dim_hid
     W1, b1, W2, b2 = ps[0:4]
-    conv_ps = [ps[4 + l * (nmat + 1): 4 + (l + 1) * (nmat + 1)] for l in range(L)]   # (bias, W_0..W_K)
-    plan, fold, glob = _ensure_plans(mod, topo, dev, ps)
+    conv_ps = mod._conv_params(ps)   # (bias, W_0..W_K)
+    rt = block_route(mod, topo, need_dx, False) if stack is None else stack.route_of(mod)
+    plan, fold = _ensure_plans(mod, topo, dev, ps, rt)
     if stack is None:
         ver = plan.refresh(fold)      # (fold + packing: one launch)
     else:
         ver = plan.version
-    if not glob:
+    if not rt.glob:
         topo.lds_check(nmat, _round8(hid), _ncg(hid))
-    # the hid -> hid layers 0 .. L-2 as ONE chained launch (activation tile stays in LDS between layers)
-    n_chain = L - 1 if (L - 1 >= 2 and chain_supported(topo, nmat, hid, False, bool(plan.fwd16))) else 0
-    use16 = bool(n_chain) and bool(plan.fwd16) and chain16_supported(topo, nmat, hid, False)
-    gw = chain_gate_words(topo, nmat, hid) if use16 else 0      # (inside autograd.Function.forward grad mode is off: always written; 1/32 of a layer output)
-    # the narrow last layer inside the same launch (the tile is still in the waves' registers): dss2_gemm_prop_chain_head
-    head_fused = bool(n_chain and FL.CHAIN_HEAD_FWD and use16 and n_chain == L - 1 and n_chain <= FL.CHAIN_MAX and not glob and is_narrow(nmat, mod.dim_out)
-                      and chain_head_supported(topo, nmat, hid, mod.dim_out, False))
-    # ... and the edge MLP's first Linear in its staging (dss2_chain_edge, mode 1): the chain computes S itself and writes it for the backward
-    edge_fused = (head_fused and fold is not None and plan.f16 and stack is None and not need_dx
-                  and chain_edge_supported(topo, nmat, hid, False))
-    if edge_fused:
+    if rt.edge:      # the forward chain computes S itself and writes it for the backward
         S = h = torch.empty(topo.N, hid, dtype=_F32, device=dev)
     else:
         S, h = _edge_aggr_forward(topo, x, ldx, ea, ldea, W1, b1, b2, plan.fwd[0], hid, hid, mod.dim_featn, mod.dim_feate,
@@ -610,7 +658,7 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
     if fold is not None:
         h = S            # conv 0 consumes the aggregated hidden directly
     acts = [h]
-    act_bits = {}              # index into acts -> sign-bit words of that activation (chain_gate_words)
+    act_bits = {}
     p = float(mod.dropout_rate)
     # dropout is active regardless of .training (a fresh nn.Dropout is built inside forward, networks.py:268).  The
     # masks are not tensors: the epilogues regenerate them from (snapshot, layer id) in forward and backward.
@@ -625,228 +673,211 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
     def drop_id(l):            # mask applied to conv l's output (none after the last conv)
         return base + l + 1 if (snap is not None and l < L - 1) else 0
 
-    if n_chain:
+    first = rt.n_chain         # first layer with a launch of its own
+    if rt.n_chain:
+        # the hid -> hid layers 0 .. L-2 as ONE chained launch (activation tile stays in LDS between layers)
         layers = []
         # the chain also writes the sign bits of its outputs; the data-gradient chain reads those instead of the
         # activations for its ReLU gates (dss2_chain_layer.y_bits / gate_bits)
-        for l in range(n_chain):
+        for l in range(rt.n_chain):
             out_l = torch.empty(topo.N, hid, dtype=_F32, device=dev)
-            layers.append(dict(Bp=(plan.fwd16[1 + l] if use16 else plan.fwd[1 + l]), Y=out_l, bias=conv_ps[l][0], relu=True,
+            layers.append(dict(Bp=(plan.fwd16[1 + l] if rt.use16 else plan.fwd[1 + l]), Y=out_l, bias=conv_ps[l][0], relu=True,
                                drop_id=drop_id(l), prebias=(fold.bf if (fold is not None and l == 0) else None)))
-            if gw:
-                act_bits[len(acts)] = layers[-1]["y_bits"] = torch.empty(topo.ntiles * gw, dtype=torch.int64, device=dev)
+            if rt.gw:      # (inside autograd.Function.forward grad mode is off: always written; 1/32 of a layer output)
+                act_bits[len(acts)] = layers[-1]["y_bits"] = torch.empty(topo.ntiles * rt.gw, dtype=torch.int64, device=dev)
             acts.append(out_l)
-        head = None
-        if head_fused:
-            y_head = torch.empty(topo.N, mod.dim_out, dtype=_F32, device=dev)
-            head = dict(W=list(conv_ps[L - 1][1:1 + nmat]), nout=mod.dim_out, Y=y_head, bias=conv_ps[L - 1][0],
+        h, head = acts[-1], None
+        if rt.head:      # the narrow last layer inside the same launch (the tile is still in the waves' registers)
+            h, first = torch.empty(topo.N, mod.dim_out, dtype=_F32, device=dev), L
+            head = dict(W=list(conv_ps[L - 1][1:1 + nmat]), nout=mod.dim_out, Y=h, bias=conv_ps[L - 1][0],
                         add_src=(x if mod.skip else None), add_ld=ldx)
-            if edge_fused:
+            if rt.edge:
                 head["edge"] = dict(x=x, ldx=ldx, ea=ea, ldea=ldea, W1=W1, b1=b1, S=S)
-        gemm_prop_chain(topo, h, hid, nmat, layers, pre_rowscale=(topo.deg_pows if fold is not None else None),
-                        drop=((snap, p) if snap is not None else None), b_format=(2 if (use16 and plan.f16) else int(use16)), head=head)
-        h = acts[-1]
-        if head_fused:
-            h, n_chain = y_head, L
-    for l in range(n_chain, L):
+        gemm_prop_chain(topo, acts[0], hid, nmat, layers, pre_rowscale=(topo.deg_pows if fold is not None else None),
+                        drop=((snap, p) if snap is not None else None), b_format=(2 if (rt.use16 and rt.f16) else int(rt.use16)), head=head)
+    for l in range(first, L):
         last = l == L - 1
         hout = mod.dim_out if last else hid
-        if glob:
-            h = _tagconv_forward_global(topo, h, plan.fwd[1 + l], conv_ps[l][0], nmat, hid, hout, relu=not last,
-                                        add_src=(x if (last and mod.skip) else None), add_ld=ldx,
-                                        drop=((snap, p, drop_id(l)) if snap is not None else None))
-            if not last:
-                acts.append(h)
-            continue
-        pre = (fold.bf, topo.deg_pows) if (fold is not None and l == 0) else (None, None)
-        g16 = (not last) and (1 + l) in plan.fwd16 and not plan.f16 and gemm16_supported(topo, nmat, hid, False)      # tall tiles: bf16x6 per layer
-        h = _tagconv_forward(topo, h, (plan.fwd16[1 + l] if g16 else plan.fwd[1 + l]), conv_ps[l][0], nmat, hid, hout, relu=not last,
-                             add_src=(x if (last and mod.skip) else None), add_ld=ldx,
-                             prebias=pre[0], pre_rowscale=pre[1],
-                             drop=((snap, p, drop_id(l)) if snap is not None else None), b_format=int(g16))
+        kw = dict(relu=not last, add_src=(x if (last and mod.skip) else None), add_ld=ldx,
+                  drop=((snap, p, drop_id(l)) if snap is not None else None))
+        if rt.glob:
+            h = _tagconv_forward_global(topo, h, plan.fwd[1 + l], conv_ps[l][0], nmat, hid, hout, **kw)
+        else:
+            pre = (fold.bf, topo.deg_pows) if (fold is not None and l == 0) else (None, None)
+            g16 = rt.g16[l]      # tall tiles: bf16x6 per layer
+            h = _tagconv_forward(topo, h, (plan.fwd16[1 + l] if g16 else plan.fwd[1 + l]), conv_ps[l][0], nmat, hid, hout,
+                                 prebias=pre[0], pre_rowscale=pre[1], b_format=int(g16), **kw)
         if not last:
             acts.append(h)
-    meta = (ldx, ldea, len(acts), (snap, p, base), fold is not None, glob, ver, act_bits)
-    return h, [x, ea, S] + acts, meta
+    return h, [x, ea, S] + acts, _BlockMeta(rt, ldx, ldea, len(acts), (snap, p, base), ver, act_bits)
+
+
+class _BlockBackward(NamedTuple):
+    """The state the sections of one block's backward share."""
+    mod: nn.Module
+    topo: Topology
+    rt: BlockRoute
+    meta: _BlockMeta
+    plan: _PackPlan
+    fold: Optional[_FoldPlan]
+    S: torch.Tensor
+    acts: list
+    ps: Sequence[torch.Tensor]
+    flat: torch.Tensor
+    offs: List[int]
+    pending: Optional[list]
+
+    def seg(self, l: int, l1: Optional[int] = None) -> torch.Tensor:
+        """Conv l's segment [W_0..W_K | bias] of the flat buffer (through conv l1's)."""
+        return self.flat[self.offs[2 + l]:self.offs[3 + (l if l1 is None else l1)]]
+
+    def drop_of(self, l: int):
+        """The mask that was applied to conv l's output: (snapshot, p, id) or None."""
+        snap, p, base = self.meta.drop
+        return (snap, p, base + l + 1) if (snap is not None and l >= 0) else None
 
 
 def _mpn_backward(mod, topo, saved, ps, meta, gout, need_dx, flat=None, pending=None):
-    """Backward of _mpn_forward.  Standalone (flat is None): allocates the block's flat gradient buffer, runs its slab
-    reductions and the fold's chain rule, calls the all-reduce hook.  Inside a stack: ``flat`` is the block's slice of the
-    stack's buffer and every slab reduction is only recorded in ``pending``; the caller runs them (and the chain rule of
-    all folds) in one launch each after the last block.  Returns (dx, parameter gradients as views into flat, fold_late)."""
-    ldx, ldea, n_acts, (snap, p_drop, base), folded, glob, ver, act_bits = meta
+    """Backward of _mpn_forward along the route the forward stored in ``meta``.  Standalone (flat is None): allocates the block's
+    flat gradient buffer, runs its slab reductions and the fold's chain rule, calls the all-reduce hook.  Inside a stack: ``flat``
+    is the block's slice of the stack's buffer and every slab reduction is only recorded in ``pending``; the caller runs them
+    (and the chain rule of all folds) in one launch each after the last block.  Returns (dx, parameter gradients as views into
+    flat, whether the fold's chain rule is due)."""
+    rt = meta.route
     x, ea, S = saved[0:3]
-    acts = list(saved[3:3 + n_acts])
-    in_stack = flat is not None
-
-    def drop_of(l):            # the mask that was applied to conv l's output: (snapshot, p, id) or None
-        return (snap, p_drop, base + l + 1) if snap is not None else None
+    standalone = flat is None
     plan, fold = mod._plan, mod._fold
-    if folded != (fold is not None) or plan.stacked != glob:
+    if not _plans_match(mod, rt):      # (another forward, on another topology or under other flags, rebuilt them in between)
         raise RuntimeError("DSS2_FOLD_W2 / the module's plan changed between forward and backward")
-    if plan.version != ver:
+    if plan.version != meta.ver:
         plan.refresh(fold)   # weights are checked unchanged by autograd's saved-tensor versioning
-    dev = gout.device
-    L, nmat, hid, fn, fe = mod.n_gnn_layers, mod.K + 1, mod.dim_hid, mod.dim_featn, mod.dim_feate
-    W1, b1 = ps[0], ps[1]
     # one flat gradient buffer; parameter gradients are returned as views into it
-    offs = mod._flat_offsets()
-    if flat is None:
-        flat = torch.empty(int(offs[-1]), dtype=_F32, device=dev)
+    lay = mod._layout()
+    if standalone:
+        flat = torch.empty(lay.offs[-1], dtype=_F32, device=gout.device)
+    if rt.bwd_chain and pending is None:
+        pending = []         # the chained route's slab reductions run in ONE launch at the end (always so inside a stack)
+    c = _BlockBackward(mod, topo, rt, meta, plan, fold, S, list(saved[3:3 + meta.n_acts]), ps, flat, lay.offs, pending)
     g = gout.contiguous()
-    deferred = []
-    l_start = L - 1
-    dS = None
-    edge_slab = None           # (the edge MLP's backward inside the data-gradient chain: its per-tile dW1 | db1 slabs)
-    # slab reductions recorded in ``pending`` run in ONE launch at the end (chained path; always inside a stack)
-    fold_late = False
-    if L >= 3 and FL.WGRAD_BATCH and chain_supported(topo, nmat, hid, True, bool(plan.bwd16)):
-        # last layer on its own; then the data-gradients of layers L-2 .. 0 as ONE chained launch
-        if pending is None:
-            pending = []
-        l = L - 1
-        use16 = bool(plan.bwd16) and chain16_supported(topo, nmat, hid, True)
-        # the head's data gradient inside the chained launch (its input tile is computed from the dim_out-wide upstream gradient):
-        # dss2_gemm_prop_chain_head, mode 2; only the head's weight gradient keeps a launch of its own
-        # (tall tiles: only the direction-specialised data-gradient chain has the head form -- its layers gate with bit words)
-        head_fused = (use16 and L - 1 <= FL.CHAIN_MAX and is_narrow(nmat, mod.dim_out)
-                      and chain_head_supported(topo, nmat, hid, mod.dim_out, True)
-                      and (topo.nrb <= 2 or all(act_bits.get(l_) is not None for l_ in range(1, L - 1))))
-        head = None
-        head_wg = None
-        # the edge MLP's backward behind the chain's last layer (dss2_chain_edge, mode 2): conv 0's input gradient never leaves the chip,
-        # one dW1 | db1 slab per tile
-        edge_fused = (head_fused and fold is not None and use16 and plan.f16 and not in_stack and not need_dx
-                      and chain_edge_supported(topo, nmat, hid, True))
-        if head_fused:
-            # ... and the head's weight gradient from the same staging (it holds the hop results and the head's input rows): one slab
-            # per tile, summed with the step's other slabs; elsewhere the narrow weight-gradient launch re-reads the activation
-            hw_fused = chain_head_wgrad_supported(topo, nmat, hid, mod.dim_out)
-            if hw_fused:
-                hw_len = nmat * mod.dim_out * hid + mod.dim_out
-                hw_stride = (hw_len + 3) & ~3      # (16-byte lanes in the reduction)
-                head_wg = (torch.empty(topo.ntiles * hw_stride, dtype=_F32, device=dev), hw_len, flat[offs[2 + l]:offs[3 + l]], hw_stride)
-            else:
-                _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, mod.dim_out, flat[offs[2 + l]:offs[3 + l]],
-                                  need_dh=False, pending=pending)
-            g_in = torch.empty(topo.N, hid, dtype=_F32, device=dev)
-            dr = drop_of(l - 1)
-            head = dict(W=list(ps[4 + l * (nmat + 1) + 1:4 + (l + 1) * (nmat + 1)]), nout=mod.dim_out, G=g, gate=acts[l], Xout=g_in,
-                        drop_id=(dr[2] if dr is not None else 0), wg_slab=(head_wg[0] if head_wg is not None else None),
-                        wg_stride=(head_wg[3] if head_wg is not None else 0))
-            if edge_fused:
-                edge_slab = torch.empty(topo.ntiles * (hid * (2 * fn + fe) + hid), dtype=_F32, device=dev)
-                head["edge"] = dict(x=x, ldx=ldx, ea=ea, ldea=ldea, W1=W1, b1=b1, slab=edge_slab)
-            g = g_in
-        else:
-            g = _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, mod.dim_out, flat[offs[2 + l]:offs[3 + l]],
-                                  relu_src=acts[l], drop=drop_of(l - 1), pending=pending)
-        gl = [None] * (L - 1)                   # gl[l]: gradient w.r.t. layer l's pre-activation output
-        gl[L - 2] = g
-        layers = []
-        for l in range(L - 2, -1, -1):
-            out_l = torch.empty(topo.N, hid, dtype=_F32, device=dev)
-            layers.append(dict(Bp=(plan.bwd16[1 + l] if use16 else plan.bwd[1 + l]), Y=out_l, relu_src=(acts[l] if l > 0 else None),
-                               gate_bits=(act_bits.get(l) if (l > 0 and use16) else None),
-                               drop_id=(base + l if (l > 0 and snap is not None) else 0)))      # mask of conv l-1: id (l-1)+1
-            if l > 0:
-                gl[l - 1] = out_l
-        gemm_prop_chain(topo, (None if head_fused else g), hid, nmat, layers, transposed=True,
-                        drop=((snap, p_drop) if snap is not None else None), b_format=(2 if (use16 and plan.f16) else int(use16)), head=head)
-        if head_wg is not None:
-            _reduce(head_wg[0], 0, topo.ntiles, head_wg[3], head_wg[2], head_wg[1], pending)
-        if edge_slab is not None:
-            e_stride = hid * (2 * fn + fe) + hid
-            _reduce(edge_slab, 0, topo.ntiles, e_stride, flat[offs[0]:offs[1]], e_stride, pending)
-        d_in = layers[-1]["Y"]                  # gradient w.r.t. conv 0's input: dS (folded) or dx0
-        # The folded conv 0 joins the batched launch of the plain layers (round 4; FL.WGRAD_JOIN_FOLDED=False: its own launch).
-        # Round 3 kept it apart because three layers x 85 workgroups leave a 13-vs-12-tile tail at C2; measured now, the
-        # joined launch is 141 us against 93 + 57, and -- what matters more -- the step writes and re-reads half the slabs
-        # (255 x 197 KB instead of 128 x 2 + 256): reduction 24.7 -> 17.8 us, C2 step 0.537 -> 0.509 ms on one box.
-        join = True if FL.WGRAD_JOIN_FOLDED is None else bool(FL.WGRAD_JOIN_FOLDED)
-        if fold is not None and L - 1 <= 8 and join:
-            # the folded conv 0 (input S, extra scaled bias sums) and the plain layers 1 .. L-2 in ONE launch
-            wgrad_batched(topo, gl, hid, [S] + acts[1:L - 1], hid, nmat, flat[offs[3]:offs[2 + L - 1]],
-                          first_rowscale2=topo.deg_pows, first_out=fold.gfold, pending=pending)
-            fold_late = True        # the chain rule of the fold needs the reduced gfold
-            dS, g = d_in, None
-        else:
-            if fold is not None:
-                wgrad(topo, gl[0], hid, S, hid, nmat, fold.gfold, rowscale2=topo.deg_pows, pending=pending)
-                fold_late = True
-                dS, g = d_in, None
-            else:
-                g = d_in
-            deferred = [(l, gl[l], acts[l]) for l in range(L - 2, (0 if fold is not None else -1), -1)]
-        l_start = -1
-    for l in range(l_start, -1, -1):
-        hout = mod.dim_out if l == L - 1 else hid
-        seg = flat[offs[2 + l]:offs[3 + l]]
-        if l == 0 and fold is not None:
-            # folded conv 0: weight gradient w.r.t. Wf / bf into the plan's buffer, data gradient is dS;
-            # one small-GEMM launch then writes dW_m, conv0.bias, dW2, db2 into the flat buffer
-            wgrad(topo, g, hout, S, hid, nmat, fold.gfold, rowscale2=topo.deg_pows, pending=pending)
-            dS = torch.empty(topo.N, hid, dtype=_F32, device=dev)
-            g16 = hout == hid and 1 in plan.bwd16 and not plan.f16 and gemm16_supported(topo, nmat, hid, True)
-            gemm_prop(topo, g, g.stride(0), hout, (plan.bwd16[1] if g16 else plan.bwd[1]), nmat, hid, dS, transposed=True, b_format=int(g16))
-            fold_late = True
-            g = None
-            break
-        # dgrad epilogue applies the ReLU / dropout mask of the layer BELOW (its output is acts[l])
-        if glob:
-            g = _tagconv_backward_global(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, hout, seg,
-                                         relu_src=(acts[l] if l > 0 else None),
-                                         drop=(drop_of(l - 1) if l > 0 else None), pending=pending)
-            continue
-        defer = FL.WGRAD_BATCH and hout == hid and not is_narrow(nmat, hout)
-        if defer:
-            deferred.append((l, g, acts[l]))
-        g16 = hout == hid and (1 + l) in plan.bwd16 and not plan.f16 and gemm16_supported(topo, nmat, hid, True)
-        g = _tagconv_backward(topo, g, acts[l], (plan.bwd16[1 + l] if g16 else plan.bwd[1 + l]), nmat, hid, hout, seg,
-                              relu_src=(acts[l] if l > 0 else None), drop=(drop_of(l - 1) if l > 0 else None),
-                              defer_wgrad=defer, pending=pending, b_format=int(g16))
-    # weight gradients of the hid -> hid layers: independent of each other, so one launch (and one slab
-    # reduction) covers up to 8 consecutive layers; their segments in the flat buffer are contiguous
-    deferred.reverse()
-    for c0 in range(0, len(deferred), 8):
-        chunk = deferred[c0:c0 + 8]
-        l0, l1 = chunk[0][0], chunk[-1][0]
-        out = flat[offs[2 + l0]:offs[3 + l1]]
-        if len(chunk) == 1:
-            wgrad(topo, chunk[0][1], hid, chunk[0][2], hid, nmat, out, pending=pending)
-        else:
-            wgrad_batched(topo, [c[1] for c in chunk], hid, [c[2] for c in chunk], hid, nmat, out, pending=pending)
-    if edge_slab is not None:      # (done inside the data-gradient chain; no input gradient asked for)
-        dx = None
-    else:
-        dx = _edge_aggr_backward(topo, g, x, ldx, ea, ldea, W1, b1, S, plan.bwd[0], hid, hid, fn, fe,
-                                 flat[offs[0]:offs[1]], flat[offs[1]:offs[2]], need_dx,
-                                 pack_dx=tuple(plan.bwd[1 + L:4 + L]), dS=(dS if fold is not None else None),
+    edge = dict(x=x, ldx=meta.ldx, ea=ea, ldea=meta.ldea, W1=ps[0], b1=ps[1])
+    d_in, deferred = _bwd_chained(c, g, edge) if rt.bwd_chain else _bwd_layers(c, g)
+    _bwd_deferred_wgrads(c, deferred)
+    dx = None
+    if not rt.bwd_edge:      # (else done inside the data-gradient chain; no input gradient asked for)
+        fn, fe, L, hid = mod.dim_featn, mod.dim_feate, mod.n_gnn_layers, mod.dim_hid
+        dx = _edge_aggr_backward(topo, (None if rt.fold else d_in), x, meta.ldx, ea, meta.ldea, ps[0], ps[1], S, plan.bwd[0], hid, hid,
+                                 fn, fe, flat[lay.offs[0]:lay.offs[1]], flat[lay.offs[1]:lay.offs[2]], need_dx,
+                                 pack_dx=tuple(plan.bwd[1 + L:4 + L]), dS=(d_in if rt.fold else None),
                                  pending=pending, dx_add=(gout if (need_dx and mod.skip) else None))
-    if not in_stack:
+    if standalone:
         # all slab reductions of the block in one launch, then the chain rule of the fold (it needs the reduced gfold)
-        if fold_late:
+        if rt.fold:
             fold._check()
-        finish_weights(pending if pending is not None else [], (fold.bwd_tab if fold_late else None), flat, dev)
+        finish_weights(pending if pending is not None else [], (fold.bwd_tab if rt.fold else None), flat, gout.device)
         hook = getattr(mod, "_grad_bucket_hook", None)
         if hook is not None:      # data-parallel: all-reduce the flat bucket once (parallel.py)
             hook(flat)
-    # parameter gradients = views into the flat buffer, in the order of MPN._params(): one split call for all pieces
-    lay = mod.__dict__.get("_grad_layout")
-    if lay is None:
-        nc = 2 * fn + fe
-        pieces = [(hid * nc, (hid, nc)), (hid, None), (hid * hid, (hid, hid)), (hid, None)]      # W1, b1, W2, b2
-        order = [0, 1, 2, 3]
-        for l in range(L):
-            hout = mod.dim_out if l == L - 1 else hid
-            base = len(pieces)
-            pieces += [(hout * hid, (hout, hid))] * nmat + [(hout, None)]                       # stored [W_0..W_K | bias]
-            order += [base + nmat] + list(range(base, base + nmat))                              # returned bias first
-        lay = mod.__dict__["_grad_layout"] = ([sz for sz, _ in pieces], [sh for _, sh in pieces], order)
-    parts = flat.split(lay[0])
-    grads = [parts[i] if lay[1][i] is None else parts[i].view(lay[1][i]) for i in lay[2]]
-    return dx, grads, fold_late
+    return dx, lay.views(flat), rt.fold
+
+
+def _bwd_chained(c: _BlockBackward, g, edge):
+    """The last layer, then the data gradients of layers L-2 .. 0 as ONE chained launch; with the route's fused forms the head's
+    data and weight gradients and the edge MLP's backward (``edge``: its inputs) ride in that launch.  Returns (gradient w.r.t.
+    conv 0's input -- dS when folded --, the layers (l, gradient, input) whose weight gradients are still due)."""
+    mod, topo, rt, plan, acts, pending = c.mod, c.topo, c.rt, c.plan, c.acts, c.pending
+    L, nmat, hid, nout = mod.n_gnn_layers, mod.K + 1, mod.dim_hid, mod.dim_out
+    dev = g.device
+    snap, p_drop, base = c.meta.drop
+    l = L - 1
+    head = head_wg = edge_slab = None
+    if rt.bwd_head:
+        # the head's input tile is computed from the dim_out-wide upstream gradient (dss2_gemm_prop_chain_head, mode 2) ...
+        if rt.bwd_head_wgrad:
+            # ... and its weight gradient from the same staging (it holds the hop results and the head's input rows): one slab
+            # per tile, summed with the step's other slabs
+            hw_len = nmat * nout * hid + nout
+            hw_stride = (hw_len + 3) & ~3      # (16-byte lanes in the reduction)
+            head_wg = torch.empty(topo.ntiles * hw_stride, dtype=_F32, device=dev)
+        else:      # the narrow weight-gradient launch re-reads the activation
+            _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, nout, c.seg(l), need_dh=False, pending=pending)
+        dr = c.drop_of(l - 1)
+        head = dict(W=list(c.ps[4 + l * (nmat + 1) + 1:4 + (l + 1) * (nmat + 1)]), nout=nout, G=g, gate=acts[l],
+                    Xout=torch.empty(topo.N, hid, dtype=_F32, device=dev), drop_id=(dr[2] if dr is not None else 0),
+                    wg_slab=head_wg, wg_stride=(hw_stride if head_wg is not None else 0))
+        if rt.bwd_edge:
+            # conv 0's input gradient never leaves the chip: one dW1 | db1 slab per tile
+            e_stride = c.offs[1] - c.offs[0]
+            edge_slab = torch.empty(topo.ntiles * e_stride, dtype=_F32, device=dev)
+            head["edge"] = dict(edge, slab=edge_slab)
+        g_top = head["Xout"]
+    else:
+        g_top = _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, nout, c.seg(l),
+                                  relu_src=acts[l], drop=c.drop_of(l - 1), pending=pending)
+    gl = [None] * (L - 1)                   # gl[l]: gradient w.r.t. layer l's pre-activation output
+    gl[L - 2] = g_top
+    layers = []
+    for l in range(L - 2, -1, -1):
+        out_l = torch.empty(topo.N, hid, dtype=_F32, device=dev)
+        layers.append(dict(Bp=(plan.bwd16[1 + l] if rt.bwd_use16 else plan.bwd[1 + l]), Y=out_l, relu_src=(acts[l] if l > 0 else None),
+                           gate_bits=(c.meta.act_bits.get(l) if (l > 0 and rt.bwd_use16) else None),
+                           drop_id=(base + l if (l > 0 and snap is not None) else 0)))      # mask of conv l-1: id (l-1)+1
+        if l > 0:
+            gl[l - 1] = out_l
+    gemm_prop_chain(topo, (None if rt.bwd_head else g_top), hid, nmat, layers, transposed=True,
+                    drop=((snap, p_drop) if snap is not None else None), b_format=(2 if (rt.bwd_use16 and rt.f16) else int(rt.bwd_use16)),
+                    head=head)
+    if head_wg is not None:
+        _reduce(head_wg, 0, topo.ntiles, hw_stride, c.seg(L - 1), hw_len, pending)
+    if edge_slab is not None:
+        _reduce(edge_slab, 0, topo.ntiles, e_stride, c.flat[c.offs[0]:c.offs[1]], e_stride, pending)
+    if rt.bwd_join:
+        # the folded conv 0 (input S, extra scaled bias sums) and the plain layers 1 .. L-2 in ONE launch
+        wgrad_batched(topo, gl, hid, [c.S] + acts[1:L - 1], hid, nmat, c.seg(1, L - 2),
+                      first_rowscale2=topo.deg_pows, first_out=c.fold.gfold, pending=pending)
+    elif rt.fold:
+        wgrad(topo, gl[0], hid, c.S, hid, nmat, c.fold.gfold, rowscale2=topo.deg_pows, pending=pending)
+    return layers[-1]["Y"], [(l, gl[l], acts[l]) for l in range(L - 1) if rt.bwd_defer[l]]
+
+
+def _bwd_layers(c: _BlockBackward, g):
+    """Layers L-1 .. 0 one launch each.  Returns as _bwd_chained."""
+    mod, topo, rt, plan, acts, pending = c.mod, c.topo, c.rt, c.plan, c.acts, c.pending
+    L, nmat, hid = mod.n_gnn_layers, mod.K + 1, mod.dim_hid
+    deferred = []
+    for l in range(L - 1, -1, -1):
+        hout = mod.dim_out if l == L - 1 else hid
+        g16 = rt.bwd_g16[l]
+        Bp = plan.bwd16[1 + l] if g16 else plan.bwd[1 + l]
+        # the data gradient's epilogue applies the ReLU / dropout mask of the layer BELOW (its output is acts[l])
+        below = dict(relu_src=(acts[l] if l > 0 else None), drop=c.drop_of(l - 1))
+        if l == 0 and rt.fold:
+            # folded conv 0: weight gradient w.r.t. Wf / bf into the plan's buffer, data gradient is dS;
+            # one small-GEMM launch then writes dW_m, conv0.bias, dW2, db2 into the flat buffer
+            wgrad(topo, g, hout, c.S, hid, nmat, c.fold.gfold, rowscale2=topo.deg_pows, pending=pending)
+            dS = torch.empty(topo.N, hid, dtype=_F32, device=g.device)
+            gemm_prop(topo, g, g.stride(0), hout, Bp, nmat, hid, dS, transposed=True, b_format=int(g16))
+            g = dS
+        elif rt.glob:
+            g = _tagconv_backward_global(topo, g, acts[l], Bp, nmat, hid, hout, c.seg(l), pending=pending, **below)
+        else:
+            if rt.bwd_defer[l]:
+                deferred.append((l, g, acts[l]))
+            g = _tagconv_backward(topo, g, acts[l], Bp, nmat, hid, hout, c.seg(l), defer_wgrad=rt.bwd_defer[l], pending=pending,
+                                  b_format=int(g16), **below)
+    return g, deferred[::-1]
+
+
+def _bwd_deferred_wgrads(c: _BlockBackward, deferred):
+    """Weight gradients of the hid -> hid layers ``deferred`` (ascending): independent of each other, so one launch (and one slab
+    reduction) covers up to 8 consecutive layers; their segments in the flat buffer are contiguous."""
+    hid, nmat = c.mod.dim_hid, c.mod.K + 1
+    for c0 in range(0, len(deferred), 8):
+        chunk = deferred[c0:c0 + 8]
+        out = c.seg(chunk[0][0], chunk[-1][0])
+        if len(chunk) == 1:
+            wgrad(c.topo, chunk[0][1], hid, chunk[0][2], hid, nmat, out, pending=c.pending)
+        else:
+            wgrad_batched(c.topo, [t[1] for t in chunk], hid, [t[2] for t in chunk], hid, nmat, out, pending=c.pending)
 
 
 class _MPNFn(torch.autograd.Function):
@@ -884,12 +915,12 @@ class _StackPlan:
         self.fold_fwd = self.fold_bwd = self.pack_tab = None
         self.table_builds = 0
 
-    def refresh(self, topo, params):
-        plans = [_ensure_plans(m, topo, self.device, ps) for m, ps in zip(self.blocks, params)]
-        key = tuple((id(p), id(f), p.pointers(), f.pointers() if f is not None else None) for p, f, _ in plans)
+    def refresh(self, topo, params, routes):
+        plans = [_ensure_plans(m, topo, self.device, ps, rt) for m, ps, rt in zip(self.blocks, params, routes)]
+        key = tuple((id(p), id(f), p.pointers(), f.pointers() if f is not None else None) for p, f in plans)
         if key != self.key:
             fwd, bwd, recs, max_elems = [], [], [], 0
-            for b, (p, f, _) in enumerate(plans):
+            for b, (p, f) in enumerate(plans):
                 if f is not None:
                     f_, b_ = f.records(self.base[b])
                     fwd += f_
@@ -903,15 +934,18 @@ class _StackPlan:
             self.key = key
             self.table_builds += 1
         prep_weights(self.fold_fwd, self.pack_tab, self.device)      # every block's fold, then every block's packing: one launch each
-        for p, _, _ in plans:
+        for p, _ in plans:
             p.version += 1
 
 
 class _StackRun:
     """Per-forward state of a stack (what one call's blocks and its backward share)."""
 
-    def __init__(self, plan: _StackPlan, snapshot):
-        self.plan, self.snapshot = plan, snapshot
+    def __init__(self, plan: _StackPlan, snapshot, routes):
+        self.plan, self.snapshot, self.routes = plan, snapshot, routes
+
+    def route_of(self, mod) -> BlockRoute:
+        return self.routes[self.plan.blocks.index(mod)]
 
     def drop_base(self, mod) -> int:
         return self.plan.blocks.index(mod) * _StackPlan.DROP_STRIDE
@@ -933,12 +967,14 @@ class _PFNFn(torch.autograd.Function):
         sp = pfn._stack_plan
         if sp is None or sp.device != dev:
             sp = pfn._stack_plan = _StackPlan(blocks, dev)
-        sp.refresh(topo, params)
+        need_dx = [bi > 0 or ctx.needs_input_grad[0] for bi in range(len(blocks))]
+        routes = [block_route(m, topo, nd, True) for m, nd in zip(blocks, need_dx)]
+        sp.refresh(topo, params, routes)
         snap = dropout_snapshot(pfn, dev) if float(pfn.dropout_rate) > 0.0 else None
-        run = _StackRun(sp, snap)
+        run = _StackRun(sp, snap, routes)
         saved, metas, counts = [], [], []
         for bi, (m, bp) in enumerate(zip(blocks, params)):
-            x, sv, meta = _mpn_forward(m, topo, x, ea, bp, stack=run, need_dx=(bi > 0 or ctx.needs_input_grad[0]))
+            x, sv, meta = _mpn_forward(m, topo, x, ea, bp, stack=run, need_dx=need_dx[bi])
             saved += sv
             metas.append(meta)
             counts.append(len(sv))
