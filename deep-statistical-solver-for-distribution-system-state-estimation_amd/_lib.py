@@ -81,6 +81,15 @@ class EllBuildArgs(C.Structure):
                 ("ellT_ent_tiles", C.c_void_p), ("meta", C.c_void_p), ("uniform_rows", C.c_int32), ("n_nodes", C.c_int64)]
 
 
+PADDED_MAX_TILINGS = 4
+
+
+class PaddedBuildArgs(C.Structure):
+    _fields_ = [("csr", CsrBuildArgs), ("nodes_per_graph", C.c_int32), ("edge_stride", C.c_int32), ("edge_count", C.c_void_p),
+                ("csr_ptr", C.c_void_p), ("edge_total", C.c_void_p), ("deg_pows", C.c_void_p), ("n_ell", C.c_int32), ("pad_", C.c_int32),
+                ("ell", EllBuildArgs * PADDED_MAX_TILINGS)]
+
+
 class CsrAxpyArgs(C.Structure):
     _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("w", C.c_void_p), ("T", C.c_void_p), ("ldt", C.c_int64),
                 ("add", C.c_void_p), ("ld_add", C.c_int64), ("out", C.c_void_p), ("ldo", C.c_int64), ("bias", C.c_void_p),
@@ -131,7 +140,7 @@ class WlsArgs(C.Structure):
                 ("lam_v", C.c_float), ("lam_p", C.c_float), ("lam_pf", C.c_float), ("lam_reg", C.c_float),
                 ("sums", C.c_void_p), ("partials", C.c_void_p), ("vminmax", C.c_void_p),
                 ("apq", C.c_void_p), ("loss", C.c_void_p), ("grad_output", C.c_void_p), ("pflow", C.c_void_p),
-                ("flags", C.c_int32), ("counter", C.c_void_p), ("gscale", C.c_void_p)]
+                ("flags", C.c_int32), ("counter", C.c_void_p), ("gscale", C.c_void_p), ("edge_count", C.c_void_p)]
 
 
 WLS_VMM_CACHED, WLS_FUSED_FINISH, WLS_NO_LOSS_WRITE = 1, 2, 4
@@ -324,6 +333,7 @@ _SIGNATURES = {
     "dss2_collate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "dss2_csr_build_graphs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "dss2_csr_build_graphs_supported": (C.c_int, [C.c_int32, C.c_int32]),
+    "dss2_csr_build_padded": (C.c_int, [C.POINTER(PaddedBuildArgs), C.c_void_p]),
     "dss2_collate_cursor": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "dss2_accum_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dss2_collate_ragged_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -160,6 +160,10 @@ __global__ void __launch_bounds__(256) collate_kernel(const CollateTable tab, co
     const float* src = static_cast<const float*>(d.src) + s * d.chunk;
     float* dst = static_cast<float*>(d.dst) + b * d.chunk;
     for (int k = threadIdx.x; k < d.chunk; k += blockDim.x) dst[k] = src[k];
+  } else if (d.kind == 2) {   // int32 words per sample (a padded store's edge counts)
+    const int32_t* src = static_cast<const int32_t*>(d.src) + s * d.chunk;
+    int32_t* dst = static_cast<int32_t*>(d.dst) + b * d.chunk;
+    for (int k = threadIdx.x; k < d.chunk; k += blockDim.x) dst[k] = src[k];
   } else {   // edge_index: src [S][2][e] (or one shared [2][e] when d.shared), dst [2][B*e]
     const int e = d.chunk;
     const long long* src = static_cast<const long long*>(d.src) + (d.shared ? 0 : s * 2 * e);

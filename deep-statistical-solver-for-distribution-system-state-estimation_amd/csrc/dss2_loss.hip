@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(LB) wls_partials_kernel(const dss2_wls_args p)
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double Nn = (double)p.n_nodes, Ee = (double)p.n_edges, lr = (double)p.lam_reg;
+    const double Nn = (double)p.n_nodes, Ee = p.edge_count ? (double)p.edge_count[0] : (double)p.n_edges, lr = (double)p.lam_reg;
     p.sums[5] = Nn; p.sums[6] = Ee; p.sums[7] = 0;
     const double mv = tot[2] / Nn, mt = tot[3] / Ee, ml = tot[4] / Ee;
     p.loss[0] = (float)(tot[0] / Nn + tot[1] / Ee + lr * mv * mv + lr * mt * mt + lr * ml * ml);
@@ -306,8 +306,10 @@ __global__ void wls_value_kernel(const double* __restrict__ sums, float lam_reg,
 // a fixed-order butterfly.  Deterministic.
 __global__ void __launch_bounds__(320) wls_finish_kernel(const double* __restrict__ partials, int n_blocks,
                                                          double* __restrict__ sums, double n_nodes, double n_edges,
-                                                         float lam_reg, float* __restrict__ loss) {
+                                                         float lam_reg, float* __restrict__ loss,
+                                                         const int32_t* __restrict__ edge_count) {
   __shared__ double tot[5];
+  if (edge_count) n_edges = (double)edge_count[0];      // (padded batches: the real edge count lives on the device)
   const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double s = 0;
   for (int b = lane; b < n_blocks; b += 64) s += partials[(size_t)b * 5 + c];
@@ -554,7 +556,7 @@ static int dss2_wls_loss_partials_launch(const dss2_wls_args* ap, void* stream) 
   hipLaunchKernelGGL(wls_partials_kernel, dim3((unsigned)nb), dim3(LB), 0, s, a);
   if (!(a.flags & DSS2_WLS_FUSED_FINISH))
     hipLaunchKernelGGL(wls_finish_kernel, dim3(1), dim3(320), 0, s, a.partials, (int)nb, a.sums, (double)a.n_nodes,
-                       (double)a.n_edges, a.lam_reg, a.loss);
+                       (double)a.n_edges, a.lam_reg, a.loss, a.edge_count);
   return check_launch("wls_loss_partials");
 }
 

@@ -415,6 +415,9 @@ struct GraphBuildArgs {
   int32_t *rowptr, *rowptrT, *inc_rowptr, *lastcut;
   const long long* edge_ptr; int n, e_uniform, emax; long long G;
   float* deg_pows;      // [N][4] or NULL
+  // padded batches (dss2_csr_build_padded): graph g owns the e_uniform stored slots from g * e_uniform, its first edge_count[g] are branches, and
+  // its CSR entries start at csr_ptr[g] -- the exclusive sum of the counts -- instead of at its first slot.  NULL: every slot is a branch
+  const int32_t* edge_count; const long long* csr_ptr;
 };
 
 // scans over a GROUP of W consecutive lanes (W = 16, 32 or 64: one graph per group)
@@ -447,6 +450,8 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
   const long long gg = live ? g : 0;
   const long long e0 = a.edge_ptr ? a.edge_ptr[gg] : gg * a.e_uniform, e1 = a.edge_ptr ? a.edge_ptr[gg + 1] : (gg + 1) * (long long)a.e_uniform;
   int ne = live ? (int)(e1 - e0) : 0;
+  long long c0 = e0;      // where the graph's entries start in the CSR arrays (per directed copy) and in the incidence lists (per end)
+  if (a.edge_count) { c0 = a.csr_ptr[gg]; ne = live ? a.edge_count[gg] : 0; }
   const long long nb = gg * n;
   const int dbl = p.doubled ? 2 : 1;
   // per-group LDS: 11 arrays of n + 2 ints, three key arrays, the local endpoints, two double vectors
@@ -458,7 +463,7 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
   int32_t *ela = keysI + 2 * emax, *elb = ela + emax;      // the graph's stored edges, local endpoints: everything after the counting pass reads these
   double* v0 = reinterpret_cast<double*>(elb + emax + ((size_t)(elb + emax) & 4 ? 1 : 0));      // (8-byte aligned)
   double* v1 = v0 + n;
-  if (ne < 0 || ne > emax) { if (sl == 0) p.meta[5] = 1; ne = 0; }
+  if (ne < 0 || ne > emax) { if (sl == 0) p.meta[5] = a.edge_count ? 3 : 1; ne = 0; }
   for (int i = sl; i < 7 * (n + 2); i += W) cnt[i] = 0;      // cnt .. curI
   wave_lds_sync();
   // ---- counts (dss2_csr_build: topo_count_kernel)
@@ -475,6 +480,9 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
     const int lo = (int)(la < lb ? la : lb), hi = (int)(la < lb ? lb : la);
     atomicAdd(cover + lo + 1, 1); atomicAdd(cover + hi + 1, -1);
   }
+  // (padding slots: endpoints only -- dss2_get_pflow / dss2_eval_batch walk every stored slot; no count, no key, no CSR entry)
+  if (a.edge_count && live)
+    for (int j = ne + sl; j < a.e_uniform; j += W) { a.efrom_w[e0 + j] = (int32_t)p.ei[e0 + j]; a.eto_w[e0 + j] = (int32_t)p.ei[p.E + e0 + j]; }
   wave_lds_sync();
   // ---- exclusive sums over the graph's nodes (chunks of W with running carries), global offsets added where they are stored
   {
@@ -491,7 +499,7 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
   }
   wave_lds_sync();
   if (live) {
-    const int32_t b2 = (int32_t)(dbl * e0), bI = (int32_t)(2 * e0);
+    const int32_t b2 = (int32_t)(dbl * c0), bI = (int32_t)(2 * c0);
     for (int i = sl; i <= n; i += W) { a.rowptr[nb + i] = b2 + rp[i]; a.rowptrT[nb + i] = b2 + rpT[i]; a.inc_rowptr[nb + i] = bI + rpI[i]; }
   }
   // ---- legal cuts: running maximum inside the graph (its first row is always one)
@@ -529,7 +537,7 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
   const FinalPtrs& f = a.f;
   if (live) {
     for (int r = sl; r < n; r += W) {
-      const int32_t b2 = (int32_t)(dbl * e0);
+      const int32_t b2 = (int32_t)(dbl * c0);
 #pragma unroll 1
       for (int which = 0; which < 2; ++which) {
         const int32_t* rpp = which == 0 ? rp : rpT;
@@ -553,7 +561,7 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
       }
       const int i0 = rpI[r], ni = rpI[r + 1] - i0;
       sort_row(keysI + i0, ni);
-      for (int k = 0; k < ni; ++k) f.inc_ent[2 * e0 + i0 + k] = keysI[i0 + k];
+      for (int k = 0; k < ni; ++k) f.inc_ent[2 * c0 + i0 + k] = keysI[i0 + k];
       const int dg = rp[r + 1] - rp[r];
       f.deg[nb + r] = (float)dg;
       mdeg = max(mdeg, dg);
@@ -607,6 +615,33 @@ __global__ void __launch_bounds__(256) topo_build_graphs_kernel(const GraphBuild
       double* t = v0; v0 = v1; v1 = t;
     }
   }
+}
+
+// ---- padded batches: csr_ptr[G + 1] = exclusive sums of the per-graph edge counts, edge_total[0] = their sum, meta reset.  ONE workgroup:
+// thread t sums the counts of its contiguous share, the 256 shares are scanned in LDS, then every thread writes its share's offsets.  A count
+// outside [0, emax] counts as 0 (the build kernel gives that graph no edges) and raises meta[5] = 3.
+__global__ void __launch_bounds__(256) padded_scan_kernel(const int32_t* __restrict__ count, long long G, int emax, long long* __restrict__ csr_ptr,
+                                                          int32_t* __restrict__ edge_total, int32_t* __restrict__ meta) {
+  __shared__ long long share[256];
+  __shared__ int bad;
+  if (threadIdx.x < 16) meta[threadIdx.x] = threadIdx.x == 4 ? 0x7fffffff : 0;      // (meta_init_kernel)
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const long long per = (G + 255) / 256, g0 = (long long)threadIdx.x * per, g1 = g0 + per < G ? g0 + per : G;
+  long long s = 0;
+  for (long long g = g0; g < g1; ++g) { const int c = count[g]; if (c < 0 || c > emax) bad = 1; else s += c; }
+  share[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long run = 0;
+    for (int t = 0; t < 256; ++t) { const long long v = share[t]; share[t] = run; run += v; }
+    csr_ptr[G] = run;
+    edge_total[0] = (int32_t)run;
+    if (bad) meta[5] = 3;
+  }
+  __syncthreads();
+  long long run = share[threadIdx.x];
+  for (long long g = g0; g < g1; ++g) { const int c = count[g]; csr_ptr[g] = run; if (c >= 0 && c <= emax) run += c; }
 }
 
 static inline unsigned grid_for(int64_t n, int per_block = 256, int cap = 2048) {
@@ -740,6 +775,54 @@ extern "C" int dss2_csr_build_graphs(const dss2_csr_build_args* ap, int32_t node
   return check_launch("csr_build_graphs");
 }
 
+static int ell_tiles_launch(const dss2_ell_build_args& b, void* stream);
+static int csr_build_padded_launch(const dss2_padded_build_args& q, void* stream) {
+  const dss2_csr_build_args& a = q.csr;
+  hipStream_t s = as_stream(stream);
+  GraphBuildArgs g = {};
+  g.p.ei = a.edge_index; g.p.E = a.n_edges; g.p.N = a.n_nodes; g.p.E2 = a.doubled ? 2 * a.n_edges : a.n_edges; g.p.doubled = a.doubled ? 1 : 0;
+  g.p.no_flip = a.no_flip ? 1 : 0; g.p.meta = a.meta;
+  g.f.col = a.col; g.f.ent = a.ent; g.f.perm = a.perm; g.f.w = a.w; g.f.colT = a.colT; g.f.entT = a.entT; g.f.permT = a.permT; g.f.wT = a.wT;
+  g.f.inc_ent = a.inc_ent; g.f.deg = a.deg;
+  g.efrom_w = a.efrom; g.eto_w = a.eto; g.rowptr = a.rowptr; g.rowptrT = a.rowptrT; g.inc_rowptr = a.inc_rowptr; g.lastcut = a.lastcut;
+  g.edge_ptr = nullptr; g.n = q.nodes_per_graph; g.e_uniform = q.edge_stride; g.emax = q.edge_stride;
+  g.G = a.n_nodes / q.nodes_per_graph; g.deg_pows = q.deg_pows;
+  g.edge_count = q.edge_count; g.csr_ptr = reinterpret_cast<const long long*>(q.csr_ptr);
+  hipLaunchKernelGGL(padded_scan_kernel, dim3(1), dim3(256), 0, s, q.edge_count, (long long)g.G, q.edge_stride,
+                     reinterpret_cast<long long*>(q.csr_ptr), q.edge_total, a.meta);
+  const int W = graphs_group_width(q.nodes_per_graph), per_wg = 4 * (64 / W);
+  const unsigned grid = (unsigned)((g.G + per_wg - 1) / per_wg);
+  const size_t lds = graphs_lds_bytes(q.nodes_per_graph, q.edge_stride);
+#define DSS2_GRAPHS(WW) { static std::atomic<uint32_t> lds_done{0}; \
+    if (ensure_max_lds(reinterpret_cast<const void*>(topo_build_graphs_kernel<WW>), lds_done, "csr_build_padded")) return 1; \
+    hipLaunchKernelGGL(topo_build_graphs_kernel<WW>, dim3(grid), dim3(256), lds, s, g); }
+  if (W == 16) DSS2_GRAPHS(16) else if (W == 32) DSS2_GRAPHS(32) else DSS2_GRAPHS(64)
+#undef DSS2_GRAPHS
+  if (int rc = check_launch("csr_build_padded")) return rc;
+  for (int i = 0; i < q.n_ell; ++i)
+    if (int rc = ell_tiles_launch(q.ell[i], stream)) return rc;
+  return 0;
+}
+
+extern "C" int dss2_csr_build_padded(const dss2_padded_build_args* qp, void* stream) {
+  if (!qp) { set_error("csr_build_padded: null argument"); return 2; }
+  const dss2_padded_build_args& q = *qp;
+  const dss2_csr_build_args& a = q.csr;
+  if (a.n_edges <= 0 || a.n_nodes <= 0 || q.nodes_per_graph <= 0 || a.n_nodes % q.nodes_per_graph) { set_error("csr_build_padded: a batch of whole graphs of nodes_per_graph rows expected"); return 2; }
+  if (a.n_nodes >= (1ll << 31) - 4 || 2 * a.n_edges >= (1ll << 31) - 4) { set_error("csr_build_padded: graph too large for the int32 CSR"); return 2; }
+  if (!dss2_csr_build_graphs_supported(q.nodes_per_graph, q.edge_stride)) { set_error("csr_build_padded: graphs of %d nodes / %d edge slots are beyond this build", q.nodes_per_graph, q.edge_stride); return 2; }
+  if ((int64_t)q.edge_stride * (a.n_nodes / q.nodes_per_graph) != a.n_edges) { set_error("csr_build_padded: n_edges must be edge_stride slots per graph"); return 2; }
+  if (!a.edge_index || !a.rowptr || !a.col || !a.ent || !a.perm || !a.w || !a.rowptrT || !a.colT || !a.entT || !a.permT || !a.wT ||
+      !a.inc_rowptr || !a.inc_ent || !a.efrom || !a.eto || !a.deg || !a.lastcut || !a.meta || !q.edge_count || !q.csr_ptr || !q.edge_total) {
+    set_error("csr_build_padded: null argument"); return 2;
+  }
+  if (q.n_ell < 0 || q.n_ell > DSS2_PADDED_MAX_TILINGS) { set_error("csr_build_padded: 0..%d tilings", DSS2_PADDED_MAX_TILINGS); return 2; }
+  for (int i = 0; i < q.n_ell; ++i)
+    if (q.ell[i].uniform_rows <= 0) { set_error("csr_build_padded: tiling %d is not closed-form (uniform_rows > 0 expected)", i); return 2; }
+  DSS2_RECORD([q](void* s_) { return csr_build_padded_launch(q, s_); });
+  return csr_build_padded_launch(q, stream);
+}
+
 extern "C" int dss2_tiles_uniform(int32_t* tile_start, int32_t ntiles, int32_t rows_per_tile, int64_t n_nodes, void* stream) {
   DSS2_NOT_IN_PLAN("dss2_tiles_uniform");
   if (ntiles <= 0 || rows_per_tile <= 0) { set_error("tiles_uniform: bad arguments"); return 2; }
@@ -761,7 +844,9 @@ extern "C" int dss2_tiles_walk(const int32_t* lastcut, int64_t n_nodes, const in
 
 extern "C" int dss2_ell_tiles_build(const dss2_ell_build_args* ap, void* stream) {
   DSS2_NOT_IN_PLAN("dss2_ell_tiles_build");
-  const dss2_ell_build_args& b = *ap;
+  return ell_tiles_launch(*ap, stream);
+}
+static int ell_tiles_launch(const dss2_ell_build_args& b, void* stream) {
   if (b.ntiles <= 0 || b.tm <= 0) { set_error("ell_tiles_build: bad arguments"); return 2; }
   EllArgs a = {};
   a.rowptr[0] = b.rowptr; a.col[0] = b.col; a.ent[0] = b.ent; a.w[0] = b.w;

@@ -63,6 +63,7 @@ def _fill_args(topo: Topology, input, edge_input, output, node_param, edge_param
     a.apq, a.loss = bufs["apq"].data_ptr(), bufs["loss"].data_ptr()
     a.grad_output = bufs["grad"].data_ptr() if bufs.get("grad") is not None else None
     a.pflow = bufs["pflow"].data_ptr() if bufs.get("pflow") is not None else None
+    a.edge_count = bufs["edge_count"].data_ptr() if bufs.get("edge_count") is not None else None
     return a
 
 
@@ -139,7 +140,7 @@ class _WlsFn(torch.autograd.Function):
     launch and a one-thread launch re-evaluates the loss from the global sums."""
 
     @staticmethod
-    def forward(ctx, output, topo, tensors, reg_coefs, group, pflow_out=None, node_param_orig=None):
+    def forward(ctx, output, topo, tensors, reg_coefs, group, pflow_out=None, node_param_orig=None, edge_count=None):
         input, edge_input, node_param, edge_param, x_mean, x_std, edge_mean, edge_std = tensors
         ctx.set_materialize_grads(False)
         dev = output.device
@@ -156,6 +157,7 @@ class _WlsFn(torch.autograd.Function):
             "loss": torch.empty(1, dtype=_F32, device=dev),
             "grad": None,
             "pflow": pflow_out,
+            "edge_count": edge_count,
         }
         a = _fill_args(topo, input, edge_input, (output, output.stride(0)), node_param, edge_param,
                        x_mean, x_std, edge_mean, edge_std, reg_coefs, bufs)
@@ -198,15 +200,18 @@ class _WlsFn(torch.autograd.Function):
             g = g + gout_unused
             npar = node_param[0]
             g[:, 1] = g[:, 1] - gout_unused[:, 1] * npar[:, 1]
-        return g, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None
 
 
 def gsp_wls_edge(input, edge_input, output, x_mean, x_std, edge_mean, edge_std, edge_index, reg_coefs,
-                 num_samples=None, node_param=None, edge_param=None, group=None, pflow_out=None):
+                 num_samples=None, node_param=None, edge_param=None, group=None, pflow_out=None, edge_count=None):
     """/root/reference/data.py:393-459.  Returns a 0-dim loss attached to autograd; zeroes
     ``output[:, 1]`` at slack buses in place like the reference.  Beyond the reference's arguments: ``group`` (data-
     parallel loss, see the module docstring) and ``pflow_out``, an optional contiguous [E, 8] fp32 buffer that receives
-    the eight get_pflow quantities exactly as the loss kernel computed them (diagnostics / tests)."""
+    the eight get_pflow quantities exactly as the loss kernel computed them (diagnostics / tests); and ``edge_count``, a device
+    int32 scalar holding the batch's REAL number of edges, which the edge means then divide by (and the data-parallel count carries)
+    instead of ``edge_index.size(1)`` -- for padded batches, whose edge list also holds padding edges (dataset.PaddedMixedDataset;
+    default: the ``edge_total`` of a padded Topology, else None = the reference's divisor)."""
     _require_gpu(input, edge_input, output, node_param, edge_param, edge_index)
     dev = output.device
     topo = get_topology(edge_index, input.size(0))
@@ -218,7 +223,11 @@ def gsp_wls_edge(input, edge_input, output, x_mean, x_std, edge_mean, edge_std, 
     if pflow_out is not None and (pflow_out.dtype != _F32 or tuple(pflow_out.shape) != (topo.E, 8) or not pflow_out.is_contiguous()
                                   or pflow_out.device != dev):
         raise ValueError("pflow_out must be a contiguous [E, 8] fp32 tensor on the output's device")
-    loss, _ = _WlsFn.apply(output, topo, tensors, dict(reg_coefs), group, pflow_out, node_param)
+    if edge_count is None:
+        edge_count = getattr(topo, "edge_total", None)
+    elif edge_count.dtype != torch.int32 or edge_count.numel() != 1 or edge_count.device != dev:
+        raise ValueError("edge_count must be an int32 device tensor of one element")
+    loss, _ = _WlsFn.apply(output, topo, tensors, dict(reg_coefs), group, pflow_out, node_param, edge_count)
     return loss
 
 

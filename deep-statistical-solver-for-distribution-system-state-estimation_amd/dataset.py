@@ -111,7 +111,7 @@ class DeviceDataset:
 
     def __getitem__(self, i):
         if isinstance(i, slice):     # data_list[a:b] (train / validation / test splits, dss2_run.py:60-66)
-            sub = DeviceDataset.__new__(DeviceDataset)
+            sub = type(self).__new__(type(self))
             sub.__dict__.update(self.__dict__)
             sub.ids = self.ids[i]
             return sub
@@ -120,7 +120,7 @@ class DeviceDataset:
 
     def shuffled(self, generator: Optional[torch.Generator] = None) -> "DeviceDataset":
         """``random.shuffle(dataset)`` of dss2_run.py:59 as a view (permutation drawn on the device)."""
-        sub = DeviceDataset.__new__(DeviceDataset)
+        sub = type(self).__new__(type(self))
         sub.__dict__.update(self.__dict__)
         sub.ids = self.ids[torch.randperm(self.ids.numel(), device=self.ids.device, generator=generator)]
         return sub
@@ -211,6 +211,142 @@ class DeviceDataset:
                    y.view(S, n, -1).to(dev).contiguous(), ei.contiguous().to(dev))
 
 
+PAD_EDGE_ATTR = np.array([0.0] * 12 + [1.0], dtype=np.float32)      # a branch that carries nothing: G = B = Gs = Bs = 0, imax_or_sn = 1
+
+
+def pad_batch(edge_index: torch.Tensor, edge_attr: torch.Tensor, nodes_per_graph: int, num_graphs: int, e_max: Optional[int] = None):
+    """A collated batch of equal-size graphs (PyG layout: the edges of graph g in one run, node ids offset by g * nodes_per_graph) in the
+    PADDED layout: every graph gets e_max edge slots (default: the largest edge count of the batch), its edges first, then PADDING
+    EDGES -- from = to = the graph's first bus, every attribute 0 except imax_or_sn (raw column 12) = 1.  Such a branch has no flow at
+    any voltage (all admittances are 0), a finite loading (0 / 1) and no measurement (z = 1/var = 0): it adds exact zeros to the five
+    sums of gsp_wls_edge and to the bus injections, and nothing to the gradient -- the loss of the padded batch is the loss of the batch
+    provided the edge means divide by the REAL edge count (tests/test_mixed_store_cpu.py).  Returns (edge_index [2, G * e_max],
+    edge_attr [G * e_max, 13], e_count [G] int32), on the inputs' device: the layout PaddedMixedDataset keeps per sample."""
+    n, G, E = int(nodes_per_graph), int(num_graphs), int(edge_index.size(1))
+    g = torch.div(edge_index[0], n, rounding_mode="floor")
+    if E and (bool((g[1:] < g[:-1]).any()) or int(g.min()) < 0 or int(g.max()) >= G or not torch.equal(g, torch.div(edge_index[1], n, rounding_mode="floor"))):
+        raise ValueError("pad_batch: the edges of every graph must form one run, in graph order, inside the graph's rows")
+    cnt = torch.bincount(g, minlength=G)
+    e_max = int(cnt.max()) if e_max is None else int(e_max)
+    if E and int(cnt.max()) > e_max:
+        raise ValueError(f"pad_batch: a graph with {int(cnt.max())} edges does not fit {e_max} slots")
+    slot = g * e_max + (torch.arange(E, device=g.device) - (torch.cumsum(cnt, 0) - cnt)[g])
+    ea = torch.as_tensor(PAD_EDGE_ATTR, device=edge_attr.device).to(edge_attr.dtype).repeat(G * e_max, 1)
+    ea[slot] = edge_attr
+    ei = (torch.arange(G, device=g.device) * n).repeat_interleave(e_max).expand(2, -1).clone()
+    ei[:, slot] = edge_index
+    return ei, ea, cnt.to(torch.int32)
+
+
+class PaddedMixedDataset(DeviceDataset):
+    """The samples of a MixedDataset whose parts share a bus count, in ONE store of static shape (``MixedDataset.padded()``): x [S, n, 11],
+    y [S, n, 2], edge_attr [S, e_max, 13], edge_index [S, 2, e_max] with e_max = the largest branch count of a part, and e_count [S]
+    int32 = the sample's real branch count; a sample with fewer branches carries trailing padding edges (``pad_batch``).  A batch of B
+    samples then has the same shapes whatever its composition, so ``dss2_collate_cursor`` gathers it -- features, edge lists and counts --
+    into static buffers, and only the graph STRUCTURE depends on device data: a padded ``topology.Topology`` rebuilds it inside the step
+    (``rebuild()``), skipping the padding edges by the gathered counts.  What ``runner.EpochTrainer`` records for mixed-topology data."""
+
+    def __init__(self, parts: Sequence[DeviceDataset], ids: Optional[torch.Tensor] = None):
+        parts = list(parts)
+        if len({p.n for p in parts}) != 1:
+            raise ValueError("a padded store needs parts with the same bus count")
+        dev = parts[0].device
+        self.n = parts[0].n
+        self.e = e_max = max(p.e for p in parts)
+        self.S = sum(p.S for p in parts)
+        self.x = torch.cat([p.x for p in parts]).contiguous()
+        self.y = torch.cat([p.y for p in parts]).contiguous()
+        eas, eis, cnt = [], [], []
+        for p in parts:
+            ea = torch.zeros(p.S, e_max, 13, dtype=_F32, device=dev)
+            ea[:, :, 12] = 1.0
+            ea[:, :p.e] = p.edge_attr
+            ei = torch.zeros(p.S, 2, e_max, dtype=torch.int64, device=dev)      # (padding: from = to = the graph's first bus)
+            ei[:, :, :p.e] = p.edge_index if p.edge_index.size(0) == p.S else p.edge_index[0:1]
+            eas.append(ea)
+            eis.append(ei)
+            cnt.append(torch.full((p.S,), p.e, dtype=torch.int32, device=dev))
+        self.edge_attr, self.edge_index, self.e_count = torch.cat(eas).contiguous(), torch.cat(eis).contiguous(), torch.cat(cnt).contiguous()
+        self.shared_topology = False
+        self.ids = ids if ids is not None else torch.arange(self.S, device=dev)
+        self._ei_cache = {}
+        # MPN.is_directed looks at the batch's first edge only (networks.py:236-238): with ONE recorded step for every composition the
+        # rule has to come out the same whichever sample leads the batch
+        facts = set()
+        for p in parts:
+            facts |= {bool(p.directed)} if p._sample_directed is None else {bool(v) for v in p._sample_directed}
+        if len(facts) != 1:
+            raise ValueError("the parts disagree on MPN.is_directed's first-edge rule (some samples store both directions of their first edge): "
+                             "one recorded step cannot serve both")
+        self.directed, self._sample_directed = facts.pop(), None
+        self.max_degree_doubled = max(p.max_degree_doubled for p in parts)
+        self.max_degree_asis = max(p.max_degree_asis for p in parts)
+
+    def hint(self, first_sample: Optional[int] = None) -> "_topology.TopologyHint":
+        return _topology.TopologyHint(directed=self.directed, nodes_per_graph=self.n,
+                                      max_degree=self.max_degree_doubled if self.directed else self.max_degree_asis,
+                                      max_edges_per_graph=self.e, edges_per_graph=self.e)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return super().__getitem__(i)
+        s = int(self.ids[i])
+        c = int(self.e_count[s])
+        return Batch(self.x[s], self.edge_index[s, :, :c], self.edge_attr[s, :c], self.y[s], 1)
+
+    def batch_edge_index(self, B: int, ids: torch.Tensor) -> torch.Tensor:
+        out = torch.empty(2, B * self.e, dtype=torch.int64, device=self.device)
+        self._launch([(self.edge_index, out, self.e, 1)], ids, B)
+        return out
+
+    def batch_structure(self, B: int):
+        raise ValueError("batch_structure: a padded store has a structure per batch (padded_topology(edge_index, e_count))")
+
+    def padded_topology(self, edge_index: torch.Tensor, e_count: torch.Tensor) -> "_topology.Topology":
+        """The padded structure of the batch these (static) buffers hold, attached to ``edge_index``: the model's forward and the loss
+        find it there; ``rebuild()`` follows the buffers' content."""
+        N = e_count.numel() * self.n
+        topo = _topology.Topology(edge_index, N, hint=self.hint(), edge_count=e_count)
+        return _topology.register_topology(edge_index, N, topo)
+
+    def collate(self, ids: torch.Tensor) -> Batch:
+        """The PADDED batch of these samples (``batch.e_count``: the slots' real edge counts), its structure built and attached."""
+        B, dev = int(ids.numel()), self.device
+        x = torch.empty(B * self.n, self.x.size(2), dtype=_F32, device=dev)
+        ea = torch.empty(B * self.e, self.edge_attr.size(2), dtype=_F32, device=dev)
+        y = torch.empty(B * self.n, self.y.size(2), dtype=_F32, device=dev)
+        ei = torch.empty(2, B * self.e, dtype=torch.int64, device=dev)
+        cnt = torch.empty(B, dtype=torch.int32, device=dev)
+        self.collate_into(self.collate_descs(x, ea, edge_index=ei, e_count=cnt), ids, B)
+        self.collate_into(self.collate_descs(y=y), ids, B)
+        self.padded_topology(ei, cnt)
+        b = Batch(x, ei, ea, y, B)
+        b.e_count = cnt
+        return b
+
+    def collate_descs(self, x: Optional[torch.Tensor] = None, edge_attr: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                      edge_index: Optional[torch.Tensor] = None, e_count: Optional[torch.Tensor] = None):
+        """DeviceDataset.collate_descs plus the edge lists ([2, B * e_max] int64: node ids offset by the slot's first row) and the
+        counts ([B] int32): up to four destinations per table (one launch each)."""
+        items = []
+        for src, dst, chunk, kind, dt in ((self.x, x, self.n * self.x.size(2), 0, _F32), (self.edge_attr, edge_attr, self.e * self.edge_attr.size(2), 0, _F32),
+                                          (self.y, y, self.n * self.y.size(2), 0, _F32), (self.edge_index, edge_index, self.e, 1, torch.int64),
+                                          (self.e_count, e_count, 1, 2, torch.int32)):
+            if dst is None:
+                continue
+            if dst.dtype != dt or not dst.is_contiguous() or dst.numel() % ((2 * chunk) if kind == 1 else chunk):
+                raise ValueError("collate_into: destination buffers must be contiguous, of the store's dtype, of B whole samples")
+            items.append((src, dst, chunk, kind))
+        if not 1 <= len(items) <= 4:
+            raise ValueError("collate_descs: one to four destinations per table")
+        if len({d.numel() // ((2 * c) if k == 1 else c) for _, d, c, k in items}) != 1:
+            raise ValueError("collate_descs: the destinations hold different numbers of samples")
+        descs = (_lib.CollateDesc * len(items))()
+        for d, (src, dst, chunk, kind) in zip(descs, items):
+            d.src, d.dst, d.chunk, d.kind, d.shared, d.nodes_per_sample = src.data_ptr(), dst.data_ptr(), chunk, kind, 0, self.n
+        return descs
+
+
 class MixedDataset:
     """Samples of several cases with the SAME bus count but different closed-branch sets in one data list (BASELINE
     config C5: cigre14 + cigre14_reswitched, "variable edge_index per sample").  Global sample g = sample
@@ -243,6 +379,12 @@ class MixedDataset:
     def shuffled(self, rng: Optional[np.random.Generator] = None) -> "MixedDataset":
         rng = rng or np.random.default_rng()
         return MixedDataset(self.parts, rng.permutation(self.ids))
+
+    def padded(self) -> PaddedMixedDataset:
+        """These samples (in this order) as one padded store of static batch shapes: what ``runner.EpochTrainer`` trains on."""
+        if self.n is None:
+            raise ValueError("MixedDataset.padded(): the parts have different bus counts (per-batch structures: DataLoader / PrefetchLoader + train_epoch)")
+        return PaddedMixedDataset(self.parts, ids=torch.from_numpy(np.ascontiguousarray(self.ids)).to(self.device))
 
     _RING_MAX = 64
 

@@ -163,8 +163,13 @@ class EpochTrainer:
     permutation (on the device) and resetting two words.  Nothing is read back until the caller asks for the epoch's mean loss.
 
     ``mode``: "plan" (graphs.PlannedStep: the library's own launch list, one ``dss2_plan_run`` per step; also at world > 1, where the
-    step's collectives cut it into segments) or "graph" (graphs.GraphedStep: a hipGraph).  Needs a single-topology ``DeviceDataset``
-    (the graph structure is part of the recorded launches) and ``FusedAdamax(capturable=True)``.  Recording a step runs it (plans:
+    step's collectives cut it into segments) or "graph" (graphs.GraphedStep: a hipGraph).  Needs ``FusedAdamax(capturable=True)`` and
+    either a single-topology ``DeviceDataset`` (the graph structure is then built once, outside the step) or a
+    ``dataset.PaddedMixedDataset`` (``MixedDataset.padded()``: samples of several topologies on one bus count, BASELINE config C5 --
+    the collation also gathers every slot's edge list and edge count, and the step's second entry is ``Topology.rebuild()``: the
+    structure of THIS batch, built on the device inside the step; the loss divides by the batch's real edge count, read on the
+    device.  The permutation runs over the union of the parts, the reference loader's uniform shuffle.  Models: MPN, SkipMPN, PFN,
+    SkipPFN).  Recording a step runs it (plans:
     three times, graphs: once), so the model, the optimizer state and the epoch position are saved before and restored after: the first
     ``train_epoch()`` starts from exactly the state the trainer was given."""
 
@@ -172,8 +177,14 @@ class EpochTrainer:
                  generator=None):
         from . import _lib
         from . import dataset as dss2_dataset
-        if not isinstance(dataset, dss2_dataset.DeviceDataset) or not dataset.shared_topology:
+        self.padded = isinstance(dataset, dss2_dataset.PaddedMixedDataset)
+        if not isinstance(dataset, dss2_dataset.DeviceDataset) or not (dataset.shared_topology or self.padded):
             raise ValueError("EpochTrainer needs a single-topology DeviceDataset (per-batch structures: DataLoader / PrefetchLoader + train_epoch)")
+        if self.padded and type(model) not in (networks.MPN, networks.SkipMPN, networks.PFN, networks.SkipPFN):
+            # (the lane-group models -- GAT_DSSE, GINE_DSSE, gnn_dsse -- and the Multi* variants build structures of their own kind from
+            #  edge_index (as given / without flip flags / with self loops), which would list the padding edges as branches)
+            raise ValueError(f"EpochTrainer on a padded mixed store supports MPN, SkipMPN, PFN and SkipPFN, not {type(model).__name__}: "
+                             "its graph structure is not rebuilt from the per-slot edge counts")
         if not getattr(opt, "capturable", False):
             raise ValueError("EpochTrainer needs FusedAdamax(capturable=True): the step count must live on the device")
         if mode not in ("plan", "graph"):
@@ -226,12 +237,23 @@ class EpochTrainer:
         dev = ds.device
         sx = torch.empty(nb * ds.n, ds.x.size(2), dtype=torch.float32, device=dev)
         sea = torch.empty(nb * ds.e, ds.edge_attr.size(2), dtype=torch.float32, device=dev)
-        ei, _ = ds.batch_structure(nb)
-        descs = ds.collate_descs(sx, sea)
         ids, cursor, acc, L = self.ids, self.cursor, self.acc, self._lib
+        if self.padded:
+            # static edge lists and per-slot edge counts, gathered with the features; the structure follows them inside the step
+            ei = torch.empty(2, nb * ds.e, dtype=torch.int64, device=dev)
+            cnt = torch.empty(nb, dtype=torch.int32, device=dev)
+            descs = ds.collate_descs(sx, sea, edge_index=ei, e_count=cnt)
+            ds.collate_into(descs, ids, nb, cursor=cursor, advance=False)      # (real content for the first build)
+            topo = ds.padded_topology(ei, cnt)
+        else:
+            ei, _ = ds.batch_structure(nb)
+            descs = ds.collate_descs(sx, sea)
+            topo, cnt = None, None
 
         def step_fn():
             ds.collate_into(descs, ids, nb, cursor=cursor, advance=True)
+            if topo is not None:
+                topo.rebuild()
             for p in params:
                 p.grad = None
             out = run_model(model, sx[:, :8], ei, sea[:, :6])
@@ -248,7 +270,7 @@ class EpochTrainer:
         else:
             rec = graphs.GraphedStep(step_fn, warmup=1, capture_error_mode=("thread_local" if group is not None else "global"),
                                      stream=(cur if cur != torch.cuda.default_stream(dev) else None))
-        return rec, sx, sea, descs
+        return rec, sx, sea, descs, ei, cnt, topo
 
     def train_epoch(self) -> torch.Tensor:
         """One pass over the dataset.  Returns the DEVICE tensor {sum of the step losses, steps} of this epoch (``mean_loss()`` reads
@@ -290,7 +312,8 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--case", default="cigre14", choices=["cigre14", "cigre14_reswitched", "ober_sub", "ober179"])
+    ap.add_argument("--case", default="cigre14", help="cigre14, cigre14_reswitched, ober_sub or ober179; or a comma-separated list of cases on one "
+                    "bus count (cigre14,cigre14_reswitched: BASELINE config C5), trained as one shuffled data list on a padded store (EpochTrainer)")
     ap.add_argument("--model", default="SkipPFN", choices=["MPN", "SkipMPN", "PFN", "SkipPFN", "GAT_DSSE", "GINE_DSSE"] + ["gnn_dsse"])
     ap.add_argument("--gnn-model", default="gcn2", choices=["gcn2", "fagcn", "tagcn"], help="gnn_dsse's conv kind")
     ap.add_argument("--graphs", type=int, default=720)
@@ -310,8 +333,9 @@ def main(argv=None):
         hp["dim_out"] = hp["dim_nodes"]
     dev = torch.device("cuda")
     torch.manual_seed(a.seed)
+    import numpy as np
+    mixed_train = None
     if a.data_folder:                                                # dss2_run.py:47-69
-        import numpy as np
         from . import dataset as dss2_dataset
         cigre = "cigre" in a.data_folder
         meas_v = np.array([0, 1, 12, 7, 11, 14] if cigre else [35, 16, 52, 47, 6, 48, 59, 27, 37, 56])
@@ -322,16 +346,36 @@ def main(argv=None):
         train_loader = dss2_dataset.DataLoader(ds[0:n_train], batch_size=a.batch_size, shuffle=True)
         test_loader = dss2_dataset.DataLoader(ds[n_train:], batch_size=a.batch_size, shuffle=False)
         stats = tuple(stats)
+    elif "," in a.case:                                              # a mixed data list: one padded device store, whole epochs recorded
+        from . import dataset as dss2_dataset
+        cases = [c.strip() for c in a.case.split(",")]
+        full = synthetic.make_batch(cases, min(a.graphs, 256), seed=a.seed)
+        stats = tuple(s.to(dev) for s in full["stats"])
+        per = -(-a.graphs // len(cases))
+        parts = [dss2_dataset.DeviceDataset.from_batch(synthetic.make_batch([c], per, seed=a.seed + 1 + k, stats=full["stats"]), device=dev)
+                 for k, c in enumerate(cases)]
+        mixed = dss2_dataset.MixedDataset(parts).shuffled(np.random.default_rng(a.seed))
+        n_train = int(0.9 * len(mixed))
+        mixed_train = mixed[0:n_train]
+        train_loader = dss2_dataset.DataLoader(mixed_train, batch_size=a.batch_size, shuffle=True)
+        test_loader = dss2_dataset.DataLoader(mixed[n_train:], batch_size=a.batch_size, shuffle=False)
     else:
         train_loader, test_loader, stats = make_loaders(a.case, a.graphs, a.batch_size, dev, a.seed)
     model = build_model(a.model, hp, gnn_model=a.gnn_model).to(dev)
-    single_topology = (not a.data_folder) or bool(getattr(train_loader.dataset, "shared_topology", False))
+    single_topology = (not a.data_folder and mixed_train is None) or bool(getattr(train_loader.dataset, "shared_topology", False))
     use_graph = (a.graph == 1) or (a.graph == -1 and single_topology and hp["dim_out"] == 2)
     opt = FusedAdamax(model.parameters(), lr=a.lr, capturable=use_graph)
     # a device-resident data folder with ONE graph structure: whole epochs without the interpreter (EpochTrainer: the loader's collation is the
     # first launch of the recorded step); pre-collated synthetic batches: the step replayed on copied inputs (GraphedTrainer); else eager
     epoch_trainer = None
-    if use_graph and a.data_folder and single_topology:
+    if mixed_train is not None and a.graph != 0 and mixed_train.n is not None and type(model) in (networks.MPN, networks.PFN, networks.SkipPFN):
+        use_graph = True
+        opt = FusedAdamax(model.parameters(), lr=a.lr, capturable=True)
+        epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, mixed_train.padded(), a.batch_size, shuffle=True, mode="graph")
+    elif mixed_train is not None:
+        use_graph = False                                            # (other models / mixed bus counts: the eager loader, a structure per batch)
+        opt = FusedAdamax(model.parameters(), lr=a.lr)
+    elif use_graph and a.data_folder and single_topology:
         epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, train_loader.dataset, a.batch_size, shuffle=True, mode="graph")
     trainer = GraphedTrainer(model, opt, stats, REG_COEFS) if (use_graph and epoch_trainer is None) else None
     how = "whole epochs as replays of one recorded step (EpochTrainer)" if epoch_trainer is not None else ("hipGraph replay" if use_graph else "eager")

@@ -81,11 +81,17 @@ class Topology:
     """Frozen device-side structure of one batched graph.  See include/dss2_hip.h."""
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int, nrb: Optional[int] = None,
-                 double: Optional[bool] = None, hint: Optional[TopologyHint] = None, flip: bool = True):
+                 double: Optional[bool] = None, hint: Optional[TopologyHint] = None, flip: bool = True,
+                 edge_count: Optional[torch.Tensor] = None):
         """double=None: the reference's rule (MPN.is_directed on the first edge; from the hint when given); False: use
         the edge list exactly as given (standalone EdgeAggregation / TAGConv / propagate); True: always double.
         flip=False: reverse edges carry no sign-flip flag (the Multi* / MaskEmbd* variants duplicate edge_attr unchanged,
-        /root/reference/networks.py:440-444, where MPN negates columns 0 and 2, :250-254)."""
+        /root/reference/networks.py:440-444, where MPN negates columns 0 and 2, :250-254).
+        edge_count (device int32 [G], with a hint of uniform graphs): a PADDED batch -- graph g owns ``hint.edges_per_graph`` stored edge
+        slots of which the first edge_count[g] are branches and the rest padding edges the structure never lists.  Every buffer is then
+        sized by the slots and stays where it is; ``rebuild()`` rebuilds the content from edge_index / edge_count as they are on the
+        device at that moment, with launches that are part of a recorded training step (dss2_csr_build_padded).  ``E`` counts the
+        slots; ``edge_total`` (device int32 [1]) is the real edge count of the batch that was last built."""
         if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
             raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
         N, E = int(num_nodes), int(edge_index.size(1))
@@ -112,7 +118,8 @@ class Topology:
                  ("entT", E2), ("permT", E2), ("wT", E2), ("inc_rowptr", N + 1), ("inc_ent", 2 * E), ("efrom", E), ("eto", E),
                  ("deg", N), ("_lastcut", N + 1), ("_meta", 16)]
         padded = [(n + 3) // 4 * 4 for _, n in sizes]
-        arena = torch.empty(sum(padded), dtype=torch.int32, device=dev)
+        # (padded batches: the entries behind rowptr[N] are never written -- zeros once, so that nothing indeterminate sits there)
+        arena = (torch.zeros if edge_count is not None else torch.empty)(sum(padded), dtype=torch.int32, device=dev)
         d = self.__dict__
         for (name, n), chunk in zip(sizes, arena.split(padded)):       # one split call: 17 views (16-byte aligned)
             d[name] = chunk[:n] if n != chunk.numel() else chunk
@@ -131,7 +138,26 @@ class Topology:
             setattr(a, name.lstrip("_"), base + 4 * off)
             off += pn
         self._deg_pows = None
-        if graphs:
+        self._padded = None
+        if edge_count is not None:
+            n = hint.nodes_per_graph if hint is not None else 0
+            if double is not None or hint is None or n <= 0 or N % n or hint.edges_per_graph <= 0 or hint.edges_per_graph * (N // n) != E:
+                raise ValueError("a padded Topology needs a TopologyHint of uniform graphs: edges_per_graph slots for each of N / nodes_per_graph graphs")
+            if edge_count.dtype != torch.int32 or edge_count.device != dev or not edge_count.is_contiguous() or edge_count.numel() != N // n:
+                raise ValueError("edge_count: a contiguous int32 device tensor with one entry per graph")
+            if not L.dss2_csr_build_graphs_supported(n, hint.edges_per_graph):
+                raise NotImplementedError(f"padded batches of {n}-node graphs with {hint.edges_per_graph} edge slots are beyond the per-graph build")
+            q = _lib.PaddedBuildArgs()
+            q.csr = a
+            q.nodes_per_graph, q.edge_stride = n, int(hint.edges_per_graph)
+            self.edge_count, self.edge_total = edge_count, torch.zeros(1, dtype=torch.int32, device=dev)
+            self._csr_ptr = torch.empty(N // n + 1, dtype=torch.int64, device=dev)
+            self._deg_pows = torch.empty(N, 4, dtype=torch.float32, device=dev)
+            q.edge_count, q.csr_ptr, q.edge_total, q.deg_pows = edge_count.data_ptr(), self._csr_ptr.data_ptr(), self.edge_total.data_ptr(), self._deg_pows.data_ptr()
+            self._padded, self._ell_jobs = q, []
+            self._keep = (ei, edge_count)
+            self.rebuild()
+        elif graphs:
             # one wave per graph: every array above AND the [N, 4] folded-bias row scales (deg_pows) in one launch
             dp = torch.empty(N, 4, dtype=torch.float32, device=dev)
             ep = hint.edge_ptr
@@ -147,6 +173,20 @@ class Topology:
         self._stats = None
         self._tiles_built = False
 
+    def rebuild(self) -> None:
+        """Padded batches: the CSR part, the folded-bias row scales and every tiling built so far, again, from what edge_index and
+        edge_count hold on the device NOW -- into the same buffers, by launches a launch plan records and a hipGraph captures.  (A
+        tiling is built lazily on first use; one first asked for while a step is being recorded is refused like every structure
+        build outside a step: run the step once before recording it.)"""
+        q = self._padded
+        if q is None:
+            raise ValueError("rebuild(): not a padded Topology (pass edge_count)")
+        q.n_ell = len(self._ell_jobs)
+        for i, b in enumerate(self._ell_jobs):
+            q.ell[i] = b
+        self._stats = None
+        _lib.check(_lib.lib().dss2_csr_build_padded(C.byref(q), _stream(self.device)), "dss2_csr_build_padded")
+
     # ---- lazily built tile part -------------------------------------------------------------------------------
     def __getattr__(self, name):
         if name in _TILE_ATTRS and not self.__dict__.get("_tiles_built", True):
@@ -161,6 +201,8 @@ class Topology:
             raise ValueError("edge_index holds node ids outside [0, num_nodes)")
         if m[5] == 2:
             raise ValueError("TopologyHint.max_degree is smaller than a row of the batch")
+        if m[5] == 3:
+            raise ValueError("edge_count holds a value outside [0, edges_per_graph]")
         return dict(max_deg=m[0], max_degT=m[1], max_segment=m[2], n_segments=m[3], min_segment=m[4], error=m[5],
                     max_nnz=m[6], max_nnzT=m[7], ntiles_cand=m[8:16])
 
@@ -279,7 +321,15 @@ class Topology:
         if uniform_rows and not (ell or ellT):      # (hub graphs: no ELL launch to fold the tile starts into)
             _lib.check(L.dss2_tiles_uniform(tile_start.data_ptr(), nt, uniform_rows, N, st), "dss2_tiles_uniform")
             b.uniform_rows = 0
+        if self._padded is not None:
+            # rebuild() re-issues this launch with the step: it has to be the closed-form, ELL-staged kind, and there is room for a few
+            if not (b.uniform_rows and ell and ellT):
+                raise NotImplementedError("padded batches: graphs with a bus of more than 8 branches have no ELL slices to rebuild")
+            if len(self._ell_jobs) >= _lib.PADDED_MAX_TILINGS:
+                raise NotImplementedError(f"padded batches: more than {_lib.PADDED_MAX_TILINGS} tilings of one batch")
         _lib.check(L.dss2_ell_tiles_build(C.byref(b), st), "dss2_ell_tiles_build")
+        if self._padded is not None:
+            self._ell_jobs.append(b)
         if not store and hint is not None and os.environ.get("DSS2_CHECK", "0") == "1":
             read_stats()      # (the hint path reads nothing back: with DSS2_CHECK the alternate build's error flag is read too)
         if exact_nnz and (ell == 0 or ellT == 0):      # CSR staging in the tile kernels (hub graphs): exact sizes needed

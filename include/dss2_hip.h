@@ -61,7 +61,8 @@ int dss2_topology_probe(const int64_t* edge_index, int64_t n_edges, uint64_t* ou
  * live as long as the plan, e.g. inside a private memory pool), by-value scalars are frozen (use the device-side step counter of    *
  * dss2_adamax_step_flat / _dev and use_host_seed = 0 of dss2_rng_next, as under capture).  Only launches of this library are         *
  * recorded.  One plan records at a time (process-wide).  Every entry point that launches a STEP's work records itself (model, loss, *
- * dss2_get_pflow / dss2_eval_batch, dropout masks, optimizer, dss2_collate / dss2_collate_cursor, dss2_accum_scalar); the entry     *
+ * dss2_get_pflow / dss2_eval_batch, dropout masks, optimizer, dss2_collate / dss2_collate_cursor, dss2_accum_scalar, and            *
+ * dss2_csr_build_padded: the structure of a padded batch is a function of device data and part of the step); the entry              *
  * points that are not launches of a step -- structure build (dss2_topology_probe, dss2_csr_build, dss2_csr_build_graphs,             *
  * dss2_tiles_*, dss2_ell_tiles_build, dss2_deg_pows), measurement model, z-score, ragged collations -- return 3 while a plan records *
  * instead of being silently left out of it.                                                                                         */
@@ -130,6 +131,30 @@ typedef struct dss2_ell_build_args {
   int64_t n_nodes;
 } dss2_ell_build_args;
 int dss2_ell_tiles_build(const dss2_ell_build_args* args_host, void* stream);
+
+/* The structure of a PADDED batch of equal-size graphs, as launches of a training step (host-free epochs on data whose topology changes
+ * per sample, BASELINE config C5).  Graph g owns the stored edge slots [g * edge_stride, (g + 1) * edge_stride) of edge_index[2][E],
+ * E = G * edge_stride; only the first edge_count[g] of them are branches, the rest are padding edges that the structure never lists:
+ * every shape is a function of (G, edge_stride) alone, the structure a function of DEVICE data (edge_index, edge_count) -- so this entry
+ * point, unlike the builds above, records itself into launch plans and is captured into hipGraphs.  Launches: one workgroup forms
+ * csr_ptr[G + 1] (exclusive sums of the counts), edge_total[0] (their sum: the batch's real edge count, what the loss divides by) and
+ * resets meta; the quarter-wave-per-graph build of dss2_csr_build_graphs writes the arrays of csr (entries of graph g at (1 or 2) *
+ * csr_ptr[g]; directed ids stay d = stored slot, reverse d + E; efrom / eto are written for every slot, padding included; array tails
+ * beyond rowptr[N] are left alone) and deg_pows[N][4]; then one ELL launch per tiling in ell[0 .. n_ell) (closed-form tilings:
+ * uniform_rows > 0).  edge_count[g] outside [0, edge_stride] sets meta[5] = 3 and the graph gets no edges (nothing is read out of
+ * bounds).  csr.work is unused. */
+#define DSS2_PADDED_MAX_TILINGS 4
+typedef struct dss2_padded_build_args {
+  dss2_csr_build_args csr;
+  int32_t nodes_per_graph; int32_t edge_stride;
+  const int32_t* edge_count;     /* DEVICE [G] */
+  int64_t* csr_ptr;              /* DEVICE [G + 1], written */
+  int32_t* edge_total;           /* DEVICE [1], written */
+  float* deg_pows;               /* DEVICE [N][4], written */
+  int32_t n_ell; int32_t pad_;
+  dss2_ell_build_args ell[DSS2_PADDED_MAX_TILINGS];
+} dss2_padded_build_args;
+int dss2_csr_build_padded(const dss2_padded_build_args* args_host, void* stream);
 
 /* out[N,4] <- columns [deg, A deg, A^2 deg, A^3 deg] (A = the gcn_norm propagation matrix of the CSR), accumulated in
  * float64 in CSR order: the row scales of a bias folded through m propagations.  work: 2 N device doubles. */
@@ -521,6 +546,8 @@ typedef struct dss2_wls_args {
   uint32_t* counter;       /* DSS2_WLS_FUSED_FINISH: one device word, zero before the first use (the kernel re-zeroes it) */
   const float* gscale;     /* dss2_wls_loss_grad: optional DEVICE scalar, the upstream gradient of the loss (autograd's
                               grad_output): the kernel scales d loss / d output by it instead of a separate multiply */
+  const int32_t* edge_count; /* optional DEVICE scalar: the batch's REAL edge count, which the edge means divide by and sums[6] carries
+                              instead of n_edges (padded batches: n_edges counts the padding slots too); NULL: n_edges */
 } dss2_wls_args;
 #define DSS2_WLS_VMM_CACHED 1     /* vminmax[] already holds this node_param's partial (min, max) pairs: no vminmax launch */
 #define DSS2_WLS_FUSED_FINISH 2   /* the LAST workgroup of the partials kernel to finish sums the workgroup partials in a
@@ -602,6 +629,7 @@ int64_t dss2_masked_zscore_scratch_doubles(int64_t rows);
 
 /* batch collation (PyG Batch semantics): for slot b of the batch and sample s = sample_ids[b] (NULL: s = b),
  * kind 0: dst[b][0..chunk) = src[s][0..chunk)                    (float rows of x / edge_attr / y, chunk floats)
+ * kind 2: the same for int32 words                                (per-sample edge counts of a padded store, chunk = 1)
  * kind 1: dst[r][b*chunk + j] = src[s][r][j] + b * nodes_per_sample   (int64 edge_index, chunk = e; shared != 0:
  *         every sample uses the one [2][e] list at src).   descs_host: HOST array of 1..4 descriptors, passed
  *         to the kernel by value (no descriptor copy); sample_ids: DEVICE int64 [batch].                     */
