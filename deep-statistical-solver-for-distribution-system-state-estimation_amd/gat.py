@@ -183,9 +183,14 @@ def run_gat(convs, head, nonlin, x, edge_index, edge_attr):
     if edge_attr is not None:
         from .networks import _no_edge_attr_grad
         _no_edge_attr_grad(edge_attr)
-    lanegroup.check_x(x)
-    topo = get_topology(edge_index, x.size(0), double=False)
-    topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
+    lanegroup.check_x(x, edge_index, int64=True)
+    if x.size(0) == 0:
+        raise ValueError("GAT: empty batch")
+    if edge_index.size(1) == 0:
+        topo = lanegroup.NoEdges(x.size(0), x.device)       # every node attends to its self loop alone (without loops: the bias)
+    else:
+        topo = get_topology(edge_index, x.size(0), double=False)
+        topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
     spec = _Spec(convs, head, nonlin, x.size(0))
     lanegroup.check_columns(x, spec)
     if spec.ed:
