@@ -224,7 +224,7 @@ def gsp_wls_edge(input, edge_input, output, x_mean, x_std, edge_mean, edge_std, 
                                   or pflow_out.device != dev):
         raise ValueError("pflow_out must be a contiguous [E, 8] fp32 tensor on the output's device")
     if edge_count is None:
-        edge_count = getattr(topo, "edge_total", None)
+        edge_count = topo.edge_total      # (a padded batch: its real edge count, on the device)
     elif edge_count.dtype != torch.int32 or edge_count.numel() != 1 or edge_count.device != dev:
         raise ValueError("edge_count must be an int32 device tensor of one element")
     loss, _ = _WlsFn.apply(output, topo, tensors, dict(reg_coefs), group, pflow_out, node_param, edge_count)

@@ -212,7 +212,7 @@ def _structure(edge_index, n, mode):
     else:
         topo = get_topology(edge_index, n, double=False)
         topo.stats()       # (cached per structure) raises on node ids outside [0, N) before a kernel reads them
-    cache = topo.__dict__.setdefault("_gnn_structures", {})
+    cache = topo._gnn_structures
     st = cache.get(mode)
     if st is None:
         dis = torch.empty(n, dtype=_F32, device=dev)

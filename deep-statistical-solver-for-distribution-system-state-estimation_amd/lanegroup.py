@@ -127,6 +127,7 @@ class NoEdges:
         self.N, self.E = n, 0
         self.rowptr = self.rowptrT = torch.zeros(n + 1, dtype=torch.int32, device=dev)
         self.col = self.ent = self.colT = self.entT = self.rowptr
+        self._gnn_structures = {}      # (gnn._structure: as on a Topology)
 
 
 def check_x(x, edge_index=None, int64=False):

@@ -13,13 +13,12 @@ features and their mask (networks.py:452-455); MultiMPN applies EdgeAggregation 
 node features of width ``dim_hid``.  No CPU fallback.
 
 Building blocks (each one autograd node over the C ABI): ``_DenseFn`` (tile GEMM + bias / activation epilogue),
-``EdgeAggregationGeneral`` (AB = X [W1a; W1b]^T as one tile GEMM, ``dss2_edge_combine_*`` per edge, second Linear after
+``EdgeAggregationGeneral`` (AB = X [W1a; W1b]^T as one tile GEMM, ``ops.edge_combine_fwd`` / ``_bwd`` per edge, second Linear after
 the aggregation), ``TAGConv`` with a fused dropout + ReLU epilogue.  ``dropout, then ReLU`` after a layer is fused into
 that layer's last kernel; its gradient is one ``dss2_gate_grad`` launch.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -27,8 +26,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .networks import (_F32, _DESC_DTYPE, _MPNFn, _PackPlan, _ncg, _require_gpu, _round8, _rows, _stream, MPN, TAGConv,
+from .networks import (_F32, _DESC_DTYPE, _MPNFn, _PackPlan, _ncg, _require_gpu, _round8, _rows, MPN, TAGConv,
                        _gate, _post_spec, _reduce, _run_tagconv, gemm_prop, wgrad)
+from .ops import edge_combine_bwd, edge_combine_fwd
 from .topology import Topology, get_topology
 
 
@@ -73,15 +73,12 @@ class _EdgeAggrGeneralFn(torch.autograd.Function):
         sp.refresh(W1)
         ctx.ver = p2.refresh()
         topo.lds_check(1, max(_round8(d), _round8(h), _round8(2 * h)), max(_ncg(2 * h), _ncg(ho)))
-        L = _lib.lib()
         N = topo.N
         AB = torch.empty(N, 2 * h, dtype=_F32, device=dev)
         gemm_prop(topo, x, ldx, d, sp.fwd, 1, 2 * h, AB)
         S = torch.empty(N, h, dtype=_F32, device=dev)
         w1c = W1.data_ptr() + 4 * 2 * d
-        _lib.check(L.dss2_edge_combine_fwd(AB.data_ptr(), 2 * h, ea.data_ptr(), ldea, w1c, W1.stride(0), b1.data_ptr(),
-                                           topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), S.data_ptr(), N, h, fe,
-                                           _stream(S)), "dss2_edge_combine_fwd")
+        edge_combine_fwd(topo, AB, ea, ldea, w1c, W1.stride(0), b1, S, h, fe)
         relu, snap, p = _post_spec(mod, mod._post, dev)
         y = torch.empty(N, ho, dtype=_F32, device=dev)
         # second Linear after the (linear) aggregation: sum_e (W2 h_e + b2) = W2 S + deg b2, then dropout + ReLU if inside a stack
@@ -102,7 +99,7 @@ class _EdgeAggrGeneralFn(torch.autograd.Function):
             sp.refresh(W1)
             p2.refresh()
         d, fe, h, ho = mod.dim_featn, mod.dim_feate, mod.dim_hid, mod.dim_out
-        dev, N, L = g.device, topo.N, _lib.lib()
+        dev, N = g.device, topo.N
         g = _gate(g, y, snap, p) if relu else g.contiguous()
         g2 = torch.empty(ho * h + ho, dtype=_F32, device=dev)
         wgrad(topo, g, ho, S, h, 1, g2, rowscale=topo.deg)
@@ -113,13 +110,8 @@ class _EdgeAggrGeneralFn(torch.autograd.Function):
         stride = h * fe + h
         slab = torch.empty(n_slabs * stride, dtype=_F32, device=dev)
         w1c = W1.data_ptr() + 4 * 2 * d
-        st = _stream(g)
-        _lib.check(L.dss2_edge_combine_bwd(AB.data_ptr(), 2 * h, ea.data_ptr(), ldea, w1c, W1.stride(0), b1.data_ptr(), dS.data_ptr(),
-                                           topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), dAB.data_ptr(),
-                                           slab.data_ptr(), n_slabs, N, h, fe, 0, st), "dss2_edge_combine_bwd")
-        _lib.check(L.dss2_edge_combine_bwd(AB.data_ptr(), 2 * h, ea.data_ptr(), ldea, w1c, W1.stride(0), b1.data_ptr(), dS.data_ptr(),
-                                           topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr(), dAB.data_ptr(),
-                                           None, n_slabs, N, h, fe, 1, st), "dss2_edge_combine_bwd")
+        for transposed in (False, True):      # dA by target with the dW1c | db1 slabs, then dB by source
+            edge_combine_bwd(topo, AB, ea, ldea, w1c, W1.stride(0), b1, dS, dAB, (None if transposed else slab), n_slabs, h, fe, transposed)
         g1c = torch.empty(stride, dtype=_F32, device=dev)
         _reduce(slab, 0, n_slabs, stride, g1c, stride, None)
         gab = torch.empty(2 * h * d + 2 * h, dtype=_F32, device=dev)          # [2h, d] dW1ab, then column sums (unused)

@@ -33,7 +33,7 @@ from .topology import Topology, get_topology
 _F32 = torch.float32
 
 from . import flags as FL
-from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
+from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, edge_hidden_bwd, edge_hidden_fwd, edge_tile_bwd, edge_tile_fwd, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
 from .plans import (_DESC_DTYPE, _FoldPlan, _MatView, _PackPlan, _SG_DTYPE, _as_view, _pack_table, _sg, _sg_table, _small_gemm)
 from .route import BlockRoute, block_route, use_global_path
 
@@ -43,17 +43,12 @@ from .route import BlockRoute, block_route, use_global_path
 # ------------------------------------------------------------------------------------------
 def _edge_aggr_forward(topo, x, ldx, ea, ldea, W1, b1, b2, pack_w2_fwd, hid, hout, fn, fe, second_linear=True, need_dx=False):
     """need_dx: the backward will be asked for the gradient w.r.t. x (the library then picks the forward whose gates that backward recomputes exactly)."""
-    N = topo.N
+    N, ts = topo.N, topo.tiling
     S = torch.empty(N, hid, dtype=_F32, device=W1.device)
-    if topo.ell_ent_tiles is not None and FL.EDGE_TILE_KERNELS:
-        _lib.check(_lib.lib().dss2_edge_tile_fwd_paired(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(),
-                                                        topo.tile_start.data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell,
-                                                        topo.nrb, topo.ntiles, S.data_ptr(), hid, fn, fe, int(bool(need_dx)), _stream(S)),
-                   "dss2_edge_tile_fwd_paired")
+    if ts.ell_ent_tiles is not None and FL.EDGE_TILE_KERNELS:
+        edge_tile_fwd(ts, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx)
     else:   # general graphs (hub nodes beyond the ELL width): row-per-wave kernel on the CSR
-        _lib.check(_lib.lib().dss2_edge_hidden_fwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(),
-                                                   topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(),
-                                                   S.data_ptr(), N, hid, fn, fe, _stream(S)), "dss2_edge_hidden_fwd")
+        edge_hidden_fwd(topo, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe)
     if not second_linear:   # folded into the consumer (see _FoldPlan)
         return S, None
     x0 = torch.empty(N, hout, dtype=_F32, device=W1.device)
@@ -68,7 +63,7 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
     With ``dS`` given (second Linear folded into the consumer) gx0 / g_w2 are not used.
     pack_dx = (W1[:, :fn] packed, W1[:, fn:2fn] packed[, both stacked along k]); dx_add [N, fn] is added to the result
     (the skip connection's gradient).  Returns dx [N, fn] or None."""
-    N = topo.N
+    N, ts = topo.N, topo.tiling
     if dS is None:
         wgrad(topo, gx0, hout, S, hid, 1, g_w2, rowscale=topo.deg, pending=pending)
         dS = torch.empty(N, hid, dtype=_F32, device=gx0.device)
@@ -76,14 +71,13 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
     gx0 = dS
     dev = dS.device
     stride = hid * (2 * fn + fe) + hid
-    tiled = topo.ell_ent_tiles is not None and topo.ellT_ent_tiles is not None and FL.EDGE_TILE_KERNELS
-    n_slabs = min(topo.ntiles, 512) if tiled else int(min(512, max(1, (N + 15) // 16)))
+    tiled = ts.ell_ent_tiles is not None and ts.ellT_ent_tiles is not None and FL.EDGE_TILE_KERNELS
+    n_slabs = min(ts.ntiles, 512) if tiled else int(min(512, max(1, (N + 15) // 16)))
     slab = torch.empty(n_slabs * stride, dtype=_F32, device=dev)
-    L = _lib.lib()
     # U0 = sum of dz over incoming edges (x enters as x_i), U1 over outgoing edges (as x_j).  Side by side in one [N, 2 hid]
     # buffer when the K = 2 hid tile fits LDS: dx is then ONE GEMM [U0 | U1] [W1[:, :fn] ; W1[:, fn:2fn]]
     merged = bool(need_dx and pack_dx is not None and len(pack_dx) > 2 and pack_dx[2] is not None and FL.DX_MERGE and
-                  L.dss2_gemm_prop_lds_bytes(topo.nrb, 1, _round8(2 * hid), 1, 0, 0) <= 160 * 1024)
+                  _lib.lib().dss2_gemm_prop_lds_bytes(ts.nrb, 1, _round8(2 * hid), 1, 0, 0) <= 160 * 1024)
     if not need_dx:
         U = u0 = u1 = None
         ldu = hid
@@ -93,28 +87,17 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
     else:
         U = torch.empty(2, N, hid, dtype=_F32, device=dev)
         u0, u1, ldu = U[0], U[1], hid
-    st = _stream(gx0)
-    if tiled:
-        _lib.check(L.dss2_edge_tile_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                        topo.tile_start.data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell, topo.nrb,
-                                        topo.ntiles, slab.data_ptr(), n_slabs, _ptr(u0), ldu, hid, fn, fe, 0, st),
-                   "dss2_edge_tile_bwd")
-    else:
-        _lib.check(L.dss2_edge_hidden_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                          topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), slab.data_ptr(),
-                                          n_slabs, _ptr(u0), ldu, N, hid, fn, fe, 0, st), "dss2_edge_hidden_bwd")
+
+    def edge_bwd(slab_, u, transposed):      # over the incoming edges (dW1 | db1 slabs, U0), then -- transposed -- the outgoing ones (U1)
+        if tiled:
+            edge_tile_bwd(ts, x, ldx, ea, ldea, W1, b1, dS, slab_, n_slabs, u, ldu, hid, fn, fe, transposed)
+        else:
+            edge_hidden_bwd(topo, x, ldx, ea, ldea, W1, b1, dS, slab_, n_slabs, u, ldu, hid, fn, fe, transposed)
+    edge_bwd(slab, u0, False)
     _reduce(slab, 0, n_slabs, stride, g_w1, stride, pending)
     if not need_dx:
         return None
-    if tiled:
-        _lib.check(L.dss2_edge_tile_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                        topo.tile_start.data_ptr(), topo.ellT_ent_tiles.data_ptr(), topo.ellT, topo.nrb,
-                                        topo.ntiles, None, n_slabs, u1.data_ptr(), ldu, hid, fn, fe, 1, st),
-                   "dss2_edge_tile_bwd")
-    else:
-        _lib.check(L.dss2_edge_hidden_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                          topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr(), None,
-                                          n_slabs, u1.data_ptr(), ldu, N, hid, fn, fe, 1, st), "dss2_edge_hidden_bwd")
+    edge_bwd(None, u1, True)
     dx = torch.empty(N, fn, dtype=_F32, device=dev)
     if merged:
         gemm_prop(topo, U, 2 * hid, 2 * hid, pack_dx[2], 1, fn, dx, add_src=dx_add,
@@ -420,7 +403,7 @@ class EdgeAggregation(MessagePassing):
     def fused_dims(self) -> bool:
         """The fused edge-MLP kernels are built for the reference's data (8 node / 6 edge features, networks.py:170) and
         dim_hid <= 256; every other width runs the general path: AB = X [W1a; W1b]^T as one tile GEMM, then per edge
-        relu(A[i] + B[src] + W1c ea + b1) summed per target (dss2_edge_combine_*), then the second Linear."""
+        relu(A[i] + B[src] + W1c ea + b1) summed per target (ops.edge_combine_fwd / _bwd), then the second Linear."""
         return self.dim_featn == 8 and self.dim_feate == 6 and self.dim_hid <= 256
 
     def message(self, x_i, x_j, edge_attr):
@@ -643,6 +626,7 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
     W1, b1, W2, b2 = ps[0:4]
     conv_ps = mod._conv_params(ps)   # (bias, W_0..W_K)
     rt = block_route(mod, topo, need_dx, False) if stack is None else stack.route_of(mod)
+    ntiles = topo.tiling.ntiles
     plan, fold = _ensure_plans(mod, topo, dev, ps, rt)
     if stack is None:
         ver = plan.refresh(fold)      # (fold + packing: one launch)
@@ -684,7 +668,7 @@ def _mpn_forward(mod, topo, x, ea, ps, stack=None, need_dx=False):
             layers.append(dict(Bp=(plan.fwd16[1 + l] if rt.use16 else plan.fwd[1 + l]), Y=out_l, bias=conv_ps[l][0], relu=True,
                                drop_id=drop_id(l), prebias=(fold.bf if (fold is not None and l == 0) else None)))
             if rt.gw:      # (inside autograd.Function.forward grad mode is off: always written; 1/32 of a layer output)
-                act_bits[len(acts)] = layers[-1]["y_bits"] = torch.empty(topo.ntiles * rt.gw, dtype=torch.int64, device=dev)
+                act_bits[len(acts)] = layers[-1]["y_bits"] = torch.empty(ntiles * rt.gw, dtype=torch.int64, device=dev)
             acts.append(out_l)
         h, head = acts[-1], None
         if rt.head:      # the narrow last layer inside the same launch (the tile is still in the waves' registers)
@@ -786,7 +770,7 @@ def _bwd_chained(c: _BlockBackward, g, edge):
     conv 0's input -- dS when folded --, the layers (l, gradient, input) whose weight gradients are still due)."""
     mod, topo, rt, plan, acts, pending = c.mod, c.topo, c.rt, c.plan, c.acts, c.pending
     L, nmat, hid, nout = mod.n_gnn_layers, mod.K + 1, mod.dim_hid, mod.dim_out
-    dev = g.device
+    dev, ntiles = g.device, topo.tiling.ntiles
     snap, p_drop, base = c.meta.drop
     l = L - 1
     head = head_wg = edge_slab = None
@@ -797,7 +781,7 @@ def _bwd_chained(c: _BlockBackward, g, edge):
             # per tile, summed with the step's other slabs
             hw_len = nmat * nout * hid + nout
             hw_stride = (hw_len + 3) & ~3      # (16-byte lanes in the reduction)
-            head_wg = torch.empty(topo.ntiles * hw_stride, dtype=_F32, device=dev)
+            head_wg = torch.empty(ntiles * hw_stride, dtype=_F32, device=dev)
         else:      # the narrow weight-gradient launch re-reads the activation
             _tagconv_backward(topo, g, acts[l], plan.bwd[1 + l], nmat, hid, nout, c.seg(l), need_dh=False, pending=pending)
         dr = c.drop_of(l - 1)
@@ -807,7 +791,7 @@ def _bwd_chained(c: _BlockBackward, g, edge):
         if rt.bwd_edge:
             # conv 0's input gradient never leaves the chip: one dW1 | db1 slab per tile
             e_stride = c.offs[1] - c.offs[0]
-            edge_slab = torch.empty(topo.ntiles * e_stride, dtype=_F32, device=dev)
+            edge_slab = torch.empty(ntiles * e_stride, dtype=_F32, device=dev)
             head["edge"] = dict(edge, slab=edge_slab)
         g_top = head["Xout"]
     else:
@@ -827,9 +811,9 @@ def _bwd_chained(c: _BlockBackward, g, edge):
                     drop=((snap, p_drop) if snap is not None else None), b_format=(2 if (rt.bwd_use16 and rt.f16) else int(rt.bwd_use16)),
                     head=head)
     if head_wg is not None:
-        _reduce(head_wg, 0, topo.ntiles, hw_stride, c.seg(L - 1), hw_len, pending)
+        _reduce(head_wg, 0, ntiles, hw_stride, c.seg(L - 1), hw_len, pending)
     if edge_slab is not None:
-        _reduce(edge_slab, 0, topo.ntiles, e_stride, c.flat[c.offs[0]:c.offs[1]], e_stride, pending)
+        _reduce(edge_slab, 0, ntiles, e_stride, c.flat[c.offs[0]:c.offs[1]], e_stride, pending)
     if rt.bwd_join:
         # the folded conv 0 (input S, extra scaled bias sums) and the plain layers 1 .. L-2 in ONE launch
         wgrad_batched(topo, gl, hid, [c.S] + acts[1:L - 1], hid, nmat, c.seg(1, L - 2),

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import flags as FL
-from .topology import Topology
+from .topology import Tiling, Topology
 
 
 def _static_replay() -> bool:
@@ -68,6 +68,26 @@ def _ncg(j: int) -> int:
 # ------------------------------------------------------------------------------------------
 # thin op wrappers over the C ABI
 # ------------------------------------------------------------------------------------------
+def _fill_graph(a: "_lib.GemmPropArgs", topo: Topology, ts: Tiling, transposed: bool) -> None:
+    """The graph side of a tile GEMM + propagation launch: the tiles and ELL slices of ``ts``, the CSR of ``topo``, by target or
+    (transposed) by source.  (max_tile_rows is the layer chain's alone: gemm_prop_chain sets it.)"""
+    a.nrb, a.ntiles, a.tile_start = ts.nrb, ts.ntiles, ts.tile_start.data_ptr()
+    if transposed:
+        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), ts.max_nnzT
+        a.ell_width, a.ell_tiles = ts.ellT, _ptr(ts.ellT_tiles)
+    else:
+        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.w.data_ptr(), ts.max_nnz
+        a.ell_width, a.ell_tiles = ts.ell, _ptr(ts.ell_tiles)
+
+
+def _fill_wgrad_graph(a: "_lib.WgradArgs", topo: Topology, ts: Tiling) -> None:
+    """The graph side of a weight-gradient launch: the by-source CSR of ``topo``, everything else from the tile set ``ts`` the
+    launch walks (_wgrad_tiles: not always the primary one)."""
+    a.nrb, a.ntiles, a.tile_start = ts.nrb, ts.ntiles, ts.tile_start.data_ptr()
+    a.rowptrT, a.colT, a.wT, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), ts.max_nnzT
+    a.ell_width, a.ell_tiles = ts.ellT, _ptr(ts.ellT_tiles)
+
+
 def gemm_prop(topo: Topology, X: torch.Tensor, ldx: int, kreal: int, Bp: torch.Tensor, nmat: int, hout: int,
               Y: torch.Tensor, bias=None, rowscale=None, relu_src=None, dmask=None, add_src=None, add_ld=0,
               relu: bool = False, transposed: bool = False, prop_in: int = 0, narrow_h: int = 0,
@@ -76,8 +96,9 @@ def gemm_prop(topo: Topology, X: torch.Tensor, ldx: int, kreal: int, Bp: torch.T
     b_format = 2: Bp holds the f16x2 group buffers of _PackPlan(f16_groups=...) and the tile GEMM runs as f16x3 (chain_f16_supported);
     b_format = 1: Bp holds bf16x3 fragments (_PackPlan.fwd16 / bwd16) and the tile GEMM runs as bf16x6 -- the tall-tile
     shapes of gemm16_supported only."""
-    if topo.global_only and (nmat > 1 or prop_in > 0):
-        raise NotImplementedError(f"largest connected component has {topo.max_segment} nodes: the fused GEMM + propagation "
+    ts = topo.tiling
+    if ts.global_only and (nmat > 1 or prop_in > 0):
+        raise NotImplementedError(f"largest connected component has {ts.max_segment} nodes: the fused GEMM + propagation "
                                   "kernels hold a whole graph in LDS (<= 192 nodes); use the MPN / TAGConv modules, which "
                                   "switch to the global-memory propagation path")
     a = _lib.GemmPropArgs()
@@ -93,104 +114,111 @@ def gemm_prop(topo: Topology, X: torch.Tensor, ldx: int, kreal: int, Bp: torch.T
     a.dmask, a.ld_dmask = _ptr(dmask), (dmask.stride(0) if dmask is not None else 0)
     a.add_src, a.ld_add = _ptr(add_src), add_ld
     a.Y, a.ldy, a.hout, a.ncg = Y.data_ptr(), Y.stride(0), hout, (1 if narrow_h else _ncg(hout))
-    a.relu, a.nmat, a.nrb, a.ntiles = int(relu), nmat, topo.nrb, topo.ntiles
-    a.tile_start = topo.tile_start.data_ptr()
-    if transposed:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), topo.max_nnzT
-        a.ell_width, a.ell_tiles = topo.ellT, _ptr(topo.ellT_tiles)
-    else:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.w.data_ptr(), topo.max_nnz
-        a.ell_width, a.ell_tiles = topo.ell, _ptr(topo.ell_tiles)
+    a.relu, a.nmat = int(relu), nmat
+    _fill_graph(a, topo, ts, transposed)
     _lib.check(_lib.lib().dss2_gemm_prop(C.byref(a), _stream(Y)), "dss2_gemm_prop")
 
 
+
+def _tiles(topo) -> Tiling:
+    """The tile record a route predicate reads: the primary Tiling of a Topology.  Anything else -- a Tiling, or the flat stand-in with
+    the same fields that tests/test_route_cpu.py routes without a device -- is read as it is."""
+    return topo.tiling if isinstance(topo, Topology) else topo
 
 
 def chain_supported(topo: Topology, nmat: int, hid: int, transposed: bool, have16: bool = False) -> bool:
     """True when n >= 2 consecutive hid -> hid layers can run as one chained launch (dss2_gemm_prop_chain).  ``have16``: the
     caller holds bf16x6 weight packs, so shapes that only the split-plane form covers (192-row tiles) count too."""
-    ell, tiles = (topo.ellT, topo.ellT_tiles) if transposed else (topo.ell, topo.ell_tiles)
+    ts = _tiles(topo)
+    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
     if not FL.CHAIN_LAYERS or tiles is None:
         return False
-    return bool(_lib.lib().dss2_gemm_prop_chain_supported(topo.nrb, nmat, hid, hid, ell)) or (
+    return bool(_lib.lib().dss2_gemm_prop_chain_supported(ts.nrb, nmat, hid, hid, ell)) or (
         have16 and chain16_supported(topo, nmat, hid, transposed))
 
 
-def _single_group_tall_veto(topo: Topology, hid: int) -> bool:
+def _single_group_tall_veto(ts: Tiling, hid: int) -> bool:
     """96- / 192-row tiles with ONE column group (hid <= 32): the split-plane chain runs them as single-wave workgroups, which pays from
     dss2_chain_sp6_single_group_min_tiles() tiles on (the library applies the same count at launch); below it the block keeps the
     multi-wave chain of that shape with its bf16x3 weights and fp32 gates, i.e. every sp6-only capability is declined here."""
-    if hid > 32 or topo.nrb not in (3, 6):
+    if hid > 32 or ts.nrb not in (3, 6):
         return False
     m = int(_lib.lib().dss2_chain_sp6_single_group_min_tiles())
-    return m < 0 or topo.ntiles < m
+    return m < 0 or ts.ntiles < m
 
 
 def chain_gate_words(topo: Topology, nmat: int, hid: int) -> int:
     """64-bit words per tile of a layer's sign-bit buffer (``y_bits`` of a forward chain -> ``gate_bits`` of the data-gradient
     chain over the same tiles); 0 where the chain kernel of this shape has no bit form (or either direction is not chained)."""
-    if not (FL.CHAIN_LAYERS and FL.CHAIN_BF16 and FL.CHAIN_GATE_BITS) or topo.ell_tiles is None or topo.ellT_tiles is None:
+    ts = _tiles(topo)
+    if not (FL.CHAIN_LAYERS and FL.CHAIN_BF16 and FL.CHAIN_GATE_BITS) or ts.ell_tiles is None or ts.ellT_tiles is None:
         return 0
-    if _single_group_tall_veto(topo, hid):
+    if _single_group_tall_veto(ts, hid):
         return 0
-    cache = topo.__dict__.setdefault("_gate_words", {})      # (asked once per forward: keep the two library calls off the step)
+    cache = ts.gate_words if isinstance(ts, Tiling) else {}      # (asked once per forward: keep the two library calls off the step)
     gw = cache.get((nmat, hid))
     if gw is None:
         L = _lib.lib()
-        gw = cache[(nmat, hid)] = min(int(L.dss2_gemm_prop_chain_gate_words(topo.nrb, nmat, hid, hid, topo.ell)),
-                                      int(L.dss2_gemm_prop_chain_gate_words(topo.nrb, nmat, hid, hid, topo.ellT)))
+        gw = cache[(nmat, hid)] = min(int(L.dss2_gemm_prop_chain_gate_words(ts.nrb, nmat, hid, hid, ts.ell)),
+                                      int(L.dss2_gemm_prop_chain_gate_words(ts.nrb, nmat, hid, hid, ts.ellT)))
     return gw
 
 
 def chain16_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
     """True when the chain can run its tile GEMM on the bf16 matrix pipe (bf16x6, fp32-accurate; dss2_gemm_chain16.hip)."""
-    ell, tiles = (topo.ellT, topo.ellT_tiles) if transposed else (topo.ell, topo.ell_tiles)
-    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop_chain16_supported(topo.nrb, nmat, hid, hid, ell))
+    ts = _tiles(topo)
+    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
+    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop_chain16_supported(ts.nrb, nmat, hid, hid, ell))
 
 
 def chain_f16_supported(topo: Topology, nmat: int, hid: int) -> bool:
     """True when BOTH chains of a block (forward, data gradients) can run their tile GEMM as f16x3 (b_format 2: weights as two fp16
     planes with scale exponents, _PackPlan f16_groups): the split-plane chain of 64-row tiles with bit-word ReLU gates
     (csrc/dss2_gemm_chain_sp.hip, MS = 2).  flags.CHAIN_F16 = False: bf16x6."""
-    if not (FL.CHAIN_F16 and FL.CHAIN_BF16 and topo.ell_tiles is not None and topo.ellT_tiles is not None and chain_gate_words(topo, nmat, hid) > 0):
+    ts = _tiles(topo)
+    if not (FL.CHAIN_F16 and FL.CHAIN_BF16 and ts.ell_tiles is not None and ts.ellT_tiles is not None and chain_gate_words(topo, nmat, hid) > 0):
         return False
     L = _lib.lib()
-    return bool(L.dss2_gemm_prop_chain_f16_supported(topo.nrb, nmat, hid, hid, topo.ell)) and bool(L.dss2_gemm_prop_chain_f16_supported(topo.nrb, nmat, hid, hid, topo.ellT))
+    return bool(L.dss2_gemm_prop_chain_f16_supported(ts.nrb, nmat, hid, hid, ts.ell)) and bool(L.dss2_gemm_prop_chain_f16_supported(ts.nrb, nmat, hid, hid, ts.ellT))
 
 
 def chain_head_supported(topo: Topology, nmat: int, hid: int, nout: int, transposed: bool) -> bool:
     """True when the narrow head TAGConv (hid -> nout) can ride inside the chained launch of the hid -> hid layers
     (dss2_gemm_prop_chain_head: forward = the head after the last chained layer, transposed = the chain's input computed from
     the head's upstream gradient); DSS2_CHAIN_HEAD=0 switches it off."""
-    ell, tiles = (topo.ellT, topo.ellT_tiles) if transposed else (topo.ell, topo.ell_tiles)
-    if _single_group_tall_veto(topo, hid):
+    ts = _tiles(topo)
+    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
+    if _single_group_tall_veto(ts, hid):
         return False
     return bool(FL.CHAIN_HEAD) and FL.CHAIN_BF16 and tiles is not None and bool(      # (a mask of modes: bit 0 forward, bit 1 backward)
-        _lib.lib().dss2_gemm_prop_chain_head_supported(topo.nrb, nmat, hid, hid, ell, nout) & (2 if transposed else 1))
+        _lib.lib().dss2_gemm_prop_chain_head_supported(ts.nrb, nmat, hid, hid, ell, nout) & (2 if transposed else 1))
 
 
 def chain_edge_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
     """True when the edge MLP's first Linear can run as a phase of the chain with the fused head (dss2_chain_edge): forward = the chain
     computes its input S, transposed = the data-gradient chain runs the edge backward on conv 0's input gradient.  64-row tiles, f16x3,
     hid 128, the bf16x6 tile edge kernels.  flags.CHAIN_EDGE = False: the edge launches of their own."""
-    if not (FL.CHAIN_EDGE and FL.EDGE_TILE_KERNELS and topo.ell_ent_tiles is not None and topo.ell_tiles is not None and topo.ellT_tiles is not None):
+    ts = _tiles(topo)
+    if not (FL.CHAIN_EDGE and FL.EDGE_TILE_KERNELS and ts.ell_ent_tiles is not None and ts.ell_tiles is not None and ts.ellT_tiles is not None):
         return False
-    ell = topo.ellT if transposed else topo.ell
-    return bool(_lib.lib().dss2_gemm_prop_chain_edge_supported(topo.nrb, nmat, hid, hid, ell, topo.ell) & (2 if transposed else 1))
+    ell = ts.ellT if transposed else ts.ell
+    return bool(_lib.lib().dss2_gemm_prop_chain_edge_supported(ts.nrb, nmat, hid, hid, ell, ts.ell) & (2 if transposed else 1))
 
 
 def chain_head_wgrad_supported(topo: Topology, nmat: int, hid: int, nout: int) -> bool:
     """True when the data-gradient chain with the fused head (mode 2) can also form the head's weight gradient in its staging
     (dss2_chain_head.wg_slab, round 5): 64-, 96- and 192-row tiles, nout <= 2.  flags.CHAIN_HEAD_WGRAD = False: the narrow weight-gradient launch."""
-    return bool(FL.CHAIN_HEAD_WGRAD) and topo.ellT_tiles is not None and bool(
-        _lib.lib().dss2_gemm_prop_chain_head_wgrad_supported(topo.nrb, nmat, hid, hid, topo.ellT, nout))
+    ts = _tiles(topo)
+    return bool(FL.CHAIN_HEAD_WGRAD) and ts.ellT_tiles is not None and bool(
+        _lib.lib().dss2_gemm_prop_chain_head_wgrad_supported(ts.nrb, nmat, hid, hid, ts.ellT, nout))
 
 
 def gemm16_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
     """True when a single hid -> hid layer (dss2_gemm_prop) can take bf16x3 weights: the tall tiles (128 / 192 rows) that
     run matrix-sequentially with K-halved staging and therefore have no layer chain."""
-    ell, tiles, nnz = (topo.ellT, topo.ellT_tiles, topo.max_nnzT) if transposed else (topo.ell, topo.ell_tiles, topo.max_nnz)
-    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop16_supported(topo.nrb, nmat, hid, hid, nnz, ell))
+    ts = _tiles(topo)
+    ell, tiles, nnz = (ts.ellT, ts.ellT_tiles, ts.max_nnzT) if transposed else (ts.ell, ts.ell_tiles, ts.max_nnz)
+    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop16_supported(ts.nrb, nmat, hid, hid, nnz, ell))
 
 
 def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: int, layers: Sequence[dict], transposed: bool = False,
@@ -214,16 +242,10 @@ def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: i
     a.X, a.ldx = (X.data_ptr(), X.stride(0)) if X is not None else (0, hid)
     a.kreal, a.kpad = hid, (_round16(hid) if b_format >= 1 else _round8(hid))
     a.hout, a.ncg, a.ldy, a.ld_relu, a.ld_dmask, a.ld_add = hid, _ncg(hid), hid, hid, hid, hid
-    a.nmat, a.nrb, a.ntiles = nmat, topo.nrb, topo.ntiles
-    a.max_tile_rows = int(getattr(topo, "max_tile_rows", 0) or 0)
-    a.tile_start = topo.tile_start.data_ptr()
+    ts = topo.tiling
+    a.nmat, a.max_tile_rows = nmat, ts.max_tile_rows
     a.pre_rowscale = _ptr(pre_rowscale)
-    if transposed:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), topo.max_nnzT
-        a.ell_width, a.ell_tiles = topo.ellT, _ptr(topo.ellT_tiles)
-    else:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.w.data_ptr(), topo.max_nnz
-        a.ell_width, a.ell_tiles = topo.ell, _ptr(topo.ell_tiles)
+    _fill_graph(a, topo, ts, transposed)
     tab = (_lib.ChainLayer * len(layers))()
     for d, ly in zip(tab, layers):
         for t_ in (ly.get("Y"), ly.get("relu_src"), ly.get("dmask")):
@@ -265,21 +287,22 @@ def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: i
     if edge is not None:
         e = hd.edge
         e.x, e.ldx, e.ea, e.ldea = edge["x"].data_ptr(), int(edge["ldx"]), edge["ea"].data_ptr(), int(edge["ldea"])
-        e.W1, e.b1, e.ell_ent, e.width = edge["W1"].data_ptr(), edge["b1"].data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell
+        e.W1, e.b1, e.ell_ent, e.width = edge["W1"].data_ptr(), edge["b1"].data_ptr(), ts.ell_ent_tiles.data_ptr(), ts.ell
         e.S, e.slab = _ptr(edge.get("S")), _ptr(edge.get("slab"))
     _lib.check(_lib.lib().dss2_gemm_prop_chain_head(C.byref(a), C.addressof(tab), len(layers), C.byref(hd), _stream(dev_t)),
                "dss2_gemm_prop_chain_head")
 
 
-def _wgrad_tiles(topo: Topology, nmat: int, hout: int, hin: int, b16: int):
-    """The tile set a weight-gradient launch walks: the topology's own, or -- 64-row tilings under the bf16x6 kernel -- a
+def _wgrad_tiles(topo: Topology, nmat: int, hout: int, hin: int, b16: int) -> Tiling:
+    """The tile set a weight-gradient launch walks: the topology's primary one, or -- 64-row tilings under the bf16x6 kernel -- a
     32-row tiling of the same graphs (Topology.tiles_for(1)), on which two 4-wave workgroups share a CU and overlap each
     other's staging / propagation with their MFMA phases (csrc/dss2_wgrad16.hip)."""
     # (each X tile is staged by the two workgroups that own its 64-column output halves, at unrelated times: beyond the
     #  Infinity Cache that is a second trip to HBM.  As bf16x6 that lost to the 64-row kernel -- B = 32768: 3.52 ms against 3.43 --, so
     #  that route takes the 32-row form only while one layer's input stays well inside the cache; as f16x3 (round 5) the 32-row kernel
     #  wins at every size: B = 32768 2.75 -> 2.45 ms, B = 16384 1.44 -> 1.28 ms)
-    if (FL.WGRAD_TM32 and b16 and topo.nrb == 2 and not topo.global_only and nmat in (2, 3) and hout > 32 and 1 <= topo.ellT <= 8
+    ts = topo.tiling
+    if (FL.WGRAD_TM32 and b16 and ts.nrb == 2 and not ts.global_only and nmat in (2, 3) and hout > 32 and 1 <= ts.ellT <= 8
             and (FL.WGRAD_F16 or topo.N * hin * 4 <= FL.WGRAD_TM32_MAX_BYTES)):
         alt = topo.tiles_for(1)
         # ... and only where the library's bf16x6 kernel covers the shape on that tiling (its LDS query answers with the fp32 kernel's
@@ -289,18 +312,17 @@ def _wgrad_tiles(topo: Topology, nmat: int, hout: int, hin: int, b16: int):
             if (L_.dss2_wgrad_lds_bytes_ex(1, nmat, hout, hin, alt.max_nnzT, alt.ellT, 1)
                     != L_.dss2_wgrad_lds_bytes_ex(1, nmat, hout, hin, alt.max_nnzT, alt.ellT, 0)):
                 return alt
-    return topo
+    return ts
 
 
-def _wgrad_mode(ts, nmat: int, b16: int, hinted: bool = False) -> int:
+def _wgrad_mode(ts: Tiling, nmat: int, b16: int, hinted: bool = False) -> int:
     """args.mfma_bf16 of a weight-gradient launch on the tile set ``ts``: 0 fp32 MFMA, 1 bf16x6, or -- flags.WGRAD_F16 on 32-row tiles
     (csrc/dss2_wgrad16h.hip) and on 96- .. 192-row tiles (csrc/dss2_wgrad16th.hip) with ELL slices -- 2 | hb << 8: the f16x3 kernels
     with hb headroom bits for the gain of the propagation hops, ceil(log2(max row sum of |P^T| ^ K)), read from the ELL slices once per
     tile set (one device-to-host copy, cached; ``hinted``: from the ELL width alone, no copy).  Shapes the f16x3 kernels do not cover run bf16x6 on the same value (the library decides)."""
     if not (b16 and FL.WGRAD_F16 and ts.nrb in (1, 3, 4, 5, 6) and nmat in (2, 3) and ts.ellT_tiles is not None and 1 <= ts.ellT <= 8):
         return b16
-    cache = ts.__dict__.setdefault("_f16_gain_bits", {})
-    hb = cache.get(nmat)
+    hb = ts.gain_bits.get(nmat)
     if hb is None:
         if hinted or torch.cuda.is_current_stream_capturing():
             # no copy to the host here (a topology built from a TopologyHint never reads anything back; neither may a capture): the
@@ -310,7 +332,7 @@ def _wgrad_mode(ts, nmat: int, b16: int, hinted: bool = False) -> int:
         else:
             w = ts.ellT_tiles[..., 1].contiguous().view(torch.float32)      # [tiles][width][rows]: the entries' weights
             gain = max(float(w.abs().sum(dim=1).max()), 1.0)
-        hb = cache[nmat] = max(0, int(math.ceil(math.log2(gain) * (nmat - 1) - 1e-6)))
+        hb = ts.gain_bits[nmat] = max(0, int(math.ceil(math.log2(gain) * (nmat - 1) - 1e-6)))
     return (2 | (hb << 8) | (0 if FL.WGRAD_HOPS_MFMA else 1 << 16)) if hb <= 10 else b16      # (bit 16: the 32-row kernel's hops as fp32 gathers)
 
 
@@ -319,7 +341,7 @@ def wgrad(topo: Topology, G: torch.Tensor, hout: int, X: torch.Tensor, hin: int,
     """out_flat[nmat*hout*hin + hout] <- [dW_0 .. dW_{nmat-1}, db] (deterministic two-pass sum); with
     rowscale2 additionally [nmat*hout] scaled column sums of P^m G (one block per matrix).  ``out_len``: reduce only
     the first out_len elements of the result."""
-    if topo.global_only and nmat > 1:
+    if topo.tiling.global_only and nmat > 1:
         raise NotImplementedError("wgrad with propagation needs LDS-resident graph tiles (graphs of <= 192 nodes)")
     narrow = nmat > 1 and nmat * hout <= 32 and rowscale2 is None
     b16 = int(FL.WGRAD_BF16 and rowscale is None and not narrow)
@@ -334,11 +356,9 @@ def wgrad(topo: Topology, G: torch.Tensor, hout: int, X: torch.Tensor, hin: int,
     a.G, a.ldg, a.hout = G.data_ptr(), G.stride(0), hout
     a.X, a.ldx, a.hin = X.data_ptr(), X.stride(0), hin
     a.rowscale, a.rowscale2 = _ptr(rowscale), _ptr(rowscale2)
-    a.slab, a.n_split, a.nmat, a.nrb, a.ntiles = slab.data_ptr(), n_split, nmat, ts.nrb, ts.ntiles
-    a.tile_start = ts.tile_start.data_ptr()
-    a.rowptrT, a.colT, a.wT, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), ts.max_nnzT
-    a.ell_width, a.ell_tiles = ts.ellT, _ptr(ts.ellT_tiles)
-    a.narrow, a.mfma_bf16 = int(narrow), (_wgrad_mode(ts, nmat, b16, getattr(topo, "hint", None) is not None) if (not narrow and rowscale is None) else b16)
+    a.slab, a.n_split, a.nmat = slab.data_ptr(), n_split, nmat
+    _fill_wgrad_graph(a, topo, ts)
+    a.narrow, a.mfma_bf16 = int(narrow), (_wgrad_mode(ts, nmat, b16, topo.hint is not None) if (not narrow and rowscale is None) else b16)
     st = _stream(G)
     _lib.check(_lib.lib().dss2_wgrad(C.byref(a), st), "dss2_wgrad")
     _reduce(slab, 0, n_split, stride, out_flat, stride if out_len is None else out_len, pending)
@@ -355,7 +375,7 @@ def wgrad_batched(topo: Topology, Gs: Sequence[torch.Tensor], hout: int, Xs: Seq
     lds = _lib.lib().dss2_wgrad_lds_bytes_ex(ts.nrb, nmat, hout, hin, ts.max_nnzT, ts.ellT, int(FL.WGRAD_BF16))
     per_cu = _wgrad_per_cu(int(lds))
     ys = _lib.lib().dss2_wgrad_y_slices(ts.nrb, nmat, hout, hin, ts.ellT, int(FL.WGRAD_BF16), int(first_rowscale2 is not None))
-    mode = _wgrad_mode(ts, nmat, int(FL.WGRAD_BF16), getattr(topo, "hint", None) is not None)
+    mode = _wgrad_mode(ts, nmat, int(FL.WGRAD_BF16), topo.hint is not None)
     nz = int(_lib.lib().dss2_wgrad_batched_groups(ts.nrb, hout, hin, mode, nl))      # workgroup groups along z (two 32-column layers may share one)
     n_split = min(ts.ntiles, max(1, (256 * per_cu) // (nz * ys)))       # the layers share the chip
     stride = nmat * hout * hin + hout
@@ -367,11 +387,8 @@ def wgrad_batched(topo: Topology, Gs: Sequence[torch.Tensor], hout: int, Xs: Seq
     for g_, x_ in zip(Gs, Xs):
         if g_.stride(0) != a.ldg or x_.stride(0) != a.ldx or g_.shape != Gs[0].shape or x_.shape != Xs[0].shape:
             raise ValueError("wgrad_batched: layers must share shapes and leading dimensions")
-    a.n_split, a.nmat, a.nrb, a.ntiles = n_split, nmat, ts.nrb, ts.ntiles
-    a.mfma_bf16 = mode
-    a.tile_start = ts.tile_start.data_ptr()
-    a.rowptrT, a.colT, a.wT, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), ts.max_nnzT
-    a.ell_width, a.ell_tiles = ts.ellT, _ptr(ts.ellT_tiles)
+    a.n_split, a.nmat, a.mfma_bf16 = n_split, nmat, mode
+    _fill_wgrad_graph(a, topo, ts)
     PtrArr = C.c_void_p * nl
     gs, xs = PtrArr(*[g_.data_ptr() for g_ in Gs]), PtrArr(*[x_.data_ptr() for x_ in Xs])
     offs = [sum(lens[:l]) for l in range(nl)]
@@ -483,6 +500,57 @@ def csr_axpy(topo: Topology, T: torch.Tensor, out: torch.Tensor, h: int, add=Non
         a.drop_thr, a.drop_scale = _dropout_params(drop[1])
     a.n_rows, a.h = topo.N, h
     _lib.check(_lib.lib().dss2_csr_axpy(C.byref(a), _stream(out)), "dss2_csr_axpy")
+
+
+def _csr_ent(topo: Topology, transposed: bool):
+    """(rowptr, col, ent) pointers of the CSR by target or (transposed) by source, for the row-per-wave edge kernels."""
+    if transposed:
+        return topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.entT.data_ptr()
+    return topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
+
+
+def edge_tile_fwd(ts: Tiling, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx: bool) -> None:
+    """S = per-target sums of relu(W1 [x_i | x_j | ea] + b1) on the tiles' ELL slices (dss2_edge_tile_fwd_paired); ``need_dx``: the
+    library picks the forward whose gates the input-gradient backward recomputes exactly."""
+    _lib.check(_lib.lib().dss2_edge_tile_fwd_paired(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(),
+                                                    ts.tile_start.data_ptr(), ts.ell_ent_tiles.data_ptr(), ts.ell, ts.nrb, ts.ntiles,
+                                                    S.data_ptr(), hid, fn, fe, int(bool(need_dx)), _stream(S)), "dss2_edge_tile_fwd_paired")
+
+
+def edge_tile_bwd(ts: Tiling, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, U, ldu, hid, fn, fe, transposed: bool) -> None:
+    """Backward of edge_tile_fwd over the incoming (or, transposed, the outgoing) edges: dW1 | db1 slabs where ``slab`` is given, the
+    per-node sums of dz into ``U`` where it is."""
+    ent, width = (ts.ellT_ent_tiles, ts.ellT) if transposed else (ts.ell_ent_tiles, ts.ell)
+    _lib.check(_lib.lib().dss2_edge_tile_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
+                                             ts.tile_start.data_ptr(), ent.data_ptr(), width, ts.nrb, ts.ntiles, _ptr(slab), n_slabs,
+                                             _ptr(U), ldu, hid, fn, fe, int(transposed), _stream(dS)), "dss2_edge_tile_bwd")
+
+
+def edge_hidden_fwd(topo: Topology, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe) -> None:
+    """edge_tile_fwd for general graphs (hub nodes beyond the ELL width): row-per-wave kernel on the CSR."""
+    _lib.check(_lib.lib().dss2_edge_hidden_fwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), *_csr_ent(topo, False),
+                                               S.data_ptr(), topo.N, hid, fn, fe, _stream(S)), "dss2_edge_hidden_fwd")
+
+
+def edge_hidden_bwd(topo: Topology, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, U, ldu, hid, fn, fe, transposed: bool) -> None:
+    """edge_tile_bwd on the CSR."""
+    _lib.check(_lib.lib().dss2_edge_hidden_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
+                                               *_csr_ent(topo, transposed), _ptr(slab), n_slabs, _ptr(U), ldu, topo.N, hid, fn, fe,
+                                               int(transposed), _stream(dS)), "dss2_edge_hidden_bwd")
+
+
+def edge_combine_fwd(topo: Topology, AB, ea, ldea, w1c: int, ldw: int, b1, S, h, fe) -> None:
+    """S[i] = sum over the edges into i of relu(A[i] + B[src] + W1c ea + b1), AB = [A | B] ([N, 2h]); ``w1c``: pointer of W1's
+    edge-feature columns, ``ldw`` its leading dimension (dss2_edge_combine_fwd: the general-width edge aggregation)."""
+    _lib.check(_lib.lib().dss2_edge_combine_fwd(AB.data_ptr(), AB.stride(0), ea.data_ptr(), ldea, w1c, ldw, b1.data_ptr(),
+                                                *_csr_ent(topo, False), S.data_ptr(), topo.N, h, fe, _stream(S)), "dss2_edge_combine_fwd")
+
+
+def edge_combine_bwd(topo: Topology, AB, ea, ldea, w1c: int, ldw: int, b1, dS, dAB, slab, n_slabs, h, fe, transposed: bool) -> None:
+    """Backward of edge_combine_fwd: dA (by target) or, transposed, dB (by source) into dAB; dW1c | db1 slabs where ``slab`` is given."""
+    _lib.check(_lib.lib().dss2_edge_combine_bwd(AB.data_ptr(), AB.stride(0), ea.data_ptr(), ldea, w1c, ldw, b1.data_ptr(), dS.data_ptr(),
+                                                *_csr_ent(topo, transposed), dAB.data_ptr(), _ptr(slab), n_slabs, topo.N, h, fe,
+                                                int(transposed), _stream(dS)), "dss2_edge_combine_bwd")
 
 
 _DROP_PARAMS = {}

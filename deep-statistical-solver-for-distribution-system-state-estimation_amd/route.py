@@ -11,7 +11,7 @@ from __future__ import annotations
 from typing import NamedTuple, Tuple
 
 from . import flags as FL
-from .ops import (chain16_supported, chain_edge_supported, chain_f16_supported, chain_gate_words, chain_head_supported,
+from .ops import (_tiles, chain16_supported, chain_edge_supported, chain_f16_supported, chain_gate_words, chain_head_supported,
                   chain_head_wgrad_supported, chain_supported, gemm16_supported, is_narrow)
 from .topology import Topology
 
@@ -19,7 +19,7 @@ from .topology import Topology
 def use_global_path(topo: Topology, nmat: int) -> bool:
     """A TAGConv runs as ONE plain tile GEMM + K propagation hops in global memory when the graphs exceed the LDS-resident
     tiles (> 192 nodes) or when K > 3 (the fused tile kernels are instantiated for K + 1 <= 4 matrices)."""
-    return bool(topo.global_only or nmat > 4)
+    return bool(_tiles(topo).global_only or nmat > 4)
 
 
 class BlockRoute(NamedTuple):
@@ -79,7 +79,7 @@ def block_route(mod, topo: Topology, need_dx: bool, in_stack: bool) -> BlockRout
     bwd_use16 = bool(bwd_chain and b16 and chain16_supported(topo, nmat, hid, True))
     # (tall tiles: only the direction-specialised data-gradient chain has the head form -- its layers gate with the forward's bit words)
     bwd_head = bool(bwd_use16 and L - 1 <= FL.CHAIN_MAX and narrow_head and chain_head_supported(topo, nmat, hid, nout, True)
-                    and (topo.nrb <= 2 or gw > 0))
+                    and (_tiles(topo).nrb <= 2 or gw > 0))
     bwd_head_wgrad = bool(bwd_head and chain_head_wgrad_supported(topo, nmat, hid, nout))
     bwd_edge = bool(bwd_head and edge_ok and chain_edge_supported(topo, nmat, hid, True))
     # The folded conv 0 joins the batched launch of the plain layers (round 4; flags.WGRAD_JOIN_FOLDED = False: its own launch).

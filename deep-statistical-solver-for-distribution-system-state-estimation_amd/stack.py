@@ -17,6 +17,7 @@ import torch
 
 
 from . import _lib
+from .topology import Tiling
 
 
 def _static_replay() -> bool:
@@ -61,16 +62,16 @@ def dims_of(blocks) -> Optional[_lib.StackDims]:
 STACK_NRB = _os.environ.get("DSS2_STACK_NRB", "auto")      # tile height of the whole-stack kernels: auto | 1 | 2
 
 
-def tiles_of(topo):
-    """The tile set the whole-stack kernels run on.  They are latency-bound per tile (one workgroup walks a tile through ~45
+def tiles_of(topo) -> Optional[Tiling]:
+    """The Tiling the whole-stack kernels run on, or None.  They are latency-bound per tile (one workgroup walks a tile through ~45
     dependent phases), so as long as 64-row tiles leave CUs idle, 32-row tiles -- twice as many workgroups, half the work
     per phase -- are faster (B = 64: 16 -> 32 workgroups); big batches keep the 64-row tiles (less overhead per graph)."""
-    if topo.global_only:
+    base = topo.tiling
+    if base.global_only:
         return None
     if STACK_NRB in ("1", "2"):
         return topo.tiles_for(int(STACK_NRB))
-    base = topo
-    if topo.nrb > 2:
+    if base.nrb > 2:
         # small graphs the primary tiling happened to pack into taller tiles (ragged or tiny batches: 29 CIGRE graphs tile as
         # well at 96 rows as at 64): the stack kernels run them on a 64-row tiling of their own, so that the route -- and
         # with it every razor-edge ReLU gate -- does not depend on the batch size (tests/test_gpu_shard_emulation.py)
@@ -86,7 +87,7 @@ def tiles_of(topo):
 
 def supported(blocks, topo) -> Optional[_lib.StackDims]:
     """The stack's dims when the whole-stack kernels cover it on this topology, else None."""
-    if not STACK_KERNEL or topo.global_only:
+    if not STACK_KERNEL or topo.tiling.global_only:
         return None
     d = dims_of(blocks)
     ts = tiles_of(topo) if d is not None else None
@@ -154,13 +155,13 @@ def _plan_of(owner, dims, device) -> _Plan:
     return plan
 
 
-def _fill_common(a: "_lib.StackArgs", plan: _Plan, topo, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache) -> None:
+def _fill_common(a: "_lib.StackArgs", plan: _Plan, topo, ts: Tiling, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache) -> None:
+    """What the forward and the backward launch share; ``ts``: tiles_of(topo)."""
     from .networks import _dropout_params
     d = plan.dims
     a.dims = d
     a.x, a.ldx, a.ea, a.ldea = x.data_ptr(), ldx, ea.data_ptr(), ldea
     a.wpack = plan.wpack.data_ptr()
-    ts = tiles_of(topo)
     a.tile_start, a.ntiles, a.tm = ts.tile_start.data_ptr(), ts.ntiles, 32 * ts.nrb
     a.ell_w, a.ell_e, a.ell_width = ts.ell_tiles.data_ptr(), ts.ell_ent_tiles.data_ptr(), ts.ell
     a.ellT_w, a.ellT_e, a.ellT_width = ts.ellT_tiles.data_ptr(), ts.ellT_ent_tiles.data_ptr(), ts.ellT
@@ -203,7 +204,7 @@ class _FusedStackFn(torch.autograd.Function):
         ts = tiles_of(topo)
         eacache = torch.empty(ts.ntiles, ts.ell + ts.ellT, 64, 8, dtype=_F32, device=dev)
         a = _lib.StackArgs()
-        _fill_common(a, plan, topo, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache)
+        _fill_common(a, plan, topo, ts, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache)
         a.out, a.ldo = out.data_ptr(), out.stride(0)
         # ONE launch: fold + fragment packing of every block's weights, the dropout state hand-over, and this batch's per-tile
         # edge-feature cache
@@ -230,14 +231,15 @@ class _FusedStackFn(torch.autograd.Function):
         if plan.version != ver:           # another forward re-packed in between (weights are unchanged: autograd checks that)
             plan.pack(ps, None, 0, False)
         g = gout.contiguous()
-        n_wg = max(1, min(tiles_of(topo).ntiles, _cu_count(dev)))
+        ts = tiles_of(topo)
+        n_wg = max(1, min(ts.ntiles, _cu_count(dev)))
         slab = torch.empty(n_wg, plan.stride, dtype=_F32, device=dev)
         flat = torch.empty(plan.total, dtype=_F32, device=dev)
         need_dx = bool(ctx.needs_input_grad[0])
         dxbuf = torch.empty(topo.N, 8, dtype=_F32, device=dev) if dims.n_blocks > 1 else None
         dx = torch.empty(topo.N, 8, dtype=_F32, device=dev) if need_dx else None
         a = _lib.StackArgs()
-        _fill_common(a, plan, topo, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache)
+        _fill_common(a, plan, topo, ts, x, ldx, ea, ldea, acts, xs, snap, p_drop, eacache)
         a.gout, a.ldg = g.data_ptr(), g.stride(0)
         a.dxbuf = dxbuf.data_ptr() if dxbuf is not None else None
         a.dx_out = dx.data_ptr() if dx is not None else None

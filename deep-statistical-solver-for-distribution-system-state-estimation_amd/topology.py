@@ -24,8 +24,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -35,8 +35,33 @@ _FLIP = 1 << 31
 _NRB_CHOICES = (2, 4, 3, 1, 6)   # preference order on utilisation ties (32*nrb rows per tile)
 _LDS_LIMIT = 160 * 1024
 _ELL_MAX = 8
-_TILE_ATTRS = frozenset(["global_only", "nrb", "ntiles", "tile_start", "utilisation", "max_segment", "max_nnz", "max_nnzT", "ell", "ellT", "max_tile_rows",
-                         "ell_tiles", "ellT_tiles", "ell_ent_tiles", "ellT_ent_tiles"])
+
+
+@dataclass(slots=True)
+class Tiling:
+    """One tile set of a batch: whole-graph tiles of 32 * nrb rows and the per-tile ELL slices the tile kernels stage in LDS.  A
+    Topology owns a primary one (``Topology.tiling``) and alternates of a forced height (``Topology.tiles_for``); the CSR arrays
+    every tiling indexes stay on the Topology."""
+    global_only: bool            # no graph-aligned tiles (a component above 192 rows): uniform 64-row tiles, no ELL slices
+    nrb: int
+    ntiles: int
+    tile_start: torch.Tensor     # int32 [ntiles + 1]
+    utilisation: float
+    max_segment: int
+    max_tile_rows: int           # rows a tile really holds where every graph has the same size, else 0
+    max_nnz: int
+    max_nnzT: int
+    ell: int                     # ELL width by target / by source (0: a row above 8 entries, CSR staging)
+    ellT: int
+    ell_tiles: Optional[torch.Tensor]          # int32 [ntiles, width, 32 * nrb, 2] (column, weight); None at width 0
+    ellT_tiles: Optional[torch.Tensor]
+    ell_ent_tiles: Optional[torch.Tensor]      # ... (column, edge entry)
+    ellT_ent_tiles: Optional[torch.Tensor]
+    gain_bits: Dict[int, int] = field(default_factory=dict)                 # ops._wgrad_mode: nmat -> headroom bits of this tile set
+    gate_words: Dict[Tuple[int, int], int] = field(default_factory=dict)    # ops.chain_gate_words: (nmat, hid) -> words per tile (primary only)
+
+
+_TILING_FIELDS = frozenset(Tiling.__slots__) - {"gain_bits", "gate_words"}
 
 
 @dataclass(frozen=True)
@@ -139,6 +164,12 @@ class Topology:
             off += pn
         self._deg_pows = None
         self._padded = None
+        self.edge_count = self.edge_total = None                 # (padded batches only)
+        self._ell_jobs: List[_lib.EllBuildArgs] = []       # padded batches: the ELL launch of every tiling, in build order (rebuild())
+        self._stats = None
+        self._tiling: Optional[Tiling] = None               # the primary tiling, built on first use
+        self._alt_tilings: Dict[int, Optional[Tiling]] = {}
+        self._gnn_structures: Dict[int, object] = {}        # gnn._structure: normalisation mode -> the lane-group models' structure
         if edge_count is not None:
             n = hint.nodes_per_graph if hint is not None else 0
             if double is not None or hint is None or n <= 0 or N % n or hint.edges_per_graph <= 0 or hint.edges_per_graph * (N // n) != E:
@@ -154,7 +185,7 @@ class Topology:
             self._csr_ptr = torch.empty(N // n + 1, dtype=torch.int64, device=dev)
             self._deg_pows = torch.empty(N, 4, dtype=torch.float32, device=dev)
             q.edge_count, q.csr_ptr, q.edge_total, q.deg_pows = edge_count.data_ptr(), self._csr_ptr.data_ptr(), self.edge_total.data_ptr(), self._deg_pows.data_ptr()
-            self._padded, self._ell_jobs = q, []
+            self._padded = q
             self._keep = (ei, edge_count)
             self.rebuild()
         elif graphs:
@@ -170,8 +201,6 @@ class Topology:
             a.work = work.data_ptr()
             _lib.check(L.dss2_csr_build(C.byref(a), _stream(dev)), "dss2_csr_build")
             self._keep = (ei,)            # the build reads edge_index asynchronously
-        self._stats = None
-        self._tiles_built = False
 
     def rebuild(self) -> None:
         """Padded batches: the CSR part, the folded-bias row scales and every tiling built so far, again, from what edge_index and
@@ -188,10 +217,19 @@ class Topology:
         _lib.check(_lib.lib().dss2_csr_build_padded(C.byref(q), _stream(self.device)), "dss2_csr_build_padded")
 
     # ---- lazily built tile part -------------------------------------------------------------------------------
+    @property
+    def tiling(self) -> Tiling:
+        """The primary tiling (built on first use)."""
+        ts = self._tiling
+        if ts is None:
+            ts = self._tiling = self._build_tiles()
+        return ts
+
     def __getattr__(self, name):
-        if name in _TILE_ATTRS and not self.__dict__.get("_tiles_built", True):
-            self._build_tiles()
-            return self.__dict__[name]
+        # the tile fields read on the Topology (benchmark, tests, tools): those of the primary tiling.  Package code on the step path
+        # takes ``topo.tiling`` once and reads the record
+        if name in _TILING_FIELDS:
+            return getattr(self.tiling, name)
         raise AttributeError(name)
 
     @staticmethod
@@ -213,25 +251,23 @@ class Topology:
             self._stats = self._read_stats(self._meta)
         return self._stats
 
-    def tiles_for(self, nrb: int):
-        """A second set of tiles / ELL slices with a FORCED tile height of 32 * nrb rows, beside the primary one (cached).
-        Used by the whole-stack kernels, which are latency-bound per tile: at small batches twice as many 32-row tiles
-        put twice as many CUs to work.  Returns a namespace with the tile attributes (nrb, ntiles, tile_start, ell, ellT,
-        ell_tiles, ell_ent_tiles, ellT_tiles, ellT_ent_tiles), or None when no whole-graph tiling of that height exists."""
-        import types
-        if not self.__dict__.get("_tiles_built", False):
-            self._build_tiles()
-        if self.global_only:
+    def tiles_for(self, nrb: int) -> Optional[Tiling]:
+        """The Tiling with a FORCED tile height of 32 * nrb rows: the primary one itself (``self.tiling``) when that is its height,
+        else an alternate built beside it (cached per height).  Used by the whole-stack kernels, which are latency-bound per tile
+        (at small batches twice as many 32-row tiles put twice as many CUs to work), and by the weight gradient.  None when no
+        whole-graph tiling of that height exists."""
+        ts = self.tiling
+        if ts.global_only:
             return None
-        if nrb == self.nrb:
-            return self
-        alt = self.__dict__.setdefault("_alt_tiles", {})
-        if nrb not in alt:
-            d = self._build_tiles(choices=(int(nrb),), store=False)
-            alt[nrb] = types.SimpleNamespace(**d) if d is not None and not d["global_only"] else None
-        return alt[nrb]
+        if nrb == ts.nrb:
+            return ts
+        if nrb not in self._alt_tilings:
+            self._alt_tilings[nrb] = self._build_tiles(choices=(int(nrb),), store=False)
+        return self._alt_tilings[nrb]
 
-    def _build_tiles(self, choices=None, store=True):
+    def _build_tiles(self, choices=None, store=True) -> Optional[Tiling]:
+        """store=True: the primary tiling (the best of ``choices``; its statistics are the Topology's own).  store=False: an alternate
+        one, or None where no graph fits a tile of the heights in ``choices``."""
         L = _lib.lib()
         dev, N = self.device, self.N
         env = os.environ.get("DSS2_NRB")
@@ -339,26 +375,22 @@ class Topology:
             max_nnz, max_nnzT = max_deg * tm, max_degT * tm
         else:
             max_nnz = max_nnzT = nnz_bound
-        d = dict(global_only=False, nrb=nrb, ntiles=nt, tile_start=tile_start, utilisation=util, max_segment=max_segment, max_tile_rows=max_tile_rows,
-                 max_nnz=max_nnz, max_nnzT=max_nnzT, ell=ell, ellT=ellT, ell_tiles=ell_tiles,
-                 ellT_tiles=ellT_tiles, ell_ent_tiles=ell_ent_tiles, ellT_ent_tiles=ellT_ent_tiles)
-        if not store:
-            return d
-        self._stats = None            # (the ELL build added the per-tile entry counts to the statistics)
-        self.__dict__.update(d)
-        self._tiles_built = True
+        if store:
+            self._stats = None            # (the ELL build added the per-tile entry counts to the statistics)
+        return Tiling(global_only=False, nrb=nrb, ntiles=nt, tile_start=tile_start, utilisation=util, max_segment=max_segment,
+                      max_tile_rows=max_tile_rows, max_nnz=max_nnz, max_nnzT=max_nnzT, ell=ell, ellT=ellT, ell_tiles=ell_tiles,
+                      ellT_tiles=ellT_tiles, ell_ent_tiles=ell_ent_tiles, ellT_ent_tiles=ellT_ent_tiles)
 
-    def _global_tiles(self, max_segment: int) -> None:
+    def _global_tiles(self, max_segment: int) -> Tiling:
         """A connected component exceeds the largest LDS-resident tile (192 rows): no graph-aligned tiles exist.  The
         plain GEMMs still run on uniform 64-row tiles; the propagation hops run in global memory on the CSR
         (dss2_csr_axpy) and the edge MLP on the row-per-wave CSR kernels (networks._tagconv_forward_global)."""
         nt = -(-self.N // 64)
         tile_start = torch.empty(nt + 1, dtype=torch.int32, device=self.device)
         _lib.check(_lib.lib().dss2_tiles_uniform(tile_start.data_ptr(), nt, 64, self.N, _stream(self.device)), "dss2_tiles_uniform")
-        self.__dict__.update(global_only=True, nrb=2, ntiles=nt, tile_start=tile_start, utilisation=self.N / float(nt * 64), max_tile_rows=0,
-                             max_segment=max_segment, max_nnz=0, max_nnzT=0, ell=0, ellT=0, ell_tiles=None, ellT_tiles=None,
-                             ell_ent_tiles=None, ellT_ent_tiles=None)
-        self._tiles_built = True
+        return Tiling(global_only=True, nrb=2, ntiles=nt, tile_start=tile_start, utilisation=self.N / float(nt * 64), max_segment=max_segment,
+                      max_tile_rows=0, max_nnz=0, max_nnzT=0, ell=0, ellT=0, ell_tiles=None, ellT_tiles=None,
+                      ell_ent_tiles=None, ellT_ent_tiles=None)
 
     @property
     def deg_pows(self) -> torch.Tensor:
@@ -374,16 +406,16 @@ class Topology:
         return self._deg_pows
 
     def lds_check(self, nmat: int, kpad: int, ncg: int) -> None:
-        if self.global_only:     # plain GEMMs only: forward K=kpad -> nmat*hout columns, data-gradient K=nmat*hout -> kpad
+        ts = self.tiling
+        if ts.global_only:     # plain GEMMs only: forward K=kpad -> nmat*hout columns, data-gradient K=nmat*hout -> kpad
             f = _lib.lib().dss2_gemm_prop_lds_bytes
-            need = max(f(self.nrb, 1, kpad, nmat * ncg, 0, 0), f(self.nrb, 1, nmat * ncg * 32, (kpad + 31) // 32, 0, 0))
+            need = max(f(ts.nrb, 1, kpad, nmat * ncg, 0, 0), f(ts.nrb, 1, nmat * ncg * 32, (kpad + 31) // 32, 0, 0))
             if need > _LDS_LIMIT:
                 raise NotImplementedError(f"global-memory path: a 64-row tile x K={nmat * ncg * 32} needs {need} B of LDS (> 160 KiB)")
             return
-        need = _lib.lib().dss2_gemm_prop_lds_bytes(self.nrb, nmat, kpad, ncg, max(self.max_nnz, self.max_nnzT),
-                                                    min(self.ell, self.ellT))
+        need = _lib.lib().dss2_gemm_prop_lds_bytes(ts.nrb, nmat, kpad, ncg, max(ts.max_nnz, ts.max_nnzT), min(ts.ell, ts.ellT))
         if need > _LDS_LIMIT:
-            raise NotImplementedError(f"tile of {32 * self.nrb} rows x K={kpad} needs {need} B of LDS (> 160 KiB)")
+            raise NotImplementedError(f"tile of {32 * ts.nrb} rows x K={kpad} needs {need} B of LDS (> 160 KiB)")
 
 
 # ------------------------------------------------------------------------------------------

@@ -206,3 +206,80 @@ def test_one_launch_build_of_equal_size_graphs_equals_the_oracle(pkg, grids, B, 
     t_bad = pkg.topology.Topology(bad.to(DEV), N, hint=hint, double=(False if asis else None), flip=not noflip)
     with pytest.raises(ValueError):
         t_bad.stats()
+
+
+def _padded(pkg, grid, G, slack=1):
+    """(padded Topology, unpadded edge_index, N, map of the oracle's ELL entry tiles to the padded slots' ids): every graph of ``grid`` with
+    ``slack`` padding slots behind its edges."""
+    b = pkg.synthetic.make_batch([grid], G, seed=7)
+    ei_u, N = b["edge_index"], b["x"].shape[0]
+    e = ei_u.shape[1] // G
+    ei, _, cnt = pkg.dataset.pad_batch(ei_u, b["edge_attr"], N // G, G, e_max=e + slack)
+    hint = pkg.topology.TopologyHint(directed=True, nodes_per_graph=N // G, max_degree=int(topo_oracle.TopologyOracle(ei_u, N).max_deg),
+                                     max_edges_per_graph=e + slack, edges_per_graph=e + slack)
+    flip = torch.tensor(-2 ** 31, dtype=torch.int32)
+
+    def to_slot(tiles):      # [.., 2] (column, stored-edge id | flip bit, -1: no entry)
+        tiles = tiles.clone()
+        ent = tiles[..., 1]
+        live = ent != -1
+        ids = (ent[live] & 0x7fffffff).long()
+        ent[live] = (ids // e * (e + slack) + ids % e).to(torch.int32) | (ent[live] & flip)
+        return tiles
+    return pkg.topology.Topology(ei.to(DEV), N, hint=hint, edge_count=cnt.to(DEV), nrb=3), ei_u, N, to_slot
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["general", "padded"])
+def test_tilings_are_records_the_topology_owns(pkg, padded):
+    """8 CIGRE graphs (120 rows), primary tiling forced to 96 rows so that the 32- and 64-row ones are both alternates: each is a
+    ``Tiling`` built once, the primary's height gives the primary itself, building alternates leaves the primary and the statistics
+    alone, each tiling keeps its own gain bits, and every tile array is the oracle's at that height.  ``padded``: the closed-form
+    build of a padded batch, whose ELL launches ``rebuild()`` replays."""
+    Tiling = pkg.topology.Tiling
+    if padded:
+        topo, ei, N, to_slot = _padded(pkg, "cigre14", 8)
+    else:
+        b = pkg.synthetic.make_batch(["cigre14"], 8, seed=7)
+        ei, N, to_slot = b["edge_index"], b["x"].shape[0], (lambda ent: ent)
+        topo = pkg.topology.Topology(ei.to(DEV), N, nrb=3)
+    assert N == 120
+    primary = topo.tiling
+    assert isinstance(primary, Tiling) and primary.nrb == topo.nrb == 3 and topo.tiles_for(3) is primary and topo.tiling is primary
+    fields = [f for f in Tiling.__slots__ if f not in ("gain_bits", "gate_words")]
+    assert len(fields) == 15 and all(getattr(topo, f) is getattr(primary, f) for f in fields)      # the names stay readable on the Topology
+    stats = dict(topo.stats())
+    before = {f: (v.clone() if torch.is_tensor(v) else v) for f in fields for v in [getattr(primary, f)]}
+    alts = {h: topo.tiles_for(h) for h in (1, 2)}
+    for h, alt in alts.items():
+        assert isinstance(alt, Tiling) and alt is not primary and alt.nrb == h and topo.tiles_for(h) is alt
+    if padded:
+        assert len(topo._ell_jobs) == 3
+        topo.rebuild()      # (replays the three ELL launches, in build order, into the same arrays)
+        assert len(topo._ell_jobs) == 3
+    torch.cuda.synchronize()
+    assert topo.tiling is primary and topo.stats() == stats and topo._read_stats(topo._meta) == stats
+    for f in fields:
+        v = getattr(primary, f)
+        assert torch.equal(v, before[f]) if torch.is_tensor(v) else v == before[f], f
+    # a height no graph fits: two 70-bus graphs have no 32-row tiling (and asking adds no ELL launch)
+    if padded:
+        big = _padded(pkg, "ober_sub", 2)[0]
+    else:
+        bb = pkg.synthetic.make_batch(["ober_sub"], 2, seed=7)
+        big = pkg.topology.Topology(bb["edge_index"].to(DEV), bb["x"].shape[0], nrb=3)
+    assert big.tiling.nrb == 3 and big.tiles_for(1) is None and big.tiles_for(1) is None and len(big._ell_jobs) == int(padded)
+    # the gain bits of the f16x3 weight gradient are each tile set's own, keyed by nmat
+    hinted = topo.hint is not None
+    pkg.ops._wgrad_mode(primary, 3, 1, hinted)
+    assert list(primary.gain_bits) == [3] and alts[1].gain_bits == {} and alts[2].gain_bits == {}
+    pkg.ops._wgrad_mode(alts[1], 2, 1, hinted)
+    assert list(alts[1].gain_bits) == [2] and list(primary.gain_bits) == [3] and alts[2].gain_bits == {}
+    assert pkg.ops._wgrad_tiles(topo, 3, 128, 128, 1) is primary      # (the 32-row form is the 64-row primaries' alone)
+    # every tiling against the oracle at its height
+    for h, ts in [(3, primary)] + sorted(alts.items()):
+        ref = topo_oracle.TopologyOracle(ei, N, nrb=h)
+        assert (ts.global_only, ts.nrb, ts.ntiles, ts.ell, ts.ellT, ts.max_segment) == (False, ref.nrb, ref.ntiles, ref.ell, ref.ellT, ref.max_segment)
+        assert abs(ts.utilisation - ref.utilisation) < 1e-12
+        for f in TILE_FIELDS:
+            want = getattr(ref, f)
+            _same(getattr(ts, f), to_slot(want) if f.endswith("ent_tiles") else want, f"{f} at nrb {h}")
