@@ -196,7 +196,8 @@ class GatConv(C.Structure):
     _fields_ = [("att", C.c_void_p), ("bias", C.c_void_p), ("Wl", C.c_void_p), ("bl", C.c_void_p), ("Wr", C.c_void_p),
                 ("br", C.c_void_p), ("We", C.c_void_p), ("h", C.c_void_p), ("ldh", C.c_int64), ("y", C.c_void_p),
                 ("m", C.c_void_p), ("s", C.c_void_p), ("dxl", C.c_void_p), ("dxr", C.c_void_p), ("dedge", C.c_void_p),
-                ("dself", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32), ("slab_off", C.c_int32), ("pad_", C.c_int32)]
+                ("dself", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32), ("slab_off", C.c_int32), ("heads", C.c_int32),
+                ("concat", C.c_int32), ("pad_", C.c_int32)]
 
 
 class GatArgs(C.Structure):

@@ -14,8 +14,17 @@ layer l - 1), one batched weight-gradient launch and one slab reduction.  Every 
 records into launch plans and hipGraphs.
 
 The semantics are PyG 2.3-2.6's ``GATv2Conv`` / ``softmax`` / ``add_self_loops`` / ``Sequential`` (torch_geometric is not a
-dependency; they are pinned by tests/golden/gat_known_answers.json and the fp64 restatement tests/gat_oracle.py).  Not
-provided (ValueError): heads > 1, attention dropout > 0, fill_value other than 'mean', bipartite (tuple) inputs,
+dependency; they are pinned by tests/golden/gat_known_answers.json and the fp64 restatements tests/gat_oracle.py and
+tests/gat_heads_oracle.py).
+
+Heads.  ``GATv2Conv(heads=H)`` with ``concat=True`` (output ``[N, H * C]``) or ``concat=False`` (the mean over the heads,
+``[N, C]``, the bias added after it).  A lane of the kernels' lane group is (head h, channel c) at ``h * Cp + c`` with ``Cp`` the
+per-head channels ``C`` rounded up to a power of two, so the supported range is ``H * Cp <= 32`` (and ``in_channels <= 32``): 1 to
+4 heads at the driver's 8 channels.  ``GAT_DSSE(heads > 1)`` with convs needs ``concat=False``: every conv maps ``channels ->
+channels`` and the first Linear takes ``dim_hidden = channels`` columns, so a concatenated output of ``heads * channels`` columns
+fits neither (the reference fails with a shape error in ``forward``); it is refused at construction with a ``ValueError``.
+
+Not provided (ValueError): ``heads * Cp > 32``, attention dropout > 0, fill_value other than 'mean', bipartite (tuple) inputs,
 return_attention_weights.  No gradient with respect to edge_attr; no CPU path.
 """
 from __future__ import annotations
@@ -45,11 +54,20 @@ def _fan_in_uniform(t: torch.Tensor, fan_in: int) -> None:
 _check_width = functools.partial(lanegroup.check_width, "GAT")
 
 
+def lane_channels(out_channels: int, heads: int) -> int:
+    """The lanes one conv's output side takes in the lane group: C with one head, H * Cp (Cp = C rounded up to a power of two)
+    with several."""
+    if heads == 1:
+        return out_channels
+    return heads * (1 << (out_channels - 1).bit_length())
+
+
 class GATv2Conv(nn.Module):
-    """PyG ``GATv2Conv`` with ``heads = 1`` on the HIP kernels.  ``state_dict`` keys: ``att [1, 1, C]``, ``bias [C]``,
-    ``lin_l.{weight, bias}``, ``lin_r.{weight, bias}`` (the same module as lin_l with share_weights), ``lin_edge.weight``
-    (with edge_dim).  Edges are used as given (not doubled); with add_self_loops the input's self loops are dropped and one per
-    node is added with the mean of its incoming edges' attributes (0 without any)."""
+    """PyG ``GATv2Conv`` on the HIP kernels.  ``state_dict`` keys, with H heads of C channels: ``att [1, H, C]``, ``bias [H * C]``
+    (``[C]`` with ``concat=False``), ``lin_l.{weight [H * C, in], bias}``, ``lin_r.{weight, bias}`` (the same module as lin_l with
+    share_weights), ``lin_edge.weight [H * C, edge_dim]`` (with edge_dim); rows ``h * C .. h * C + C - 1`` belong to head h.  Edges
+    are used as given (not doubled); with add_self_loops the input's self loops are dropped and one per node is added with the
+    mean of its incoming edges' attributes (0 without any)."""
 
     def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
                  dropout: float = 0.0, add_self_loops: bool = True, edge_dim: Optional[int] = None, fill_value="mean",
@@ -57,8 +75,8 @@ class GATv2Conv(nn.Module):
         super().__init__()
         if isinstance(in_channels, (tuple, list)):
             raise ValueError("GATv2Conv: bipartite (tuple) in_channels are not supported")
-        if heads != 1:
-            raise ValueError(f"GATv2Conv: heads = {heads}; only heads = 1 is supported")
+        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
+            raise ValueError(f"GATv2Conv: heads = {heads!r}; a positive integer")
         if dropout > 0:
             raise ValueError(f"GATv2Conv: attention dropout = {dropout}; only dropout = 0 is supported")
         if not (isinstance(fill_value, str) and fill_value == "mean"):
@@ -67,12 +85,16 @@ class GATv2Conv(nn.Module):
         _check_width("out_channels", out_channels, MAX_CHANNELS)
         if edge_dim is not None:
             _check_width("edge_dim", edge_dim, MAX_EDGE_DIM)
+        if lane_channels(out_channels, heads) > MAX_CHANNELS:
+            raise ValueError(f"GATv2Conv: heads = {heads} of out_channels = {out_channels} take {lane_channels(out_channels, heads)} "
+                             f"lanes (heads * out_channels rounded up to a power of two); the GAT kernels have {MAX_CHANNELS}")
+        concat = bool(concat)
         self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
         self.negative_slope, self.dropout, self.add_self_loops = float(negative_slope), float(dropout), bool(add_self_loops)
         self.edge_dim, self.fill_value, self.share_weights = edge_dim, fill_value, bool(share_weights)
         self.att = nn.Parameter(torch.empty(1, heads, out_channels))
         if bias:
-            self.bias = nn.Parameter(torch.empty(heads * out_channels))
+            self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
         else:
             self.register_parameter("bias", None)
         self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
@@ -92,6 +114,11 @@ class GATv2Conv(nn.Module):
         if self.bias is not None:
             with torch.no_grad():
                 self.bias.zero_()
+
+    @property
+    def out_columns(self) -> int:
+        """Columns of the output: H * C concatenated, C as the head mean."""
+        return self.heads * self.out_channels if self.concat else self.out_channels
 
     def _slots(self) -> List[Optional[torch.Tensor]]:
         """The 7 kernel slots (att, bias, W_l, b_l, W_r, b_r, W_e) in the slab's column order."""
@@ -134,6 +161,11 @@ class GAT_DSSE(nn.Module):
             raise ValueError("invalid model type")
         if num_layers < 1:
             raise ValueError(f"num_layers = {num_layers}: at least 1 (the two Linears)")
+        if isinstance(heads, int) and heads > 1 and concat and num_layers > 1:
+            # (every conv is channels -> channels and the first Linear takes dim_hidden = channels columns: the reference's
+            # forward fails on the heads * channels columns of a concatenated output)
+            raise ValueError(f"GAT_DSSE: heads = {heads} with concat=True gives {heads} * {dim_feat} columns, which fit neither "
+                             f"the next conv nor Linear(dim_hidden, dim_dense); pass concat=False (the head mean)")
         _check_width("dim_feat", dim_feat, MAX_CHANNELS)
         _check_width("dim_dense", dim_dense, MAX_DENSE)
         _check_width("dim_out", dim_out, MAX_DENSE)
@@ -161,11 +193,19 @@ class _Spec(lanegroup.Spec):
         self.ed = (c0.edge_dim or 0) if c0 is not None else 0
         self.loops = int(c0.add_self_loops) if c0 is not None else 1
         self.slope = float(c0.negative_slope) if c0 is not None else 0.2
+        self.heads = c0.heads if c0 is not None else 1
+        self.concat = c0.concat if c0 is not None else True
         for cv in convs:
             if (cv.edge_dim or 0) != self.ed or int(cv.add_self_loops) != self.loops or float(cv.negative_slope) != self.slope:
                 raise ValueError("GAT stack: every conv must share edge_dim, add_self_loops and negative_slope")
-        widths = [w for cv in convs for w in (cv.in_channels, cv.out_channels)]
-        cols = [4 * cv.out_channels + 2 * cv.out_channels * cv.in_channels + cv.out_channels * self.ed for cv in convs]
+            if cv.heads != self.heads or cv.concat != self.concat:
+                raise ValueError("GAT stack: every conv must share heads and concat")
+        if head and convs and self.heads > 1 and self.concat:
+            raise ValueError("GAT stack: the head Linears after concatenated heads are not supported; pass concat=False")
+        # the lane group covers a conv's input channels and the lanes of its heads; slab columns in parameter order:
+        # att[w], bias[out columns], lin_l.weight[w][cin], lin_l.bias[w], lin_r.weight[w][cin], lin_r.bias[w], lin_edge.weight[w][ed]
+        widths = [w for cv in convs for w in (cv.in_channels, lane_channels(cv.out_channels, cv.heads))]
+        cols = [3 * w + cv.out_columns + 2 * w * cv.in_channels + w * self.ed for cv in convs for w in (cv.heads * cv.out_channels,)]
         super().__init__("GAT", convs, head, nonlin, n_nodes, widths, cols)
 
 
@@ -217,7 +257,7 @@ def _conv(d, cv, ps7, h, ldh, st, off):
     for k in ("dxl", "dxr", "dedge", "dself"):
         if k in st:
             setattr(d, k, st[k].data_ptr())
-    d.cin, d.cout, d.slab_off = cv.in_channels, cv.out_channels, off
+    d.cin, d.cout, d.slab_off, d.heads, d.concat = cv.in_channels, cv.out_channels, off, cv.heads, int(cv.concat)
 
 
 class _GATFn(torch.autograd.Function):
@@ -229,8 +269,8 @@ class _GATFn(torch.autograd.Function):
         if ea is not None:
             ea, ldea = _rows(ea)
         convs, n = spec.convs, len(spec.convs)
-        states, hs = lanegroup.state_chain(x, ldx, [cv.out_channels for cv in convs],
-                                           lambda l: {"ms": torch.empty(2, N, dtype=_F32, device=dev)})
+        states, hs = lanegroup.state_chain(x, ldx, [cv.out_columns for cv in convs],
+                                           lambda l: {"ms": torch.empty(2, N * convs[l].heads, dtype=_F32, device=dev)})
 
         def conv_into(d, l):
             _conv(d, convs[l], ps[7 * l:7 * l + 7], hs[l][0], hs[l][1], states[l], spec.offs[l])
@@ -255,12 +295,12 @@ class _GATFn(torch.autograd.Function):
         n = len(convs)
         slab = torch.empty(spec.n_slabs, spec.total, dtype=_F32, device=dev)
         flat = torch.empty(spec.total, dtype=_F32, device=dev)
-        cmax = max([cv.out_channels for cv in convs] or [1])
+        cmax = max([cv.heads * cv.out_channels for cv in convs] or [1])      # d x_l, d x_r and the per-edge terms: every head's row
         pp = [(torch.empty(E, cmax, dtype=_F32, device=dev), torch.empty(N, cmax, dtype=_F32, device=dev)) for _ in range(2 if n > 1 else 1)]
         for l, cv in enumerate(convs):
             st = states[l]
-            st["dxl"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
-            st["dxr"] = torch.empty(N, cv.out_channels, dtype=_F32, device=dev)
+            st["dxl"] = torch.empty(N, cv.heads * cv.out_channels, dtype=_F32, device=dev)
+            st["dxr"] = torch.empty(N, cv.heads * cv.out_channels, dtype=_F32, device=dev)
             st["dedge"], st["dself"] = pp[l % len(pp)]
         dx = torch.empty(N, x.size(1), dtype=_F32, device=dev) if ctx.needs_input_grad[0] else None
 
@@ -274,18 +314,18 @@ class _GATFn(torch.autograd.Function):
         # outer-product weight gradients of every layer, then ONE fixed-order reduction of the slab
         jobs = []
         for l, cv in enumerate(convs):
-            co, ci, off = cv.out_channels, cv.in_channels, spec.offs[l]
+            w, ci, off = cv.heads * cv.out_channels, cv.in_channels, spec.offs[l] + cv.out_columns
             h, ldh = hs[l]
-            jobs.append((states[l]["dxl"], co, h, ldh, co, ci, off + 2 * co))
-            jobs.append((states[l]["dxr"], co, h, ldh, co, ci, off + 3 * co + co * ci))
+            jobs.append((states[l]["dxl"], w, h, ldh, w, ci, off + w))
+            jobs.append((states[l]["dxr"], w, h, ldh, w, ci, off + 2 * w + w * ci))
         if head:
             jobs += lanegroup.head_wgrad_jobs(spec, states, x, ldx, hst, gout, ldgo)
         lanegroup.wgrad(jobs, slab, spec, N, dev)
         lanegroup.reduce_slabs([(slab, flat, spec.total, spec.total, spec.n_slabs)], dev)
         grads = []
         for l, cv in enumerate(convs):
-            co, ci, ed, off = cv.out_channels, cv.in_channels, spec.ed, spec.offs[l]
-            sizes = [co, co, co * ci, co, co * ci, co, co * ed]
+            w, ci, ed, off = cv.heads * cv.out_channels, cv.in_channels, spec.ed, spec.offs[l]
+            sizes = [w, cv.out_columns, w * ci, w, w * ci, w, w * ed]
             parts, o = [], off
             for sz in sizes:
                 parts.append(flat[o:o + sz])

@@ -34,9 +34,9 @@ def build_model(name: str, hp: Dict, gnn_model: str = "gcn2") -> torch.nn.Module
     if name == "gnn_dsse":     # dss2_run.py:86 with the third model family; cached=False so a short last batch works
         return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], num_layers=hp["gnn_layers"],
                    K=hp["K"], model=gnn_model, cached=False)
-    if name == "GAT_DSSE":     # dss2_run.py:86
+    if name == "GAT_DSSE":     # dss2_run.py:86; several heads as their mean (concat=False): the only multi-head GAT_DSSE that runs
         return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], heads=hp["heads"],
-                   num_layers=hp["gnn_layers"], edge_dim=hp["dim_lines"])
+                   num_layers=hp["gnn_layers"], edge_dim=hp["dim_lines"], concat=(hp["heads"] == 1))
     if name == "GINE_DSSE":    # dss2_run.py:86 with the GIN model (no heads argument)
         return cls(dim_feat=hp["dim_nodes"], dim_dense=hp["dim_hid"], dim_out=hp["dim_out"], num_layers=hp["gnn_layers"],
                    edge_dim=hp["dim_lines"])
@@ -320,8 +320,11 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=600)
     ap.add_argument("--lr", type=float, default=3e-3)
+    hyper_help = {"heads": "GAT_DSSE: attention heads per conv (heads * dim_nodes rounded up to a power of two <= 32: 1 to 4 at 8 "
+                           "channels).  Above 1 the model is built with concat=False, the mean over the heads: the only multi-head "
+                           "GAT_DSSE the reference can train (its concatenated output fits neither the next conv nor the Linear)"}
     for k, v in HYPER.items():
-        ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
+        ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v, help=hyper_help.get(k))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default="")
     ap.add_argument("--data-folder", default="", help="folder with the reference's pickles (nodes, edges, labels, noise_param)")

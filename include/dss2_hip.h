@@ -786,15 +786,21 @@ typedef struct dss2_lanegroup_wgrad_args { /* node chunk s of ceil(N / n_slabs) 
 } dss2_lanegroup_wgrad_args;
 int dss2_lanegroup_wgrad(const dss2_lanegroup_wgrad_args* args_host, void* stream);
 
-/* ---- GATv2 (PyG GATv2Conv, heads = 1) and the GAT_DSSE model (reference networks.py:113-156), csrc/dss2_gat.hip ------------ *
+/* ---- GATv2 (PyG GATv2Conv, heads >= 1, concatenated or averaged) and the GAT_DSSE model (reference networks.py:113-156),      *
+ * csrc/dss2_gat.hip -------------------------------------------------------------------------------------------------------------- *
  * Graph: the Topology of the edge list AS GIVEN (no doubling): CSR by target (rowptr / col = source / ent = stored edge id) and by  *
  * source (rowptrT / colT = target / entT).  add_self_loops != 0: entries with source == target are skipped and one self loop per   *
  * node is added whose edge term is the mean over the remaining incoming edges (fill_value 'mean'; 0 without any).  Lane group of   *
- * `group` (8 / 16 / 32) lanes per node: every channel count <= group, edge_dim <= 16, head dense / out widths <= 32.  The grid is   *
- * n_slabs workgroups; every launch that produces weight-gradient partials writes its columns of ALL n_slabs rows of `slab`       *
- * ([n_slabs][slab_len]); one dss2_reduce_slabs(_multi) over the whole slab gives the flat gradient.  Slab columns of a conv at    *
- * slab_off: att[cout], bias[cout], lin_l.weight[cout][cin], lin_l.bias[cout], lin_r.weight[cout][cin], lin_r.bias[cout],         *
- * lin_edge.weight[cout][ed] (its parameter order); of the head: W1[dense][c], b1[dense], W2[nout][dense], b2[nout].              */
+ * `group` (8 / 16 / 32) lanes per node: cin <= group, edge_dim <= 16, head dense / out widths <= 32; with H = heads (0 means 1)   *
+ * and cout the channels of ONE head, H == 1 needs cout <= group, H > 1 needs H * Cp <= group, Cp = cout rounded up to a power of   *
+ * two (a lane is head h, channel c at h * Cp + c).  Rows h * cout .. h * cout + cout - 1 of lin_l / lin_r / lin_edge / att belong  *
+ * to head h; softmax per head.  concat != 0 (or H == 1): output [N][H * cout], bias[H * cout]; concat == 0: the mean over the     *
+ * heads, output [N][cout], bias[cout] added after the mean.  The head Linears read a mean (or one head), not a concatenation.     *
+ * The grid is n_slabs workgroups; every launch that produces weight-gradient partials writes its columns of ALL n_slabs rows of    *
+ * `slab` ([n_slabs][slab_len]); one dss2_reduce_slabs(_multi) over the whole slab gives the flat gradient.  Slab columns of a     *
+ * conv at slab_off, with w = H * cout and oc the output's columns: att[w], bias[oc], lin_l.weight[w][cin], lin_l.bias[w],          *
+ * lin_r.weight[w][cin], lin_r.bias[w], lin_edge.weight[w][ed] (its parameter order); of the head: W1[dense][c], b1[dense],       *
+ * W2[nout][dense], b2[nout].                                                                                                      */
 typedef struct dss2_gat_graph {
   const int32_t* rowptr; const int32_t* col; const int32_t* ent;
   const int32_t* rowptrT; const int32_t* colT; const int32_t* entT;
@@ -807,10 +813,12 @@ typedef struct dss2_gat_graph {
 typedef struct dss2_gat_conv {
   const float* att; const float* bias; const float* Wl; const float* bl; const float* Wr; const float* br; const float* We;  /* bias, bl, br, We may be NULL */
   const float* h; int64_t ldh;             /* layer input [N][cin] */
-  float* y; float* m; float* s;            /* forward: output after the nonlinearity [N][cout]; per-target softmax max / sum [N] */
-  float* dxl; float* dxr;                  /* backward: d x_l, d x_r [N][cout] (kept for dss2_lanegroup_wgrad) */
-  float* dedge; float* dself;              /* backward: per-edge [E][cout] / self-loop [N][cout] d x_l contributions */
-  int32_t cin; int32_t cout; int32_t slab_off; int32_t pad_;
+  float* y; float* m; float* s;            /* forward: output after the nonlinearity [N][oc]; per-target, per-head softmax max / sum [N][H] */
+  float* dxl; float* dxr;                  /* backward: d x_l, d x_r [N][H * cout] (kept for dss2_lanegroup_wgrad) */
+  float* dedge; float* dself;              /* backward: per-edge [E][H * cout] / self-loop [N][H * cout] d x_l contributions */
+  int32_t cin; int32_t cout; int32_t slab_off;   /* cout: the channels of one head */
+  int32_t heads;                           /* H; 0 means 1 (a zero-initialised struct of an older caller) */
+  int32_t concat; int32_t pad_;            /* with H > 1: != 0 concatenates the heads, 0 takes their mean; ignored with one head */
 } dss2_gat_conv;
 typedef struct dss2_gat_args {
   dss2_gat_graph g;

@@ -13,6 +13,8 @@ recorded training step of the EpochTrainer.  GINE lines also carry the algorithm
 and the optimizer are not included).  One JSON line per model and configuration.
 
     python tools/ginebench.py [--configs cigre14:64,cigre14:4096,ober_sub:1024] [--steps 50] [--warmup 10] [--models GINE_DSSE,GAT_DSSE]
+
+``GAT_DSSE:H`` in --models is the driver's GAT model with H attention heads (their mean, as runner.build_model builds it).
 """
 import argparse
 import ctypes as C
@@ -63,6 +65,8 @@ def count_launches(fn):
 def describe(name):
     """The constructor call runner.build_model makes for a --models entry."""
     base, _, kind = name.partition(":")
+    if base == "GAT_DSSE" and kind:          # GAT_DSSE:4 -- four heads, averaged (runner.build_model passes concat=False)
+        return f"GAT_DSSE(8, 32, 2, 8, 6, heads={int(kind)}, concat={int(kind) == 1})"
     if base in ("GINE_DSSE", "GAT_DSSE"):
         return f"{base}(8, 32, 2, 8, 6)"
     if base == "gnn_dsse":
@@ -72,8 +76,11 @@ def describe(name):
 
 def model_and_opt(name, capturable, seed=0):
     torch.manual_seed(seed)
-    base, _, kind = name.partition(":")       # gnn_dsse:gcn2 / gnn_dsse:fagcn / gnn_dsse:tagcn
-    m = pkg.runner.build_model(base, pkg.runner.HYPER, gnn_model=kind or "gcn2").to(DEV)
+    base, _, kind = name.partition(":")       # gnn_dsse:gcn2 / gnn_dsse:fagcn / gnn_dsse:tagcn; GAT_DSSE:<heads>
+    if base == "GAT_DSSE":
+        m = pkg.runner.build_model(base, {**pkg.runner.HYPER, "heads": int(kind or 1)}).to(DEV)
+    else:
+        m = pkg.runner.build_model(base, pkg.runner.HYPER, gnn_model=kind or "gcn2").to(DEV)
     return m, pkg.FusedAdamax(m.parameters(), lr=3e-3, capturable=capturable)
 
 
