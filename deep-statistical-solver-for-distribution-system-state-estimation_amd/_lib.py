@@ -64,6 +64,18 @@ class WgradArgs(C.Structure):
                 ("narrow", C.c_int32), ("mfma_bf16", C.c_int32)]
 
 
+class WgradPlan(C.Structure):
+    """dss2_wgrad_plan_t: the kernel a weight-gradient launch runs and its geometry (include/dss2_hip.h)."""
+    _fields_ = [("kernel", C.c_int32), ("reason", C.c_int32), ("nb", C.c_int32), ("w8", C.c_int32),
+                ("grid_y", C.c_int32), ("z_groups", C.c_int32), ("y_slices", C.c_int32), ("f16x3_covers", C.c_int32),
+                ("launch_lds", C.c_uint64), ("sizing_lds", C.c_uint64)]
+
+
+# dss2_wgrad_kernel
+(WGRAD_NONE, WGRAD_NARROW_STREAM, WGRAD_FP32_NARROW, WGRAD_FP32, WGRAD_BF16_64, WGRAD_BF16_32, WGRAD_BF16_TALL,
+ WGRAD_F16_32, WGRAD_F16_TALL, WGRAD_F16_TALL_PAIR) = range(10)
+
+
 class CsrBuildArgs(C.Structure):
     _fields_ = [("edge_index", C.c_void_p), ("n_edges", C.c_int64), ("n_nodes", C.c_int64), ("doubled", C.c_int32), ("no_flip", C.c_int32),
                 ("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("perm", C.c_void_p), ("w", C.c_void_p),
@@ -310,6 +322,7 @@ _SIGNATURES = {
     "dss2_gemm_prop_chain_gate_words": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dss2_gemm_prop16_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dss2_wgrad": (C.c_int, [C.POINTER(WgradArgs), C.c_void_p]),
+    "dss2_wgrad_plan": (C.c_int, [C.POINTER(WgradArgs), C.c_int, C.POINTER(WgradPlan)]),
     "dss2_wgrad_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "dss2_reduce_slabs_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dss2_reduce_slabs": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -686,18 +686,19 @@ __global__ void __launch_bounds__(256) wgrad_narrow_stream_kernel(const dss2_wgr
 }
 
 static bool wgrad_narrow_stream_ok(const dss2_wgrad_args& a) {
-  static const int enabled = [] { const char* e = getenv("DSS2_NARROW_STREAM"); return e ? atoi(e) : 1; }();
   const int tpr = a.hin >> 2;
-  return enabled && a.narrow && a.nmat * a.hout <= WN_MAXO && (a.hin & 3) == 0 && tpr > 0 && tpr <= 256 && (256 % tpr) == 0 &&
+  return a.narrow && a.nmat * a.hout <= WN_MAXO && (a.hin & 3) == 0 && tpr > 0 && tpr <= 256 && (256 % tpr) == 0 &&
          (a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && !a.rowscale && (a.nrb <= 4 || a.nrb == 6) &&
          (a.nmat == 1 || (a.ell_width > 0 && a.ell_tiles));
 }
 
+static size_t wgrad_narrow_stream_lds(int nrb, int nmat, int ell_width) {      // (red: nrg * 8 * hin floats = 256 * 4 * 8)
+  return (size_t)nrb * 32 * WN_MAXO * 4 + (nmat > 1 ? (size_t)ell_width * nrb * 32 * 8 : 0) + (size_t)256 * 4 * WN_MAXO * 4;
+}
+
 template <int NRB>
-static int launch_wgrad_narrow_stream(const dss2_wgrad_args& a, hipStream_t stream) {
-  const size_t lds = (size_t)NRB * 32 * WN_MAXO * 4 + (a.nmat > 1 ? (size_t)a.ell_width * NRB * 32 * 8 : 0) +
-                     (size_t)256 * 4 * WN_MAXO * 4;     // red: nrg * 8 * hin floats = 256 * 4 * 8
-  hipLaunchKernelGGL(wgrad_narrow_stream_kernel<NRB>, dim3(a.n_split), dim3(256), lds, stream, a);
+static int launch_wgrad_narrow_stream(const dss2_wgrad_args& a, hipStream_t stream, const dss2_wgrad_plan_t& p) {
+  hipLaunchKernelGGL(wgrad_narrow_stream_kernel<NRB>, dim3(a.n_split), dim3(256), p.launch_lds, stream, a);
   return check_launch("wgrad_narrow_stream");
 }
 
@@ -726,9 +727,8 @@ constexpr bool wgrad_spills(int nrb, int nmat, int nb) {
 
 static int pick_nb(int nrb, int nmat, int hout, int max_nnz, int ell_width) {
   const int nob = (hout + 31) / 32;
-  static const int nb_max = [] { const char* e = getenv("DSS2_WGRAD_NB"); return e ? atoi(e) : 4; }();   // tuning knob
   for (int nb = 4; nb >= 1; nb >>= 1) {
-    if (nb > nb_max) continue;
+    if (nb > wgrad_switches().nb_max) continue;   // tuning knob
     if (nb > 1 && nb / 2 >= nob) continue;  // do not over-allocate columns
     if (wgrad_spills(nrb, nmat, nb)) continue;
     if (wgrad_lds(nrb, nmat, nb, max_nnz, ell_width, nmat > 1) <= (size_t)kMaxLdsBytes) return nb;
@@ -743,92 +743,20 @@ static bool wgrad_w8(const dss2_wgrad_args& a, int nb) {
 }
 
 template <int NRB, int NMAT, int NB, bool W8 = false>
-static int launch_wgrad(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch_wgrad(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
   auto kern = wgrad_kernel<NRB, NMAT, NB, W8>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad")) return 1;
-  const int nob = (a.hout + 31) / 32, nib = (a.hin + 31) / 32;
-  const int nobg = (nob + NB - 1) / NB, nibg = (nib + 3) / 4;
-  const size_t lds = wgrad_lds(NRB, NMAT, NB, a.max_nnz, a.ell_width, NMAT > 1 || a.narrow, a.hin, W8);
-  static const int ksplit = [] { const char* e = getenv("DSS2_WGRAD_KSPLIT"); return e ? atoi(e) : 1; }();
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(WgradGeom<NB, W8>::NT), lds, stream, a, nibg, wb, ksplit);
+  const int nibg = ((a.hin + 31) / 32 + 3) / 4;
+  hipLaunchKernelGGL(kern, dim3(a.n_split, p.grid_y, p.z_groups), dim3(WgradGeom<NB, W8>::NT), p.launch_lds, stream, a, nibg, wb, wgrad_switches().ksplit);
   return check_launch("wgrad");
 }
 
-}  // namespace dss2
-
-extern "C" size_t dss2_wgrad_lds_bytes_ex(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width, int mfma_bf16);
-
-extern "C" size_t dss2_wgrad_lds_bytes(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width) {
-  if (nmat > 1 && nmat * hout <= 32) return dss2::wgrad_lds(nrb, 1, 1, max_nnz, ell_width, true, hin);   // narrow mode
-  const int nb = dss2::pick_nb(nrb, nmat, hout, max_nnz, ell_width);
-  return nb ? dss2::wgrad_lds(nrb, nmat, nb, max_nnz, ell_width, nmat > 1, hin) : (size_t)-1;
-}
-
-extern "C" size_t dss2_wgrad_lds_bytes_ex(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width, int mfma_bf16) {
-  if (mfma_bf16) {
-    const size_t b = dss2::wgrad16_lds_bytes(nrb, nmat, hout, hin, ell_width);
-    if (b != 0 && b <= (size_t)dss2::kMaxLdsBytes) return b;
-  }
-  return dss2_wgrad_lds_bytes(nrb, nmat, hout, hin, max_nnz, ell_width);
-}
-
-// Workgroups a launch puts on EACH tile-list slice (grid.y): callers that want one workgroup per CU divide their n_split by
-// it.  The bf16x6 kernel is one workgroup per CU by LDS, so its column groups over grid.y (H > 128; H > 64 for layers with
-// rowscale2) would otherwise run in rounds, each round writing its own slabs.
-extern "C" int dss2_wgrad_y_slices(int nrb, int nmat, int hout, int hin, int ell_width, int mfma_bf16, int has_rowscale2) {
-  if (!mfma_bf16) return 1;
-  const size_t b = dss2::wgrad16_lds_bytes(nrb, nmat, hout, hin, ell_width);
-  if (b == 0 || b > (size_t)dss2::kMaxLdsBytes) return 1;
-  (void)has_rowscale2;
-  return dss2::wgrad16_y_slices(nrb, hout, hin);          // 64-row tiles: a workgroup owns 128 output x 128 input columns; 32-row tiles: 64 x 128
-}
-
-// workgroup groups along grid.z of a batched launch of n_layers layers: one per layer, except where the f16x3 tall-tile kernel walks TWO
-// 32-column layers per workgroup (dss2_wgrad16th.hip, PAIR) -- the host sizes n_split (slabs per layer) with it so that the launch fills the chip
-extern "C" int dss2_wgrad_batched_groups(int nrb, int hout, int hin, int mfma_bf16, int n_layers) {
-  static const int pair_on = [] { const char* e = getenv("DSS2_WGRAD_TALL_PAIR"); return e ? atoi(e) : 1; }();
-  static const int tall_on = [] { const char* e = getenv("DSS2_WGRAD_TALL_F16"); return e ? atoi(e) : 1; }();
-  if (pair_on && tall_on && (mfma_bf16 & 255) == 2 && nrb == 3 && hout == 32 && hin == 32 && n_layers >= 2) return (n_layers + 1) / 2;
-  return n_layers;
-}
-
-static int wgrad_dispatch(const dss2_wgrad_args& a, void* stream, const dss2::WgradBatch& wb) {
-  using namespace dss2;
-  if (a.n_split <= 0 || !a.slab) { set_error("wgrad: n_split/slab missing"); return 2; }
-  if (a.nmat > 1 && (!a.rowptrT || !a.colT || !a.wT)) { set_error("wgrad: nmat > 1 needs the transposed CSR"); return 2; }
-  if (a.ell_width < 0 || a.ell_width > 32) { set_error("wgrad: ell_width %d out of range 0..32", a.ell_width); return 2; }
-  if (a.rowscale2 && a.narrow) { set_error("wgrad: rowscale2 is not supported in narrow mode"); return 2; }
-  if (a.narrow) {
-    if (a.nmat * a.hout > 32) { set_error("wgrad: narrow mode needs nmat*hout <= 32"); return 2; }
-    hipStream_t sn = as_stream(stream);
-    if (wb.n == 0 && wgrad_narrow_stream_ok(a)) {
-      switch (a.nrb) {
-        case 1: return launch_wgrad_narrow_stream<1>(a, sn);
-        case 2: return launch_wgrad_narrow_stream<2>(a, sn);
-        case 3: return launch_wgrad_narrow_stream<3>(a, sn);
-        case 6: return launch_wgrad_narrow_stream<6>(a, sn);
-        default: return launch_wgrad_narrow_stream<4>(a, sn);
-      }
-    }
-    switch (a.nrb) {
-      case 1: return launch_wgrad<1, 1, 1>(a, sn, wb);
-      case 2: return launch_wgrad<2, 1, 1>(a, sn, wb);
-      case 3: return launch_wgrad<3, 1, 1>(a, sn, wb);
-      case 4: return launch_wgrad<4, 1, 1>(a, sn, wb);
-      case 6: return launch_wgrad<6, 1, 1>(a, sn, wb);
-      default: set_error("wgrad(narrow): unsupported nrb=%d", a.nrb); return 2;
-    }
-  }
-  if (wgrad16h_covers(a)) return launch_wgrad16h(a, as_stream(stream), wb);        // f16x3 kernel (dss2_wgrad16h.hip): args.mfma_bf16 & 255 == 2, 32-row tiles
-  if (wgrad16th_covers(a)) return launch_wgrad16th(a, as_stream(stream), wb);      // f16x3 kernel of 96- / 192-row tiles (dss2_wgrad16th.hip)
-  if (wgrad16_covers(a)) return launch_wgrad16(a, as_stream(stream), wb);          // bf16x6 kernel (dss2_wgrad16.hip)
-  const int nb = pick_nb(a.nrb, a.nmat, a.hout, a.max_nnz, a.ell_width);
-  if (!nb) { set_error("wgrad: tile of %d rows does not fit LDS (nmat=%d nnz=%d)", a.nrb * 32, a.nmat, a.max_nnz); return 3; }
-  hipStream_t s = as_stream(stream);
-  if (wgrad_w8(a, nb)) return launch_wgrad<6, 3, 1, true>(a, s, wb);
+// the launcher of wgrad<nrb, nmat, nb>, or null: the instantiations that exist (no nrb = 5, no <6, ., 4>, none that spills)
+using WgradLauncher = int (*)(const dss2_wgrad_args&, hipStream_t, const WgradBatch&, const dss2_wgrad_plan_t&);
+static WgradLauncher wgrad_launcher(int nrb, int nmat, int nb) {
 #define DSS2_CASE(NRB, NMAT, NB) \
-  if constexpr (!wgrad_spills(NRB, NMAT, NB)) { if (a.nrb == NRB && a.nmat == NMAT && nb == NB) return launch_wgrad<NRB, NMAT, NB>(a, s, wb); }
+  if constexpr (!wgrad_spills(NRB, NMAT, NB)) { if (nrb == NRB && nmat == NMAT && nb == NB) return launch_wgrad<NRB, NMAT, NB>; }
 #define DSS2_NMATS(NRB, NB) DSS2_CASE(NRB, 1, NB) DSS2_CASE(NRB, 2, NB) DSS2_CASE(NRB, 3, NB) DSS2_CASE(NRB, 4, NB)
   DSS2_NMATS(1, 1) DSS2_NMATS(1, 2) DSS2_NMATS(1, 4)
   DSS2_NMATS(2, 1) DSS2_NMATS(2, 2) DSS2_NMATS(2, 4)
@@ -837,8 +765,139 @@ static int wgrad_dispatch(const dss2_wgrad_args& a, void* stream, const dss2::Wg
   DSS2_NMATS(6, 1) DSS2_NMATS(6, 2)
 #undef DSS2_NMATS
 #undef DSS2_CASE
-  set_error("wgrad: unsupported (nrb=%d, nmat=%d, nb=%d)", a.nrb, a.nmat, nb);
-  return 2;
+  return nullptr;
+}
+
+const WgradSwitches& wgrad_switches() {
+  static const WgradSwitches sw = [] {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    return WgradSwitches{env("DSS2_WGRAD_TALL_F16", 1), env("DSS2_WGRAD_TALL_PAIR", 1), env("DSS2_WGRAD_TALL16", 1), env("DSS2_WGRAD_TALL_DB", 1),
+                         env("DSS2_WGRAD_NB", 4), env("DSS2_NARROW_STREAM", 1), env("DSS2_WGRAD_KSPLIT", 1)};
+  }();
+  return sw;
+}
+
+// The ONE place a weight-gradient launch gets its kernel and geometry (see dss2_wgrad_plan_t in include/dss2_hip.h).
+dss2_wgrad_plan_t wgrad_select(const dss2_wgrad_args& a, int n_layers) {
+  const WgradSwitches& sw = wgrad_switches();
+  dss2_wgrad_plan_t p = {};
+  p.grid_y = p.y_slices = 1;
+  p.z_groups = n_layers > 1 ? n_layers : 1;
+  const bool shape16 = a.mfma_bf16 && wgrad16_shape(a);
+  const int nb = pick_nb(a.nrb, a.nmat, a.hout, a.max_nnz, a.ell_width);
+  // ---- what the host sizes n_split by: from the shape alone, the bf16x6 kernel's figures wherever its SHAPE conditions hold, else the fp32
+  // kernel's LDS (the narrow form by nmat * hout, whatever args.narrow says) and no column groups.  NOT what the launch below uses wherever
+  // an f16x3 kernel, the eight-wave form, or an operand the 16-bit kernels refuse decides otherwise: every n_split in use was tuned on these
+  // figures, and sizing by the kernel that runs changes summation order and speed -- a separate, measured change.
+  if (shape16) { p.sizing_lds = wgrad16_lds_bytes(a.nrb, a.nmat, a.ell_width); p.y_slices = wgrad16_grid_y(a.nrb, a.hout, a.hin); }
+  else if (a.nmat > 1 && a.nmat * a.hout <= 32) p.sizing_lds = wgrad_lds(a.nrb, 1, 1, a.max_nnz, a.ell_width, true, a.hin);
+  else p.sizing_lds = nb ? wgrad_lds(a.nrb, a.nmat, nb, a.max_nnz, a.ell_width, a.nmat > 1, a.hin) : (size_t)-1;
+  // ---- the kernel of the launch
+  auto fp32 = [&](int kernel, int nmat_passes, int nb_, bool w8) {      // wgrad<nrb, nmat_passes, nb_, w8>
+    p.kernel = kernel; p.nb = nb_; p.w8 = w8;
+    p.launch_lds = wgrad_lds(a.nrb, nmat_passes, nb_, a.max_nnz, a.ell_width, nmat_passes > 1 || a.narrow, a.hin, w8);
+    p.grid_y = (((a.hout + 31) / 32 + nb_ - 1) / nb_) * (((a.hin + 31) / 32 + 3) / 4);
+    return p;
+  };
+  auto none = [&](int reason) { p.reason = reason; p.nb = nb; return p; };
+  if (a.narrow) {
+    if (n_layers > 0 || !sw.narrow_stream || !wgrad_narrow_stream_ok(a)) return wgrad_launcher(a.nrb, 1, 1) ? fp32(DSS2_WGRAD_FP32_NARROW, 1, 1, false) : none(2);
+    p.kernel = DSS2_WGRAD_NARROW_STREAM;      // (no table form: a batch of one takes the kernel above)
+    p.launch_lds = wgrad_narrow_stream_lds(((a.nrb >= 1 && a.nrb <= 3) || a.nrb == 6) ? a.nrb : 4, a.nmat, a.ell_width);
+    return p;
+  }
+  // what every 16-bit kernel asks of the operands (a launch that misses one takes the fp32 kernel; the layers of a batch: wgrad_dispatch)
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const bool operands16 = !a.rowscale && a.ell_tiles && al16(a.G) && al16(a.X) && (a.ldg & 3) == 0 && (a.ldx & 3) == 0 && (!a.rowscale2 || al16(a.rowscale2));
+  const bool h32 = operands16 && wgrad16h_shape(a), tall = operands16 && wgrad16th_shape(a), f16 = (a.mfma_bf16 & 255) == 2;
+  p.f16x3_covers = h32 || tall;
+  if (f16 && h32) {
+    p.kernel = DSS2_WGRAD_F16_32;
+    p.launch_lds = wgrad16h_lds_bytes(a.nmat, !((a.mfma_bf16 >> 16) & 1));
+  } else if (f16 && tall && sw.tall_f16) {
+    const bool pair = sw.tall_pair && wgrad16th_pair_shape(a, n_layers);
+    p.kernel = pair ? DSS2_WGRAD_F16_TALL_PAIR : DSS2_WGRAD_F16_TALL;
+    if (pair) p.z_groups = (n_layers + 1) / 2;
+    p.launch_lds = wgrad16th_lds_bytes(a.nrb, a.nmat, a.ell_width);
+  } else if (operands16 && shape16) {
+    p.kernel = a.nrb == 2 ? DSS2_WGRAD_BF16_64 : (a.nrb == 1 ? DSS2_WGRAD_BF16_32 : DSS2_WGRAD_BF16_TALL);
+    p.launch_lds = p.sizing_lds;
+  } else {
+    if (!nb) return none(3);
+    if (wgrad_w8(a, nb)) return fp32(DSS2_WGRAD_FP32, 3, 1, true);
+    return wgrad_launcher(a.nrb, a.nmat, nb) ? fp32(DSS2_WGRAD_FP32, a.nmat, nb, false) : none(2);
+  }
+  p.grid_y = wgrad16_grid_y(a.nrb, a.hout, a.hin);
+  return p;
+}
+
+}  // namespace dss2
+
+extern "C" int dss2_wgrad_plan(const dss2_wgrad_args* ap, int n_layers, dss2_wgrad_plan_t* out) {
+  if (!ap || !out) { dss2::set_error("dss2_wgrad_plan: null argument"); return 2; }
+  *out = dss2::wgrad_select(*ap, n_layers);
+  return 0;
+}
+
+// the record of a launch known by its shape only: operands aligned, ELL slices present where the tiling has a width (never dereferenced here)
+static dss2_wgrad_plan_t wgrad_shape_plan(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width, int mfma_bf16, int n_layers) {
+  dss2_wgrad_args a = {};
+  a.nrb = nrb; a.nmat = nmat; a.hout = hout; a.hin = hin; a.max_nnz = max_nnz; a.ell_width = ell_width; a.mfma_bf16 = mfma_bf16;
+  a.ell_tiles = ell_width > 0 ? &a : nullptr;
+  return dss2::wgrad_select(a, n_layers);
+}
+extern "C" size_t dss2_wgrad_lds_bytes_ex(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width, int mfma_bf16) {
+  return wgrad_shape_plan(nrb, nmat, hout, hin, max_nnz, ell_width, mfma_bf16, 0).sizing_lds;
+}
+extern "C" size_t dss2_wgrad_lds_bytes(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width) { return dss2_wgrad_lds_bytes_ex(nrb, nmat, hout, hin, max_nnz, ell_width, 0); }
+extern "C" int dss2_wgrad_y_slices(int nrb, int nmat, int hout, int hin, int ell_width, int mfma_bf16, int /* has_rowscale2: never entered the answer */) {
+  return wgrad_shape_plan(nrb, nmat, hout, hin, 0, ell_width, mfma_bf16, 0).y_slices;
+}
+// (its signature names neither K nor the ELL width: asked for a shape the tall f16x3 kernel takes wherever it takes hout and hin)
+extern "C" int dss2_wgrad_batched_groups(int nrb, int hout, int hin, int mfma_bf16, int n_layers) {
+  return n_layers >= 1 ? wgrad_shape_plan(nrb, 2, hout, hin, 0, 1, mfma_bf16, n_layers).z_groups : n_layers;
+}
+
+static int wgrad_dispatch(const dss2_wgrad_args& a, void* stream, const dss2::WgradBatch& wb) {
+  using namespace dss2;
+  if (a.n_split <= 0 || !a.slab) { set_error("wgrad: n_split/slab missing"); return 2; }
+  if (a.nmat > 1 && (!a.rowptrT || !a.colT || !a.wT)) { set_error("wgrad: nmat > 1 needs the transposed CSR"); return 2; }
+  if (a.ell_width < 0 || a.ell_width > 32) { set_error("wgrad: ell_width %d out of range 0..32", a.ell_width); return 2; }
+  if (a.rowscale2 && a.narrow) { set_error("wgrad: rowscale2 is not supported in narrow mode"); return 2; }
+  if (a.narrow && a.nmat * a.hout > 32) { set_error("wgrad: narrow mode needs nmat*hout <= 32"); return 2; }
+  const dss2_wgrad_plan_t p = wgrad_select(a, wb.n);
+  hipStream_t s = as_stream(stream);
+  const bool f16x3_tall = p.kernel == DSS2_WGRAD_F16_TALL || p.kernel == DSS2_WGRAD_F16_TALL_PAIR, f16x3 = f16x3_tall || p.kernel == DSS2_WGRAD_F16_32;
+  if (f16x3 || p.kernel == DSS2_WGRAD_BF16_64 || p.kernel == DSS2_WGRAD_BF16_32 || p.kernel == DSS2_WGRAD_BF16_TALL) {
+    // the 16-bit families: every layer of a batch is read 16 bytes at a time
+    const char* const fam = f16x3_tall ? "f16x3, tall tiles" : (f16x3 ? "f16x3" : "bf16x6");
+    bool rs2 = a.rowscale2 != nullptr;
+    for (int l = 0; l < wb.n; ++l) {
+      if ((reinterpret_cast<uintptr_t>(wb.G[l]) | reinterpret_cast<uintptr_t>(wb.X[l]) | reinterpret_cast<uintptr_t>(wb.rowscale2[l])) & 15) {
+        set_error("wgrad(%s): layer %d has a misaligned operand", fam, l); return 2;
+      }
+      rs2 = rs2 || wb.rowscale2[l] != nullptr;
+    }
+    if (!f16x3) return launch_wgrad16(a, s, wb, p, rs2);
+    return f16x3_tall ? launch_wgrad16th(a, s, wb, p, rs2) : launch_wgrad16h(a, s, wb, p, rs2);
+  }
+  if (p.kernel == DSS2_WGRAD_NARROW_STREAM) {
+    switch (a.nrb) {
+      case 1: return launch_wgrad_narrow_stream<1>(a, s, p);
+      case 2: return launch_wgrad_narrow_stream<2>(a, s, p);
+      case 3: return launch_wgrad_narrow_stream<3>(a, s, p);
+      case 6: return launch_wgrad_narrow_stream<6>(a, s, p);
+      default: return launch_wgrad_narrow_stream<4>(a, s, p);
+    }
+  }
+  if (p.kernel == DSS2_WGRAD_NONE) {
+    if (a.narrow) set_error("wgrad(narrow): unsupported nrb=%d", a.nrb);
+    else if (p.reason == 3) set_error("wgrad: tile of %d rows does not fit LDS (nmat=%d nnz=%d)", a.nrb * 32, a.nmat, a.max_nnz);
+    else set_error("wgrad: unsupported (nrb=%d, nmat=%d, nb=%d)", a.nrb, a.nmat, p.nb);
+    return p.reason;
+  }
+  if (p.w8) return launch_wgrad<6, 3, 1, true>(a, s, wb, p);
+  return wgrad_launcher(a.nrb, a.narrow ? 1 : a.nmat, p.nb)(a, s, wb, p);      // (narrow: the matrices are columns of ONE pass; non-null: wgrad_select asked)
 }
 
 static int dss2_wgrad_launch(const dss2_wgrad_args* ap, void* stream);

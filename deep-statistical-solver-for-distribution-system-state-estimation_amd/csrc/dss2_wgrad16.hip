@@ -803,27 +803,23 @@ __global__ void __launch_bounds__(W16T_NT) wgrad16t_kernel(const dss2_wgrad_args
   }
 }
 
-// two sets of planes (one barrier per chunk instead of two) wherever they fit
-static bool wgrad16t_double(int nrb, int nmat, int ell_width) {
-  static const int on = [] { const char* e = getenv("DSS2_WGRAD_TALL_DB"); return e ? atoi(e) : 1; }();
+// tall tiles: the fp32 image, `sets` sets of planes, the ELL slice
+static size_t wgrad16t_bytes(int nrb, int nmat, int ell_width, int sets) {
   const size_t fimg = (size_t)32 * nrb * W16B_LDZF * 4, planes = (size_t)nmat * 3 * W16B_ZC * 64 + 3 * (size_t)W16B_XW * 64;
-  return on && fimg + 2 * (fimg > planes ? fimg : planes) + (size_t)((ell_width + 3) & ~3) * 32 * nrb * 8 <= (size_t)kMaxLdsBytes;
+  return fimg + sets * (fimg > planes ? fimg : planes) + (size_t)((ell_width + 3) & ~3) * 32 * nrb * 8;
 }
-
+// two sets of planes (one barrier per chunk instead of two) wherever they fit
+static bool wgrad16t_double(int nrb, int nmat, int ell_width) { return wgrad_switches().tall_db && wgrad16t_bytes(nrb, nmat, ell_width, 2) <= (size_t)kMaxLdsBytes; }
 static size_t wgrad16t_lds_bytes(int nrb, int nmat, int ell_width) {
-  const size_t fimg = (size_t)32 * nrb * W16B_LDZF * 4, planes = (size_t)nmat * 3 * W16B_ZC * 64 + 3 * (size_t)W16B_XW * 64;
-  const size_t b = fimg + (wgrad16t_double(nrb, nmat, ell_width) ? 2 : 1) * (fimg > planes ? fimg : planes) + (size_t)((ell_width + 3) & ~3) * 32 * nrb * 8;
-  const size_t red = (size_t)(1 + nmat) * W16T_NT * 16;
+  const size_t b = wgrad16t_bytes(nrb, nmat, ell_width, wgrad16t_double(nrb, nmat, ell_width) ? 2 : 1), red = (size_t)(1 + nmat) * W16T_NT * 16;
   return b > red ? b : red;
 }
 
-
-size_t wgrad16_lds_bytes(int nrb, int nmat, int hout, int hin, int ell_width) {
-  if (nrb < 1 || nrb > 6 || nmat < 2 || nmat > 3 || ell_width < 1 || ell_width > W16_DMAX || hout <= 32 || (hout & 3) || (hin & 3)) return 0;
-  if (nrb >= 3) {      // wgrad16t_kernel: tall tiles, chunks of 32 rows
-    static const int tall = [] { const char* e = getenv("DSS2_WGRAD_TALL16"); return e ? atoi(e) : 1; }();
-    return tall ? wgrad16t_lds_bytes(nrb, nmat, ell_width) : 0;
-  }
+static_assert(W16B_ZC == 64 && W16B_XW == 128 && 2 * W16_ZC == 128 && W16_XW == 128,      // (the 64-row kernel: NP = 2 passes of W16_ZC)
+              "wgrad16_grid_y and launch_wgrad16_kernel (dss2_wgrad_batch.hpp) count 64 output x 128 input columns per workgroup");
+// dynamic LDS of the launch, by tile height
+size_t wgrad16_lds_bytes(int nrb, int nmat, int ell_width) {
+  if (nrb >= 3) return wgrad16t_lds_bytes(nrb, nmat, ell_width);      // wgrad16t_kernel: tall tiles, chunks of 32 rows
   if (nrb == 1) {      // wgrad16b_kernel: two workgroups per CU
     const size_t b1 = 2 * (size_t)W16B_TM * W16B_LDZF * 4 + (size_t)nmat * 3 * W16B_ZC * 64 + 3 * (size_t)W16B_XW * 64 + (size_t)((ell_width + 3) & ~3) * W16B_TM * 8;
     const size_t red1 = (size_t)(1 + nmat) * W16B_NT * 16;
@@ -834,73 +830,43 @@ size_t wgrad16_lds_bytes(int nrb, int nmat, int hout, int hin, int ell_width) {
   return b > red ? b : red;
 }
 
-bool wgrad16_covers(const dss2_wgrad_args& a) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return a.mfma_bf16 && !a.narrow && !a.rowscale && a.ell_tiles && al16(a.G) && al16(a.X) && (a.ldg & 3) == 0 && (a.ldx & 3) == 0 &&
-         (!a.rowscale2 || al16(a.rowscale2)) && wgrad16_lds_bytes(a.nrb, a.nmat, a.hout, a.hin, a.ell_width) != 0 &&
-         wgrad16_lds_bytes(a.nrb, a.nmat, a.hout, a.hin, a.ell_width) <= (size_t)kMaxLdsBytes;
-}
-
-int wgrad16_y_slices(int nrb, int hout, int hin) {
-  return nrb != 2 ? ((hout + W16B_ZC - 1) / W16B_ZC) * ((hin + W16B_XW - 1) / W16B_XW) : ((hout + 127) / 128) * ((hin + 127) / 128);
+// K <= 2 on ELL slices of at most 8 entries, more than one 32-column output block; tall tiles unless DSS2_WGRAD_TALL16=0
+bool wgrad16_shape(const dss2_wgrad_args& a) {
+  return a.nrb >= 1 && a.nrb <= 6 && (a.nmat == 2 || a.nmat == 3) && a.ell_width >= 1 && a.ell_width <= W16_DMAX && a.hout > 32 && (a.hout & 3) == 0 &&
+         (a.hin & 3) == 0 && (a.nrb < 3 || wgrad_switches().tall16) && wgrad16_lds_bytes(a.nrb, a.nmat, a.ell_width) <= (size_t)kMaxLdsBytes;
 }
 
 template <int NMAT, bool RS2>
-static int launch16b(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch16b(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16b_kernel<NMAT, RS2>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(bf16x6, 32 rows)")) return 1;
-  const int nobg = (a.hout + W16B_ZC - 1) / W16B_ZC, nibg = (a.hin + W16B_XW - 1) / W16B_XW;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16B_NT),
-                     wgrad16_lds_bytes(a.nrb, a.nmat, a.hout, a.hin, a.ell_width), stream, a, nibg, wb);
-  return check_launch("wgrad(bf16x6, 32 rows)");
+  return launch_wgrad16_kernel(wgrad16b_kernel<NMAT, RS2>, lds_done, "wgrad(bf16x6, 32 rows)", W16B_NT, a, stream, wb, p);
 }
 
 template <int NRB, int NMAT, bool RS2, bool DB>
-static int launch16t(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch16t(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16t_kernel<NRB, NMAT, RS2, DB>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(bf16x6, tall tiles)")) return 1;
-  const int nobg = (a.hout + W16B_ZC - 1) / W16B_ZC, nibg = (a.hin + W16B_XW - 1) / W16B_XW;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16T_NT),
-                     wgrad16_lds_bytes(a.nrb, a.nmat, a.hout, a.hin, a.ell_width), stream, a, nibg, wb);
-  return check_launch("wgrad(bf16x6, tall tiles)");
+  return launch_wgrad16_kernel(wgrad16t_kernel<NRB, NMAT, RS2, DB>, lds_done, "wgrad(bf16x6, tall tiles)", W16T_NT, a, stream, wb, p);
 }
 
 template <int NMAT, int NP, bool RS2>
-static int launch16(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch16(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16_kernel<NMAT, NP, RS2>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(bf16x6)")) return 1;
-  const int nobg = (a.hout + NP * W16_ZC - 1) / (NP * W16_ZC), nibg = (a.hin + W16_XW - 1) / W16_XW;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16_NT),
-                     wgrad16_lds_bytes(a.nrb, a.nmat, a.hout, a.hin, a.ell_width), stream, a, nibg, wb);
-  return check_launch("wgrad(bf16x6)");
+  return launch_wgrad16_kernel(wgrad16_kernel<NMAT, NP, RS2>, lds_done, "wgrad(bf16x6)", W16_NT, a, stream, wb, p);
 }
 
-int launch_wgrad16(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
-  bool rs2 = a.rowscale2 != nullptr;
-  for (int l = 0; l < wb.n; ++l) {
-    if ((reinterpret_cast<uintptr_t>(wb.G[l]) | reinterpret_cast<uintptr_t>(wb.X[l]) | reinterpret_cast<uintptr_t>(wb.rowscale2[l])) & 15) {
-      set_error("wgrad(bf16x6): layer %d has a misaligned operand", l); return 2;
-    }
-    rs2 = rs2 || wb.rowscale2[l] != nullptr;
-  }
-  if (a.nrb == 1) {
-    if (a.nmat == 2) return rs2 ? launch16b<2, true>(a, stream, wb) : launch16b<2, false>(a, stream, wb);
-    if (a.nmat == 3) return rs2 ? launch16b<3, true>(a, stream, wb) : launch16b<3, false>(a, stream, wb);
-  }
+int launch_wgrad16(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p, bool rs2) {      // (K is 1 or 2: wgrad16_shape)
+  if (p.kernel == DSS2_WGRAD_BF16_32 && a.nmat == 2) return rs2 ? launch16b<2, true>(a, stream, wb, p) : launch16b<2, false>(a, stream, wb, p);
+  if (p.kernel == DSS2_WGRAD_BF16_32) return rs2 ? launch16b<3, true>(a, stream, wb, p) : launch16b<3, false>(a, stream, wb, p);
+  if (p.kernel == DSS2_WGRAD_BF16_64 && a.nmat == 2) return rs2 ? launch16<2, 2, true>(a, stream, wb, p) : launch16<2, 2, false>(a, stream, wb, p);
+  if (p.kernel == DSS2_WGRAD_BF16_64) return rs2 ? launch16<3, 2, true>(a, stream, wb, p) : launch16<3, 2, false>(a, stream, wb, p);
 #define DSS2_TALL(NRB, DB) \
   if (a.nrb == NRB && wgrad16t_double(a.nrb, a.nmat, a.ell_width) == DB) { \
-    if (a.nmat == 2) return rs2 ? launch16t<NRB, 2, true, DB>(a, stream, wb) : launch16t<NRB, 2, false, DB>(a, stream, wb); \
-    if (a.nmat == 3) return rs2 ? launch16t<NRB, 3, true, DB>(a, stream, wb) : launch16t<NRB, 3, false, DB>(a, stream, wb); \
+    if (a.nmat == 2) return rs2 ? launch16t<NRB, 2, true, DB>(a, stream, wb, p) : launch16t<NRB, 2, false, DB>(a, stream, wb, p); \
+    return rs2 ? launch16t<NRB, 3, true, DB>(a, stream, wb, p) : launch16t<NRB, 3, false, DB>(a, stream, wb, p); \
   }
   DSS2_TALL(3, true) DSS2_TALL(4, true) DSS2_TALL(5, true) DSS2_TALL(6, true) DSS2_TALL(3, false) DSS2_TALL(4, false) DSS2_TALL(5, false) DSS2_TALL(6, false)
 #undef DSS2_TALL
-  if (a.nrb != 2) { set_error("wgrad(bf16x6): no kernel for nrb=%d nmat=%d", a.nrb, a.nmat); return 2; }
-  if (a.nmat == 2) return rs2 ? launch16<2, 2, true>(a, stream, wb) : launch16<2, 2, false>(a, stream, wb);
-  if (a.nmat == 3) return rs2 ? launch16<3, 2, true>(a, stream, wb) : launch16<3, 2, false>(a, stream, wb);
-  set_error("wgrad(bf16x6): unsupported nmat=%d", a.nmat);
+  set_error("wgrad(bf16x6): no kernel for nrb=%d nmat=%d", a.nrb, a.nmat);
   return 2;
 }
 

@@ -435,49 +435,32 @@ __global__ void __launch_bounds__(W16H_NT, 2) wgrad16h_kernel(const dss2_wgrad_a
   }
 }
 
-size_t wgrad16h_lds_bytes(int nmat, int ell_width, bool hops_mfma) {
+static_assert(W16H_ZC == 64 && W16H_XW == 128, "wgrad16_grid_y and launch_wgrad16_kernel (dss2_wgrad_batch.hpp) count 64 output x 128 input columns per workgroup");
+size_t wgrad16h_lds_bytes(int nmat, bool hops_mfma) {
   const size_t planes = (size_t)nmat * 2 * W16H_ZC * 64 + 2 * (size_t)W16H_XW * 64;
   const size_t b = hops_mfma ? planes + 2 * (size_t)W16H_TM * 64 + 32 : 2 * (size_t)W16H_TM * W16H_LDZF * 4 + planes + (size_t)W16H_DMAX * W16H_TM * 8 + 32;
   const size_t red = (size_t)(1 + nmat) * W16H_NT * 16;
-  (void)ell_width;
   return b > red ? b : red;
 }
 
-bool wgrad16h_covers(const dss2_wgrad_args& a) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return (a.mfma_bf16 & 255) == 2 && a.nrb == 1 && (a.nmat == 2 || a.nmat == 3) && !a.narrow && !a.rowscale && a.ell_tiles && al16(a.G) && al16(a.X) &&
-         (a.ldg & 3) == 0 && (a.ldx & 3) == 0 && (!a.rowscale2 || al16(a.rowscale2)) && a.ell_width >= 1 && a.ell_width <= W16H_DMAX &&
-         a.hout > 32 && (a.hout & 3) == 0 && (a.hin & 3) == 0;
+bool wgrad16h_shape(const dss2_wgrad_args& a) {
+  return a.nrb == 1 && (a.nmat == 2 || a.nmat == 3) && a.ell_width >= 1 && a.ell_width <= W16H_DMAX && a.hout > 32 && (a.hout & 3) == 0 && (a.hin & 3) == 0;
 }
 
 template <int NMAT, bool RS2, bool HM>
-static int launch16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16h_kernel<NMAT, RS2, HM>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(f16x3, 32 rows)")) return 1;
-  const int nobg = (a.hout + W16H_ZC - 1) / W16H_ZC, nibg = (a.hin + W16H_XW - 1) / W16H_XW;
-  const int hb = (a.mfma_bf16 >> 8) & 255;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, wb.n > 0 ? wb.n : 1), dim3(W16H_NT), wgrad16h_lds_bytes(a.nmat, a.ell_width, HM), stream, a, nibg, wb, hb);
-  return check_launch("wgrad(f16x3, 32 rows)");
+  return launch_wgrad16_kernel(wgrad16h_kernel<NMAT, RS2, HM>, lds_done, "wgrad(f16x3, 32 rows)", W16H_NT, a, stream, wb, p, (a.mfma_bf16 >> 8) & 255);
 }
 
-int launch_wgrad16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
-  bool rs2 = a.rowscale2 != nullptr;
-  for (int l = 0; l < wb.n; ++l) {
-    if ((reinterpret_cast<uintptr_t>(wb.G[l]) | reinterpret_cast<uintptr_t>(wb.X[l]) | reinterpret_cast<uintptr_t>(wb.rowscale2[l])) & 15) {
-      set_error("wgrad(f16x3): layer %d has a misaligned operand", l); return 2;
-    }
-    rs2 = rs2 || wb.rowscale2[l] != nullptr;
-  }
+int launch_wgrad16h(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p, bool rs2) {
   if (((a.mfma_bf16 >> 8) & 255) > 10) { set_error("wgrad(f16x3): %d headroom bits for the propagation leave no precision", (a.mfma_bf16 >> 8) & 255); return 2; }
   // the hops as f16x3 products unless the caller asks for the gathered fp32 form (bit 16; flags.WGRAD_HOPS_MFMA = 0)
   const bool hm = !((a.mfma_bf16 >> 16) & 1);
-  if (a.nmat == 2) return rs2 ? (hm ? launch16h<2, true, true>(a, stream, wb) : launch16h<2, true, false>(a, stream, wb))
-                              : (hm ? launch16h<2, false, true>(a, stream, wb) : launch16h<2, false, false>(a, stream, wb));
-  if (a.nmat == 3) return rs2 ? (hm ? launch16h<3, true, true>(a, stream, wb) : launch16h<3, true, false>(a, stream, wb))
-                              : (hm ? launch16h<3, false, true>(a, stream, wb) : launch16h<3, false, false>(a, stream, wb));
-  set_error("wgrad(f16x3): unsupported nmat=%d", a.nmat);
-  return 2;
+  if (a.nmat == 2) return rs2 ? (hm ? launch16h<2, true, true>(a, stream, wb, p) : launch16h<2, true, false>(a, stream, wb, p))
+                              : (hm ? launch16h<2, false, true>(a, stream, wb, p) : launch16h<2, false, false>(a, stream, wb, p));
+  return rs2 ? (hm ? launch16h<3, true, true>(a, stream, wb, p) : launch16h<3, true, false>(a, stream, wb, p))      // (K = 2: wgrad16h_shape)
+             : (hm ? launch16h<3, false, true>(a, stream, wb, p) : launch16h<3, false, false>(a, stream, wb, p));
 }
 
 }  // namespace dss2

@@ -418,7 +418,7 @@ __global__ void __launch_bounds__(W16TH_NT) wgrad16th_kernel(const dss2_wgrad_ar
   }
 }
 
-
+static_assert(W16TH_ZC == 64 && W16TH_XW == 128, "wgrad16_grid_y and launch_wgrad16_kernel (dss2_wgrad_batch.hpp) count 64 output x 128 input columns per workgroup");
 size_t wgrad16th_lds_bytes(int nrb, int nmat, int ell_width) {
   const size_t fimg = (size_t)32 * nrb * W16TH_LDZF * 4, planes = (size_t)nmat * 2 * W16TH_ZC * 64 + 2 * (size_t)W16TH_XW * 64;
   const size_t b = fimg + 2 * (fimg > planes ? fimg : planes) + (size_t)((ell_width + 3) & ~3) * 32 * nrb * 8 + 64;      // (+ the maxima)
@@ -430,45 +430,29 @@ size_t wgrad16th_lds_bytes(int nrb, int nmat, int ell_width) {
 // bf16x6 kernels start above 32): one wave of eight multiplies, but the propagation, the splits and the prefetch are what a tile costs at
 // that width -- the driver's model on ober_sub (dim_hid 32, 7 layers per launch): 206 -> ~150 us per launch against the fp32 kernel,
 // replayed step 2.63 -> 2.37 ms
-bool wgrad16th_covers(const dss2_wgrad_args& a) {
-  static const int on = [] { const char* e = getenv("DSS2_WGRAD_TALL_F16"); return e ? atoi(e) : 1; }();
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return on && (a.mfma_bf16 & 255) == 2 && a.nrb >= 3 && a.nrb <= 6 && (a.nmat == 2 || a.nmat == 3) && !a.narrow && !a.rowscale && a.ell_tiles &&
-         al16(a.G) && al16(a.X) && (a.ldg & 3) == 0 && (a.ldx & 3) == 0 && (!a.rowscale2 || al16(a.rowscale2)) && a.ell_width >= 1 &&
-         a.ell_width <= W16TH_DMAX && a.hout >= 32 && (a.hout & 3) == 0 && (a.hin & 3) == 0 &&
-         wgrad16th_lds_bytes(a.nrb, a.nmat, a.ell_width) <= (size_t)kMaxLdsBytes;
+bool wgrad16th_shape(const dss2_wgrad_args& a) {
+  return a.nrb >= 3 && a.nrb <= 6 && (a.nmat == 2 || a.nmat == 3) && a.ell_width >= 1 && a.ell_width <= W16TH_DMAX && a.hout >= 32 && (a.hout & 3) == 0 &&
+         (a.hin & 3) == 0 && wgrad16th_lds_bytes(a.nrb, a.nmat, a.ell_width) <= (size_t)kMaxLdsBytes;
 }
+
+// two layers per workgroup where a layer is one 32-column block (DSS2_WGRAD_TALL_PAIR=0: one layer per workgroup)
+bool wgrad16th_pair_shape(const dss2_wgrad_args& a, int n_layers) { return a.nrb == 3 && a.hout == 32 && a.hin == 32 && n_layers >= 2; }
 
 template <int NRB, int NMAT, bool RS2, bool PC, bool PAIR = false>
-static int launch16th(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
+static int launch16th(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
-  auto kern = wgrad16th_kernel<NRB, NMAT, RS2, PC, PAIR>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "wgrad(f16x3, tall tiles)")) return 1;
-  const int nobg = (a.hout + W16TH_ZC - 1) / W16TH_ZC, nibg = (a.hin + W16TH_XW - 1) / W16TH_XW;
-  const int hb = (a.mfma_bf16 >> 8) & 255;
-  const int nz = wb.n > 0 ? (PAIR ? (wb.n + 1) / 2 : wb.n) : 1;
-  hipLaunchKernelGGL(kern, dim3(a.n_split, nobg * nibg, nz), dim3(W16TH_NT), wgrad16th_lds_bytes(a.nrb, a.nmat, a.ell_width), stream, a, nibg, wb, hb);
-  return check_launch("wgrad(f16x3, tall tiles)");
+  return launch_wgrad16_kernel(wgrad16th_kernel<NRB, NMAT, RS2, PC, PAIR>, lds_done, "wgrad(f16x3, tall tiles)", W16TH_NT, a, stream, wb, p, (a.mfma_bf16 >> 8) & 255);
 }
 
-int launch_wgrad16th(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb) {
-  bool rs2 = a.rowscale2 != nullptr;
-  for (int l = 0; l < wb.n; ++l) {
-    if ((reinterpret_cast<uintptr_t>(wb.G[l]) | reinterpret_cast<uintptr_t>(wb.X[l]) | reinterpret_cast<uintptr_t>(wb.rowscale2[l])) & 15) {
-      set_error("wgrad(f16x3, tall tiles): layer %d has a misaligned operand", l); return 2;
-    }
-    rs2 = rs2 || wb.rowscale2[l] != nullptr;
-  }
-  // two layers per workgroup where a layer is one 32-column block (DSS2_WGRAD_TALL_PAIR=0: one layer per workgroup as before)
-  static const int pair_on = [] { const char* e = getenv("DSS2_WGRAD_TALL_PAIR"); return e ? atoi(e) : 1; }();
-  if (pair_on && a.nrb == 3 && a.hout == 32 && a.hin == 32 && wb.n >= 2) {
-    if (a.nmat == 2) return rs2 ? launch16th<3, 2, true, false, true>(a, stream, wb) : launch16th<3, 2, false, false, true>(a, stream, wb);
-    return rs2 ? launch16th<3, 3, true, false, true>(a, stream, wb) : launch16th<3, 3, false, false, true>(a, stream, wb);
+int launch_wgrad16th(const dss2_wgrad_args& a, hipStream_t stream, const WgradBatch& wb, const dss2_wgrad_plan_t& p, bool rs2) {
+  if (p.kernel == DSS2_WGRAD_F16_TALL_PAIR) {
+    if (a.nmat == 2) return rs2 ? launch16th<3, 2, true, false, true>(a, stream, wb, p) : launch16th<3, 2, false, false, true>(a, stream, wb, p);
+    return rs2 ? launch16th<3, 3, true, false, true>(a, stream, wb, p) : launch16th<3, 3, false, false, true>(a, stream, wb, p);
   }
 #define DSS2_TALLH(NRB, PC) \
   if (a.nrb == NRB) { \
-    if (a.nmat == 2) return rs2 ? launch16th<NRB, 2, true, PC>(a, stream, wb) : launch16th<NRB, 2, false, PC>(a, stream, wb); \
-    return rs2 ? launch16th<NRB, 3, true, PC>(a, stream, wb) : launch16th<NRB, 3, false, PC>(a, stream, wb); \
+    if (a.nmat == 2) return rs2 ? launch16th<NRB, 2, true, PC>(a, stream, wb, p) : launch16th<NRB, 2, false, PC>(a, stream, wb, p); \
+    return rs2 ? launch16th<NRB, 3, true, PC>(a, stream, wb, p) : launch16th<NRB, 3, false, PC>(a, stream, wb, p); \
   }
   DSS2_TALLH(3, false) DSS2_TALLH(4, true) DSS2_TALLH(5, true) DSS2_TALLH(6, true)
 #undef DSS2_TALLH

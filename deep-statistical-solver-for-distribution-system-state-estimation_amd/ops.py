@@ -293,6 +293,16 @@ def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: i
                "dss2_gemm_prop_chain_head")
 
 
+def _wgrad_shape_plan(ts: Tiling, nmat: int, hout: int, hin: int, mode: int, n_layers: int = 0) -> "_lib.WgradPlan":
+    """The record the library launches from (dss2_wgrad_plan: kernel, grid factors, LDS), for a launch known by its shape and the tile set
+    ``ts`` (no operands: they count as aligned; n_layers 0: ops.wgrad, >= 1: ops.wgrad_batched)."""
+    a, p = _lib.WgradArgs(), _lib.WgradPlan()
+    a.hout, a.hin, a.nmat, a.mfma_bf16 = hout, hin, nmat, mode
+    a.nrb, a.max_nnz, a.ell_width, a.ell_tiles = ts.nrb, ts.max_nnzT, ts.ellT, _ptr(ts.ellT_tiles)
+    _lib.check(_lib.lib().dss2_wgrad_plan(C.byref(a), n_layers, C.byref(p)), "dss2_wgrad_plan")
+    return p
+
+
 def _wgrad_tiles(topo: Topology, nmat: int, hout: int, hin: int, b16: int) -> Tiling:
     """The tile set a weight-gradient launch walks: the topology's primary one, or -- 64-row tilings under the bf16x6 kernel -- a
     32-row tiling of the same graphs (Topology.tiles_for(1)), on which two 4-wave workgroups share a CU and overlap each
@@ -301,29 +311,28 @@ def _wgrad_tiles(topo: Topology, nmat: int, hout: int, hin: int, b16: int) -> Ti
     #  Infinity Cache that is a second trip to HBM.  As bf16x6 that lost to the 64-row kernel -- B = 32768: 3.52 ms against 3.43 --, so
     #  that route takes the 32-row form only while one layer's input stays well inside the cache; as f16x3 (round 5) the 32-row kernel
     #  wins at every size: B = 32768 2.75 -> 2.45 ms, B = 16384 1.44 -> 1.28 ms)
-    ts = topo.tiling
+    ts = topo.tiling      # (the shape conditions below only keep a 32-row tiling from being BUILT for layers that could not use it)
     if (FL.WGRAD_TM32 and b16 and ts.nrb == 2 and not ts.global_only and nmat in (2, 3) and hout > 32 and 1 <= ts.ellT <= 8
             and (FL.WGRAD_F16 or topo.N * hin * 4 <= FL.WGRAD_TM32_MAX_BYTES)):
         alt = topo.tiles_for(1)
-        # ... and only where the library's bf16x6 kernel covers the shape on that tiling (its LDS query answers with the fp32 kernel's
-        # size when it does not: hout % 4, hin % 4, hout > 32, K <= 2 -- the conditions live in ONE place, wgrad16_covers)
-        if alt is not None and alt.ellT_tiles is not None and 1 <= alt.ellT <= 8:
-            L_ = _lib.lib()
-            if (L_.dss2_wgrad_lds_bytes_ex(1, nmat, hout, hin, alt.max_nnzT, alt.ellT, 1)
-                    != L_.dss2_wgrad_lds_bytes_ex(1, nmat, hout, hin, alt.max_nnzT, alt.ellT, 0)):
-                return alt
+        # ... and only where the library runs one of its 32-row 16-bit kernels on that tiling
+        if alt is not None and _wgrad_shape_plan(alt, nmat, hout, hin, 1).kernel in (_lib.WGRAD_BF16_32, _lib.WGRAD_F16_32):
+            return alt
     return ts
 
 
 def _wgrad_mode(ts: Tiling, nmat: int, b16: int, hinted: bool = False) -> int:
-    """args.mfma_bf16 of a weight-gradient launch on the tile set ``ts``: 0 fp32 MFMA, 1 bf16x6, or -- flags.WGRAD_F16 on 32-row tiles
-    (csrc/dss2_wgrad16h.hip) and on 96- .. 192-row tiles (csrc/dss2_wgrad16th.hip) with ELL slices -- 2 | hb << 8: the f16x3 kernels
+    """args.mfma_bf16 of a weight-gradient launch on the tile set ``ts``: 0 fp32 MFMA, 1 bf16x6, or -- flags.WGRAD_F16 where the library has
+    an f16x3 kernel for this tile set and K (csrc/dss2_wgrad16h.hip, dss2_wgrad16th.hip) -- 2 | hb << 8: the f16x3 kernels
     with hb headroom bits for the gain of the propagation hops, ceil(log2(max row sum of |P^T| ^ K)), read from the ELL slices once per
-    tile set (one device-to-host copy, cached; ``hinted``: from the ELL width alone, no copy).  Shapes the f16x3 kernels do not cover run bf16x6 on the same value (the library decides)."""
-    if not (b16 and FL.WGRAD_F16 and ts.nrb in (1, 3, 4, 5, 6) and nmat in (2, 3) and ts.ellT_tiles is not None and 1 <= ts.ellT <= 8):
+    tile set (one device-to-host copy, cached; ``hinted``: from the ELL width alone, no copy).  Widths the f16x3 kernels do not cover run bf16x6 on the same value (the library decides)."""
+    if not (b16 and FL.WGRAD_F16):
         return b16
     hb = ts.gain_bits.get(nmat)
     if hb is None:
+        # are the bits worth forming?  Asked at widths every f16x3 kernel takes: the tile height, K and the ELL slices decide
+        if not _wgrad_shape_plan(ts, nmat, 64, 64, 2).f16x3_covers:
+            return b16
         if hinted or torch.cuda.is_current_stream_capturing():
             # no copy to the host here (a topology built from a TopologyHint never reads anything back; neither may a capture): the
             # bound that needs no data -- gcn_norm weights are <= 1, a row of P^T has at most ellT entries -- costs the smallest
@@ -336,6 +345,19 @@ def _wgrad_mode(ts: Tiling, nmat: int, b16: int, hinted: bool = False) -> int:
     return (2 | (hb << 8) | (0 if FL.WGRAD_HOPS_MFMA else 1 << 16)) if hb <= 10 else b16      # (bit 16: the 32-row kernel's hops as fp32 gathers)
 
 
+def _wgrad_geometry(a: "_lib.WgradArgs", topo: Topology, b16: int, n_layers: int = 0) -> int:
+    """Completes the arguments of a weight-gradient launch whose shape and operands are filled in: the tile set it walks with the graph
+    side, the mode word (``b16``: may the launch leave the fp32 kernel) and n_split, sized from the library's plan of the launch so that
+    its n_split x y_slices x z_groups workgroups fill the chip (of the SHAPE: a stride or an address the 16-bit kernels refuse sends the
+    launch to the fp32 kernel and does not re-size it, as it never did).  Returns n_split."""
+    ts = _wgrad_tiles(topo, a.nmat, a.hout, a.hin, b16)
+    _fill_wgrad_graph(a, topo, ts)
+    a.mfma_bf16 = _wgrad_mode(ts, a.nmat, b16, topo.hint is not None)
+    p = _wgrad_shape_plan(ts, a.nmat, a.hout, a.hin, a.mfma_bf16, n_layers)
+    a.n_split = min(ts.ntiles, max(1, (256 * _wgrad_per_cu(int(p.sizing_lds))) // (p.y_slices * p.z_groups)))
+    return a.n_split
+
+
 def wgrad(topo: Topology, G: torch.Tensor, hout: int, X: torch.Tensor, hin: int, nmat: int, out_flat: torch.Tensor,
           rowscale=None, rowscale2=None, pending=None, out_len: Optional[int] = None) -> None:
     """out_flat[nmat*hout*hin + hout] <- [dW_0 .. dW_{nmat-1}, db] (deterministic two-pass sum); with
@@ -344,23 +366,15 @@ def wgrad(topo: Topology, G: torch.Tensor, hout: int, X: torch.Tensor, hin: int,
     if topo.tiling.global_only and nmat > 1:
         raise NotImplementedError("wgrad with propagation needs LDS-resident graph tiles (graphs of <= 192 nodes)")
     narrow = nmat > 1 and nmat * hout <= 32 and rowscale2 is None
-    b16 = int(FL.WGRAD_BF16 and rowscale is None and not narrow)
-    ts = _wgrad_tiles(topo, nmat, hout, hin, b16)
-    lds = _lib.lib().dss2_wgrad_lds_bytes_ex(ts.nrb, nmat, hout, hin, ts.max_nnzT, ts.ellT, b16)
-    per_cu = _wgrad_per_cu(int(lds))
-    ys = _lib.lib().dss2_wgrad_y_slices(ts.nrb, nmat, hout, hin, ts.ellT, b16, int(rowscale2 is not None))
-    n_split = min(ts.ntiles, max(1, (256 * per_cu) // ys))
-    stride = nmat * hout * hin + hout + (nmat * hout if rowscale2 is not None else 0)
-    slab = torch.empty(n_split * stride, dtype=_F32, device=G.device)
     a = _lib.WgradArgs()
     a.G, a.ldg, a.hout = G.data_ptr(), G.stride(0), hout
     a.X, a.ldx, a.hin = X.data_ptr(), X.stride(0), hin
-    a.rowscale, a.rowscale2 = _ptr(rowscale), _ptr(rowscale2)
-    a.slab, a.n_split, a.nmat = slab.data_ptr(), n_split, nmat
-    _fill_wgrad_graph(a, topo, ts)
-    a.narrow, a.mfma_bf16 = int(narrow), (_wgrad_mode(ts, nmat, b16, topo.hint is not None) if (not narrow and rowscale is None) else b16)
-    st = _stream(G)
-    _lib.check(_lib.lib().dss2_wgrad(C.byref(a), st), "dss2_wgrad")
+    a.rowscale, a.rowscale2, a.nmat, a.narrow = _ptr(rowscale), _ptr(rowscale2), nmat, int(narrow)
+    n_split = _wgrad_geometry(a, topo, int(FL.WGRAD_BF16 and rowscale is None and not narrow))
+    stride = nmat * hout * hin + hout + (nmat * hout if rowscale2 is not None else 0)
+    slab = torch.empty(n_split * stride, dtype=_F32, device=G.device)
+    a.slab = slab.data_ptr()
+    _lib.check(_lib.lib().dss2_wgrad(C.byref(a), _stream(G)), "dss2_wgrad")
     _reduce(slab, 0, n_split, stride, out_flat, stride if out_len is None else out_len, pending)
 
 
@@ -371,32 +385,22 @@ def wgrad_batched(topo: Topology, Gs: Sequence[torch.Tensor], hout: int, Xs: Seq
     With ``first_rowscale2`` layer 0 is a folded layer (see ``wgrad``): its result, with the extra nmat*hout
     scaled sums, goes to ``first_out`` and the remaining layers to ``out_flat`` (two slab reductions)."""
     nl = len(Gs)
-    ts = _wgrad_tiles(topo, nmat, hout, hin, int(FL.WGRAD_BF16))
-    lds = _lib.lib().dss2_wgrad_lds_bytes_ex(ts.nrb, nmat, hout, hin, ts.max_nnzT, ts.ellT, int(FL.WGRAD_BF16))
-    per_cu = _wgrad_per_cu(int(lds))
-    ys = _lib.lib().dss2_wgrad_y_slices(ts.nrb, nmat, hout, hin, ts.ellT, int(FL.WGRAD_BF16), int(first_rowscale2 is not None))
-    mode = _wgrad_mode(ts, nmat, int(FL.WGRAD_BF16), topo.hint is not None)
-    nz = int(_lib.lib().dss2_wgrad_batched_groups(ts.nrb, hout, hin, mode, nl))      # workgroup groups along z (two 32-column layers may share one)
-    n_split = min(ts.ntiles, max(1, (256 * per_cu) // (nz * ys)))       # the layers share the chip
+    a = _lib.WgradArgs()
+    a.ldg, a.hout, a.ldx, a.hin, a.nmat = Gs[0].stride(0), hout, Xs[0].stride(0), hin, nmat
+    for g_, x_ in zip(Gs, Xs):
+        if g_.stride(0) != a.ldg or x_.stride(0) != a.ldx or g_.shape != Gs[0].shape or x_.shape != Xs[0].shape:
+            raise ValueError("wgrad_batched: layers must share shapes and leading dimensions")
+    n_split = _wgrad_geometry(a, topo, int(FL.WGRAD_BF16), nl)      # the layers share the chip
     stride = nmat * hout * hin + hout
     lens = [stride + (nmat * hout if (first_rowscale2 is not None and l == 0) else 0) for l in range(nl)]
     total = sum(lens)
     slab = torch.empty(n_split * total, dtype=_F32, device=Gs[0].device)
-    a = _lib.WgradArgs()
-    a.ldg, a.hout, a.ldx, a.hin = Gs[0].stride(0), hout, Xs[0].stride(0), hin
-    for g_, x_ in zip(Gs, Xs):
-        if g_.stride(0) != a.ldg or x_.stride(0) != a.ldx or g_.shape != Gs[0].shape or x_.shape != Xs[0].shape:
-            raise ValueError("wgrad_batched: layers must share shapes and leading dimensions")
-    a.n_split, a.nmat, a.mfma_bf16 = n_split, nmat, mode
-    _fill_wgrad_graph(a, topo, ts)
     PtrArr = C.c_void_p * nl
     gs, xs = PtrArr(*[g_.data_ptr() for g_ in Gs]), PtrArr(*[x_.data_ptr() for x_ in Xs])
     offs = [sum(lens[:l]) for l in range(nl)]
     sl = PtrArr(*[slab.data_ptr() + 4 * o for o in offs])
     rs = PtrArr(*[(first_rowscale2.data_ptr() if (first_rowscale2 is not None and l == 0) else None) for l in range(nl)])
-    st = _stream(Gs[0])
-    L_ = _lib.lib()
-    _lib.check(L_.dss2_wgrad_batched(C.byref(a), gs, xs, sl, rs, total, nl, st), "dss2_wgrad_batched")
+    _lib.check(_lib.lib().dss2_wgrad_batched(C.byref(a), gs, xs, sl, rs, total, nl, _stream(Gs[0])), "dss2_wgrad_batched")
     if first_rowscale2 is not None:
         _reduce(slab, 0, n_split, total, first_out, lens[0], pending)
         if nl > 1:

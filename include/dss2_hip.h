@@ -462,31 +462,63 @@ typedef struct dss2_wgrad_args {
                                          * every m, sum_n rowscale2[n][m] G[n, o] (the gradient of  *
                                          * dss2_gemm_prop's prebias_m when rowscale2 is its          *
                                          * pre_rowscale); slab = [nmat*hout*hin][hout][nmat*hout]    */
-  int32_t narrow; int32_t mfma_bf16;    /* mfma_bf16 != 0: products as bf16x6 on the bf16 matrix *
-                                         * pipe (fp32-accurate) where that kernel covers the     *
-                                         * shape (64-row tiles, K <= 2, ELL slices, 16-byte      *
-                                         * aligned operands), else the fp32 MFMA kernel.         *
-                                         * narrow != 0 (needs nmat*hout <= 32): the propagated  *
+  int32_t narrow; int32_t mfma_bf16;    /* narrow != 0 (needs nmat*hout <= 32): the propagated  *
                                          * copies P^m G are appended as extra COLUMNS of one    *
                                          * 32-wide block instead of nmat separate blocks; same  *
                                          * slab layout [nmat*hout*hin + hout].                  *
-                                         * (mfma_bf16 & 255) == 2: as f16x3 where that kernel    *
-                                         * covers the shape (32-, 96- and 192-row tiles with ELL *
-                                         * slices), bits 8..15 = headroom bits for the gain of   *
-                                         * the propagation hops, ceil(log2(max row sum of        *
-                                         * |P^T|^K)); elsewhere the bf16x6 / fp32 kernels.       *
-                                         * Bit 16 set: the 32-row f16x3 kernel forms its hops as *
-                                         * fp32 gathers (clear: f16x3 products, P as fp16 planes)*/
+                                         * mfma_bf16: the mode word.  0: fp32 MFMA.  != 0: the  *
+                                         * products on the 16-bit matrix pipe, fp32-accurate,   *
+                                         * as bf16x6; (mfma_bf16 & 255) == 2: as f16x3, bits    *
+                                         * 8..15 = headroom bits for the gain of the hops,      *
+                                         * ceil(log2(max row sum of |P^T|^K)), bit 16 = the     *
+                                         * 32-row kernel forms its hops as fp32 gathers.  Which *
+                                         * kernel takes a launch is decided in ONE place and    *
+                                         * can be asked: dss2_wgrad_plan below.                 */
 } dss2_wgrad_args;
 
 int dss2_wgrad(const dss2_wgrad_args* args_host, void* stream);
-/* dynamic LDS of the kernel dss2_wgrad launches for this shape (callers size n_split by it); _ex: with args.mfma_bf16 */
+/* Which kernel a launch of these arguments runs and its geometry: the record the library's own dispatch launches from.
+ * Families fall through in this order: narrow (args.narrow) -> f16x3 on 32-row tiles -> f16x3 on 96- .. 192-row tiles
+ * -> bf16x6 -> fp32 MFMA.  The 16-bit families share one set of operand conditions (no rowscale, ELL slices, G / X /
+ * rowscale2 16-byte aligned, ldg and ldx multiples of 4); a launch that misses them, or a kernel's own shape
+ * conditions, takes the next family.                                                                               */
+typedef enum dss2_wgrad_kernel {
+  DSS2_WGRAD_NONE = 0,            /* no kernel: see dss2_wgrad_plan_t.reason                                         */
+  DSS2_WGRAD_NARROW_STREAM,       /* narrow, nmat*hout <= 8: streaming kernel (un-batched launches only)           */
+  DSS2_WGRAD_FP32_NARROW,         /* narrow: wgrad<nrb, 1, 1>                                                      */
+  DSS2_WGRAD_FP32,                /* wgrad<nrb, nmat, nb, w8>                                                      */
+  DSS2_WGRAD_BF16_64,             /* bf16x6, 64-row tiles                                                          */
+  DSS2_WGRAD_BF16_32,             /* bf16x6, 32-row tiles                                                          */
+  DSS2_WGRAD_BF16_TALL,           /* bf16x6, 96- .. 192-row tiles                                                  */
+  DSS2_WGRAD_F16_32,              /* f16x3, 32-row tiles                                                           */
+  DSS2_WGRAD_F16_TALL,            /* f16x3, 96- .. 192-row tiles                                                   */
+  DSS2_WGRAD_F16_TALL_PAIR        /* ... two 32-column layers of a batch per workgroup                             */
+} dss2_wgrad_kernel;
+typedef struct dss2_wgrad_plan_t {
+  int32_t kernel;                 /* dss2_wgrad_kernel                                                             */
+  int32_t reason;                 /* kernel == NONE: the code dss2_wgrad returns (3: no tile fits LDS, 2: no such instantiation) */
+  int32_t nb; int32_t w8;         /* FP32: output blocks per workgroup, eight-wave form                            */
+  int32_t grid_y; int32_t z_groups;   /* the launch is n_split x grid_y x z_groups workgroups                      */
+  int32_t y_slices;
+  int32_t f16x3_covers;           /* an f16x3 kernel covers these operands, tile height, K, ELL width and columns, whatever the mode
+                                   * word and DSS2_WGRAD_TALL_F16 say: are headroom bits worth forming (a device read) at all?       */
+  uint64_t launch_lds;            /* dynamic LDS of the launch                                                     */
+  uint64_t sizing_lds;            /* what callers size n_split by, together with y_slices and z_groups             */
+  /* sizing_lds / y_slices are NOT always launch_lds / grid_y: they answer from the shape alone with the bf16x6
+   * kernel's figures wherever that kernel's shape conditions hold and the mode word is non-zero, else with the fp32
+   * kernel's LDS and 1 -- also where an f16x3 kernel takes the launch (smaller LDS; hout = 32 on tall tiles), where
+   * the operands send a launch on to the fp32 kernel, and for the fp32 family's own column groups.  n_split, and
+   * with it the summation order and the speed of every configuration, was tuned on these figures; sizing by the
+   * kernel that runs is a separate, measured change.                                                               */
+} dss2_wgrad_plan_t;
+/* fills *out for a launch of args with n_layers layers (0: dss2_wgrad; >= 1: dss2_wgrad_batched, whose pointer tables are
+ * not seen here -- a misaligned layer is that call's error).  args->slab and args->n_split are not read: ask first,
+ * size them after.  Returns 0, or 2 for a null pointer.                                                             */
+int dss2_wgrad_plan(const dss2_wgrad_args* args_host, int n_layers, dss2_wgrad_plan_t* out);
+/* Readers of that record for callers that hold a shape only (operands taken as aligned, ELL slices as present where
+ * ell_width > 0): sizing_lds (_ex: with the mode word, else 0), y_slices, and z_groups of an n_layers batch.        */
 size_t dss2_wgrad_lds_bytes_ex(int nrb, int nmat, int hout, int hin, int max_nnz, int ell_width, int mfma_bf16);
-/* workgroups the launch puts on each of the n_split tile-list slices (> 1 only for the bf16x6 kernel at H > 128): a caller
- * that wants one workgroup per CU divides its n_split by it                                                                */
 int dss2_wgrad_y_slices(int nrb, int nmat, int hout, int hin, int ell_width, int mfma_bf16, int has_rowscale2);
-/* workgroup groups along grid.z of dss2_wgrad_batched for n_layers layers (one per layer; (n_layers + 1) / 2 where the f16x3 tall-tile kernel
- * walks two 32-column layers per workgroup, round 6): n_split x y_slices x this = the launch's workgroups */
 int dss2_wgrad_batched_groups(int nrb, int hout, int hin, int mfma_bf16, int n_layers);
 
 /* The same for n_layers (<= 8) layers of IDENTICAL shape and leading dimensions in one launch (one grid

@@ -61,10 +61,10 @@ def test_weight_gradient_bf16x6_equals_fp32_mfma(pkg, grids, B, H, nmat, n_layer
         got64b = run(True, tm32=False)
     finally:
         pkg.flags.WGRAD_BF16, pkg.flags.WGRAD_TM32 = saved
-    lds = pkg._lib.lib().dss2_wgrad_lds_bytes_ex
-    covered = lds(2, nmat, H, H, topo.max_nnzT, topo.ellT, 1) != lds(2, nmat, H, H, topo.max_nnzT, topo.ellT, 0)
-    assert covered                                                     # these shapes do run the bf16x6 kernel
-    assert pkg.networks._wgrad_tiles(topo, nmat, H, H, 1).nrb == 1       # ... and the default walks the 32-row tiling
+    plan = lambda ts: pkg.ops._wgrad_shape_plan(ts, nmat, H, H, 1).kernel
+    assert plan(topo.tiling) == pkg._lib.WGRAD_BF16_64                  # these shapes do run the bf16x6 kernel on their own tiles
+    alt = pkg.networks._wgrad_tiles(topo, nmat, H, H, 1)
+    assert alt.nrb == 1 and plan(alt) == pkg._lib.WGRAD_BF16_32         # ... and the default walks the 32-row tiling
     for a, b_, c, d, e in zip(got, ref, got2, got64, got64b):
         assert torch.equal(a, c) and torch.equal(d, e)                 # fixed-order sums: bitwise reproducible
         assert rel_err(a, b_) < 2e-6 and rel_err(d, b_) < 2e-6
@@ -111,9 +111,7 @@ def test_tall_tile_weight_gradient_bf16x6_equals_fp32_mfma(pkg, grids, B, H, nma
         got2 = run(True, topo)
     finally:
         pkg.flags.WGRAD_BF16 = saved
-    lds = pkg._lib.lib().dss2_wgrad_lds_bytes_ex
-    if topo.nrb != 5:                                                  # (the fp32 kernel has no 160-row instantiation)
-        assert lds(topo.nrb, nmat, H, H, topo.max_nnzT, topo.ellT, 1) != lds(topo.nrb, nmat, H, H, topo.max_nnzT, topo.ellT, 0)
+    assert pkg.ops._wgrad_shape_plan(topo.tiling, nmat, H, H, 1).kernel == pkg._lib.WGRAD_BF16_TALL
     for a, b_, c in zip(got, ref, got2):
         assert torch.equal(a, c)                                        # fixed-order sums: bitwise reproducible
         assert rel_err(a, b_) < 2e-6

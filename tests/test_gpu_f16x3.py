@@ -76,7 +76,7 @@ def _run(pkg, topo, Gs, Xs, H, nmat, rs2, f16):
 
 def _uses_f16(pkg, topo, nmat, H):
     ts = pkg.ops._wgrad_tiles(topo, nmat, H, H, 1)
-    return (pkg.ops._wgrad_mode(ts, nmat, 1) & 255) == 2
+    return pkg.ops._wgrad_shape_plan(ts, nmat, H, H, pkg.ops._wgrad_mode(ts, nmat, 1)).kernel in (pkg._lib.WGRAD_F16_32, pkg._lib.WGRAD_F16_TALL, pkg._lib.WGRAD_F16_TALL_PAIR)
 
 
 def _check(pkg, topo, Gs, Xs, H, nmat, rs2, tol=2e-6, against_bf16=True):

@@ -73,7 +73,7 @@ def _errors(res, refs):
 
 def _takes_the_kernel(pkg, topo):
     ts = pkg.ops._wgrad_tiles(topo, NMAT, H, H, 1)
-    return ts.nrb == 1 and (pkg.ops._wgrad_mode(ts, NMAT, 1) & 255) == 2
+    return pkg.ops._wgrad_shape_plan(ts, NMAT, H, H, pkg.ops._wgrad_mode(ts, NMAT, 1)).kernel == pkg._lib.WGRAD_F16_32
 
 
 CASES = {
