@@ -71,6 +71,17 @@ class WgradPlan(C.Structure):
                 ("launch_lds", C.c_uint64), ("sizing_lds", C.c_uint64)]
 
 
+class ChainKernel(C.Structure):
+    """dss2_chain_kernel_t: the layer chain's kernel for one weight format, its geometry and what it carries (include/dss2_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "row_split", "waves", "block", "lds_bytes", "gate_words", "head_modes", "head_wgrad", "edge_modes")]
+
+
+class ChainPlan(C.Structure):
+    _fields_ = [("fmt", ChainKernel * 3)]      # by args.b_format: fp32, bf16x3, f16x2 weights
+
+
+CHAIN_NONE, CHAIN_FP32, CHAIN_BF16X6, CHAIN_SP, CHAIN_SP6 = range(5)      # dss2_chain_family
+
 # dss2_wgrad_kernel
 (WGRAD_NONE, WGRAD_NARROW_STREAM, WGRAD_FP32_NARROW, WGRAD_FP32, WGRAD_BF16_64, WGRAD_BF16_32, WGRAD_BF16_TALL,
  WGRAD_F16_32, WGRAD_F16_TALL, WGRAD_F16_TALL_PAIR) = range(10)
@@ -313,6 +324,7 @@ _SIGNATURES = {
     "dss2_chain_sp6_single_group_min_tiles": (C.c_int, []),
     "dss2_gemm_prop_chain": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p, C.c_int, C.c_void_p]),
     "dss2_gemm_prop_chain_head": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p, C.c_int, C.POINTER(ChainHead), C.c_void_p]),
+    "dss2_gemm_prop_chain_plan": (C.c_int, [C.c_int] * 7 + [C.POINTER(ChainPlan)]),
     "dss2_gemm_prop_chain_head_supported": (C.c_int, [C.c_int] * 6),
     "dss2_gemm_prop_chain_head_wgrad_supported": (C.c_int, [C.c_int] * 6),
     "dss2_gemm_prop_chain_edge_supported": (C.c_int, [C.c_int] * 6),

@@ -10,31 +10,22 @@
 // Round 2 met it as run-to-run different values of the epilogue's `v += prebias[m] * rowscale[row][m]`; with today's paired
 // operand split (split3_pair -> v_pk_add_f32) a packed build returns garbage in every lane (tools/pk_stress.py).  Plain VALU
 // ops are also the cheaper fillers beside MFMAs (MI355X_MICROARCH.md).
-#include <stdlib.h>
-
 #include "dss2_gemm_chain_kernel.hpp"
 
 namespace dss2 {
 
-int launch_chain16(const dss2_gemm_prop_args& a, const ChainTable& ct, int rsplit, hipStream_t s) {
-#define DSS2_CASE16(NRB, NMAT)                                                           \
-  if (a.nrb == NRB && a.nmat == NMAT && rsplit == 1)                                     \
-    return a.ncg <= 4 ? launch_chain<NRB, NMAT, 4, 1, true>(a, ct, s) : launch_chain<NRB, NMAT, 8, 1, true>(a, ct, s);
-#define DSS2_CASE16_2(NRB, NMAT)                                                         \
-  if (a.nrb == NRB && a.nmat == NMAT && rsplit == 2)                                     \
-    return 2 * a.ncg <= 4 ? launch_chain<NRB, NMAT, 4, 2, true>(a, ct, s) : launch_chain<NRB, NMAT, 8, 2, true>(a, ct, s);
-  DSS2_CASE16(1, 2) DSS2_CASE16(1, 3) DSS2_CASE16(1, 4) DSS2_CASE16(2, 2) DSS2_CASE16(2, 3)
-  DSS2_CASE16(3, 2) DSS2_CASE16(4, 2)
+ChainLauncher chain16_launcher(int nrb, int nmat, int nw, int rs) {
+#define DSS2_CASE16(NRB, NMAT, RS)                                                        \
+  if (nrb == NRB && nmat == NMAT && rs == RS) return nw == 4 ? launch_chain<NRB, NMAT, 4, RS, true> : nw == 8 ? launch_chain<NRB, NMAT, 8, RS, true> : nullptr;
+  DSS2_CASE16(1, 2, 1) DSS2_CASE16(1, 3, 1) DSS2_CASE16(1, 4, 1) DSS2_CASE16(2, 2, 1) DSS2_CASE16(2, 3, 1)      // (2, 4, 1) would spill
+  DSS2_CASE16(3, 2, 1) DSS2_CASE16(4, 2, 1)
+  DSS2_CASE16(2, 2, 2) DSS2_CASE16(2, 3, 2) DSS2_CASE16(2, 4, 2) DSS2_CASE16(4, 2, 2)
+#undef DSS2_CASE16
   // 96-row tiles: three waves per column group (one row block each, twelve waves = three per SIMD) instead of one wave per SIMD
   // with three row blocks -- the VALU-issue-bound phases of a wave run beside the other waves' MFMAs (DSS2_CHAIN_RS3=0: four waves)
-  static const int rs3 = [] { const char* e = getenv("DSS2_CHAIN_RS3"); return e ? atoi(e) : 1; }();
-  if (a.nrb == 3 && a.nmat == 3 && rsplit == 1 && a.ncg <= 4 && rs3) return launch_chain<3, 3, 12, 3, true>(a, ct, s);
-  if (a.nrb == 3 && a.nmat == 3 && rsplit == 1 && a.ncg <= 4) return launch_chain<3, 3, 4, 1, true>(a, ct, s);   // (8 waves would spill)
-  DSS2_CASE16_2(2, 2) DSS2_CASE16_2(2, 3) DSS2_CASE16_2(2, 4) DSS2_CASE16_2(4, 2)
-#undef DSS2_CASE16
-#undef DSS2_CASE16_2
-  set_error("gemm_prop_chain(bf16x6): unsupported (nrb=%d, nmat=%d, row split %d)", a.nrb, a.nmat, rsplit);
-  return 2;
+  if (nrb == 3 && nmat == 3 && rs == 3 && nw == 12) return launch_chain<3, 3, 12, 3, true>;
+  if (nrb == 3 && nmat == 3 && rs == 1 && nw == 4) return launch_chain<3, 3, 4, 1, true>;   // (8 waves would spill)
+  return nullptr;
 }
 
 }  // namespace dss2

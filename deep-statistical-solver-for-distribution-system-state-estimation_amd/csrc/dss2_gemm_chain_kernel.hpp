@@ -453,24 +453,28 @@ inline size_t chain_lds_bytes(int nrb, int kpad, int ncg, int ell_width, int rm_
   return TM * (size_t)(kpad + 4) * 4 + stage + TM * (size_t)ell_width * 8;
 }
 
+// A launch takes its block size and LDS bytes from the selection's record (chain_select, dss2_gemm_chain.hip).
+using ChainLauncher = int (*)(const dss2_gemm_prop_args&, const ChainTable&, const dss2_chain_kernel_t&, hipStream_t);
 template <int NRB, int NMAT, int NW, int RS, bool B16 = false>
-inline int launch_chain(const dss2_gemm_prop_args& a, const ChainTable& ct, hipStream_t stream) {
+inline int launch_chain(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_kernel_t& k, hipStream_t stream) {
   static std::atomic<uint32_t> lds_done{0};
   auto kern = gemm_chain_kernel<NRB, NMAT, NW, RS, B16>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_prop_chain")) return 1;
-  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * a.ncg * RS), chain_lds_bytes(NRB, a.kpad, a.ncg, a.ell_width, chain_rm(NRB, RS, B16, NMAT) ? NMAT : 0), stream, a, ct);
+  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(k.block), (size_t)k.lds_bytes, stream, a, ct);
   return check_launch("gemm_prop_chain");
 }
 
-
-// the bf16x6 instantiations live in their own translation unit (dss2_gemm_chain16.hip, compiled without packed fp32 ops)
-int launch_chain16(const dss2_gemm_prop_args& a, const ChainTable& ct, int rsplit, hipStream_t s);
-// 64-row tiles, one wave per column group: the tile kept in LDS as split bf16 planes (dss2_gemm_chain_sp.hip; DSS2_CHAIN_SP=0: off)
-bool chain_sp_supported(const dss2_gemm_prop_args& a);
-int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width);      // dss2_gemm_prop_chain_edge_supported's mask for a b_format-2 launch
-int launch_chain_sp(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, hipStream_t s);
-// 192-row tiles, six row blocks per wave (dss2_gemm_chain_sp6.hip)
-bool chain_sp6_supported(const dss2_gemm_prop_args& a);
-int launch_chain_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, hipStream_t s);
+// Which instantiations exist, written once per table: the selection asks (NULL: none), the dispatch calls what it gets.  The bf16x6
+// table lives in its own translation unit (dss2_gemm_chain16.hip, compiled without packed fp32 ops).
+ChainLauncher chain_launcher(int nrb, int nmat, int nw, int rs);
+ChainLauncher chain16_launcher(int nrb, int nmat, int nw, int rs);
+// The split-plane families: each says whether ITS kernels cover the shape (a.b_format 1 or 2) and with how much LDS; switches and
+// policy are chain_select's.  64-row tiles, one wave per column group (dss2_gemm_chain_sp.hip) ...
+bool chain_sp_shape(const dss2_gemm_prop_args& a, size_t* lds);
+int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width);      // the edge phases beside that kernel's f16x3 form
+int launch_chain_sp(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, const dss2_chain_kernel_t& k, hipStream_t s);
+// ... and 96- / 192-row tiles, three or six row blocks per wave (dss2_gemm_chain_sp6.hip)
+bool chain_sp6_shape(const dss2_gemm_prop_args& a, size_t* lds);
+int launch_chain_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, const dss2_chain_kernel_t& k, hipStream_t s);
 
 }  // namespace dss2

@@ -918,16 +918,15 @@ __global__ void __launch_bounds__(NW * 64, 2) gemm_chain_sp_kernel(const dss2_ge
 
 inline size_t chain_sp_lds_bytes(int ncg, int ell_width) { return (size_t)ncg * SP_REGION * 4 + (size_t)SP_TM * ell_width * 8 + 64; }      // (+ the f16x3 form's maxima)
 
-bool chain_sp_supported(const dss2_gemm_prop_args& a) {
-  static const int on = [] { const char* e = getenv("DSS2_CHAIN_SP"); return e ? atoi(e) : 1; }();
-  static const int f16on = [] { const char* e = getenv("DSS2_CHAIN_SP_F16"); return e ? atoi(e) : 1; }();
-  if (a.b_format == 2 && (!f16on || (a.kpad & 31) != 0)) return false;      // the f16x3 form: 16x16x32 MFMAs only
-  return on && (a.b_format == 1 || a.b_format == 2) && a.nrb == 2 && a.nmat >= 2 && a.nmat <= 3 && (a.kpad & 15) == 0 && a.kpad <= 32 * a.ncg &&
-         a.ncg >= 3 && a.ncg <= 8 && chain_sp_lds_bytes(a.ncg, a.ell_width) <= (size_t)kMaxLdsBytes;
+bool chain_sp_shape(const dss2_gemm_prop_args& a, size_t* lds) {
+  *lds = chain_sp_lds_bytes(a.ncg, a.ell_width);
+  if (a.b_format == 2 && (a.kpad & 31) != 0) return false;      // the f16x3 form: 16x16x32 MFMAs only
+  return (a.b_format == 1 || a.b_format == 2) && a.nrb == 2 && a.nmat >= 2 && a.nmat <= 3 && (a.kpad & 15) == 0 && a.kpad <= 32 * a.ncg &&
+         a.ncg >= 3 && a.ncg <= 8 && *lds <= (size_t)kMaxLdsBytes;
 }
 
 int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width) {
-  if (!(a.b_format == 2 && a.nrb == 2 && a.nmat == 3 && a.ncg == 4 && a.hout == 128 && a.kreal == 128 && chain_sp_supported(a))) return 0;
+  if (!(a.b_format == 2 && a.nrb == 2 && a.nmat == 3 && a.ncg == 4 && a.hout == 128 && a.kreal == 128)) return 0;
   const size_t region = (size_t)a.ncg * SP_REGION * 4;      // the edge images live where the planes / Horner slots do
   int m = 0;
   if (edge16_tile_route(a.hout, 2, edge_width, false) && e16_lds_bytes(SP_TM, edge_width, SP_TM) <= region) m |= 1;
@@ -936,16 +935,16 @@ int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width) {
 }
 
 template <int NMAT, int NW, int HM, int MS>
-static int launch_sp(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, hipStream_t stream) {
+static int launch_sp(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, const dss2_chain_kernel_t& k, hipStream_t stream) {
   static std::atomic<uint32_t> lds_done{0};
   auto kern = gemm_chain_sp_kernel<NMAT, NW, HM, MS>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_prop_chain(split planes)")) return 1;
-  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * a.ncg), chain_sp_lds_bytes(a.ncg, a.ell_width), stream, a, ct, hd);
+  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(k.block), (size_t)k.lds_bytes, stream, a, ct, hd);
   return check_launch("gemm_prop_chain(split planes)");
 }
 
 template <int HM>
-static int launch_sp_hm(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, hipStream_t s) {
+static int launch_sp_hm(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, const dss2_chain_kernel_t& k, hipStream_t s) {
   static const int ms16 = [] { const char* e = getenv("DSS2_CHAIN_MFMA16"); return e ? atoi(e) : 1; }();      // 0: the 32x32x16 form
   // (a layer gated by fp32 activations instead of bit words keeps eight row pieces of gate values beside the accumulators: the 16x16
   //  form has 24 registers less room, spills them on arrival and waits a memory latency per layer -- 124 us against 107)
@@ -953,27 +952,27 @@ static int launch_sp_hm(const dss2_gemm_prop_args& a, const ChainTable& ct, cons
   for (int i = 0; i < ct.n; ++i) fp32_gates = fp32_gates || (ct.l[i].relu_src && !ct.l[i].gate_bits);
   if (a.b_format == 2) {      // weights as two fp16 planes: the f16x3 form
     if (fp32_gates) { set_error("gemm_prop_chain(f16x3): layers gated by fp32 activations need bf16x3 weights (b_format 1)"); return 2; }
-    if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 2>(a, ct, hd, s) : launch_sp<2, 8, HM, 2>(a, ct, hd, s);
-    return a.ncg <= 4 ? launch_sp<3, 4, HM, 2>(a, ct, hd, s) : launch_sp<3, 8, HM, 2>(a, ct, hd, s);
+    if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 2>(a, ct, hd, k, s) : launch_sp<2, 8, HM, 2>(a, ct, hd, k, s);
+    return a.ncg <= 4 ? launch_sp<3, 4, HM, 2>(a, ct, hd, k, s) : launch_sp<3, 8, HM, 2>(a, ct, hd, k, s);
   }
   if (ms16 && (a.kpad & 31) == 0 && !fp32_gates) {
-    if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 1>(a, ct, hd, s) : launch_sp<2, 8, HM, 1>(a, ct, hd, s);
-    return a.ncg <= 4 ? launch_sp<3, 4, HM, 1>(a, ct, hd, s) : launch_sp<3, 8, HM, 1>(a, ct, hd, s);
+    if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 1>(a, ct, hd, k, s) : launch_sp<2, 8, HM, 1>(a, ct, hd, k, s);
+    return a.ncg <= 4 ? launch_sp<3, 4, HM, 1>(a, ct, hd, k, s) : launch_sp<3, 8, HM, 1>(a, ct, hd, k, s);
   }
-  if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 0>(a, ct, hd, s) : launch_sp<2, 8, HM, 0>(a, ct, hd, s);
-  return a.ncg <= 4 ? launch_sp<3, 4, HM, 0>(a, ct, hd, s) : launch_sp<3, 8, HM, 0>(a, ct, hd, s);      // (K = 3 would spill: chain_sp_supported says no)
+  if (a.nmat == 2) return a.ncg <= 4 ? launch_sp<2, 4, HM, 0>(a, ct, hd, k, s) : launch_sp<2, 8, HM, 0>(a, ct, hd, k, s);
+  return a.ncg <= 4 ? launch_sp<3, 4, HM, 0>(a, ct, hd, k, s) : launch_sp<3, 8, HM, 0>(a, ct, hd, k, s);      // (K = 3 would spill: chain_sp_shape says no)
 }
 
 static std::atomic<unsigned long long*> g_chain_clock_probe{nullptr};
 
-int launch_chain_sp(const dss2_gemm_prop_args& a, const ChainTable& ct_in, const dss2_chain_head* head, hipStream_t s) {
+int launch_chain_sp(const dss2_gemm_prop_args& a, const ChainTable& ct_in, const dss2_chain_head* head, const dss2_chain_kernel_t& k, hipStream_t s) {
   dss2_chain_head hd = {};
   if (head) hd = *head;
   ChainTable ct = ct_in;
   ct.clock_probe = g_chain_clock_probe.load(std::memory_order_relaxed);
-  if (hd.mode == 1) return launch_sp_hm<1>(a, ct, hd, s);
-  if (hd.mode == 2) return launch_sp_hm<2>(a, ct, hd, s);
-  return launch_sp_hm<0>(a, ct, hd, s);
+  if (hd.mode == 1) return launch_sp_hm<1>(a, ct, hd, k, s);
+  if (hd.mode == 2) return launch_sp_hm<2>(a, ct, hd, k, s);
+  return launch_sp_hm<0>(a, ct, hd, k, s);
 }
 
 }  // namespace dss2

@@ -585,38 +585,24 @@ __global__ void __launch_bounds__(256, NRB <= 3 ? 2 : 1) gemm_chain_sp6_kernel(c
 
 static size_t chain_sp6_lds_bytes(int nrb, int ncg, int ell_width) { return (size_t)ncg * s6_region(nrb) * 4 + (size_t)32 * nrb * ell_width * 8 + 64; }      // (+ the f16x3 form's maxima)
 
-}  // namespace dss2
-extern "C" int dss2_chain_sp6_single_group_min_tiles(void) {
-  static const int v = [] { const char* e = getenv("DSS2_CHAIN_SP6_NCG1"); return (e ? atoi(e) : 1) ? 768 : -1; }();
-  return v;
-}
-namespace dss2 {
-
-bool chain_sp6_supported(const dss2_gemm_prop_args& a) {
-  static const int on = [] { const char* e = getenv("DSS2_CHAIN_SP"); return e ? atoi(e) : 1; }();
-  static const int f16on = [] { const char* e = getenv("DSS2_CHAIN_SP_F16"); return e ? atoi(e) : 1; }();
-  if (a.b_format == 2 && !f16on) return false;
-  // (round 6: ONE column group -- dim_hid 32, the reference driver's model on 70-bus grids -- runs this form too, as single-wave
-  //  workgroups, seven of them per CU, where there are enough tiles to fill the chip that way: measured on the driver's model line,
-  //  2.47 -> 2.33 ms per step at 1024 tiles against the three-waves-per-column-group bf16x6 chain, but 1.55 -> 1.63 at 512 and 1.06 -> 1.15 ms at 64 tiles, where
-  //  a tile's latency is what counts.  A query (ntiles = 0) answers for the capability; the launch and the host's policy
-  //  (ops.py, dss2_chain_sp6_single_group_min_tiles) apply the tile count.  DSS2_CHAIN_SP6_NCG1=0: never)
-  if (a.ncg == 1 && (dss2_chain_sp6_single_group_min_tiles() < 0 || (a.ntiles > 0 && a.ntiles < dss2_chain_sp6_single_group_min_tiles()))) return false;
-  const int min_ncg = 1;
-  return on && (a.b_format == 1 || a.b_format == 2) && (a.nrb == 6 || a.nrb == 3) && a.nmat >= 2 && a.nmat <= 3 && (a.kpad & 15) == 0 && a.kpad <= 32 * a.ncg &&
-         a.ncg >= min_ncg && a.ncg <= 4 && chain_sp6_lds_bytes(a.nrb, a.ncg, a.ell_width) <= (size_t)(a.nrb == 3 ? kMaxLdsBytes / 2 : kMaxLdsBytes);
+// (ONE column group -- dim_hid 32, the reference driver's model on 70-bus grids -- runs this form too, as single-wave workgroups, seven
+//  of them per CU; from how many tiles on that pays is chain_select's policy, dss2_gemm_chain.hip)
+bool chain_sp6_shape(const dss2_gemm_prop_args& a, size_t* lds) {
+  *lds = chain_sp6_lds_bytes(a.nrb, a.ncg, a.ell_width);
+  return (a.b_format == 1 || a.b_format == 2) && (a.nrb == 6 || a.nrb == 3) && a.nmat >= 2 && a.nmat <= 3 && (a.kpad & 15) == 0 && a.kpad <= 32 * a.ncg &&
+         a.ncg >= 1 && a.ncg <= 4 && *lds <= (size_t)(a.nrb == 3 ? kMaxLdsBytes / 2 : kMaxLdsBytes);
 }
 
 template <int NRB, int NMAT, int DIR, int HM = 0, bool F16 = false, int RPA = 4 * NRB>
-static int launch_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, hipStream_t stream) {
+static int launch_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head& hd, const dss2_chain_kernel_t& k, hipStream_t stream) {
   static std::atomic<uint32_t> lds_done{0};
   auto kern = gemm_chain_sp6_kernel<NRB, NMAT, DIR, HM, F16, RPA>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_prop_chain(split planes, 192 rows)")) return 1;
-  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * a.ncg), chain_sp6_lds_bytes(NRB, a.ncg, a.ell_width), stream, a, ct, hd);
+  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(k.block), (size_t)k.lds_bytes, stream, a, ct, hd);
   return check_launch("gemm_prop_chain(split planes, 192 rows)");
 }
 
-int launch_chain_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, hipStream_t s) {
+int launch_chain_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const dss2_chain_head* head, const dss2_chain_kernel_t& k, hipStream_t s) {
   bool fwd = true, bwd = true;
   for (int i = 0; i < ct.n; ++i) {
     const dss2_chain_layer& L = ct.l[i];
@@ -631,24 +617,24 @@ int launch_chain_sp6(const dss2_gemm_prop_args& a, const ChainTable& ct, const d
   if (head) {      // the backward head (mode 2) rides in the staging of the data-gradient launch; nothing else is built here
     if (head->mode != 2 || !bwd) { set_error("gemm_prop_chain_head: tall tiles take the backward head (mode 2) on a data-gradient chain only"); return 2; }
     hd = *head;
-    if (rpa9) return launch_sp6<3, 3, 2, 2, true, 9>(a, ct, hd, s);
+    if (rpa9) return launch_sp6<3, 3, 2, 2, true, 9>(a, ct, hd, k, s);
     if (a.b_format == 2) {
-      if (a.nrb == 3) return a.nmat == 2 ? launch_sp6<3, 2, 2, 2, true>(a, ct, hd, s) : launch_sp6<3, 3, 2, 2, true>(a, ct, hd, s);
-      return a.nmat == 2 ? launch_sp6<6, 2, 2, 2, true>(a, ct, hd, s) : launch_sp6<6, 3, 2, 2, true>(a, ct, hd, s);
+      if (a.nrb == 3) return a.nmat == 2 ? launch_sp6<3, 2, 2, 2, true>(a, ct, hd, k, s) : launch_sp6<3, 3, 2, 2, true>(a, ct, hd, k, s);
+      return a.nmat == 2 ? launch_sp6<6, 2, 2, 2, true>(a, ct, hd, k, s) : launch_sp6<6, 3, 2, 2, true>(a, ct, hd, k, s);
     }
-    if (a.nrb == 3) return a.nmat == 2 ? launch_sp6<3, 2, 2, 2>(a, ct, hd, s) : launch_sp6<3, 3, 2, 2>(a, ct, hd, s);
-    return a.nmat == 2 ? launch_sp6<6, 2, 2, 2>(a, ct, hd, s) : launch_sp6<6, 3, 2, 2>(a, ct, hd, s);
+    if (a.nrb == 3) return a.nmat == 2 ? launch_sp6<3, 2, 2, 2>(a, ct, hd, k, s) : launch_sp6<3, 3, 2, 2>(a, ct, hd, k, s);
+    return a.nmat == 2 ? launch_sp6<6, 2, 2, 2>(a, ct, hd, k, s) : launch_sp6<6, 3, 2, 2>(a, ct, hd, k, s);
   }
   const int dir = fwd ? 1 : (bwd ? 2 : 0);      // (0: a layer table that mixes the feature sets runs the generic instantiation)
   if (a.b_format == 2) {      // f16x3: the direction-specialised forms only
     if (dir == 0) { set_error("gemm_prop_chain(f16x3): a layer table that mixes forward and data-gradient features needs bf16x3 weights (b_format 1)"); return 2; }
-    if (rpa9) return dir == 1 ? launch_sp6<3, 3, 1, 0, true, 9>(a, ct, hd, s) : launch_sp6<3, 3, 2, 0, true, 9>(a, ct, hd, s);
-#define DSS2_S6_LAUNCH_H(NRB, NMAT) (dir == 1 ? launch_sp6<NRB, NMAT, 1, 0, true>(a, ct, hd, s) : launch_sp6<NRB, NMAT, 2, 0, true>(a, ct, hd, s))
+    if (rpa9) return dir == 1 ? launch_sp6<3, 3, 1, 0, true, 9>(a, ct, hd, k, s) : launch_sp6<3, 3, 2, 0, true, 9>(a, ct, hd, k, s);
+#define DSS2_S6_LAUNCH_H(NRB, NMAT) (dir == 1 ? launch_sp6<NRB, NMAT, 1, 0, true>(a, ct, hd, k, s) : launch_sp6<NRB, NMAT, 2, 0, true>(a, ct, hd, k, s))
     if (a.nrb == 3) return a.nmat == 2 ? DSS2_S6_LAUNCH_H(3, 2) : DSS2_S6_LAUNCH_H(3, 3);
     return a.nmat == 2 ? DSS2_S6_LAUNCH_H(6, 2) : DSS2_S6_LAUNCH_H(6, 3);
 #undef DSS2_S6_LAUNCH_H
   }
-#define DSS2_S6_LAUNCH(NRB, NMAT) (dir == 1 ? launch_sp6<NRB, NMAT, 1>(a, ct, hd, s) : (dir == 2 ? launch_sp6<NRB, NMAT, 2>(a, ct, hd, s) : launch_sp6<NRB, NMAT, 0>(a, ct, hd, s)))
+#define DSS2_S6_LAUNCH(NRB, NMAT) (dir == 1 ? launch_sp6<NRB, NMAT, 1>(a, ct, hd, k, s) : (dir == 2 ? launch_sp6<NRB, NMAT, 2>(a, ct, hd, k, s) : launch_sp6<NRB, NMAT, 0>(a, ct, hd, k, s)))
   if (a.nrb == 3) return a.nmat == 2 ? DSS2_S6_LAUNCH(3, 2) : DSS2_S6_LAUNCH(3, 3);
   return a.nmat == 2 ? DSS2_S6_LAUNCH(6, 2) : DSS2_S6_LAUNCH(6, 3);
 #undef DSS2_S6_LAUNCH

@@ -126,91 +126,70 @@ def _tiles(topo) -> Tiling:
     return topo.tiling if isinstance(topo, Topology) else topo
 
 
-def chain_supported(topo: Topology, nmat: int, hid: int, transposed: bool, have16: bool = False) -> bool:
+def chain_plan(topo, nmat: int, hid: int, nout: int = 0, transposed: bool = False) -> "_lib.ChainPlan":
+    """The record the library dispatches a chain of hid -> hid layers from (dss2_gemm_prop_chain_plan), per weight format: kernel family,
+    geometry, gate words, head / edge capability -- for the tile set's real tile count and the direction's ELL width (no ELL slices:
+    an empty record).  ``nout``: the head that would ride in the launch (0: none)."""
+    ts, p = _tiles(topo), _lib.ChainPlan()
+    ell = (ts.ellT if ts.ellT_tiles is not None else 0) if transposed else (ts.ell if ts.ell_tiles is not None else 0)
+    _lib.check(_lib.lib().dss2_gemm_prop_chain_plan(ts.nrb, nmat, hid, ell, ts.ntiles, nout, ts.ell if ts.ell_ent_tiles is not None else 0,
+                                                    C.byref(p)), "dss2_gemm_prop_chain_plan")
+    return p
+
+
+# Readers of that record with the flags that govern them.  ``plan`` / ``plans`` (forward, transposed): records the caller already holds
+# (route.block_route asks once per direction); else the library is asked.
+def chain_supported(topo: Topology, nmat: int, hid: int, transposed: bool, have16: bool = False, plan=None) -> bool:
     """True when n >= 2 consecutive hid -> hid layers can run as one chained launch (dss2_gemm_prop_chain).  ``have16``: the
     caller holds bf16x6 weight packs, so shapes that only the split-plane form covers (192-row tiles) count too."""
-    ts = _tiles(topo)
-    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
-    if not FL.CHAIN_LAYERS or tiles is None:
-        return False
-    return bool(_lib.lib().dss2_gemm_prop_chain_supported(ts.nrb, nmat, hid, hid, ell)) or (
-        have16 and chain16_supported(topo, nmat, hid, transposed))
+    p = plan or chain_plan(topo, nmat, hid, 0, transposed)
+    return bool(FL.CHAIN_LAYERS and (p.fmt[0].family or (have16 and FL.CHAIN_BF16 and p.fmt[1].family)))
 
 
-def _single_group_tall_veto(ts: Tiling, hid: int) -> bool:
-    """96- / 192-row tiles with ONE column group (hid <= 32): the split-plane chain runs them as single-wave workgroups, which pays from
-    dss2_chain_sp6_single_group_min_tiles() tiles on (the library applies the same count at launch); below it the block keeps the
-    multi-wave chain of that shape with its bf16x3 weights and fp32 gates, i.e. every sp6-only capability is declined here."""
-    if hid > 32 or ts.nrb not in (3, 6):
-        return False
-    m = int(_lib.lib().dss2_chain_sp6_single_group_min_tiles())
-    return m < 0 or ts.ntiles < m
+def chain16_supported(topo: Topology, nmat: int, hid: int, transposed: bool, plan=None) -> bool:
+    """True when the chain can run its tile GEMM on the bf16 matrix pipe (bf16x6, fp32-accurate; dss2_gemm_chain16.hip)."""
+    return bool(FL.CHAIN_BF16 and (plan or chain_plan(topo, nmat, hid, 0, transposed)).fmt[1].family)
 
 
-def chain_gate_words(topo: Topology, nmat: int, hid: int) -> int:
+def chain_gate_words(topo: Topology, nmat: int, hid: int, plans=None) -> int:
     """64-bit words per tile of a layer's sign-bit buffer (``y_bits`` of a forward chain -> ``gate_bits`` of the data-gradient
     chain over the same tiles); 0 where the chain kernel of this shape has no bit form (or either direction is not chained)."""
-    ts = _tiles(topo)
-    if not (FL.CHAIN_LAYERS and FL.CHAIN_BF16 and FL.CHAIN_GATE_BITS) or ts.ell_tiles is None or ts.ellT_tiles is None:
+    if not (FL.CHAIN_LAYERS and FL.CHAIN_BF16 and FL.CHAIN_GATE_BITS):
         return 0
-    if _single_group_tall_veto(ts, hid):
-        return 0
-    cache = ts.gate_words if isinstance(ts, Tiling) else {}      # (asked once per forward: keep the two library calls off the step)
-    gw = cache.get((nmat, hid))
-    if gw is None:
-        L = _lib.lib()
-        gw = cache[(nmat, hid)] = min(int(L.dss2_gemm_prop_chain_gate_words(ts.nrb, nmat, hid, hid, ts.ell)),
-                                      int(L.dss2_gemm_prop_chain_gate_words(ts.nrb, nmat, hid, hid, ts.ellT)))
-    return gw
+    return min(p.fmt[1].gate_words for p in plans or (chain_plan(topo, nmat, hid), chain_plan(topo, nmat, hid, 0, True)))
 
 
-def chain16_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
-    """True when the chain can run its tile GEMM on the bf16 matrix pipe (bf16x6, fp32-accurate; dss2_gemm_chain16.hip)."""
-    ts = _tiles(topo)
-    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
-    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop_chain16_supported(ts.nrb, nmat, hid, hid, ell))
-
-
-def chain_f16_supported(topo: Topology, nmat: int, hid: int) -> bool:
+def chain_f16_supported(topo: Topology, nmat: int, hid: int, plans=None) -> bool:
     """True when BOTH chains of a block (forward, data gradients) can run their tile GEMM as f16x3 (b_format 2: weights as two fp16
-    planes with scale exponents, _PackPlan f16_groups): the split-plane chain of 64-row tiles with bit-word ReLU gates
-    (csrc/dss2_gemm_chain_sp.hip, MS = 2).  flags.CHAIN_F16 = False: bf16x6."""
-    ts = _tiles(topo)
-    if not (FL.CHAIN_F16 and FL.CHAIN_BF16 and ts.ell_tiles is not None and ts.ellT_tiles is not None and chain_gate_words(topo, nmat, hid) > 0):
-        return False
-    L = _lib.lib()
-    return bool(L.dss2_gemm_prop_chain_f16_supported(ts.nrb, nmat, hid, hid, ts.ell)) and bool(L.dss2_gemm_prop_chain_f16_supported(ts.nrb, nmat, hid, hid, ts.ellT))
+    planes with scale exponents, _PackPlan f16_groups): the split-plane chains with bit-word ReLU gates
+    (csrc/dss2_gemm_chain_sp.hip, MS = 2; _sp6.hip).  flags.CHAIN_F16 = False: bf16x6."""
+    plans = plans or (chain_plan(topo, nmat, hid), chain_plan(topo, nmat, hid, 0, True))
+    return bool(FL.CHAIN_F16 and FL.CHAIN_BF16 and chain_gate_words(topo, nmat, hid, plans) > 0 and all(p.fmt[2].gate_words > 0 for p in plans))
 
 
-def chain_head_supported(topo: Topology, nmat: int, hid: int, nout: int, transposed: bool) -> bool:
+def chain_head_supported(topo: Topology, nmat: int, hid: int, nout: int, transposed: bool, plan=None) -> bool:
     """True when the narrow head TAGConv (hid -> nout) can ride inside the chained launch of the hid -> hid layers
     (dss2_gemm_prop_chain_head: forward = the head after the last chained layer, transposed = the chain's input computed from
     the head's upstream gradient); DSS2_CHAIN_HEAD=0 switches it off."""
-    ts = _tiles(topo)
-    ell, tiles = (ts.ellT, ts.ellT_tiles) if transposed else (ts.ell, ts.ell_tiles)
-    if _single_group_tall_veto(ts, hid):
-        return False
-    return bool(FL.CHAIN_HEAD) and FL.CHAIN_BF16 and tiles is not None and bool(      # (a mask of modes: bit 0 forward, bit 1 backward)
-        _lib.lib().dss2_gemm_prop_chain_head_supported(ts.nrb, nmat, hid, hid, ell, nout) & (2 if transposed else 1))
+    p = plan or chain_plan(topo, nmat, hid, nout, transposed)      # (a mask of modes: bit 0 forward, bit 1 backward)
+    return bool(FL.CHAIN_HEAD and FL.CHAIN_BF16 and p.fmt[1].head_modes & (2 if transposed else 1))
 
 
-def chain_edge_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:
+def chain_edge_supported(topo: Topology, nmat: int, hid: int, transposed: bool, plan=None) -> bool:
     """True when the edge MLP's first Linear can run as a phase of the chain with the fused head (dss2_chain_edge): forward = the chain
     computes its input S, transposed = the data-gradient chain runs the edge backward on conv 0's input gradient.  64-row tiles, f16x3,
     hid 128, the bf16x6 tile edge kernels.  flags.CHAIN_EDGE = False: the edge launches of their own."""
     ts = _tiles(topo)
-    if not (FL.CHAIN_EDGE and FL.EDGE_TILE_KERNELS and ts.ell_ent_tiles is not None and ts.ell_tiles is not None and ts.ellT_tiles is not None):
+    if not (FL.CHAIN_EDGE and FL.EDGE_TILE_KERNELS and ts.ell_tiles is not None and ts.ellT_tiles is not None):
         return False
-    ell = ts.ellT if transposed else ts.ell
-    return bool(_lib.lib().dss2_gemm_prop_chain_edge_supported(ts.nrb, nmat, hid, hid, ell, ts.ell) & (2 if transposed else 1))
+    return bool((plan or chain_plan(topo, nmat, hid, 0, transposed)).fmt[2].edge_modes & (2 if transposed else 1))
 
 
-def chain_head_wgrad_supported(topo: Topology, nmat: int, hid: int, nout: int) -> bool:
+def chain_head_wgrad_supported(topo: Topology, nmat: int, hid: int, nout: int, plan=None) -> bool:
     """True when the data-gradient chain with the fused head (mode 2) can also form the head's weight gradient in its staging
-    (dss2_chain_head.wg_slab, round 5): 64-, 96- and 192-row tiles, nout <= 2.  flags.CHAIN_HEAD_WGRAD = False: the narrow weight-gradient launch."""
-    ts = _tiles(topo)
-    return bool(FL.CHAIN_HEAD_WGRAD) and ts.ellT_tiles is not None and bool(
-        _lib.lib().dss2_gemm_prop_chain_head_wgrad_supported(ts.nrb, nmat, hid, hid, ts.ellT, nout))
+    (dss2_chain_head.wg_slab, round 5): 64-, 96- and 192-row tiles, nout <= 2.  flags.CHAIN_HEAD_WGRAD = False: the narrow
+    weight-gradient launch."""
+    return bool(FL.CHAIN_HEAD_WGRAD and (plan or chain_plan(topo, nmat, hid, nout, True)).fmt[1].head_wgrad)
 
 
 def gemm16_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> bool:

@@ -1,18 +1,18 @@
 """Which kernels an MPN / SkipMPN block runs, decided ONCE per forward call.
 
-``block_route`` reads ``flags`` and the library's shape queries when the forward starts and returns every decision of the
-block, forward and backward, as one immutable record.  ``networks._ensure_plans`` and ``networks._mpn_forward`` follow it, and
-the forward hands it to ``networks._mpn_backward``, which evaluates no predicate of its own: the two chains of a block (the
-forward chain writes ``S`` and the gate bits that the data-gradient chain reads) cannot disagree.  A new fused form registers
-its condition HERE, once, as a field.  Nothing is cached: a flag flipped between two calls takes effect at the next forward
-(not between a forward and its own backward)."""
+``block_route`` reads ``flags`` and the library's chain record (``ops.chain_plan``, once per direction) when the forward starts
+and returns every decision of the block, forward and backward, as one immutable record.  ``networks._ensure_plans`` and
+``networks._mpn_forward`` follow it, and the forward hands it to ``networks._mpn_backward``, which evaluates no predicate of its
+own: the two chains of a block (the forward chain writes ``S`` and the gate bits that the data-gradient chain reads) cannot
+disagree.  A new fused form registers its condition HERE, once, as a field.  Nothing is cached: a flag flipped between two calls
+takes effect at the next forward (not between a forward and its own backward)."""
 from __future__ import annotations
 
 from typing import NamedTuple, Tuple
 
 from . import flags as FL
 from .ops import (_tiles, chain16_supported, chain_edge_supported, chain_f16_supported, chain_gate_words, chain_head_supported,
-                  chain_head_wgrad_supported, chain_supported, gemm16_supported, is_narrow)
+                  chain_head_wgrad_supported, chain_plan, chain_supported, gemm16_supported, is_narrow)
 from .topology import Topology
 
 
@@ -53,35 +53,36 @@ def block_route(mod, topo: Topology, need_dx: bool, in_stack: bool) -> BlockRout
     L, nmat, hid, nout = mod.n_gnn_layers, mod.K + 1, mod.dim_hid, mod.dim_out
     houts = [nout if l == L - 1 else hid for l in range(L)]
     glob = use_global_path(topo, nmat)
+    pf, pb = chain_plan(topo, nmat, hid, nout, False), chain_plan(topo, nmat, hid, nout, True)      # what the chain kernels say, per direction
     fold = bool(FL.FOLD_W2 and not is_narrow(nmat, houts[0]) and not glob)
     b16 = tuple(range(1, L)) if (FL.CHAIN_BF16 and not glob and hid % 4 == 0 and hid <= 256 and not is_narrow(nmat, hid) and L >= 2
                                  and (L >= 3 or gemm16_supported(topo, nmat, hid, False))) else ()
     # ... as f16x3 where both chains of the block have the form (64-row tiles; csrc/dss2_gemm_chain_sp.hip MS = 2) and the backward
     # takes the chained route
-    f16 = bool(b16 and L >= 3 and FL.WGRAD_BATCH and chain_f16_supported(topo, nmat, hid))
+    f16 = bool(b16 and L >= 3 and FL.WGRAD_BATCH and chain_f16_supported(topo, nmat, hid, (pf, pb)))
     narrow_head = is_narrow(nmat, nout)
     # the edge MLP inside the chains: what both directions ask for besides their own fused head and shape query
     edge_ok = fold and f16 and not in_stack and not need_dx
 
-    n_chain = L - 1 if (L - 1 >= 2 and chain_supported(topo, nmat, hid, False, bool(b16))) else 0
-    use16 = bool(n_chain and b16 and chain16_supported(topo, nmat, hid, False))
-    gw = chain_gate_words(topo, nmat, hid) if use16 else 0
+    n_chain = L - 1 if (L - 1 >= 2 and chain_supported(topo, nmat, hid, False, bool(b16), pf)) else 0
+    use16 = bool(n_chain and b16 and chain16_supported(topo, nmat, hid, False, pf))
+    gw = chain_gate_words(topo, nmat, hid, (pf, pb)) if use16 else 0
     head = bool(use16 and FL.CHAIN_HEAD_FWD and n_chain <= FL.CHAIN_MAX and not glob and narrow_head
-                and chain_head_supported(topo, nmat, hid, nout, False))
-    edge = bool(head and edge_ok and chain_edge_supported(topo, nmat, hid, False))
+                and chain_head_supported(topo, nmat, hid, nout, False, pf))
+    edge = bool(head and edge_ok and chain_edge_supported(topo, nmat, hid, False, pf))
 
     def tall16(l, transposed):      # a single hid -> hid layer with bf16x3 weights (b16 is empty on the global path)
         return bool(houts[l] == hid and (1 + l) in b16 and not f16 and gemm16_supported(topo, nmat, hid, transposed))
     first = L if head else n_chain
     g16 = tuple(first <= l < L - 1 and tall16(l, False) for l in range(L))
 
-    bwd_chain = bool(L >= 3 and FL.WGRAD_BATCH and chain_supported(topo, nmat, hid, True, bool(b16)))
-    bwd_use16 = bool(bwd_chain and b16 and chain16_supported(topo, nmat, hid, True))
+    bwd_chain = bool(L >= 3 and FL.WGRAD_BATCH and chain_supported(topo, nmat, hid, True, bool(b16), pb))
+    bwd_use16 = bool(bwd_chain and b16 and chain16_supported(topo, nmat, hid, True, pb))
     # (tall tiles: only the direction-specialised data-gradient chain has the head form -- its layers gate with the forward's bit words)
-    bwd_head = bool(bwd_use16 and L - 1 <= FL.CHAIN_MAX and narrow_head and chain_head_supported(topo, nmat, hid, nout, True)
+    bwd_head = bool(bwd_use16 and L - 1 <= FL.CHAIN_MAX and narrow_head and chain_head_supported(topo, nmat, hid, nout, True, pb)
                     and (_tiles(topo).nrb <= 2 or gw > 0))
-    bwd_head_wgrad = bool(bwd_head and chain_head_wgrad_supported(topo, nmat, hid, nout))
-    bwd_edge = bool(bwd_head and edge_ok and chain_edge_supported(topo, nmat, hid, True))
+    bwd_head_wgrad = bool(bwd_head and chain_head_wgrad_supported(topo, nmat, hid, nout, pb))
+    bwd_edge = bool(bwd_head and edge_ok and chain_edge_supported(topo, nmat, hid, True, pb))
     # The folded conv 0 joins the batched launch of the plain layers (round 4; flags.WGRAD_JOIN_FOLDED = False: its own launch).
     # Round 3 kept it apart because three layers x 85 workgroups leave a 13-vs-12-tile tail at C2; measured now, the
     # joined launch is 141 us against 93 + 57, and -- what matters more -- the step writes and re-reads half the slabs

@@ -58,10 +58,9 @@ class Tiling:
     ell_ent_tiles: Optional[torch.Tensor]      # ... (column, edge entry)
     ellT_ent_tiles: Optional[torch.Tensor]
     gain_bits: Dict[int, int] = field(default_factory=dict)                 # ops._wgrad_mode: nmat -> headroom bits of this tile set
-    gate_words: Dict[Tuple[int, int], int] = field(default_factory=dict)    # ops.chain_gate_words: (nmat, hid) -> words per tile (primary only)
 
 
-_TILING_FIELDS = frozenset(Tiling.__slots__) - {"gain_bits", "gate_words"}
+_TILING_FIELDS = frozenset(Tiling.__slots__) - {"gain_bits"}
 
 
 @dataclass(frozen=True)

@@ -317,9 +317,10 @@ typedef struct dss2_gemm_prop_args {
 } dss2_gemm_prop_args;
 
 int dss2_gemm_prop(const dss2_gemm_prop_args* args_host, void* stream);
-/* Policy constant shared with the host: 96- / 192-row tiles with ONE column group (hout <= 32) take the split-plane chain -- single-wave
- * workgroups -- only from this many tiles on (a launch with fewer runs the multi-wave chain of that shape); -1: never
- * (DSS2_CHAIN_SP6_NCG1=0).  The *_supported queries below answer for the capability, without a tile count. */
+/* Policy constant: 96- / 192-row tiles with ONE column group (hout <= 32) take the split-plane chain -- single-wave workgroups -- only
+ * from this many tiles on (a launch with fewer runs the multi-wave chain of that shape, which 192-row tiles do not have); -1: never
+ * (DSS2_CHAIN_SP6_NCG1=0).  Applied in one place, dss2_gemm_prop_chain_plan; the *_supported queries below answer for the
+ * capability, without a tile count. */
 int dss2_chain_sp6_single_group_min_tiles(void);
 
 /* ---- layer chain: n_layers (<= 8) H -> H layers of dss2_gemm_prop in ONE launch, the activation
@@ -403,6 +404,33 @@ int dss2_gemm_prop_chain16_supported(int nrb, int nmat, int kreal, int hout, int
  * activations (relu_src without gate_bits) are refused -- callers keep bf16x3 weights for those.  Also through
  * dss2_gemm_prop_chain_head.  Errors of the size of fp32 arithmetic's own rounding. */
 int dss2_gemm_prop_chain_f16_supported(int nrb, int nmat, int kreal, int hout, int ell_width);
+
+/* The ONE decision behind the seven queries above and behind the dispatch of dss2_gemm_prop_chain(_head) (chain_select in
+ * csrc/dss2_gemm_chain.hip): for a chain of hid -> hid layers on tiles of 32 * nrb rows, per weight format (args.b_format 0, 1, 2),
+ * the kernel a launch runs, its geometry, and what that kernel can carry. */
+enum dss2_chain_family {
+  DSS2_CHAIN_NONE = 0,   /* the launch is refused                                                                              */
+  DSS2_CHAIN_FP32,       /* fp32 MFMAs, multi-wave (dss2_gemm_chain.hip)                                                       */
+  DSS2_CHAIN_BF16X6,     /* bf16x6, multi-wave (dss2_gemm_chain16.hip)                                                         */
+  DSS2_CHAIN_SP,         /* split planes, 64-row tiles (dss2_gemm_chain_sp.hip): bf16x6 (format 1) or f16x3 (format 2)         */
+  DSS2_CHAIN_SP6         /* split planes, 96- / 192-row tiles (dss2_gemm_chain_sp6.hip)                                        */
+};
+typedef struct dss2_chain_kernel_t {
+  int32_t family;        /* dss2_chain_family                                                                                  */
+  int32_t row_split;     /* waves that share a column group (1, 2, or 3 on 96-row tiles)                                       */
+  int32_t waves;         /* the wave count the kernel is instantiated for (split planes of tall tiles: the column groups)      */
+  int32_t block, lds_bytes;   /* threads per workgroup, dynamic LDS of the launch                                              */
+  int32_t gate_words;    /* 64-bit words per tile of y_bits / gate_bits of the format's split-plane form; 0: it has none.
+                          * (> 0 beside family NONE: an ELL width above 32, which the chain refuses for these tiles)           */
+  int32_t head_modes;    /* mask of the dss2_chain_head modes (bit 0: mode 1, bit 1: mode 2) for the nout asked; 0: no head    */
+  int32_t head_wgrad;    /* != 0: a mode-2 launch also forms the head's weight gradient (dss2_chain_head.wg_slab)              */
+  int32_t edge_modes;    /* mask of the dss2_chain_edge phases for the edge_width asked (format 2 only)                        */
+} dss2_chain_kernel_t;
+typedef struct dss2_chain_plan_t { dss2_chain_kernel_t fmt[3]; } dss2_chain_plan_t;
+/* ntiles: the launch's tile count, 0 = "for the capability" (what the queries above ask).  nout / edge_width: 0 = no head / no edge
+ * phase asked.  ell_width is the chain's own (the transposed one for a data-gradient chain). */
+int dss2_gemm_prop_chain_plan(int nrb, int nmat, int hid, int ell_width, int ntiles, int nout, int edge_width, dss2_chain_plan_t* out);
+
 /* != 0: dss2_gemm_prop (one layer) accepts args.b_format = 1 for this shape -- the tall tiles (128 / 192 rows) that run
  * matrix-sequentially with the X tile staged in two K halves; same bf16x6 arithmetic as the chain. */
 int dss2_gemm_prop16_supported(int nrb, int nmat, int kreal, int hout, int max_nnz, int ell_width);

@@ -602,6 +602,45 @@ def test_tall_tiles_matrix_sequential(pkg, oracle, hid, L, K):
         assert rel_err(p.grad, q.grad) < 2e-5, n
 
 
+def test_tall_tiles_one_column_group_below_the_chain_tile_count(pkg, oracle):
+    """dim_hid 32 on 192-row tiles, six of them: the split-plane chain takes one column group only from
+    dss2_chain_sp6_single_group_min_tiles() tiles on and 192 rows have no multi-wave chain, so the block runs layer by layer -- the
+    launches of flags.CHAIN_LAYERS = False, bit for bit.  (Routed from queries without a tile count the forward ended in a refusal.)"""
+    torch.manual_seed(0)
+    b = pkg.synthetic.make_batch(["ober179"], 6, seed=0)
+    ref = oracle.MPN(8, 6, 2, 32, 4, 2, 0.0).double()
+    mine = pkg.MPN(8, 6, 2, 32, 4, 2, 0.0)
+    mine.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    mine = mine.to(DEV)
+    b64 = {"x": b["x"].double(), "edge_index": b["edge_index"], "edge_attr": b["edge_attr"].double()}
+    out64, _ = oracle.train_step(ref, b64, tuple(s.double() for s in b["stats"]))
+    x, ei, ea = b["x"].to(DEV), b["edge_index"].to(DEV), b["edge_attr"].to(DEV)
+    st = tuple(s.to(DEV) for s in b["stats"])
+    topo = pkg.topology.get_topology(ei, x.shape[0])
+    assert (topo.nrb, topo.ntiles) == (6, 6) and 0 < topo.ntiles < pkg._lib.lib().dss2_chain_sp6_single_group_min_tiles()
+    route = pkg.route.block_route(mine, topo, False, False)
+    assert (route.n_chain, route.bwd_chain, route.gw) == (0, False, 0)
+
+    def step():
+        for q in mine.parameters():
+            q.grad = None
+        out = mine(x[:, :8], ei, ea[:, :6])
+        _loss(pkg.data, x, ei, ea, st, out, oracle.DEFAULT_REG_COEFS).backward()
+        return out.detach().clone(), [q.grad.clone() for q in mine.parameters()]
+
+    out, grads = step()
+    keep = pkg.flags.CHAIN_LAYERS
+    pkg.flags.CHAIN_LAYERS = False
+    try:
+        out_u, grads_u = step()
+    finally:
+        pkg.flags.CHAIN_LAYERS = keep
+    assert torch.equal(out, out_u) and all(torch.equal(g, h) for g, h in zip(grads, grads_u))
+    assert rel_err(out, out64) < TOL_OUT
+    for g, (n, q) in zip(grads, ref.named_parameters()):
+        assert rel_err(g, q.grad) < TOL_GRAD, (n, rel_err(g, q.grad))
+
+
 def test_fused_loss_finish_is_bitwise_the_two_launch_form_under_repetition(pkg, oracle):
     """data.py:443-459's five batch sums: the LAST workgroup of the partials launch sums the workgroups' partials (DSS2_WLS_FUSED_FINISH;
     handed over through memory without a release fence, csrc/dss2_loss.hip).  Same summation order as the one-workgroup finish launch,

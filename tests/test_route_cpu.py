@@ -20,6 +20,7 @@ BATCHES = {
     "ober_sub_64": (3, 64, 4480, 3, 3, 288, 288, 70),            # ... below the single-group tile count (768)
     "ober179_1024": (6, 1024, 183296, 3, 3, 576, 576, 179),      # the 179-bus feeder: 192-row tiles
     "mixed_4096": (2, 1024, 61440, 4, 4, 256, 256, 60),          # C5 shard: cigre14 + cigre14_reswitched
+    "ober179_64": (6, 64, 11456, 3, 3, 576, 576, 179),           # ... 192-row tiles below the single-group tile count
 }
 
 FIELDS = ("glob", "fold", "b16", "f16", "n_chain", "use16", "gw", "head", "edge", "g16",
@@ -75,6 +76,13 @@ CASES = [
      (False, False, (1, 2, 3), True, 3, True, 128, True, False, (False, False, False, False), True, True, True, True, False, False, (False, False, False, False), (True, True, True, False))),
     ('C2, WGRAD_JOIN_FOLDED off', 'cigre14_4096', (128, 4, 2, 2), False, False, 'WGRAD_JOIN_FOLDED',
      (False, True, (1, 2, 3), True, 3, True, 128, True, True, (False, False, False, False), True, True, True, True, True, False, (False, False, False, False), (False, True, True, False))),
+    # 192-row tiles, ONE column group, fewer tiles than the split-plane chain takes: there is no multi-wave chain of 192 rows, so the block
+    # runs layer by layer -- the route of CHAIN_LAYERS = False (the queries without a tile count said "chained"; the launch refused)
+    ('feeder179 B=64, H=32', 'ober179_64', (32, 4, 2, 2), False, False, None,
+     (False, True, (1, 2, 3), False, 0, False, 0, False, False, (False,) * 4, False, False, False, False, False, False, (False,) * 4, (False, True, True, False))),
+    ('driver block, ober179 B=64', 'ober179_64', (32, 8, 2, 8), True, True, None,
+     (False, True, (1, 2, 3, 4, 5, 6, 7), False, 0, False, 0, False, False, (False,) * 8, False, False, False, False, False, False, (False,) * 8,
+      (False, True, True, True, True, True, True, False))),
 ]
 
 
