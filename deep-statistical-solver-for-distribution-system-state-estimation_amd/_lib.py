@@ -87,6 +87,26 @@ CHAIN_NONE, CHAIN_FP32, CHAIN_BF16X6, CHAIN_SP, CHAIN_SP6 = range(5)      # dss2
  WGRAD_F16_32, WGRAD_F16_TALL, WGRAD_F16_TALL_PAIR) = range(10)
 
 
+class EdgeArgs(C.Structure):
+    """dss2_edge_args: the operands of the edge MLP's forward / backward and the graph, as tiles with an entry table or as the CSR."""
+    _fields_ = ([(n, C.c_void_p if t == "p" else C.c_int64) for n, t in zip(("x", "ldx", "ea", "ldea", "W1", "b1", "dS", "tile_start", "ell_ent"), "plplppppp")] +
+                [(n, C.c_int32) for n in ("ell_width", "nrb", "ntiles", "pad_")] + [("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p),
+                ("n_nodes", C.c_int64), ("S", C.c_void_p), ("slab", C.c_void_p), ("U", C.c_void_p), ("ldu", C.c_int64)] +
+                [(n, C.c_int32) for n in ("n_slabs", "h", "fn", "fe", "bwd_with_u", "by_source")])
+
+
+class EdgePass(C.Structure):
+    """dss2_edge_pass_t: the kernel one pass of the edge MLP runs and its launch geometry (include/dss2_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "nrb", "parts", "block", "wg_per_tile", "lds_bytes")]
+
+
+class EdgePlan(C.Structure):
+    _fields_ = [("fwd", EdgePass), ("bwd", EdgePass), ("bwd_src", EdgePass), ("pair_exact", C.c_int32), ("pad_", C.c_int32)]
+
+
+EDGE_NONE, EDGE_CSR, EDGE_VALU, EDGE_VALU_HALF, EDGE_FP32_MFMA, EDGE_BF16X6 = range(6)      # dss2_edge_family
+
+
 class CsrBuildArgs(C.Structure):
     _fields_ = [("edge_index", C.c_void_p), ("n_edges", C.c_int64), ("n_nodes", C.c_int64), ("doubled", C.c_int32), ("no_flip", C.c_int32),
                 ("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("perm", C.c_void_p), ("w", C.c_void_p),
@@ -299,27 +319,14 @@ _SIGNATURES = {
     "dss2_dropout_params": (None, [C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "dss2_csr_axpy": (C.c_int, [C.POINTER(CsrAxpyArgs), C.c_void_p]),
     "dss2_pack_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "dss2_edge_hidden_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                       C.c_int, C.c_int, C.c_void_p]),
-    "dss2_edge_hidden_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p]),
+    "dss2_edge_fwd": (C.c_int, [C.POINTER(EdgeArgs), C.c_void_p]),
+    "dss2_edge_bwd": (C.c_int, [C.POINTER(EdgeArgs), C.c_void_p]),
+    "dss2_edge_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(EdgePlan)]),
     "dss2_edge_combine_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "dss2_edge_combine_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),
-    "dss2_edge_tile_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p]),
-    "dss2_edge_tile_fwd_paired": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                            C.c_int, C.c_void_p]),
-    "dss2_edge_tile_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                     C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dss2_gemm_prop": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p]),
     "dss2_chain_sp6_single_group_min_tiles": (C.c_int, []),
     "dss2_gemm_prop_chain": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p, C.c_int, C.c_void_p]),

@@ -5,6 +5,8 @@
 // j % 64, FPL = ceil(h/64) features per lane), the 22 first-layer weights of each owned feature
 // live in registers.  Node / edge inputs of a row are wave-uniform, so they are fetched with
 // scalar loads and broadcast for free; the only vector memory traffic is the coalesced S row.
+#include <assert.h>
+
 #include "dss2_common.hpp"
 #include "dss2_edge_tile.hpp"
 #include "dss2_weightspace.hpp"
@@ -588,45 +590,6 @@ __global__ void __launch_bounds__(256) reduce_slabs_multi_v4_kernel(const Reduce
 
 using namespace dss2;
 
-static int dss2_edge_hidden_fwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fn, int fe, void* stream);
-extern "C" int dss2_edge_hidden_fwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fn, int fe, void* stream) {
-  DSS2_RECORD([x, ldx, ea, ldea, W1, b1, rowptr, col, ent, S, n_nodes, h, fn, fe](void* s_) { return dss2_edge_hidden_fwd_launch(x, ldx, ea, ldea, W1, b1, rowptr, col, ent, S, n_nodes, h, fn, fe, s_); });
-  return dss2_edge_hidden_fwd_launch(x, ldx, ea, ldea, W1, b1, rowptr, col, ent, S, n_nodes, h, fn, fe, stream);
-}
-static int dss2_edge_hidden_fwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fn, int fe, void* stream) {
-  if (fn != FN || fe != FE) { set_error("edge_hidden_fwd: only dim_featn=8, dim_feate=6 are built (got %d, %d)", fn, fe); return 2; }
-  if (h <= 0 || h > 256) { set_error("edge_hidden_fwd: h=%d unsupported (1..256)", h); return 2; }
-  if (n_nodes <= 0) return 0;
-  const int wpb = 4;
-  int64_t blocks = (n_nodes + wpb - 1) / wpb;
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  hipStream_t s = as_stream(stream);
-  const int fpl = (h + 63) / 64;
-#define L(FPL) hipLaunchKernelGGL(edge_hidden_fwd_kernel<FPL>, dim3((unsigned)blocks), dim3(64 * wpb), 0, s, x, ldx, ea, ldea, W1, b1, rowptr, col, ent, S, n_nodes, h)
-  if (fpl == 1) L(1); else if (fpl == 2) L(2); else if (fpl == 3) L(3); else L(4);
-#undef L
-  return check_launch("edge_hidden_fwd");
-}
-
-static int dss2_edge_hidden_bwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* slab, int n_slabs, float* U, int64_t ldu, int64_t n_nodes, int h, int fn, int fe, int by_source, void* stream);
-extern "C" int dss2_edge_hidden_bwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* slab, int n_slabs, float* U, int64_t ldu, int64_t n_nodes, int h, int fn, int fe, int by_source, void* stream) {
-  DSS2_RECORD([x, ldx, ea, ldea, W1, b1, dS, rowptr, col, ent, slab, n_slabs, U, ldu, n_nodes, h, fn, fe, by_source](void* s_) { return dss2_edge_hidden_bwd_launch(x, ldx, ea, ldea, W1, b1, dS, rowptr, col, ent, slab, n_slabs, U, ldu, n_nodes, h, fn, fe, by_source, s_); });
-  return dss2_edge_hidden_bwd_launch(x, ldx, ea, ldea, W1, b1, dS, rowptr, col, ent, slab, n_slabs, U, ldu, n_nodes, h, fn, fe, by_source, stream);
-}
-static int dss2_edge_hidden_bwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* slab, int n_slabs, float* U, int64_t ldu, int64_t n_nodes, int h, int fn, int fe, int by_source, void* stream) {
-  if (fn != FN || fe != FE) { set_error("edge_hidden_bwd: only dim_featn=8, dim_feate=6 are built (got %d, %d)", fn, fe); return 2; }
-  if (h <= 0 || h > 256) { set_error("edge_hidden_bwd: h=%d unsupported (1..256)", h); return 2; }
-  if (n_slabs <= 0) { set_error("edge_hidden_bwd: n_slabs must be > 0"); return 2; }
-  if (!by_source && !slab) { set_error("edge_hidden_bwd: slab is NULL"); return 2; }
-  if (by_source && !U) { set_error("edge_hidden_bwd: by_source needs U"); return 2; }
-  hipStream_t s = as_stream(stream);
-  const int fpl = (h + 63) / 64;
-#define L(FPL) hipLaunchKernelGGL(edge_hidden_bwd_kernel<FPL>, dim3(n_slabs), dim3(256), 0, s, x, ldx, ea, ldea, W1, b1, dS, rowptr, col, ent, slab, U, ldu, n_nodes, h, by_source)
-  if (fpl == 1) L(1); else if (fpl == 2) L(2); else if (fpl == 3) L(3); else L(4);
-#undef L
-  return check_launch("edge_hidden_bwd");
-}
-
 // ------------------------------------------------------------------------------------------
 // Edge MLP on the matrix pipe.  For ELL slot k the inputs of the k-th incoming edge of every row of the tile
 // form a dense [TM x 24] matrix A_k = [x_i | x_j | edge_attr | 0]; Z_k = A_k W1^T is three k-steps of the
@@ -798,135 +761,168 @@ __global__ void __launch_bounds__(512) edge_mfma_bwd_kernel(const EdgeTileArgs p
   }
 }
 
+// ---- Which edge kernel takes a launch.  The backward recomputes the forward's ReLU gates, so the two passes must run the same
+// arithmetic: edge_select decides all three passes of a shape together, and everything below launches from its record.
+static size_t edge_tile_lds(int TM, int D) { return ((size_t)TM * FN + (size_t)D * TM * 8) * 4 + (size_t)D * TM * 4; }      // the VALU tile kernel
+
 static size_t edge_mfma_lds(int TM, int D, int nw, bool bwd) {
-  size_t b = ((size_t)TM * FN + (size_t)D * TM * 8) * 4 + (size_t)D * TM * 4 + (size_t)TM * EM_LDA * 4;
+  size_t b = edge_tile_lds(TM, D) + (size_t)TM * EM_LDA * 4;
   if (bwd) b += (size_t)nw * TM * 32 * 4;
   return b;
 }
 
-static bool edge_mfma_ok(int h, int nrb, int D, bool bwd = false) {
-  // Default: both passes on the matrix pipe (forward 26 -> 24 us, backward 55 -> 40 us at C2), so that the forward's
-  // ReLU gates and the gates the backward recomputes come from the same arithmetic.  DSS2_EDGE_MFMA=0 (or _FWD / _BWD)
-  // selects the VALU tile kernels, which also serve shapes the MFMA kernels do not cover (h % 32 != 0, tall tiles).
-  // (read per call: lets a test switch paths inside one process)
-  const char* env = getenv("DSS2_EDGE_MFMA");
-  const char* env2 = getenv(bwd ? "DSS2_EDGE_MFMA_BWD" : "DSS2_EDGE_MFMA_FWD");
-  const int enabled = env2 ? atoi(env2) : (env ? atoi(env) : 1);
-  if (!enabled || (h & 31) || h > 256 || !(nrb == 1 || nrb == 2 || nrb == 3)) return false;
+// the matrix-pipe kernels cover the shape (h % 32 != 0 and tall tiles run the VALU tile kernels).  Sized with the backward's LDS for
+// the forward as well: a shape takes the matrix pipe in both passes or in neither.
+static bool edge_mfma_ok(int h, int nrb, int D) {
+  if ((h & 31) || h > 256 || !(nrb == 1 || nrb == 2 || nrb == 3)) return false;
   return edge_mfma_lds(nrb * 32, D, h >> 5, true) <= (size_t)kMaxLdsBytes;
 }
 
-// the tile kernels of 32 / 64 / 96-row tiles run the bf16x6 forms of dss2_edge16.hip (by target, without U): what the edge phases of the
-// 64-row split-plane chain reproduce (dss2_gemm_chain_sp.hip)
-bool dss2::edge16_tile_route(int h, int nrb, int D, bool bwd) {
-  return edge_mfma_ok(h, nrb, D, bwd) && edge16_ok(h, nrb, D, bwd, false);
+// DSS2_EDGE_MFMA (or _FWD / _BWD for one pass) = 0: the VALU tile kernels instead of the matrix pipe; DSS2_EDGE_BF16 = 0: its fp32 MFMA
+// form instead of bf16x6.  Read per call: lets a test switch paths inside one process.  DSS2_EDGE_TILE_HALF = 0 (read once): the VALU
+// tile kernel runs a wave per row at every width.
+struct EdgeSwitches { bool mfma_fwd, mfma_bwd, bf16, half; };
+static EdgeSwitches edge_switches() {
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  static const int half = num("DSS2_EDGE_TILE_HALF", 1);
+  const int mfma = num("DSS2_EDGE_MFMA", 1);
+  return {num("DSS2_EDGE_MFMA_FWD", mfma) != 0, num("DSS2_EDGE_MFMA_BWD", mfma) != 0, num("DSS2_EDGE_BF16", 1) != 0, half != 0};
+}
+
+dss2_edge_plan_t dss2::edge_select(int h, int nrb, int ell_width, int ellT_width, bool with_u) {
+  dss2_edge_plan_t p = {};
+  if (h <= 0 || h > 256) return p;
+  const EdgeSwitches sw = edge_switches();
+  const int block = 64 * (h >> 5);      // matrix pipe: one wave per 32-column group of the hidden layer (<= 8)
+  const dss2_edge_pass_t csr = {DSS2_EDGE_CSR, 0, 1, 256, 0, 0};
+  auto valu = [&](int D, int wg) {
+    return dss2_edge_pass_t{h <= 32 && sw.half ? DSS2_EDGE_VALU_HALF : DSS2_EDGE_VALU, nrb, 1, 256, wg, (int32_t)edge_tile_lds(nrb * 32, D)};
+  };
+  // by source (only a backward with U has that pass): the VALU tile kernel at every height
+  if (with_u && ellT_width >= 0 && ellT_width <= 32) p.bwd_src = ellT_width ? valu(ellT_width, 0) : csr;
+  if (ell_width == 0) p.fwd = p.bwd = csr;
+  if (ell_width >= 1 && ell_width <= 32) {
+    const int D = ell_width;
+    // neither matrix-pipe backward with U is built above 64 rows (that instantiation misses its register budget): the VALU tile kernel
+    // serves it, and a forward that announces such a backward runs the VALU tile kernel too
+    const bool on_f = sw.mfma_fwd && !(with_u && nrb >= 3), on_b = sw.mfma_bwd && !(with_u && nrb >= 3);
+    // 128- / 192-row tiles: the bf16x6 kernels on two parts of 64 / 96 rows, the forward with a workgroup per part
+    const int part = nrb == 4 ? 2 : (nrb == 6 ? 3 : 0);
+    size_t lds_f = 0, lds_b = 0;
+    const bool b16_f = sw.bf16 && edge16_ok(h, nrb, D, false, &lds_f), b16_b = sw.bf16 && edge16_ok(h, nrb, D, true, &lds_b);
+    p.fwd = valu(D, 1), p.bwd = valu(D, 0);
+    if (part) {      // both passes or neither, as far as the shape and DSS2_EDGE_BF16 go; no fp32 MFMA form
+      if (edge_mfma_ok(h, part, D) && b16_f && b16_b && sw.mfma_fwd) {
+        if (on_f) p.fwd = {DSS2_EDGE_BF16X6, part, 2, block, 2, (int32_t)lds_f};
+        if (on_b) p.bwd = {DSS2_EDGE_BF16X6, part, 2, block, 0, (int32_t)lds_b};
+      }
+    } else if (edge_mfma_ok(h, nrb, D)) {
+      if (on_f) p.fwd = b16_f ? dss2_edge_pass_t{DSS2_EDGE_BF16X6, nrb, 1, block, 1, (int32_t)lds_f}
+                              : dss2_edge_pass_t{DSS2_EDGE_FP32_MFMA, nrb, 1, block, 1, (int32_t)edge_mfma_lds(nrb * 32, D, h >> 5, false)};
+      if (on_b) p.bwd = b16_b ? dss2_edge_pass_t{DSS2_EDGE_BF16X6, nrb, 1, block, 0, (int32_t)lds_b}
+                              : dss2_edge_pass_t{DSS2_EDGE_FP32_MFMA, nrb, 1, block, 0, (int32_t)edge_mfma_lds(nrb * 32, D, h >> 5, true)};
+    }
+  }
+  p.pair_exact = p.fwd.family != DSS2_EDGE_NONE && p.fwd.family == p.bwd.family;      // (VALU / VALU_HALF follow h alone: the same in both passes)
+  return p;
+}
+
+extern "C" int dss2_edge_plan(int h, int nrb, int ell_width, int ellT_width, int with_u, dss2_edge_plan_t* out) {
+  if (!out) { set_error("dss2_edge_plan: null argument"); return 2; }
+  *out = edge_select(h, nrb, ell_width, ellT_width, with_u != 0);
+  return 0;
 }
 
 template <int NRB>
-static int launch_edge_mfma(const EdgeTileArgs& a, int grid, bool bwd, hipStream_t s) {
-  const int nw = a.h >> 5;                  // one wave per 32-column group of the hidden layer (<= 8)
-  const size_t lds = edge_mfma_lds(NRB * 32, a.D, nw, bwd);
-  if (bwd && a.U) {
-    if constexpr (NRB <= 2) {
-      static std::atomic<uint32_t> lds_done{0};
-      auto kern = edge_mfma_bwd_kernel<NRB, true>;
-      if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge_mfma_bwd")) return 1;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-    } else {
-      set_error("edge_mfma_bwd with U: tiles above 64 rows are served by the VALU kernel"); return 2;
-    }
-  } else if (bwd) {
-    static std::atomic<uint32_t> lds_done{0};
-    auto kern = edge_mfma_bwd_kernel<NRB, false>;
-    if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge_mfma_bwd")) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-  } else {
-    static std::atomic<uint32_t> lds_done{0};
-    auto kern = edge_mfma_fwd_kernel<NRB>;
-    if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge_mfma_fwd")) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-  }
-  return check_launch(bwd ? "edge_mfma_bwd" : "edge_mfma_fwd");
+static int launch_edge_mfma(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, bool bwd, hipStream_t s) {
+  if (!bwd) return launch_edge_kernel<edge_mfma_fwd_kernel<NRB>>("edge_mfma_fwd", a, k, grid, s);
+  if (!a.U) return launch_edge_kernel<edge_mfma_bwd_kernel<NRB, false>>("edge_mfma_bwd", a, k, grid, s);
+  assert(NRB <= 2);      // (edge_select: U above 64 rows is the VALU tile kernel's)
+  if constexpr (NRB <= 2) return launch_edge_kernel<edge_mfma_bwd_kernel<NRB, true>>("edge_mfma_bwd", a, k, grid, s);
+  return 1;
 }
 
-static int dispatch_edge_mfma(const EdgeTileArgs& a, int nrb, int grid, bool bwd, hipStream_t s) {
-  switch (nrb) {
-    case 1: return launch_edge_mfma<1>(a, grid, bwd, s);
-    case 2: return launch_edge_mfma<2>(a, grid, bwd, s);
-    default: return launch_edge_mfma<3>(a, grid, bwd, s);
-  }
+static int dispatch_edge_mfma(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, bool bwd, hipStream_t s) {
+  return k.nrb == 1 ? launch_edge_mfma<1>(a, k, grid, bwd, s) : k.nrb == 2 ? launch_edge_mfma<2>(a, k, grid, bwd, s) : launch_edge_mfma<3>(a, k, grid, bwd, s);
 }
 
 template <bool BWD>
-static int launch_edge_tile(const EdgeTileArgs& a, int grid, hipStream_t s) {
-  const size_t lds = ((size_t)a.TM * FN + (size_t)a.D * a.TM * 8) * 4 + (size_t)a.D * a.TM * 4;
+static int launch_edge_tile(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, hipStream_t s) {
   const int fpl = (a.h + 63) / 64;
-#define L(FPL) hipLaunchKernelGGL((edge_tile_kernel<FPL, BWD>), dim3(grid), dim3(256), lds, s, a)
-  static const int half_on = [] { const char* e = getenv("DSS2_EDGE_TILE_HALF"); return e ? atoi(e) : 1; }();      // 0: a wave per row at every width
-  if (a.h <= 32 && half_on) hipLaunchKernelGGL((edge_tile_kernel<1, BWD, true>), dim3(grid), dim3(256), lds, s, a);
+#define L(FPL) hipLaunchKernelGGL((edge_tile_kernel<FPL, BWD>), dim3(grid), dim3(k.block), (size_t)k.lds_bytes, s, a)
+  if (k.family == DSS2_EDGE_VALU_HALF) hipLaunchKernelGGL((edge_tile_kernel<1, BWD, true>), dim3(grid), dim3(k.block), (size_t)k.lds_bytes, s, a);
   else if (fpl == 1) L(1); else if (fpl == 2) L(2); else if (fpl == 3) L(3); else L(4);
 #undef L
   return check_launch(BWD ? "edge_tile_bwd" : "edge_tile_fwd");
 }
 
-extern "C" int dss2_edge_tile_fwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1,
-                                  const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width,
-                                  int nrb, int ntiles, float* S, int h, int fn, int fe, void* stream) {
-  return dss2_edge_tile_fwd_paired(x, ldx, ea, ldea, W1, b1, tile_start, ell_ent, ell_width, nrb, ntiles, S, h, fn, fe, 0, stream);
+// the row-per-wave kernels on the CSR (general graphs: hub nodes beyond the ELL width)
+static int launch_edge_csr(const dss2_edge_args& a, const dss2_edge_pass_t& k, int64_t grid, bool bwd, hipStream_t s) {
+  const int fpl = (a.h + 63) / 64;
+#define L(FPL) do { \
+    if (bwd) hipLaunchKernelGGL(edge_hidden_bwd_kernel<FPL>, dim3((unsigned)grid), dim3(k.block), 0, s, a.x, a.ldx, a.ea, a.ldea, a.W1, a.b1, a.dS, a.rowptr, a.col, a.ent, a.slab, a.U, a.ldu, a.n_nodes, a.h, a.by_source); \
+    else hipLaunchKernelGGL(edge_hidden_fwd_kernel<FPL>, dim3((unsigned)grid), dim3(k.block), 0, s, a.x, a.ldx, a.ea, a.ldea, a.W1, a.b1, a.rowptr, a.col, a.ent, a.S, a.n_nodes, a.h); \
+  } while (0)
+  if (fpl == 1) L(1); else if (fpl == 2) L(2); else if (fpl == 3) L(3); else L(4);
+#undef L
+  return check_launch(bwd ? "edge_hidden_bwd" : "edge_hidden_fwd");
 }
 
-static int dss2_edge_tile_fwd_paired_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* S, int h, int fn, int fe, int bwd_with_u, void* stream);
-extern "C" int dss2_edge_tile_fwd_paired(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* S, int h, int fn, int fe, int bwd_with_u, void* stream) {
-  DSS2_RECORD([x, ldx, ea, ldea, W1, b1, tile_start, ell_ent, ell_width, nrb, ntiles, S, h, fn, fe, bwd_with_u](void* s_) { return dss2_edge_tile_fwd_paired_launch(x, ldx, ea, ldea, W1, b1, tile_start, ell_ent, ell_width, nrb, ntiles, S, h, fn, fe, bwd_with_u, s_); });
-  return dss2_edge_tile_fwd_paired_launch(x, ldx, ea, ldea, W1, b1, tile_start, ell_ent, ell_width, nrb, ntiles, S, h, fn, fe, bwd_with_u, stream);
-}
-static int dss2_edge_tile_fwd_paired_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* S, int h, int fn, int fe, int bwd_with_u, void* stream) {
-  if (fn != FN || fe != FE) { set_error("edge_tile_fwd: only dim_featn=8, dim_feate=6 are built (got %d, %d)", fn, fe); return 2; }
-  if (h <= 0 || h > 256 || ell_width <= 0 || ell_width > 32) { set_error("edge_tile_fwd: bad h=%d or ell_width=%d", h, ell_width); return 2; }
-  if (ntiles <= 0) return 0;
-  EdgeTileArgs a{x, ldx, ea, ldea, W1, b1, nullptr, tile_start, reinterpret_cast<const int2*>(ell_ent), S, nullptr, nullptr, 0,
-                 h, ell_width, nrb * 32, 0, ntiles};
-  // The backward recomputes the ReLU gates, so forward and backward must run the same arithmetic.  dss2_edge_tile_bwd with U on 96-row
-  // tiles runs the VALU tile kernel (neither matrix-pipe backward is built for it): a caller that announces such a backward gets the
-  // VALU tile forward.
-  const bool valu_pair = bwd_with_u && nrb >= 3;
-  const int part_nrb = nrb == 4 ? 2 : 3;      // 128- / 192-row tiles: the bf16x6 kernels on two parts of 64 / 96 rows (both passes or neither)
-  if ((nrb == 4 || nrb == 6) && !valu_pair && edge_mfma_ok(h, part_nrb, ell_width) && edge16_ok(h, nrb, ell_width, false, false) && edge16_ok(h, nrb, ell_width, true, false))
-    return launch_edge16(a, nrb, ntiles, false, as_stream(stream));
-  if (edge_mfma_ok(h, nrb, ell_width) && !valu_pair) {
-    // first Linear as bf16x6 on the bf16 matrix pipe (dss2_edge16.hip; DSS2_EDGE_BF16=0: the fp32 MFMA form below)
-    if (edge16_ok(h, nrb, ell_width, false, false)) return launch_edge16(a, nrb, ntiles, false, as_stream(stream));
-    return dispatch_edge_mfma(a, nrb, ntiles, false, as_stream(stream));
-  }
-  return launch_edge_tile<false>(a, ntiles, as_stream(stream));
+// the refusals of both entry points; bwd: the backward's as well
+static bool edge_refused(const dss2_edge_args& a, const char* who, bool bwd) {
+  if (a.fn != FN || a.fe != FE) { set_error("%s: only dim_featn=8, dim_feate=6 are built (got %d, %d)", who, a.fn, a.fe); return true; }
+  if (a.h <= 0 || a.h > 256 || (a.ell_ent && (a.ell_width <= 0 || a.ell_width > 32))) { set_error("%s: bad h=%d (1..256) or ell_width=%d", who, a.h, a.ell_width); return true; }
+  if (!bwd) return false;
+  if (!a.by_source && !a.slab) { set_error("%s: slab is NULL", who); return true; }
+  if (a.by_source && !a.U) { set_error("%s: by_source needs U", who); return true; }
+  if (a.n_slabs <= 0) { set_error("%s: n_slabs must be > 0", who); return true; }
+  return false;
 }
 
-static int dss2_edge_tile_bwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* slab, int n_slabs, float* U, int64_t ldu, int h, int fn, int fe, int by_source, void* stream);
-extern "C" int dss2_edge_tile_bwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* slab, int n_slabs, float* U, int64_t ldu, int h, int fn, int fe, int by_source, void* stream) {
-  DSS2_RECORD([x, ldx, ea, ldea, W1, b1, dS, tile_start, ell_ent, ell_width, nrb, ntiles, slab, n_slabs, U, ldu, h, fn, fe, by_source](void* s_) { return dss2_edge_tile_bwd_launch(x, ldx, ea, ldea, W1, b1, dS, tile_start, ell_ent, ell_width, nrb, ntiles, slab, n_slabs, U, ldu, h, fn, fe, by_source, s_); });
-  return dss2_edge_tile_bwd_launch(x, ldx, ea, ldea, W1, b1, dS, tile_start, ell_ent, ell_width, nrb, ntiles, slab, n_slabs, U, ldu, h, fn, fe, by_source, stream);
-}
-static int dss2_edge_tile_bwd_launch(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1, const float* b1, const float* dS, const int32_t* tile_start, const void* ell_ent, int ell_width, int nrb, int ntiles, float* slab, int n_slabs, float* U, int64_t ldu, int h, int fn, int fe, int by_source, void* stream) {
-  if (fn != FN || fe != FE) { set_error("edge_tile_bwd: only dim_featn=8, dim_feate=6 are built (got %d, %d)", fn, fe); return 2; }
-  if (h <= 0 || h > 256 || ell_width <= 0 || ell_width > 32) { set_error("edge_tile_bwd: bad h=%d or ell_width=%d", h, ell_width); return 2; }
-  if (!by_source && !slab) { set_error("edge_tile_bwd: slab is NULL"); return 2; }
-  if (by_source && !U) { set_error("edge_tile_bwd: by_source needs U"); return 2; }
-  if (n_slabs <= 0) { set_error("edge_tile_bwd: n_slabs must be > 0"); return 2; }
-  if (ntiles <= 0) return 0;
-  EdgeTileArgs a{x, ldx, ea, ldea, W1, b1, dS, tile_start, reinterpret_cast<const int2*>(ell_ent), nullptr, slab, U, ldu,
-                 h, ell_width, nrb * 32, by_source, ntiles};
-  // n_slabs workgroups walk the tiles (the slab buffer holds one partial per workgroup)
-  // (96-row tiles WITH the per-row sums U, the PFN inner-block case: that instantiation misses its register budget, so it is
-  //  not compiled -- the VALU tile kernel below serves it)
-  const int part_nrb = nrb == 4 ? 2 : 3;
-  if (!by_source && (nrb == 4 || nrb == 6) && !U && edge_mfma_ok(h, part_nrb, ell_width, true) && edge_mfma_ok(h, part_nrb, ell_width) && edge16_ok(h, nrb, ell_width, false, false) && edge16_ok(h, nrb, ell_width, true, false))
-    return launch_edge16(a, nrb, n_slabs < ntiles ? n_slabs : ntiles, true, as_stream(stream));
-  if (!by_source && edge_mfma_ok(h, nrb, ell_width, true) && !(nrb == 3 && U)) {
-    if (edge16_ok(h, nrb, ell_width, true, U != nullptr))      // (the recomputed gates come from the arithmetic of the bf16x6 forward)
-      return launch_edge16(a, nrb, n_slabs < ntiles ? n_slabs : ntiles, true, as_stream(stream));
-    return dispatch_edge_mfma(a, nrb, n_slabs < ntiles ? n_slabs : ntiles, true, as_stream(stream));
+static int edge_launch(const dss2_edge_args& a, const dss2_edge_pass_t& k, bool bwd, void* stream) {
+  hipStream_t s = as_stream(stream);
+  if (k.family == DSS2_EDGE_CSR) {
+    if (bwd) return launch_edge_csr(a, k, a.n_slabs, true, s);
+    const int64_t blocks = (a.n_nodes + 3) / 4;      // a wavefront per row, four to a workgroup
+    return launch_edge_csr(a, k, blocks > 256 * 8 ? 256 * 8 : blocks, false, s);
   }
-  return launch_edge_tile<true>(a, n_slabs < ntiles ? n_slabs : ntiles, as_stream(stream));
+  const EdgeTileArgs t{a.x, a.ldx, a.ea, a.ldea, a.W1, a.b1, bwd ? a.dS : nullptr, a.tile_start, reinterpret_cast<const int2*>(a.ell_ent),
+                       bwd ? nullptr : a.S, bwd ? a.slab : nullptr, bwd ? a.U : nullptr, bwd ? a.ldu : 0,
+                       a.h, a.ell_width, a.nrb * 32, bwd ? a.by_source : 0, a.ntiles};
+  // backward: min(n_slabs, ntiles) persistent workgroups walk the tiles (the slab buffer holds one partial per workgroup)
+  const int grid = bwd ? (a.n_slabs < a.ntiles ? a.n_slabs : a.ntiles) : k.wg_per_tile * a.ntiles;
+  switch (k.family) {
+    case DSS2_EDGE_BF16X6: return launch_edge16(t, k, grid, bwd, s);
+    case DSS2_EDGE_FP32_MFMA: return dispatch_edge_mfma(t, k, grid, bwd, s);
+    case DSS2_EDGE_VALU: case DSS2_EDGE_VALU_HALF: return bwd ? launch_edge_tile<true>(t, k, grid, s) : launch_edge_tile<false>(t, k, grid, s);
+    default: set_error("dss2_edge_%s: no kernel for h=%d, nrb=%d, ell_width=%d", bwd ? "bwd" : "fwd", a.h, a.nrb, a.ell_width); return 2;
+  }
+}
+
+static int dss2_edge_fwd_launch(const dss2_edge_args* ap, void* stream) {
+  const dss2_edge_args& a = *ap;
+  if (edge_refused(a, "dss2_edge_fwd", false)) return 2;
+  if (a.ell_ent ? a.ntiles <= 0 : a.n_nodes <= 0) return 0;
+  return edge_launch(a, edge_select(a.h, a.nrb, a.ell_ent ? a.ell_width : 0, 0, a.bwd_with_u != 0).fwd, false, stream);
+}
+extern "C" int dss2_edge_fwd(const dss2_edge_args* ap, void* stream) {
+  if (!ap) { set_error("dss2_edge_fwd: null argument"); return 2; }
+  DSS2_RECORD([a = *ap](void* s_) { return dss2_edge_fwd_launch(&a, s_); });
+  return dss2_edge_fwd_launch(ap, stream);
+}
+
+static int dss2_edge_bwd_launch(const dss2_edge_args* ap, void* stream) {
+  const dss2_edge_args& a = *ap;
+  if (edge_refused(a, "dss2_edge_bwd", true)) return 2;
+  if (a.ell_ent && a.ntiles <= 0) return 0;
+  const int width = a.ell_ent ? a.ell_width : 0;      // of the table this pass reads: by target, or by source
+  const dss2_edge_plan_t p = edge_select(a.h, a.nrb, width, width, a.U != nullptr);
+  return edge_launch(a, a.by_source ? p.bwd_src : p.bwd, true, stream);
+}
+extern "C" int dss2_edge_bwd(const dss2_edge_args* ap, void* stream) {
+  if (!ap) { set_error("dss2_edge_bwd: null argument"); return 2; }
+  DSS2_RECORD([a = *ap](void* s_) { return dss2_edge_bwd_launch(&a, s_); });
+  return dss2_edge_bwd_launch(ap, stream);
 }
 
 static int dss2_edge_combine_fwd_launch(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fe, void* stream);

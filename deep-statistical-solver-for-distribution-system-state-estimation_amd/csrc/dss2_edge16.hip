@@ -18,7 +18,7 @@
 // The backward recomputes the pre-activation with the very same plane values, fragments and MFMA order -- its gates are bit for
 // bit the forward's -- and forms dW1 += dZ_k^T A_k, a contraction over the tile's rows, as bf16x6 too (see edge16_bwd_kernel).
 // Built without packed fp32 VALU ops like every translation unit that runs bf16 MFMAs beside other workgroups (csrc/build.sh).
-#include <stdlib.h>
+#include <assert.h>
 
 #include "dss2_edge16_tile.hpp"
 
@@ -184,62 +184,27 @@ __global__ void __launch_bounds__(512) edge16_bwd_kernel(const EdgeTileArgs p) {
   e16_store_slab(p.slab + (size_t)blockIdx.x * ((size_t)p.h * FC + p.h), p.h, cg, c32, half, dWacc);
 }
 
-bool edge16_ok(int h, int nrb, int D, bool bwd, bool with_u) {
-  // (read per call, like DSS2_EDGE_MFMA: lets a test switch forms inside one process; both passes must switch together,
-  //  the backward recomputes the forward's gates)
-  const char* env = getenv("DSS2_EDGE_BF16");
-  if (env && atoi(env) == 0) return false;
+bool edge16_ok(int h, int nrb, int D, bool bwd, size_t* lds) {
   if ((h & 31) || h > 256 || !(nrb == 1 || nrb == 2 || nrb == 3 || nrb == 4 || nrb == 6) || D < 1 || D > 32) return false;      // (no kernel of the library tiles at 160 rows)
-  if (bwd && with_u && nrb >= 3) return false;      // (that instantiation misses its register budget, as in dss2_edge.hip)
   // (128- / 192-row tiles: two parts of 64 / 96 rows, the whole tile's x rows staged for each)
   const int tm = nrb == 4 ? 64 : (nrb == 6 ? 96 : nrb * 32);
-  return (bwd ? e16_bwd_lds_bytes(tm, D, nrb * 32) : e16_lds_bytes(tm, D, nrb * 32)) <= (size_t)kMaxLdsBytes;
+  *lds = bwd ? e16_bwd_lds_bytes(tm, D, nrb * 32) : e16_lds_bytes(tm, D, nrb * 32);
+  return *lds <= (size_t)kMaxLdsBytes;
 }
 
 template <int NRB>
-static int launch16(const EdgeTileArgs& a, int grid, bool bwd, hipStream_t s) {
-  const int nw = a.h >> 5;
-  const int xt = a.xtm > 0 ? a.xtm : NRB * 32;
-  const size_t lds = bwd ? e16_bwd_lds_bytes(NRB * 32, a.D, xt) : e16_lds_bytes(NRB * 32, a.D, xt);
-  if (bwd && a.U) {
-    if constexpr (NRB <= 2) {
-      static std::atomic<uint32_t> lds_done{0};
-      auto kern = edge16_bwd_kernel<NRB, true>;
-      if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge16_bwd")) return 1;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-    } else {
-      set_error("edge16_bwd with U: tiles above 64 rows are served by the VALU kernel"); return 2;
-    }
-  } else if (bwd) {
-    static std::atomic<uint32_t> lds_done{0};
-    auto kern = edge16_bwd_kernel<NRB, false>;
-    if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge16_bwd")) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-  } else {
-    static std::atomic<uint32_t> lds_done{0};
-    auto kern = edge16_fwd_kernel<NRB>;
-    if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "edge16_fwd")) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, a);
-  }
-  return check_launch(bwd ? "edge16_bwd" : "edge16_fwd");
+static int launch16(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, bool bwd, hipStream_t s) {
+  if (!bwd) return launch_edge_kernel<edge16_fwd_kernel<NRB>>("edge16_fwd", a, k, grid, s);
+  if (!a.U) return launch_edge_kernel<edge16_bwd_kernel<NRB, false>>("edge16_bwd", a, k, grid, s);
+  assert(NRB <= 2);      // (with U that instantiation misses its register budget: edge_select sends it to the VALU tile kernel)
+  if constexpr (NRB <= 2) return launch_edge_kernel<edge16_bwd_kernel<NRB, true>>("edge16_bwd", a, k, grid, s);
+  return 1;
 }
 
-int launch_edge16(const EdgeTileArgs& a, int nrb, int grid, bool bwd, hipStream_t s) {
-  switch (nrb) {
-    case 1: return launch16<1>(a, grid, bwd, s);
-    case 2: return launch16<2>(a, grid, bwd, s);
-    case 4: {      // 128-row tiles as two parts of 64 rows (round 6; the VALU tile kernels before)
-      EdgeTileArgs b = a;
-      b.xtm = 128; b.parts = 2;
-      return launch16<2>(b, bwd ? grid : 2 * grid, bwd, s);
-    }
-    case 6: {      // 192-row tiles as two parts of 96 rows each (the forward: one workgroup per part)
-      EdgeTileArgs b = a;
-      b.xtm = 32 * nrb; b.parts = 2;
-      return launch16<3>(b, bwd ? grid : 2 * grid, bwd, s);
-    }
-    default: return launch16<3>(a, grid, bwd, s);
-  }
+int launch_edge16(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, bool bwd, hipStream_t s) {
+  EdgeTileArgs b = a;
+  if (k.parts == 2) { b.xtm = a.TM; b.parts = 2; }      // 128- / 192-row tiles as two parts of 64 / 96 rows (the forward: one workgroup per part)
+  return k.nrb == 1 ? launch16<1>(b, k, grid, bwd, s) : k.nrb == 2 ? launch16<2>(b, k, grid, bwd, s) : launch16<3>(b, k, grid, bwd, s);
 }
 
 }  // namespace dss2

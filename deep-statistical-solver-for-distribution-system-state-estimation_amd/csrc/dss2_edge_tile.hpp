@@ -112,11 +112,23 @@ __device__ __forceinline__ void edge_build_ak(const EdgeStage& s, int k, int tid
 }
 
 
+// One launch of a tile kernel of the edge MLP with the block and dynamic LDS of its pass record (the kernel's LDS limit is raised once).
+template <auto KERN>
+int launch_edge_kernel(const char* what, const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, hipStream_t s) {
+  static std::atomic<uint32_t> lds_done{0};
+  if (ensure_max_lds(reinterpret_cast<const void*>(KERN), lds_done, what)) return 1;
+  hipLaunchKernelGGL(KERN, dim3(grid), dim3(k.block), (size_t)k.lds_bytes, s, a);
+  return check_launch(what);
+}
+
+// Which kernel each pass of an edge MLP runs, with its geometry (dss2_hip.h: dss2_edge_plan_t) -- the one decision behind
+// dss2_edge_fwd / dss2_edge_bwd, dss2_edge_plan and the chain's edge phases (dss2_edge.hip).
+dss2_edge_plan_t edge_select(int h, int nrb, int ell_width, int ellT_width, bool with_u);
+
 // dss2_edge16.hip: the edge MLP's first Linear on the bf16 matrix pipe (bf16x6, fp32-accurate), forward and the backward's
-// recomputation.  edge16_ok: the shape is covered (h % 32 == 0, h <= 256, 32 / 64 / 96-row tiles, LDS).
-bool edge16_ok(int h, int nrb, int D, bool bwd, bool with_u);
-int launch_edge16(const EdgeTileArgs& a, int nrb, int grid, bool bwd, hipStream_t s);
-// the route dss2_edge_tile_fwd_paired / dss2_edge_tile_bwd take for nrb <= 3 without U is the bf16x6 one (dss2_edge.hip)
-bool edge16_tile_route(int h, int nrb, int D, bool bwd);
+// recomputation.  edge16_ok: the shape is covered (h % 32 == 0, h <= 256, 32 / 64 / 96-row tiles or two such parts) and *lds,
+// the launch's dynamic LDS, fits.  Called from edge_select only; the launcher takes its geometry from the pass record k.
+bool edge16_ok(int h, int nrb, int D, bool bwd, size_t* lds);
+int launch_edge16(const EdgeTileArgs& a, const dss2_edge_pass_t& k, int grid, bool bwd, hipStream_t s);
 
 }  // namespace dss2

@@ -929,8 +929,9 @@ int chain_sp_edge_modes(const dss2_gemm_prop_args& a, int edge_width) {
   if (!(a.b_format == 2 && a.nrb == 2 && a.nmat == 3 && a.ncg == 4 && a.hout == 128 && a.kreal == 128)) return 0;
   const size_t region = (size_t)a.ncg * SP_REGION * 4;      // the edge images live where the planes / Horner slots do
   int m = 0;
-  if (edge16_tile_route(a.hout, 2, edge_width, false) && e16_lds_bytes(SP_TM, edge_width, SP_TM) <= region) m |= 1;
-  if (edge16_tile_route(a.hout, 2, edge_width, true) && e16_bwd_lds_bytes(SP_TM, edge_width, SP_TM) <= region) m |= 2;
+  const dss2_edge_plan_t e = edge_select(a.hout, SP_TM / 32, edge_width, edge_width, false);      // (the phases are the bf16x6 edge kernels', by target, without U)
+  if (e.fwd.family == DSS2_EDGE_BF16X6 && (size_t)e.fwd.lds_bytes <= region) m |= 1;
+  if (e.bwd.family == DSS2_EDGE_BF16X6 && (size_t)e.bwd.lds_bytes <= region) m |= 2;
   return m;
 }
 

@@ -33,7 +33,7 @@ from .topology import Topology, get_topology
 _F32 = torch.float32
 
 from . import flags as FL
-from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, edge_hidden_bwd, edge_hidden_fwd, edge_tile_bwd, edge_tile_fwd, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
+from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, edge_bwd, edge_fwd, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
 from .plans import (_DESC_DTYPE, _FoldPlan, _MatView, _PackPlan, _SG_DTYPE, _as_view, _pack_table, _sg, _sg_table, _small_gemm)
 from .route import BlockRoute, block_route, use_global_path
 
@@ -41,14 +41,19 @@ from .route import BlockRoute, block_route, use_global_path
 # ------------------------------------------------------------------------------------------
 # functional pieces (raw tensors in, raw tensors out); used by the autograd Functions below
 # ------------------------------------------------------------------------------------------
+def _edge_tiled(ts, N: int = 0):
+    """(tiled, n_slabs) of an edge MLP on the tile set ``ts``: forward and backward run the tile kernels together or not at all (the
+    backward recomputes the forward's gates) -- where the entry tables of BOTH directions exist; else the row-per-wave kernels on the
+    CSR (general graphs: hub nodes beyond the ELL width, on either side).  n_slabs: the backward's slabs over ``N`` nodes."""
+    tiled = ts.ell_ent_tiles is not None and ts.ellT_ent_tiles is not None and FL.EDGE_TILE_KERNELS
+    return tiled, (min(ts.ntiles, 512) if tiled else int(min(512, max(1, (N + 15) // 16))))
+
+
 def _edge_aggr_forward(topo, x, ldx, ea, ldea, W1, b1, b2, pack_w2_fwd, hid, hout, fn, fe, second_linear=True, need_dx=False):
     """need_dx: the backward will be asked for the gradient w.r.t. x (the library then picks the forward whose gates that backward recomputes exactly)."""
-    N, ts = topo.N, topo.tiling
+    N = topo.N
     S = torch.empty(N, hid, dtype=_F32, device=W1.device)
-    if ts.ell_ent_tiles is not None and FL.EDGE_TILE_KERNELS:
-        edge_tile_fwd(ts, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx)
-    else:   # general graphs (hub nodes beyond the ELL width): row-per-wave kernel on the CSR
-        edge_hidden_fwd(topo, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe)
+    edge_fwd(topo, _edge_tiled(topo.tiling)[0], x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx)
     if not second_linear:   # folded into the consumer (see _FoldPlan)
         return S, None
     x0 = torch.empty(N, hout, dtype=_F32, device=W1.device)
@@ -71,8 +76,7 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
     gx0 = dS
     dev = dS.device
     stride = hid * (2 * fn + fe) + hid
-    tiled = ts.ell_ent_tiles is not None and ts.ellT_ent_tiles is not None and FL.EDGE_TILE_KERNELS
-    n_slabs = min(ts.ntiles, 512) if tiled else int(min(512, max(1, (N + 15) // 16)))
+    tiled, n_slabs = _edge_tiled(ts, N)
     slab = torch.empty(n_slabs * stride, dtype=_F32, device=dev)
     # U0 = sum of dz over incoming edges (x enters as x_i), U1 over outgoing edges (as x_j).  Side by side in one [N, 2 hid]
     # buffer when the K = 2 hid tile fits LDS: dx is then ONE GEMM [U0 | U1] [W1[:, :fn] ; W1[:, fn:2fn]]
@@ -88,16 +92,12 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
         U = torch.empty(2, N, hid, dtype=_F32, device=dev)
         u0, u1, ldu = U[0], U[1], hid
 
-    def edge_bwd(slab_, u, transposed):      # over the incoming edges (dW1 | db1 slabs, U0), then -- transposed -- the outgoing ones (U1)
-        if tiled:
-            edge_tile_bwd(ts, x, ldx, ea, ldea, W1, b1, dS, slab_, n_slabs, u, ldu, hid, fn, fe, transposed)
-        else:
-            edge_hidden_bwd(topo, x, ldx, ea, ldea, W1, b1, dS, slab_, n_slabs, u, ldu, hid, fn, fe, transposed)
-    edge_bwd(slab, u0, False)
+    # over the incoming edges (dW1 | db1 slabs, U0), then -- transposed -- the outgoing ones (U1)
+    edge_bwd(topo, tiled, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, u0, ldu, hid, fn, fe, False)
     _reduce(slab, 0, n_slabs, stride, g_w1, stride, pending)
     if not need_dx:
         return None
-    edge_bwd(None, u1, True)
+    edge_bwd(topo, tiled, x, ldx, ea, ldea, W1, b1, dS, None, n_slabs, u1, ldu, hid, fn, fe, True)
     dx = torch.empty(N, fn, dtype=_F32, device=dev)
     if merged:
         gemm_prop(topo, U, 2 * hid, 2 * hid, pack_dx[2], 1, fn, dx, add_src=dx_add,

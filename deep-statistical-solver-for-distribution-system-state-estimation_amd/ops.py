@@ -492,34 +492,46 @@ def _csr_ent(topo: Topology, transposed: bool):
     return topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr()
 
 
-def edge_tile_fwd(ts: Tiling, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx: bool) -> None:
-    """S = per-target sums of relu(W1 [x_i | x_j | ea] + b1) on the tiles' ELL slices (dss2_edge_tile_fwd_paired); ``need_dx``: the
+def edge_plan(hid: int, nrb: int, ell: int, ellT: int, with_u: bool) -> "_lib.EdgePlan":
+    """The record the library launches the edge MLP's three passes from (dss2_edge_plan): kernel family and geometry per pass, and
+    whether the backward recomputes the forward's gates exactly.  ``ell`` / ``ellT``: 0 = no entry table on that side (CSR kernels)."""
+    p = _lib.EdgePlan()
+    _lib.check(_lib.lib().dss2_edge_plan(hid, nrb, ell, ellT, int(bool(with_u)), C.byref(p)), "dss2_edge_plan")
+    return p
+
+
+def _fill_edge_graph(a: "_lib.EdgeArgs", topo: Topology, ts: Tiling, transposed: bool, tiled: bool) -> None:
+    """The graph side of an edge MLP launch, by target or (transposed) by source: ``tiled`` the tiles of ``ts`` with their entry table,
+    else the CSR of ``topo`` (general graphs: hub nodes beyond the ELL width)."""
+    if tiled:
+        a.nrb, a.ntiles, a.tile_start = ts.nrb, ts.ntiles, ts.tile_start.data_ptr()
+        a.ell_ent, a.ell_width = (ts.ellT_ent_tiles.data_ptr(), ts.ellT) if transposed else (ts.ell_ent_tiles.data_ptr(), ts.ell)
+    else:
+        a.rowptr, a.col, a.ent, a.n_nodes = *_csr_ent(topo, transposed), topo.N
+
+
+def _edge_args(x, ldx, ea, ldea, W1, b1, hid, fn, fe) -> "_lib.EdgeArgs":
+    a = _lib.EdgeArgs()
+    a.x, a.ldx, a.ea, a.ldea, a.W1, a.b1, a.h, a.fn, a.fe = x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), hid, fn, fe
+    return a
+
+
+def edge_fwd(topo: Topology, tiled: bool, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe, need_dx: bool) -> None:
+    """S = per-target sums of relu(W1 [x_i | x_j | ea] + b1) (dss2_edge_fwd), on the tiles' ELL slices or on the CSR; ``need_dx``: the
     library picks the forward whose gates the input-gradient backward recomputes exactly."""
-    _lib.check(_lib.lib().dss2_edge_tile_fwd_paired(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(),
-                                                    ts.tile_start.data_ptr(), ts.ell_ent_tiles.data_ptr(), ts.ell, ts.nrb, ts.ntiles,
-                                                    S.data_ptr(), hid, fn, fe, int(bool(need_dx)), _stream(S)), "dss2_edge_tile_fwd_paired")
+    a = _edge_args(x, ldx, ea, ldea, W1, b1, hid, fn, fe)
+    a.S, a.bwd_with_u = S.data_ptr(), int(bool(need_dx))
+    _fill_edge_graph(a, topo, topo.tiling, False, tiled)
+    _lib.check(_lib.lib().dss2_edge_fwd(C.byref(a), _stream(S)), "dss2_edge_fwd")
 
 
-def edge_tile_bwd(ts: Tiling, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, U, ldu, hid, fn, fe, transposed: bool) -> None:
-    """Backward of edge_tile_fwd over the incoming (or, transposed, the outgoing) edges: dW1 | db1 slabs where ``slab`` is given, the
+def edge_bwd(topo: Topology, tiled: bool, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, U, ldu, hid, fn, fe, transposed: bool) -> None:
+    """Backward of edge_fwd over the incoming (or, transposed, the outgoing) edges: dW1 | db1 slabs where ``slab`` is given, the
     per-node sums of dz into ``U`` where it is."""
-    ent, width = (ts.ellT_ent_tiles, ts.ellT) if transposed else (ts.ell_ent_tiles, ts.ell)
-    _lib.check(_lib.lib().dss2_edge_tile_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                             ts.tile_start.data_ptr(), ent.data_ptr(), width, ts.nrb, ts.ntiles, _ptr(slab), n_slabs,
-                                             _ptr(U), ldu, hid, fn, fe, int(transposed), _stream(dS)), "dss2_edge_tile_bwd")
-
-
-def edge_hidden_fwd(topo: Topology, x, ldx, ea, ldea, W1, b1, S, hid, fn, fe) -> None:
-    """edge_tile_fwd for general graphs (hub nodes beyond the ELL width): row-per-wave kernel on the CSR."""
-    _lib.check(_lib.lib().dss2_edge_hidden_fwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), *_csr_ent(topo, False),
-                                               S.data_ptr(), topo.N, hid, fn, fe, _stream(S)), "dss2_edge_hidden_fwd")
-
-
-def edge_hidden_bwd(topo: Topology, x, ldx, ea, ldea, W1, b1, dS, slab, n_slabs, U, ldu, hid, fn, fe, transposed: bool) -> None:
-    """edge_tile_bwd on the CSR."""
-    _lib.check(_lib.lib().dss2_edge_hidden_bwd(x.data_ptr(), ldx, ea.data_ptr(), ldea, W1.data_ptr(), b1.data_ptr(), dS.data_ptr(),
-                                               *_csr_ent(topo, transposed), _ptr(slab), n_slabs, _ptr(U), ldu, topo.N, hid, fn, fe,
-                                               int(transposed), _stream(dS)), "dss2_edge_hidden_bwd")
+    a = _edge_args(x, ldx, ea, ldea, W1, b1, hid, fn, fe)
+    a.dS, a.slab, a.n_slabs, a.U, a.ldu, a.by_source = dS.data_ptr(), _ptr(slab), n_slabs, _ptr(U), ldu, int(transposed)
+    _fill_edge_graph(a, topo, topo.tiling, transposed, tiled)
+    _lib.check(_lib.lib().dss2_edge_bwd(C.byref(a), _stream(dS)), "dss2_edge_bwd")
 
 
 def edge_combine_fwd(topo: Topology, AB, ea, ldea, w1c: int, ldw: int, b1, S, h, fe) -> None:

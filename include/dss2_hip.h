@@ -204,25 +204,61 @@ int dss2_pack_weights(const dss2_pack_desc* descs, int n_desc, int max_elems, vo
 
 /* S[i,:] = sum_{e: tgt(e)=i} relu(W1 . [x_i | x_src(e) | ea'(e)] + b1)      (first Linear + ReLU
  * of networks.py:170-174,181, aggregated before the second Linear, which is linear:
- * out = S . W2^T + deg * b2 is finished by dss2_gemm_prop with nmat = 1).
- * fn must be 8 and fe must be 6 (the only dims the reference's data produces). h <= 256. */
-int dss2_edge_hidden_fwd(const float* x, int64_t ldx, const float* ea, int64_t ldea,
-                         const float* W1, const float* b1,
-                         const int32_t* rowptr, const int32_t* col, const int32_t* ent,
-                         float* S, int64_t n_nodes, int h, int fn, int fe, void* stream);
+ * out = S . W2^T + deg * b2 is finished by dss2_gemm_prop with nmat = 1), and its backward, which RECOMPUTES the ReLU
+ * gates: the two passes must run the same arithmetic.  One argument struct serves both:
+ *   graph, one of two forms.  ell_ent != NULL: tiles of 32 * nrb rows holding whole graphs (tile_start [ntiles + 1]) and their
+ *     ELL entry table, int2 {local other node, stored edge id | flip << 31 (-1 = empty slot)} [ntiles][ell_width][32 * nrb],
+ *     built once per topology from the CSR by target (forward, backward with by_source = 0) or by source (by_source = 1);
+ *     1 <= ell_width <= 32.  ell_ent == NULL: the CSR (rowptr, col, ent over n_nodes rows; by_source = 1: the transposed one),
+ *     one row per wavefront -- any degree.
+ *   dss2_edge_fwd writes S [N, h].  bwd_with_u != 0 announces that the backward will be asked for U (the gradient w.r.t. x):
+ *     the forward then takes the arithmetic that backward recomputes its gates with (dss2_edge_plan).
+ *   dss2_edge_bwd reads dS [N, h], the gradient w.r.t. S.
+ *     by_source = 0: per-workgroup partials of dW1 [h, 2 fn + fe] and db1 [h] into slab[n_slabs][h * (2 fn + fe) + h] (finish
+ *       with dss2_reduce_slabs*; on tiles min(n_slabs, ntiles) persistent workgroups write one slab each) and, if U != NULL,
+ *       U[i,:] = sum_{e -> i} dz_e (ldu floats per row).
+ *     by_source = 1: U[i,:] = sum_{e: src(e) = i} dz_e; slab is not touched.
+ * fn must be 8 and fe must be 6 (the only dims the reference's data produces).  h <= 256. */
+typedef struct dss2_edge_args {
+  const float* x; int64_t ldx; const float* ea; int64_t ldea; const float* W1; const float* b1; const float* dS;
+  const int32_t* tile_start; const void* ell_ent; int32_t ell_width, nrb, ntiles, pad_;
+  const int32_t* rowptr; const int32_t* col; const int32_t* ent; int64_t n_nodes;
+  float* S; float* slab; float* U; int64_t ldu; int32_t n_slabs;
+  int32_t h, fn, fe, bwd_with_u, by_source;
+} dss2_edge_args;
+int dss2_edge_fwd(const dss2_edge_args* args_host, void* stream);
+int dss2_edge_bwd(const dss2_edge_args* args_host, void* stream);
 
-/* Backward of the above.  dS[N,h] is the gradient w.r.t. S.
- * by_source = 0: walks the CSR by target; accumulates per-workgroup partial dW1[h,fn*2+fe] and
- *               db1[h] into slab[n_slabs][h*(2fn+fe) + h] (reduced by dss2_reduce_slabs) and,
- *               if U != NULL, writes U[i,:] = sum_{e->i} dz_e          (ldu floats per row).
- * by_source = 1: walks the transposed CSR (pass rowptrT/colT/entT); writes
- *               U[i,:] = sum_{e: src(e)=i} dz_e; slab is not touched.
- * Returns the number of slabs it will write through *n_slabs_out (host) when slab == NULL. */
-int dss2_edge_hidden_bwd(const float* x, int64_t ldx, const float* ea, int64_t ldea,
-                         const float* W1, const float* b1, const float* dS,
-                         const int32_t* rowptr, const int32_t* col, const int32_t* ent,
-                         float* slab, int n_slabs, float* U, int64_t ldu,
-                         int64_t n_nodes, int h, int fn, int fe, int by_source, void* stream);
+/* Which kernel each of the three passes of an edge MLP runs, and its launch geometry: the record dss2_edge_fwd / dss2_edge_bwd
+ * dispatch from (edge_select in csrc/dss2_edge.hip) and the layer chain's edge phases are derived from.  Families fall through
+ * bf16x6 -> fp32 MFMA -> VALU tile; no entry table: the CSR kernels (DESIGN.md 4.3 holds the table). */
+enum dss2_edge_family {
+  DSS2_EDGE_NONE = 0,     /* the pass is refused (h, an ELL width above 32) or not run (by source without U)                    */
+  DSS2_EDGE_CSR,          /* one CSR row per wavefront (edge_hidden_*_kernel)                                                   */
+  DSS2_EDGE_VALU,         /* VALU tile kernel, a row per wavefront (edge_tile_kernel)                                           */
+  DSS2_EDGE_VALU_HALF,    /* ... two rows per wavefront (h <= 32; DSS2_EDGE_TILE_HALF=0: off)                                   */
+  DSS2_EDGE_FP32_MFMA,    /* first Linear as fp32 MFMAs (edge_mfma_*_kernel)                                                    */
+  DSS2_EDGE_BF16X6        /* first Linear as bf16x6 (dss2_edge16.hip)                                                           */
+};
+typedef struct dss2_edge_pass_t {
+  int32_t family;         /* dss2_edge_family                                                                                   */
+  int32_t nrb;            /* 32-row blocks the kernel is instantiated (matrix pipe) or staged (VALU) for; CSR: 0                */
+  int32_t parts;          /* 2: 128- / 192-row tiles walked as two parts of 64 / 96 rows; else 1                                */
+  int32_t block;          /* threads per workgroup                                                                              */
+  int32_t wg_per_tile;    /* forward: workgroups per tile (2 with parts); backward passes: 0 = min(n_slabs, ntiles) persistent
+                           * workgroups (CSR: n_slabs); CSR forward: 0 = a wavefront per row                                    */
+  int32_t lds_bytes;      /* dynamic LDS of the launch                                                                          */
+} dss2_edge_pass_t;
+typedef struct dss2_edge_plan_t {
+  dss2_edge_pass_t fwd, bwd, bwd_src;   /* forward, backward by target, backward by source                                     */
+  int32_t pair_exact;     /* 1: forward and backward by target form the pre-activation with the same values in the same order
+                           * (same family), so the recomputed gates are the forward's bit for bit                               */
+  int32_t pad_;
+} dss2_edge_plan_t;
+/* ell_width / ellT_width: the ELL widths of the entry tables by target / by source, 0 = no table (the passes that would read it
+ * run on the CSR).  with_u: the backward forms U (dss2_edge_args.bwd_with_u, U != NULL); without it there is no pass by source.
+ * Answers from the arguments and the environment alone: no GPU needed. */
+int dss2_edge_plan(int h, int nrb, int ell_width, int ellT_width, int with_u, dss2_edge_plan_t* out);
 
 /* EdgeAggregation with node features of any width (networks.py:159-209 as MultiMPN / MaskEmbdMultiMPN instantiate it on the
  * hidden activation, networks.py:486-498).  AB[N, 2h] = X [W1[:, :d] ; W1[:, d:2d]]^T (one dss2_gemm_prop); W1c = &W1[0][2d]
@@ -238,26 +274,6 @@ int dss2_edge_combine_fwd(const float* AB, int64_t ldab, const float* ea, int64_
 int dss2_edge_combine_bwd(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw,
                           const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent,
                           float* dAB, float* slab, int n_slabs, int64_t n_nodes, int h, int fe, int by_source, void* stream);
-
-/* Tile-based variants of the two functions above (same arithmetic, same outputs): one workgroup per
- * tile with the tile's x rows, an ELL slice carrying edge ids and the gathered edge_attr rows staged
- * in LDS.  ell_ent: int2 {local other node, stored edge id | flip<<31 (-1 = empty slot)}
- * [ntiles][ell_width][32*nrb], built once per topology from the CSR by target (forward, backward with
- * by_source = 0) or by source (by_source = 1).  min(n_slabs, ntiles) persistent workgroups walk the
- * tiles and write one partial slab each. */
-int dss2_edge_tile_fwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1,
-                       const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width,
-                       int nrb, int ntiles, float* S, int h, int fn, int fe, void* stream);
-/* dss2_edge_tile_fwd for a caller that announces its backward.  bwd_with_u != 0: the caller's dss2_edge_tile_bwd will be asked for U
- * (the gradient w.r.t. x): the forward then takes the arithmetic that backward recomputes its ReLU gates with (on 96-row tiles the
- * fp32 form: the bf16x6 backward with U is not built there).  bwd_with_u == 0: exactly dss2_edge_tile_fwd. */
-int dss2_edge_tile_fwd_paired(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1,
-                              const float* b1, const int32_t* tile_start, const void* ell_ent, int ell_width,
-                              int nrb, int ntiles, float* S, int h, int fn, int fe, int bwd_with_u, void* stream);
-int dss2_edge_tile_bwd(const float* x, int64_t ldx, const float* ea, int64_t ldea, const float* W1,
-                       const float* b1, const float* dS, const int32_t* tile_start, const void* ell_ent,
-                       int ell_width, int nrb, int ntiles, float* slab, int n_slabs, float* U, int64_t ldu,
-                       int h, int fn, int fe, int by_source, void* stream);
 
 /* ---- K2/K4: fused tile GEMM + Horner graph propagation --------------------------------- *
  * Y = epilogue( sum_{m=0..nmat-1} P^m (X . B_m) ),  P = A_hat given by (rowptr, col, w).
@@ -351,7 +367,7 @@ int dss2_gemm_prop_chain(const dss2_gemm_prop_args* args_host, const dss2_chain_
  *   X = (gate > 0) * dropout(drop_id) * sum_m (P^T)^m G W_m with G[N][nout] the gradient w.r.t. the head's output, gate the
  *   head's input activation; X is also written to Xout (the weight-gradient kernels read it); args.X is ignored.
  * W[m]: the head's weights [nout][hid] row-major, m < nmat.  nout <= 4.  Same tiles / ELL slices as the chain. */
-/* The edge MLP's first Linear (the bf16x6 tile kernels of dss2_edge_tile_fwd / dss2_edge_tile_bwd, by target, without U) as a phase
+/* The edge MLP's first Linear (the bf16x6 tile kernels of dss2_edge_fwd / dss2_edge_bwd, by target, without U) as a phase
  * of the chain with the fused head, tile by tile (where dss2_gemm_prop_chain_edge_supported says so):
  *   mode 1: the chain's input tile is S = sum over the incoming edges of relu(W1 [x_i | x_j | edge_attr] + b1), computed in the
  *     launch's staging instead of read from args.X; S [N][hid] is still written (row-major, ld = hid).

@@ -142,6 +142,39 @@ def test_edge_aggregation_fwd_bwd(pkg, oracle, grid, hid, mfma, monkeypatch):
         assert rel_err(p.grad, q.grad) < TOL_GRAD, n
 
 
+@pytest.mark.parametrize("need_dx", [True, False])
+def test_edge_aggregation_one_sided_entry_table(pkg, oracle, need_dx, monkeypatch):
+    """A directed edge list with in-degree <= 8 < out-degree: seven stars of ten nodes, node 0 of each the source of nine edges.  The tiling
+    has the entry table by target (ell = 1) and none by source (ellT = 0); two 64-row tiles (forced: 70 rows alone would take one
+    96-row tile), the second holding one graph.  Forward and
+    backward then run the same kernels -- the row-per-wave ones on the CSR (the forward used to take the tile kernels, bf16x6, in front
+    of an fp32 backward that recomputed its gates)."""
+    monkeypatch.setenv("DSS2_NRB", "2")
+    torch.manual_seed(11)
+    stars, n, hid = 7, 10, 64
+    ei = torch.cat([torch.stack([torch.full((n - 1,), s * n), torch.arange(1, n) + s * n]) for s in range(stars)], 1)
+    x, ea = torch.randn(stars * n, 8), torch.randn(ei.shape[1], 6)
+    ts = pkg.networks.get_topology_asis(ei.to(DEV), stars * n).tiling
+    assert (ts.nrb, ts.ntiles, ts.ell, ts.ellT) == (2, 2, 1, 0) and ts.ell_ent_tiles is not None and ts.ellT_ent_tiles is None
+    assert (ts.tile_start[1:] - ts.tile_start[:-1]).tolist() == [60, 10]
+    assert pkg.networks._edge_tiled(ts, stars * n) == (False, 5)
+    ref = oracle.EdgeAggregation(8, 6, hid, hid).double()
+    mine = pkg.EdgeAggregation(8, 6, hid, hid).to(DEV)
+    mine.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    xr = x.double().requires_grad_(need_dx)
+    outr = ref(xr, ei, ea.double())
+    g = torch.randn(outr.shape)
+    outr.backward(g.double())
+    xm = x.to(DEV).requires_grad_(need_dx)
+    outm = mine(xm, ei.to(DEV), ea.to(DEV))
+    outm.backward(g.to(DEV))
+    assert rel_err(outm, outr) < TOL_OUT
+    if need_dx:
+        assert rel_err(xm.grad, xr.grad) < TOL_GRAD
+    for (name, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
+        assert rel_err(p.grad, q.grad) < TOL_GRAD, name
+
+
 def test_segment_sum(pkg):
     b = pkg.synthetic.make_batch(["cigre14", "cigre14_reswitched"], 64, seed=9)
     N = b["x"].shape[0]

@@ -44,10 +44,10 @@ cases = {
   "tag_fwd  H->2": (lambda: nw.gemm_prop(topo, h, H, H, plan.fwd[2], nmat, 2, out2, bias=bias2, narrow_h=2), 2.0 * N * H * nmat * 2),
   "tag_dgrad 2->H": (lambda: nw.gemm_prop(topo, g2, 2, nmat * 2, plan.bwd[2], 1, H, out, relu_src=h, transposed=True, prop_in=nmat - 1), 2.0 * N * H * nmat * 2),
   "tag_wgrad H->2": (lambda: nw.wgrad(topo, g2, 2, h, H, nmat, flatl), 2.0 * N * H * nmat * 2),
-  "edge_hidden_fwd": (lambda: pkg._lib.check(L.dss2_edge_hidden_fwd(xin.data_ptr(), 11, ein.data_ptr(), 13, W1.data_ptr(), b1.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), S.data_ptr(), N, H, 8, 6, st), "f"), 2.0 * topo.E2 * 14 * H + 2.0 * N * 8 * H),
-  "edge_hidden_bwd": (lambda: pkg._lib.check(L.dss2_edge_hidden_bwd(xin.data_ptr(), 11, ein.data_ptr(), 13, W1.data_ptr(), b1.data_ptr(), g.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.ent.data_ptr(), slab1.data_ptr(), 512, None, H, N, H, 8, 6, 0, st), "b"), 4.0 * topo.E2 * 22 * H),
-  "edge_tile_fwd": (lambda: pkg._lib.check(L.dss2_edge_tile_fwd(xin.data_ptr(), 11, ein.data_ptr(), 13, W1.data_ptr(), b1.data_ptr(), topo.tile_start.data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell, topo.nrb, topo.ntiles, S.data_ptr(), H, 8, 6, st), "f"), 2.0 * topo.E2 * 14 * H + 2.0 * N * 8 * H),
-  "edge_tile_bwd": (lambda: pkg._lib.check(L.dss2_edge_tile_bwd(xin.data_ptr(), 11, ein.data_ptr(), 13, W1.data_ptr(), b1.data_ptr(), g.data_ptr(), topo.tile_start.data_ptr(), topo.ell_ent_tiles.data_ptr(), topo.ell, topo.nrb, topo.ntiles, slab2.data_ptr(), 512, None, H, H, 8, 6, 0, st), "b"), 4.0 * topo.E2 * 22 * H),
+  "edge_fwd (CSR)": (lambda: nw.edge_fwd(topo, False, xin, 11, ein, 13, W1, b1, S, H, 8, 6, False), 2.0 * topo.E2 * 14 * H + 2.0 * N * 8 * H),
+  "edge_bwd (CSR)": (lambda: nw.edge_bwd(topo, False, xin, 11, ein, 13, W1, b1, g, slab1, 512, None, H, H, 8, 6, False), 4.0 * topo.E2 * 22 * H),
+  "edge_fwd (tiles)": (lambda: nw.edge_fwd(topo, True, xin, 11, ein, 13, W1, b1, S, H, 8, 6, False), 2.0 * topo.E2 * 14 * H + 2.0 * N * 8 * H),
+  "edge_bwd (tiles)": (lambda: nw.edge_bwd(topo, True, xin, 11, ein, 13, W1, b1, g, slab2, 512, None, H, H, 8, 6, False), 4.0 * topo.E2 * 22 * H),
   "pack_weights": (lambda: plan.refresh(), 1.0),
 }
 res = {k: [] for k in cases}
