@@ -1,6 +1,6 @@
 """MI355X-native (gfx950) implementation of the DSS2 message-passing + WLS-loss hot path.
 
-Drop-in modules ``networks`` (EdgeAggregation, TAGConv, MPN, SkipMPN, PFN, SkipPFN, GATv2Conv, GAT_DSSE, GINEConv, GINE_DSSE, GCN2Conv, FAConv, gnn_dsse) and ``data``
+Drop-in modules ``networks`` (EdgeAggregation, TAGConv, MPN, SkipMPN, PFN, SkipPFN, GATv2Conv, GAT_DSSE, GINEConv, GINE_DSSE, GCN2Conv, FAConv, gnn_dsse, ChebConv, WrappedMultiConv, MultiConvNet) and ``data``
 (gsp_wls_edge, get_pflow) mirror /root/reference/networks.py and /root/reference/data.py for the
 path BASELINE.json names; everything below them is hand-written HIP in libdss2_hip.so.
 """
@@ -14,9 +14,10 @@ from .networks import EdgeAggregation, TAGConv, MPN, SkipMPN, PFN, SkipPFN, Mess
 from .gat import GATv2Conv, GAT_DSSE  # noqa: F401
 from .gine import GINEConv, GINE_DSSE  # noqa: F401
 from .gnn import GCN2Conv, FAConv, gnn_dsse  # noqa: F401
+from .cheb import ChebConv, WrappedMultiConv, MultiConvNet  # noqa: F401
 from .data import gsp_wls_edge, get_pflow  # noqa: F401
 from .dataset import data_from_pickles, DataLoader, DeviceDataset, MixedDataset  # noqa: F401
 
-__all__ = ["MaskEmbdMPN", "MultiMPN", "MaskEmbdMultiMPN", "MaskEmbdMultiMPN_NoMP", "EdgeAggregationGeneral", "EdgeAggregation", "TAGConv", "MPN", "SkipMPN", "PFN", "SkipPFN", "MessagePassing", "GATv2Conv", "GAT_DSSE", "GINEConv", "GINE_DSSE", "GCN2Conv", "FAConv", "gnn_dsse",
+__all__ = ["MaskEmbdMPN", "MultiMPN", "MaskEmbdMultiMPN", "MaskEmbdMultiMPN_NoMP", "EdgeAggregationGeneral", "EdgeAggregation", "TAGConv", "MPN", "SkipMPN", "PFN", "SkipPFN", "MessagePassing", "GATv2Conv", "GAT_DSSE", "GINEConv", "GINE_DSSE", "GCN2Conv", "FAConv", "gnn_dsse", "ChebConv", "WrappedMultiConv", "MultiConvNet",
            "gsp_wls_edge", "get_pflow", "data_from_pickles", "DataLoader", "DeviceDataset", "MixedDataset", "FusedAdamax", "dataset", "networks", "data", "parallel", "graphs", "optim", "synthetic",
-           "topology", "flags", "ops", "plans", "gat", "gine", "gnn"]
+           "topology", "flags", "ops", "plans", "gat", "gine", "gnn", "cheb"]

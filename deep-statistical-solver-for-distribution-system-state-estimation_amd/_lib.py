@@ -292,6 +292,40 @@ class GnnArgs(C.Structure):
                 ("dh_cols", C.c_int32), ("pad_", C.c_int32), ("dx0", C.c_void_p)]
 
 
+CHEB_MAX_K, CHEB_MAX_CONVS = 4, 4
+
+
+class ChebGraph(C.Structure):
+    _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("ent", C.c_void_p), ("perm", C.c_void_p), ("rowptrT", C.c_void_p),
+                ("colT", C.c_void_p), ("entT", C.c_void_p), ("permT", C.c_void_p), ("efrom", C.c_void_p), ("eto", C.c_void_p),
+                ("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("n_rows", C.c_int64), ("ed", C.c_int32), ("n_convs", C.c_int32),
+                ("w", C.c_void_p), ("what", C.c_void_p), ("dn", C.c_void_p), ("lam", C.c_void_p), ("arg", C.c_void_p),
+                ("slab", C.c_void_p), ("n_slabs", C.c_int32), ("slab_len", C.c_int32)]
+
+
+class ChebLayer(C.Structure):
+    _fields_ = [("W", (C.c_void_p * CHEB_MAX_K) * CHEB_MAX_CONVS), ("bias", C.c_void_p * CHEB_MAX_CONVS), ("h", C.c_void_p),
+                ("ldh", C.c_int64), ("y", C.c_void_p), ("T", C.c_void_p), ("dv", C.c_void_p), ("r", C.c_void_p * 2),
+                ("cin", C.c_int32), ("cout", C.c_int32), ("K", C.c_int32), ("relu", C.c_int32), ("drop_id", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class ChebArgs(C.Structure):
+    _fields_ = [("g", ChebGraph), ("up", ChebLayer), ("lo", ChebLayer), ("head", LanegroupHead), ("has_up", C.c_int32),
+                ("has_lo", C.c_int32), ("has_head", C.c_int32), ("group", C.c_int32), ("hop", C.c_int32), ("acc_first", C.c_int32),
+                ("gy", C.c_void_p), ("ldgy", C.c_int64), ("dh", C.c_void_p), ("dh_cols", C.c_int32), ("pad_", C.c_int32),
+                ("dwh", C.c_void_p), ("ddn", C.c_void_p), ("drop_state", C.c_void_p), ("drop_thr", C.c_uint32),
+                ("drop_scale", C.c_float)]
+
+
+class ChebEdgeArgs(C.Structure):
+    _fields_ = [("g", ChebGraph), ("ea", C.c_void_p), ("ldea", C.c_int64), ("W1", C.c_void_p), ("b1", C.c_void_p),
+                ("W2", C.c_void_p), ("b2", C.c_void_p), ("w_in", C.c_void_p), ("ldw", C.c_int64), ("has_mlp", C.c_int32),
+                ("hid", C.c_int32), ("lambda_given", C.c_int32), ("lambda_", C.c_float), ("n_wg", C.c_int32), ("zero_in", C.c_int32),
+                ("pmax", C.c_void_p), ("parg", C.c_void_p), ("psum", C.c_void_p), ("dwh", C.c_void_p), ("ddn", C.c_void_p),
+                ("dw", C.c_void_p), ("dz1", C.c_void_p), ("a1", C.c_void_p)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "dss2_last_error": (C.c_char_p, []),
@@ -397,6 +431,10 @@ _SIGNATURES = {
     "dss2_gnn_forward": (C.c_int, [C.POINTER(GnnArgs), C.c_void_p]),
     "dss2_gnn_backward": (C.c_int, [C.POINTER(GnnArgs), C.c_void_p]),
     "dss2_gnn_dis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "dss2_cheb_edge_forward": (C.c_int, [C.POINTER(ChebEdgeArgs), C.c_void_p]),
+    "dss2_cheb_edge_backward": (C.c_int, [C.POINTER(ChebEdgeArgs), C.c_void_p]),
+    "dss2_cheb_forward": (C.c_int, [C.POINTER(ChebArgs), C.c_void_p]),
+    "dss2_cheb_backward": (C.c_int, [C.POINTER(ChebArgs), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1041,3 +1041,5 @@ from .gat import GATv2Conv, GAT_DSSE  # noqa: E402,F401
 from .gine import GINEConv, GINE_DSSE  # noqa: E402,F401
 # the reference's GCN2 / FA / TAG model (networks.py:11-69), defined in gnn.py on its own kernels
 from .gnn import GCN2Conv, FAConv, gnn_dsse  # noqa: E402,F401
+# the reference's parallel-ChebConv model (networks.py:737-835), defined in cheb.py on its own kernels
+from .cheb import ChebConv, WrappedMultiConv, MultiConvNet  # noqa: E402,F401

@@ -1008,6 +1008,84 @@ int dss2_gnn_backward(const dss2_gnn_args* args_host, void* stream);
  * 2 entries with col == i dropped and one loop added (add_remaining_self_loops) */
 int dss2_gnn_dis(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int mode, float* dis, void* stream);
 
+/* ---- MultiConvNet (reference networks.py:737-835): parallel PyG ChebConv (normalization=None), one per edge feature, with LEARNED  *
+ * edge weights, csrc/dss2_cheb.hip -------------------------------------------------------------------------------------------------- *
+ * Graph: a Topology, doubled by the reference's rule or as given: n_edges directed entries (perm / permT: the directed id d of a CSR  *
+ * entry), n_rows stored edges (ent / entT: the stored id r; efrom / eto its endpoints); d >= n_rows is the reverse of row d - n_rows   *
+ * and carries the same weight.  Entries with source == target are dropped (get_laplacian).  Conv f < n_convs has the edge weights     *
+ * w[f][r].  dss2_cheb_edge_forward builds, per f: w (from the edge MLP or from w_in), deg_i = sum of w over the edges LEAVING i,       *
+ * lambda = 2 max over every -w_d and every deg_i of the call (one scalar for the whole batch; the FIRST entry in the order d = 0 ..    *
+ * n_edges - 1, then the nodes, on a tie), what[f][r] = 2 (-w) / lambda and dn[f][i] = 2 deg_i / lambda, +inf replaced by 0.  Then      *
+ *     (A t)_i = (dn_i - 1) t_i + sum_{d: j->i} what_d t_j,   T_0 = x, T_1 = A x, T_k = 2 A T_{k-1} - T_{k-2},                          *
+ *     out = sum_f (sum_{k<K} lins[k] T_k + bias)                                                                                       *
+ * one node per lane group (`group` = 8 / 16 / 32 lanes, cin, cout <= group), the grid is n_slabs workgroups.  Forward hop launches 1.. *
+ * K-1 (one launch, hop 0, when K = 1): hop k writes T_k of every conv and adds its products to y; the first adds the k = 0 products    *
+ * and the biases, the last applies dropout (drop_id > 0) and ReLU.  Backward, with r_k the adjoint of T_k and dv the gradient of the   *
+ * layer's output before dropout / ReLU: hop launches k = K-1 .. 1 (hop 0 when K = 1) of the layer `up`                                 *
+ *     r_{k-1} = lins[k-1]^T dv + c_k A^T r_k - r_{k+1},  dwh_d (+)= c_k <r_k(i), T_{k-1}(j)>,  ddn_i (+)= c_k <r_k(i), T_{k-1}(i)>     *
+ * (c_1 = 1, c_k = 2; acc_first != 0 stores, else adds: each entry has one owning lane group per launch), the last one hands sum_f r_0   *
+ * to the local step of the layer `lo` below (dv through its gate, r_{K-1} = lins[K-1]^T dv) or writes it to dh.  The weight gradients  *
+ * of the lins are outer products of dv and the saved T_k: dss2_lanegroup_wgrad.  dss2_cheb_edge_backward turns dwh / ddn into the      *
+ * gradient of w (through what, dn and lambda's arg-max entry; fixed-order sums) and, with the MLP, into dz1 / a1 / dw for              *
+ * dss2_lanegroup_wgrad over the n_rows stored edges.                                                                                   */
+#define DSS2_CHEB_MAX_K 4                  /* Chebyshev terms of one conv (PyG's K) */
+#define DSS2_CHEB_MAX_CONVS 4              /* parallel convs of one layer */
+typedef struct dss2_cheb_graph {
+  const int32_t* rowptr; const int32_t* col; const int32_t* ent; const int32_t* perm;
+  const int32_t* rowptrT; const int32_t* colT; const int32_t* entT; const int32_t* permT;
+  const int32_t* efrom; const int32_t* eto; /* [n_rows] source / target of the stored edges */
+  int64_t n_nodes; int64_t n_edges; int64_t n_rows;
+  int32_t ed;                              /* 0 (the shared lane-group checks read it) */
+  int32_t n_convs;
+  float* w; float* what;                   /* [n_convs][n_rows] */
+  float* dn;                               /* [n_convs][n_nodes] */
+  float* lam; int64_t* arg;                /* [n_convs]: lambda_max; its arg-max entry (d, or n_edges + i; -1 with a given lambda) */
+  float* slab; int32_t n_slabs; int32_t slab_len;
+} dss2_cheb_graph;
+typedef struct dss2_cheb_layer {
+  const float* W[DSS2_CHEB_MAX_CONVS][DSS2_CHEB_MAX_K];   /* lins.k.weight of conv f, [cout][cin] */
+  const float* bias[DSS2_CHEB_MAX_CONVS];  /* [cout] or NULL */
+  const float* h; int64_t ldh;             /* layer input [N][cin] */
+  float* y;                                /* forward: output after dropout and ReLU [N][cout] */
+  float* T;                                /* forward: T_k of conv f at ((f (K - 1) + k - 1) N) cin, k = 1..K-1; NULL when K = 1 */
+  float* dv;                               /* backward: gradient of the output before dropout / ReLU [N][cout] */
+  float* r[2];                             /* backward: r_k of conv f at r[k % 2] + f N cin; NULL when K = 1 */
+  int32_t cin; int32_t cout; int32_t K; int32_t relu; int32_t drop_id; int32_t pad_;
+} dss2_cheb_layer;
+typedef struct dss2_cheb_args {
+  dss2_cheb_graph g;
+  dss2_cheb_layer up;                      /* backward: the layer whose adjoint hop this launch runs (has_up) */
+  dss2_cheb_layer lo;                      /* forward: the layer; backward: the layer whose local step this launch runs */
+  dss2_lanegroup_head head;                /* unused: these models have no head Linears (has_head must be 0) */
+  int32_t has_up; int32_t has_lo; int32_t has_head; int32_t group;
+  int32_t hop; int32_t acc_first;
+  const float* gy; int64_t ldgy;           /* backward without up: gradient of lo's output */
+  float* dh; int32_t dh_cols; int32_t pad_;  /* backward without lo: gradient of the model input [N][dh_cols], or NULL */
+  float* dwh; float* ddn;                  /* backward: gradients of what per DIRECTED edge [n_convs][n_edges] and of dn [n_convs][n_nodes] */
+  const uint64_t* drop_state; uint32_t drop_thr; float drop_scale;   /* dropout of the layers with drop_id > 0 */
+} dss2_cheb_args;
+typedef struct dss2_cheb_edge_args {
+  dss2_cheb_graph g;
+  const float* ea; int64_t ldea;           /* has_mlp: edge attributes [n_rows][>= 2]; w = ea[:, :2] + W2 relu(W1 ea[:, :2] + b1) + b2 */
+  const float* W1; const float* b1; const float* W2; const float* b2;   /* Linear(2, hid), Linear(hid, 2) */
+  const float* w_in; int64_t ldw;          /* without the MLP: the weights [n_rows][n_convs] */
+  int32_t has_mlp; int32_t hid;            /* hid <= 64; the MLP needs n_convs == 2 */
+  int32_t lambda_given; float lambda;      /* != 0: lambda_max is `lambda` (no gradient through it) */
+  int32_t n_wg; int32_t zero_in;           /* workgroups (<= 256); backward: dwh / ddn are all zero and not read (K = 1) */
+  float* pmax; int64_t* parg; float* psum; /* [n_convs][n_wg] partials of the maximum, its arg-max and the backward's sum */
+  const float* dwh; const float* ddn;      /* backward, as in dss2_cheb_args */
+  float* dw;                               /* backward: gradient of the weights [n_rows][n_convs] (both directions summed) */
+  float* dz1; float* a1;                   /* backward, has_mlp: gradient of the hidden pre-activation and the hidden activation [n_rows][hid] */
+} dss2_cheb_edge_args;
+/* w, dn (holding deg), the partial maxima; then lambda, what and dn (two kernels, one after the other on the stream) */
+int dss2_cheb_edge_forward(const dss2_cheb_edge_args* args_host, void* stream);
+/* the partial sums of lambda's chain; then dw (and dz1, a1) */
+int dss2_cheb_edge_backward(const dss2_cheb_edge_args* args_host, void* stream);
+/* forward hop args.hop of the layer lo */
+int dss2_cheb_forward(const dss2_cheb_args* args_host, void* stream);
+/* backward: (adjoint hop args.hop of up | gy), then lo's local step, or the input gradient into dh */
+int dss2_cheb_backward(const dss2_cheb_args* args_host, void* stream);
+
 /* LDS bytes a dss2_gemm_prop / dss2_wgrad launch will request (host-side helper; lets the
  * caller reject configurations that do not fit the 160 KiB LDS before launching). */
 size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width);
