@@ -71,6 +71,14 @@ class WgradPlan(C.Structure):
                 ("launch_lds", C.c_uint64), ("sizing_lds", C.c_uint64)]
 
 
+class GemmPlan(C.Structure):
+    """dss2_gemm_prop_plan_t: the kernel a single-layer tile GEMM + propagation launch runs and its geometry (include/dss2_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "reason", "row_split", "waves", "block", "pad_")] + [("lds_bytes", C.c_uint64), ("sizing_lds", C.c_uint64)]
+
+
+GEMM_NONE, GEMM_NARROW_STREAM, GEMM_NARROW, GEMM_FP32, GEMM_FP32_KHALF, GEMM_BF16X6_KHALF = range(6)      # dss2_gemm_kernel
+
+
 class ChainKernel(C.Structure):
     """dss2_chain_kernel_t: the layer chain's kernel for one weight format, its geometry and what it carries (include/dss2_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("family", "row_split", "waves", "block", "lds_bytes", "gate_words", "head_modes", "head_wgrad", "edge_modes")]
@@ -362,6 +370,7 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),
     "dss2_gemm_prop": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p]),
+    "dss2_gemm_prop_plan": (C.c_int, [C.POINTER(GemmPropArgs), C.POINTER(GemmPlan)]),
     "dss2_chain_sp6_single_group_min_tiles": (C.c_int, []),
     "dss2_gemm_prop_chain": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p, C.c_int, C.c_void_p]),
     "dss2_gemm_prop_chain_head": (C.c_int, [C.POINTER(GemmPropArgs), C.c_void_p, C.c_int, C.POINTER(ChainHead), C.c_void_p]),

@@ -880,40 +880,20 @@ __global__ void __launch_bounds__(256) gemm_narrow_stream_kernel(const dss2_gemm
   }
 }
 
-static bool narrow_stream_ok(const dss2_gemm_prop_args& a) {
-  static const int enabled = [] { const char* e = getenv("DSS2_NARROW_STREAM"); return e ? atoi(e) : 1; }();
-  return enabled && a.nmat * a.narrow_h <= NS_MAXO && (a.kpad & 15) == 0 && (a.kreal & 3) == 0 && (a.ldx & 3) == 0 &&
-         (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && (a.nrb <= 4 || a.nrb == 6) && (a.nmat == 1 || (a.ell_width > 0 && a.ell_tiles));
-}
-
-template <int NRB>
-static int launch_narrow_stream(const dss2_gemm_prop_args& a, hipStream_t stream) {
-  const size_t lds = (size_t)NS_MAXO * a.kpad * 4 + (size_t)NRB * 32 * NS_MAXO * 4 +
-                     (a.nmat > 1 ? (size_t)NRB * 32 * a.ell_width * 8 : 0);
-  hipLaunchKernelGGL(gemm_narrow_stream_kernel<NRB>, dim3(a.ntiles), dim3(256), lds, stream, a);
-  return check_launch("gemm_narrow_stream");
-}
-
-static size_t narrow_lds_bytes(int nrb, int nmat, int kpad, int max_nnz, int ell_width) {
-  const size_t TM = (size_t)nrb * 32;
-  size_t b = TM * (size_t)(kpad + 4) * 4 + TM * 32 * 4;
-  if (nmat > 1) b += ell_width > 0 ? TM * (size_t)ell_width * 8 : (TM + 2) * 4 + (size_t)max_nnz * 8;
-  return b;
-}
-
-template <int NRB>
-static int launch_narrow(const dss2_gemm_prop_args& a, hipStream_t stream) {
-  static std::atomic<uint32_t> lds_done{0};
-  auto kern = gemm_narrow_kernel<NRB>;
-  if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_narrow")) return 1;
-  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), narrow_lds_bytes(NRB, a.nmat, a.kpad, a.max_nnz, a.ell_width),
-                     stream, a);
-  return check_launch("gemm_narrow");
+// Host side.  Which kernel a launch runs and with which geometry is decided in ONE function, gemm_select; the exported queries and
+// the dispatch read its record (dss2_gemm_prop_plan_t in include/dss2_hip.h).  Every environment switch of it, read once per process:
+struct GemmSwitches { int narrow_stream, khalf, rs; };
+static const GemmSwitches& gemm_switches() {
+  static const GemmSwitches sw = [] {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    return GemmSwitches{env("DSS2_NARROW_STREAM", 1), env("DSS2_GEMM_KHALF", 1), env("DSS2_GEMM_RS", 2)};
+  }();
+  return sw;
 }
 
 static size_t lds_bytes_nw(int nrb, int nmat, int kpad, int nw, int max_nnz, int ell_width) {
   const size_t TM = (size_t)nrb * 32;
-  size_t b = TM * (size_t)(kpad + 4) * 4 + (size_t)nw * 32 * (TM + 4) * 4;   // X tile + wave stages
+  size_t b = TM * (size_t)(kpad + 4) * 4 + (size_t)nw * 32 * (TM + 4) * 4;   // X tile + wave stages (+ the graph slice, ELL or CSR)
   if (nmat > 1) b += ell_width > 0 ? TM * (size_t)ell_width * 8 : (TM + 2) * 4 + (size_t)max_nnz * 8;
   return b;
 }
@@ -926,55 +906,98 @@ static int gemm_waves(int ncg, int nrb, int nmat, int kpad, int max_nnz, int ell
   return nw;
 }
 
-static size_t lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width) {
-  return lds_bytes_nw(nrb, nmat, kpad, gemm_waves(ncg, nrb, nmat, kpad, max_nnz, ell_width), max_nnz, ell_width);
-}
-
-// bf16x6 variant: the matrix-sequential, K-halved configuration only (every column group its own wave)
-static bool gemm16_shape_ok(int nrb, int nmat, int kreal, int hout, int max_nnz, int ell_width) {
-  const int kpad = (kreal + 15) / 16 * 16, ncg = (hout + 31) / 32;
-  const bool seq = nmat > 1 && nrb * nmat >= 16;
-  return seq && (nrb == 6 || nrb == 4) && ncg <= 4 && (kpad & 31) == 0 && (kreal & 3) == 0 && (hout & 3) == 0 && ell_width > 0 && ell_width <= 32 &&
-         gemm_waves(ncg, nrb, nmat, kpad, max_nnz, ell_width) < ncg &&
-         lds_bytes_nw(nrb, nmat, kpad / 2, ncg, max_nnz, ell_width) <= (size_t)kMaxLdsBytes;
+// a launch takes its block size and LDS bytes from the selection's record
+using GemmLauncher = int (*)(const dss2_gemm_prop_args&, hipStream_t, const dss2_gemm_prop_plan_t&);
+template <int NRB, bool STREAM>
+static int launch_narrow(const dss2_gemm_prop_args& a, hipStream_t stream, const dss2_gemm_prop_plan_t& p) {
+  static std::atomic<uint32_t> lds_done{0};
+  auto kern = STREAM ? gemm_narrow_stream_kernel<NRB> : gemm_narrow_kernel<NRB>;
+  if (!STREAM && ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_narrow")) return 1;      // (streaming: a few KB)
+  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(p.block), p.lds_bytes, stream, a);
+  return check_launch(STREAM ? "gemm_narrow_stream" : "gemm_narrow");
 }
 
 template <int NRB, int NMAT, bool B16 = false, int RSP = 1>
-static int launch(const dss2_gemm_prop_args& a_in, hipStream_t stream) {
-  dss2_gemm_prop_args a = a_in;
+static int launch(const dss2_gemm_prop_args& a, hipStream_t stream, const dss2_gemm_prop_plan_t& p) {
   static std::atomic<uint32_t> lds_done{0};
   auto kern = gemm_prop_kernel<NRB, NMAT, B16, RSP>;
   if (ensure_max_lds(reinterpret_cast<const void*>(kern), lds_done, "gemm_prop")) return 1;
-  size_t lds = lds_bytes(NRB, a.prop_in > 0 ? 2 : NMAT, a.kpad, a.ncg, a.max_nnz, a.ell_width);
-  int nw = gemm_waves(a.ncg, NRB, a.prop_in > 0 ? 2 : NMAT, a.kpad, a.max_nnz, a.ell_width);
-  // tall tiles in matrix-sequential mode: stage the X tile in two K halves if that lets every column group have its wave
-  constexpr bool seq = NMAT > 1 && NRB * NMAT >= 16;
-  static const int kh_env = [] { const char* e = getenv("DSS2_GEMM_KHALF"); return e ? atoi(e) : 1; }();
-  const bool vec = ((a.kreal & 3) == 0) && ((a.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.X) & 15) == 0);
-  if (seq && kh_env && a.prop_in == 0 && a.ncg <= 4 && nw < a.ncg && (a.kpad & 15) == 0 && vec && a.ell_width > 0 &&
-      lds_bytes_nw(NRB, NMAT, a.kpad / 2, a.ncg, a.max_nnz, a.ell_width) <= (size_t)kMaxLdsBytes) {
-    nw = a.ncg;
-    lds = lds_bytes_nw(NRB, NMAT, a.kpad / 2, a.ncg, a.max_nnz, a.ell_width);
-    a.relu |= 1 << 24;
-  } else if (B16) {
-    set_error("gemm_prop(bf16x6): needs the K-halved matrix-sequential configuration (nrb=%d nmat=%d kpad=%d ncg=%d)", NRB, NMAT, a.kpad, a.ncg);
-    return 2;
-  }
-  // persistent over tiles: at most two workgroups per CU are co-resident at the LDS sizes of the
-  // compute-heavy shapes, so 512 workgroups cover the chip; each walks tiles blockIdx.x, +grid, ...
-  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * nw * RSP), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(p.block), p.lds_bytes, stream, a);      // one workgroup per tile
   return check_launch("gemm_prop");
+}
+
+// the launcher of a kernel family at (nrb, nmat, row split), or null: the instantiations that exist
+static GemmLauncher gemm_launcher(int kernel, int nrb, int nmat, int rs) {
+  const bool narrow = kernel == DSS2_GEMM_NARROW || kernel == DSS2_GEMM_NARROW_STREAM, fp32 = kernel == DSS2_GEMM_FP32 || kernel == DSS2_GEMM_FP32_KHALF;
+#define DSS2_CASE(NRB) /* narrow: the matrices sit side by side in one column group, no nmat in the instantiation */ \
+  if (narrow && nrb == NRB) return kernel == DSS2_GEMM_NARROW ? launch_narrow<NRB, false> : launch_narrow<NRB, true>; \
+  if (fp32 && nrb == NRB && rs == 1) return nmat == 1 ? launch<NRB, 1> : nmat == 2 ? launch<NRB, 2> : nmat == 3 ? launch<NRB, 3> : nmat == 4 ? launch<NRB, 4> : nullptr;
+  DSS2_CASE(1) DSS2_CASE(2) DSS2_CASE(3) DSS2_CASE(4) DSS2_CASE(6)
+#undef DSS2_CASE
+#define DSS2_CASE(NRB, NMAT) /* bf16x6: the matrix-sequential tall tiles; one wave per column group or two (row split) */ \
+  if (kernel == DSS2_GEMM_BF16X6_KHALF && nrb == NRB && nmat == NMAT) return rs == 1 ? launch<NRB, NMAT, true> : rs == 2 ? launch<NRB, NMAT, true, 2> : nullptr;
+  DSS2_CASE(6, 3) DSS2_CASE(6, 4) DSS2_CASE(4, 4)
+#undef DSS2_CASE
+  return nullptr;
+}
+
+// The ONE place a single-layer launch gets its kernel and geometry: from the shape, the operand facts (alignment of X, ldx, rowscale,
+// ell_tiles) and the switches.  What is an error whatever the kernel is the dispatch's to refuse first (dss2_gemm_prop_launch, step 1).
+static dss2_gemm_prop_plan_t gemm_select(const dss2_gemm_prop_args& a) {
+  const GemmSwitches& sw = gemm_switches();
+  dss2_gemm_prop_plan_t p = {};
+  auto none = [&](int reason) { p.reason = reason; return p; };
+  auto take = [&](int kernel, int rs, int waves, size_t lds) {
+    if (!gemm_launcher(kernel, a.nrb, a.nmat, rs)) return none(2);
+    p.kernel = kernel; p.row_split = rs; p.waves = waves; p.block = 64 * waves * rs; p.lds_bytes = lds;
+    return p;
+  };
+  const int nmat_staged = a.prop_in > 0 ? 2 : a.nmat;      // input-side propagation stages a graph slice like two matrices do
+  const int nw = gemm_waves(a.ncg, a.nrb, nmat_staged, a.kpad, a.max_nnz, a.ell_width);
+  p.sizing_lds = lds_bytes_nw(a.nrb, nmat_staged, a.kpad, nw, a.max_nnz, a.ell_width);
+  const bool vec = (a.kreal & 3) == 0 && (a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;      // 16-byte loads of X rows
+  if (a.narrow_h > 0) {
+    const size_t TM = (size_t)a.nrb * 32, lds = lds_bytes_nw(a.nrb, a.nmat, a.kpad, 0, a.max_nnz, a.ell_width) + TM * 32 * 4;      // (one [rows][32] stage)
+    if (lds > (size_t)kMaxLdsBytes) return none(3);
+    const bool stream = sw.narrow_stream && a.nmat * a.narrow_h <= NS_MAXO && (a.kpad & 15) == 0 && vec &&
+                        (a.nmat == 1 || (a.ell_width > 0 && a.ell_tiles));
+    if (stream) return take(DSS2_GEMM_NARROW_STREAM, 1, 4, (size_t)NS_MAXO * a.kpad * 4 + TM * NS_MAXO * 4 + (a.nmat > 1 ? TM * a.ell_width * 8 : 0));
+    return take(DSS2_GEMM_NARROW, 1, 4, lds);
+  }
+  if (p.sizing_lds > (size_t)kMaxLdsBytes) return none(3);      // (also where K-halving would fit: the refusal every caller sizes by)
+  if (a.b_format != 0 && a.b_format != 1) return none(2);
+  // K-halved staging: tall tiles in matrix-sequential mode stage the X tile in two K halves if that lets every column group have its
+  // wave.  The conditions both weight formats share, then each format's own, side by side:
+  const size_t lds_half = lds_bytes_nw(a.nrb, a.nmat, a.kpad / 2, a.ncg, a.max_nnz, a.ell_width);
+  const bool khalf = sw.khalf && a.nmat > 1 && a.nrb * a.nmat >= 16 && a.prop_in == 0 && a.ncg <= 4 && nw < a.ncg && vec &&
+                     a.ell_width > 0 && lds_half <= (size_t)kMaxLdsBytes;
+  const bool khalf_fp32 = khalf && (a.kpad & 15) == 0;
+  const bool khalf_bf16 = khalf && (a.kpad & 31) == 0 && a.kpad == (a.kreal + 15) / 16 * 16 && (a.hout & 3) == 0 && !a.rowscale && a.ell_width <= 32;
+  if (a.b_format == 1) return khalf_bf16 ? take(DSS2_GEMM_BF16X6_KHALF, sw.rs == 2 ? 2 : 1, a.ncg, lds_half) : none(2);      // (bf16x6 exists K-halved only)
+  return khalf_fp32 ? take(DSS2_GEMM_FP32_KHALF, 1, a.ncg, lds_half) : take(DSS2_GEMM_FP32, 1, nw, p.sizing_lds);
 }
 
 }  // namespace dss2
 
-extern "C" size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width) {
-  return dss2::lds_bytes(nrb, nmat, kpad, ncg, max_nnz, ell_width);
+extern "C" int dss2_gemm_prop_plan(const dss2_gemm_prop_args* ap, dss2_gemm_prop_plan_t* out) {
+  if (!ap || !out) { dss2::set_error("dss2_gemm_prop_plan: null argument"); return 2; }
+  *out = dss2::gemm_select(*ap);
+  return 0;
 }
 
+// The older queries: readers of the record for a launch known by its shape only (operands aligned, ELL slices present where there is a
+// width; never dereferenced here).
+static dss2_gemm_prop_plan_t gemm_shape_plan(int nrb, int nmat, int kreal, int kpad, int hout, int ncg, int max_nnz, int ell_width, int b_format) {
+  dss2_gemm_prop_args a = {};
+  a.nrb = nrb; a.nmat = nmat; a.kreal = kreal; a.kpad = kpad; a.hout = hout; a.ncg = ncg; a.max_nnz = max_nnz; a.ell_width = ell_width; a.b_format = b_format;
+  a.ell_tiles = ell_width > 0 ? &a : nullptr;
+  return dss2::gemm_select(a);
+}
+extern "C" size_t dss2_gemm_prop_lds_bytes(int nrb, int nmat, int kpad, int ncg, int max_nnz, int ell_width) {
+  return gemm_shape_plan(nrb, nmat, kpad, kpad, ncg * 32, ncg, max_nnz, ell_width, 0).sizing_lds;
+}
 extern "C" int dss2_gemm_prop16_supported(int nrb, int nmat, int kreal, int hout, int max_nnz, int ell_width) {
-  if (!((nrb == 6 && (nmat == 3 || nmat == 4)) || (nrb == 4 && nmat == 4))) return 0;
-  return dss2::gemm16_shape_ok(nrb, nmat, kreal, hout, max_nnz, ell_width) ? 1 : 0;
+  return gemm_shape_plan(nrb, nmat, kreal, (kreal + 15) / 16 * 16, hout, (hout + 31) / 32, max_nnz, ell_width, 1).kernel == DSS2_GEMM_BF16X6_KHALF;
 }
 
 static int dss2_pack_weights_launch(const dss2_pack_desc* descs, int n_desc, int max_elems, void* stream);
@@ -997,65 +1020,29 @@ extern "C" int dss2_gemm_prop(const dss2_gemm_prop_args* ap, void* stream) {
 }
 static int dss2_gemm_prop_launch(const dss2_gemm_prop_args* ap, void* stream) {
   using namespace dss2;
-  const dss2_gemm_prop_args& a = *ap;
+  dss2_gemm_prop_args a = *ap;
   if (a.ntiles <= 0) return 0;
+  // 1. what is an error whatever the kernel
   if ((a.kpad & 7) || a.kpad < a.kreal || a.kpad <= 0) { set_error("gemm_prop: bad kpad %d (kreal %d)", a.kpad, a.kreal); return 2; }
   if (a.ncg * 32 < a.hout || a.ncg <= 0) { set_error("gemm_prop: ncg %d too small for hout %d", a.ncg, a.hout); return 2; }
   if ((a.nmat > 1 || a.prop_in > 0) && (!a.rowptr || !a.col || !a.w)) { set_error("gemm_prop: propagation needs a CSR"); return 2; }
   if (a.prop_in > 0 && (a.nmat != 1 || a.kreal % (a.prop_in + 1) != 0)) { set_error("gemm_prop: prop_in needs nmat == 1 and kreal divisible by prop_in+1"); return 2; }
   if (a.prebias && (!a.pre_rowscale || a.narrow_h > 0 || a.prop_in > 0)) { set_error("gemm_prop: prebias needs pre_rowscale and the general kernel"); return 2; }
   if (a.drop_id && (!a.drop_state || a.narrow_h > 0)) { set_error("gemm_prop: in-kernel dropout needs drop_state and the general kernel"); return 2; }
-  if (a.narrow_h > 0) {
-    if (a.nmat * a.narrow_h > 32 || a.hout != a.narrow_h || a.prop_in) { set_error("gemm_prop: narrow mode needs nmat*narrow_h <= 32 and hout == narrow_h"); return 2; }
-    if (narrow_lds_bytes(a.nrb, a.nmat, a.kpad, a.max_nnz, a.ell_width) > (size_t)kMaxLdsBytes) { set_error("gemm_prop(narrow): tile does not fit LDS"); return 3; }
-    hipStream_t sn = as_stream(stream);
-    if (narrow_stream_ok(a)) {
-      switch (a.nrb) {
-        case 1: return launch_narrow_stream<1>(a, sn);
-        case 2: return launch_narrow_stream<2>(a, sn);
-        case 3: return launch_narrow_stream<3>(a, sn);
-        case 6: return launch_narrow_stream<6>(a, sn);
-        default: return launch_narrow_stream<4>(a, sn);
-      }
-    }
-    switch (a.nrb) {
-      case 1: return launch_narrow<1>(a, sn);
-      case 2: return launch_narrow<2>(a, sn);
-      case 3: return launch_narrow<3>(a, sn);
-      case 4: return launch_narrow<4>(a, sn);
-      case 6: return launch_narrow<6>(a, sn);
-      default: set_error("gemm_prop(narrow): unsupported nrb=%d", a.nrb); return 2;
-    }
+  if (a.narrow_h > 0 && (a.nmat * a.narrow_h > 32 || a.hout != a.narrow_h || a.prop_in)) { set_error("gemm_prop: narrow mode needs nmat*narrow_h <= 32 and hout == narrow_h"); return 2; }
+  if (a.narrow_h <= 0 && (a.ell_width < 0 || a.ell_width > 32)) { set_error("gemm_prop: ell_width %d out of range 0..32", a.ell_width); return 2; }
+  // 2. the record, 3. its launch
+  const dss2_gemm_prop_plan_t p = gemm_select(a);
+  if (p.kernel == DSS2_GEMM_NONE) {
+    if (a.narrow_h > 0 && p.reason == 3) set_error("gemm_prop(narrow): tile does not fit LDS");
+    else if (a.narrow_h > 0) set_error("gemm_prop(narrow): unsupported nrb=%d", a.nrb);
+    else if (p.reason == 3) set_error("gemm_prop: tile needs %zu B of LDS (> 160 KiB): nrb=%d kpad=%d nnz=%d", (size_t)p.sizing_lds, a.nrb, a.kpad, a.max_nnz);
+    else if (a.b_format == 1 && gemm_launcher(DSS2_GEMM_BF16X6_KHALF, a.nrb, a.nmat, 1)) set_error("gemm_prop(bf16x6): unsupported shape (nrb=%d nmat=%d k=%d kpad=%d hout=%d)", a.nrb, a.nmat, a.kreal, a.kpad, a.hout);
+    else if (a.b_format == 1) set_error("gemm_prop(bf16x6): no instantiation for nrb=%d nmat=%d", a.nrb, a.nmat);
+    else if (a.b_format != 0) set_error("gemm_prop: unknown b_format %d", a.b_format);
+    else set_error("gemm_prop: unsupported (nrb=%d, nmat=%d); nrb in {1,2,3,4,6}, nmat in 1..4", a.nrb, a.nmat);
+    return p.reason;
   }
-  if (a.ell_width < 0 || a.ell_width > 32) { set_error("gemm_prop: ell_width %d out of range 0..32", a.ell_width); return 2; }
-  if (lds_bytes(a.nrb, a.prop_in > 0 ? 2 : a.nmat, a.kpad, a.ncg, a.max_nnz, a.ell_width) > (size_t)kMaxLdsBytes) {
-    set_error("gemm_prop: tile needs %zu B of LDS (> 160 KiB): nrb=%d kpad=%d nnz=%d",
-              lds_bytes(a.nrb, a.prop_in > 0 ? 2 : a.nmat, a.kpad, a.ncg, a.max_nnz, a.ell_width), a.nrb, a.kpad, a.max_nnz);
-    return 3;
-  }
-  hipStream_t s = as_stream(stream);
-  if (a.b_format == 1) {
-    if (!gemm16_shape_ok(a.nrb, a.nmat, a.kreal, a.hout, a.max_nnz, a.ell_width) || a.prop_in || a.rowscale || (a.kpad & 15) ||
-        a.kpad != (a.kreal + 15) / 16 * 16 || (a.ldx & 3) || (reinterpret_cast<uintptr_t>(a.X) & 15)) {
-      set_error("gemm_prop(bf16x6): unsupported shape (nrb=%d nmat=%d k=%d kpad=%d hout=%d)", a.nrb, a.nmat, a.kreal, a.kpad, a.hout);
-      return 2;
-    }
-    static const int rs_env = [] { const char* e = getenv("DSS2_GEMM_RS"); return e ? atoi(e) : 2; }();
-    if (a.nrb == 6 && a.nmat == 3) return rs_env == 2 ? launch<6, 3, true, 2>(a, s) : launch<6, 3, true>(a, s);
-    if (a.nrb == 6 && a.nmat == 4) return rs_env == 2 ? launch<6, 4, true, 2>(a, s) : launch<6, 4, true>(a, s);
-    if (a.nrb == 4 && a.nmat == 4) return rs_env == 2 ? launch<4, 4, true, 2>(a, s) : launch<4, 4, true>(a, s);
-    set_error("gemm_prop(bf16x6): no instantiation for nrb=%d nmat=%d", a.nrb, a.nmat);
-    return 2;
-  }
-  if (a.b_format != 0) { set_error("gemm_prop: unknown b_format %d", a.b_format); return 2; }
-#define DSS2_CASE(NRB, NMAT) \
-  if (a.nrb == NRB && a.nmat == NMAT) return launch<NRB, NMAT>(a, s);
-  DSS2_CASE(1, 1) DSS2_CASE(1, 2) DSS2_CASE(1, 3) DSS2_CASE(1, 4)
-  DSS2_CASE(2, 1) DSS2_CASE(2, 2) DSS2_CASE(2, 3) DSS2_CASE(2, 4)
-  DSS2_CASE(3, 1) DSS2_CASE(3, 2) DSS2_CASE(3, 3) DSS2_CASE(3, 4)
-  DSS2_CASE(4, 1) DSS2_CASE(4, 2) DSS2_CASE(4, 3) DSS2_CASE(4, 4)
-  DSS2_CASE(6, 1) DSS2_CASE(6, 2) DSS2_CASE(6, 3) DSS2_CASE(6, 4)
-#undef DSS2_CASE
-  set_error("gemm_prop: unsupported (nrb=%d, nmat=%d); nrb in {1,2,3,4,6}, nmat in 1..4", a.nrb, a.nmat);
-  return 2;
+  a.relu = (a.relu & ~(1 << 24)) | (p.kernel == DSS2_GEMM_FP32_KHALF || p.kernel == DSS2_GEMM_BF16X6_KHALF ? 1 << 24 : 0);      // bit 24: K-halved staging, the record's alone
+  return gemm_launcher(p.kernel, a.nrb, a.nmat, p.row_split)(a, as_stream(stream), p);      // (non-null: gemm_select asked)
 }

@@ -28,12 +28,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .topology import Topology, get_topology
+from .topology import LDS_LIMIT, Topology, get_topology
 
 _F32 = torch.float32
 
 from . import flags as FL
-from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, edge_bwd, edge_fwd, gather_rows, gemm16_supported, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
+from .ops import (_DROP_PARAMS, _dropout_params, _ncg, _ptr, _reduce, _require_gpu, _round16, _round8, _rows, _stream, _wgrad_per_cu, _wgrad_tiles, chain16_supported, chain_f16_supported, chain_gate_words, chain_edge_supported, chain_head_supported, chain_head_wgrad_supported, chain_supported, csr_axpy, dropout_mask, dropout_snapshot, edge_bwd, edge_fwd, gather_rows, gemm16_supported, gemm_plan, gemm_prop, gemm_prop_chain, is_narrow, finish_weights, prep_weights, reduce_pending, segment_sum, wgrad, wgrad_batched)
 from .plans import (_DESC_DTYPE, _FoldPlan, _MatView, _PackPlan, _SG_DTYPE, _as_view, _pack_table, _sg, _sg_table, _small_gemm)
 from .route import BlockRoute, block_route, use_global_path
 
@@ -81,7 +81,7 @@ def _edge_aggr_backward(topo, gx0, x, ldx, ea, ldea, W1, b1, S, pack_w2_bwd, hid
     # U0 = sum of dz over incoming edges (x enters as x_i), U1 over outgoing edges (as x_j).  Side by side in one [N, 2 hid]
     # buffer when the K = 2 hid tile fits LDS: dx is then ONE GEMM [U0 | U1] [W1[:, :fn] ; W1[:, fn:2fn]]
     merged = bool(need_dx and pack_dx is not None and len(pack_dx) > 2 and pack_dx[2] is not None and FL.DX_MERGE and
-                  _lib.lib().dss2_gemm_prop_lds_bytes(ts.nrb, 1, _round8(2 * hid), 1, 0, 0) <= 160 * 1024)
+                  gemm_plan(ts, 1, 2 * hid, fn, graph=(0, 0)).sizing_lds <= LDS_LIMIT)
     if not need_dx:
         U = u0 = u1 = None
         ldu = hid
@@ -122,6 +122,7 @@ def _dx_views(W1, hid, fn, fe):
 def _tagconv_forward(topo, h, pack_fwd, bias, nmat, hin, hout, dmask=None, relu=False, add_src=None, add_ld=0,
                      prebias=None, pre_rowscale=None, drop=None, b_format=0):
     out = torch.empty(topo.N, hout, dtype=_F32, device=h.device)
+    # (a folded bias or in-kernel dropout needs the general kernel: dss2_gemm_prop refuses them on a narrow launch, include/dss2_hip.h)
     narrow = is_narrow(nmat, hout) and prebias is None and (drop is None or drop[2] == 0)
     gemm_prop(topo, h, h.stride(0), hin, pack_fwd, nmat, hout, out, bias=bias, dmask=dmask, relu=relu,
               add_src=add_src, add_ld=add_ld, narrow_h=(hout if narrow else 0),

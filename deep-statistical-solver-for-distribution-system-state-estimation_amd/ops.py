@@ -68,16 +68,16 @@ def _ncg(j: int) -> int:
 # ------------------------------------------------------------------------------------------
 # thin op wrappers over the C ABI
 # ------------------------------------------------------------------------------------------
-def _fill_graph(a: "_lib.GemmPropArgs", topo: Topology, ts: Tiling, transposed: bool) -> None:
+def _fill_graph(a: "_lib.GemmPropArgs", topo: Optional[Topology], ts: Tiling, transposed: bool) -> None:
     """The graph side of a tile GEMM + propagation launch: the tiles and ELL slices of ``ts``, the CSR of ``topo``, by target or
-    (transposed) by source.  (max_tile_rows is the layer chain's alone: gemm_prop_chain sets it.)"""
-    a.nrb, a.ntiles, a.tile_start = ts.nrb, ts.ntiles, ts.tile_start.data_ptr()
-    if transposed:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptrT.data_ptr(), topo.colT.data_ptr(), topo.wT.data_ptr(), ts.max_nnzT
-        a.ell_width, a.ell_tiles = ts.ellT, _ptr(ts.ellT_tiles)
-    else:
-        a.rowptr, a.col, a.w, a.max_nnz = topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.w.data_ptr(), ts.max_nnz
-        a.ell_width, a.ell_tiles = ts.ell, _ptr(ts.ell_tiles)
+    (transposed) by source.  (max_tile_rows is the layer chain's alone: gemm_prop_chain sets it.)  ``topo`` None (gemm_plan): the sizes only."""
+    a.nrb, a.ntiles = ts.nrb, ts.ntiles
+    a.max_nnz, a.ell_width, tiles = (ts.max_nnzT, ts.ellT, ts.ellT_tiles) if transposed else (ts.max_nnz, ts.ell, ts.ell_tiles)
+    if topo is None:
+        a.ell_tiles = None if tiles is None else 1      # (whether ELL slices exist; never dereferenced)
+        return
+    a.tile_start, a.ell_tiles = ts.tile_start.data_ptr(), _ptr(tiles)
+    a.rowptr, a.col, a.w = (t.data_ptr() for t in ((topo.rowptrT, topo.colT, topo.wT) if transposed else (topo.rowptr, topo.col, topo.w)))
 
 
 def _fill_wgrad_graph(a: "_lib.WgradArgs", topo: Topology, ts: Tiling) -> None:
@@ -101,23 +101,36 @@ def gemm_prop(topo: Topology, X: torch.Tensor, ldx: int, kreal: int, Bp: torch.T
         raise NotImplementedError(f"largest connected component has {ts.max_segment} nodes: the fused GEMM + propagation "
                                   "kernels hold a whole graph in LDS (<= 192 nodes); use the MPN / TAGConv modules, which "
                                   "switch to the global-memory propagation path")
-    a = _lib.GemmPropArgs()
+    a = _gemm_args(topo, ts, kreal, nmat, hout, transposed, prop_in, narrow_h, b_format)
     if drop is not None and drop[2] > 0:
         a.drop_state, a.drop_id = drop[0].data_ptr(), int(drop[2])
         a.drop_thr, a.drop_scale = _dropout_params(drop[1])
     a.prebias, a.pre_rowscale = _ptr(prebias), _ptr(pre_rowscale)
-    a.prop_in, a.narrow_h = prop_in, narrow_h
-    a.X, a.ldx, a.kreal, a.kpad = X.data_ptr(), ldx, kreal, (_round16(kreal) if b_format == 1 else _round8(kreal))
-    a.b_format = b_format
-    a.Bp, a.bias, a.rowscale = Bp.data_ptr(), _ptr(bias), _ptr(rowscale)
+    a.X, a.ldx, a.Bp, a.bias, a.rowscale = X.data_ptr(), ldx, Bp.data_ptr(), _ptr(bias), _ptr(rowscale)
     a.relu_src, a.ld_relu = _ptr(relu_src), (relu_src.stride(0) if relu_src is not None else 0)
     a.dmask, a.ld_dmask = _ptr(dmask), (dmask.stride(0) if dmask is not None else 0)
     a.add_src, a.ld_add = _ptr(add_src), add_ld
-    a.Y, a.ldy, a.hout, a.ncg = Y.data_ptr(), Y.stride(0), hout, (1 if narrow_h else _ncg(hout))
-    a.relu, a.nmat = int(relu), nmat
-    _fill_graph(a, topo, ts, transposed)
+    a.Y, a.ldy, a.relu = Y.data_ptr(), Y.stride(0), int(relu)
     _lib.check(_lib.lib().dss2_gemm_prop(C.byref(a), _stream(Y)), "dss2_gemm_prop")
 
+
+def _gemm_args(topo, ts, kreal, nmat, hout, transposed, prop_in, narrow_h, b_format) -> "_lib.GemmPropArgs":
+    """What a single-layer launch and a question about one (gemm_plan: ``topo`` None) fill alike: the padded shape and the graph side."""
+    a = _lib.GemmPropArgs()
+    a.kreal, a.kpad, a.b_format, a.prop_in, a.narrow_h = kreal, (_round16(kreal) if b_format == 1 else _round8(kreal)), b_format, prop_in, narrow_h
+    a.hout, a.ncg, a.nmat = hout, (1 if narrow_h else _ncg(hout)), nmat
+    _fill_graph(a, topo, ts, transposed)
+    return a
+
+
+def gemm_plan(ts, nmat: int, kreal: int, hout: int, transposed=False, prop_in=0, narrow_h=0, b_format=0, X=None, ldx=0, graph=None) -> "_lib.GemmPlan":
+    """The record the library launches ``gemm_prop`` of this shape from (dss2_gemm_prop_plan), asked without tensors: operands count as
+    aligned unless ``X`` / ``ldx`` are given; ``graph`` = (max_nnz, ell_width) replaces the direction's own (a plain GEMM: (0, 0))."""
+    a, p = _gemm_args(None, ts, kreal, nmat, hout, transposed, prop_in, narrow_h, b_format), _lib.GemmPlan()
+    a.X, a.ldx = _ptr(X), ldx
+    a.max_nnz, a.ell_width = graph or (a.max_nnz, a.ell_width)
+    _lib.check(_lib.lib().dss2_gemm_prop_plan(C.byref(a), C.byref(p)), "dss2_gemm_prop_plan")
+    return p
 
 
 def _tiles(topo) -> Tiling:
@@ -196,8 +209,7 @@ def gemm16_supported(topo: Topology, nmat: int, hid: int, transposed: bool) -> b
     """True when a single hid -> hid layer (dss2_gemm_prop) can take bf16x3 weights: the tall tiles (128 / 192 rows) that
     run matrix-sequentially with K-halved staging and therefore have no layer chain."""
     ts = _tiles(topo)
-    ell, tiles, nnz = (ts.ellT, ts.ellT_tiles, ts.max_nnzT) if transposed else (ts.ell, ts.ell_tiles, ts.max_nnz)
-    return FL.CHAIN_BF16 and tiles is not None and bool(_lib.lib().dss2_gemm_prop16_supported(ts.nrb, nmat, hid, hid, nnz, ell))
+    return FL.CHAIN_BF16 and (ts.ellT_tiles if transposed else ts.ell_tiles) is not None and gemm_plan(ts, nmat, hid, hid, transposed, b_format=1).kernel == _lib.GEMM_BF16X6_KHALF
 
 
 def gemm_prop_chain(topo: Topology, X: Optional[torch.Tensor], hid: int, nmat: int, layers: Sequence[dict], transposed: bool = False,

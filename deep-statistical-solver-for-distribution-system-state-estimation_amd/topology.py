@@ -33,7 +33,7 @@ from . import _lib
 
 _FLIP = 1 << 31
 _NRB_CHOICES = (2, 4, 3, 1, 6)   # preference order on utilisation ties (32*nrb rows per tile)
-_LDS_LIMIT = 160 * 1024
+LDS_LIMIT = 160 * 1024
 _ELL_MAX = 8
 
 
@@ -405,15 +405,15 @@ class Topology:
         return self._deg_pows
 
     def lds_check(self, nmat: int, kpad: int, ncg: int) -> None:
+        from .ops import gemm_plan      # (ops imports this module)
         ts = self.tiling
         if ts.global_only:     # plain GEMMs only: forward K=kpad -> nmat*hout columns, data-gradient K=nmat*hout -> kpad
-            f = _lib.lib().dss2_gemm_prop_lds_bytes
-            need = max(f(ts.nrb, 1, kpad, nmat * ncg, 0, 0), f(ts.nrb, 1, nmat * ncg * 32, (kpad + 31) // 32, 0, 0))
-            if need > _LDS_LIMIT:
+            need = max(gemm_plan(ts, 1, kpad, nmat * ncg * 32, graph=(0, 0)).sizing_lds, gemm_plan(ts, 1, nmat * ncg * 32, kpad, graph=(0, 0)).sizing_lds)
+            if need > LDS_LIMIT:
                 raise NotImplementedError(f"global-memory path: a 64-row tile x K={nmat * ncg * 32} needs {need} B of LDS (> 160 KiB)")
             return
-        need = _lib.lib().dss2_gemm_prop_lds_bytes(ts.nrb, nmat, kpad, ncg, max(ts.max_nnz, ts.max_nnzT), min(ts.ell, ts.ellT))
-        if need > _LDS_LIMIT:
+        need = gemm_plan(ts, nmat, kpad, ncg * 32, graph=(max(ts.max_nnz, ts.max_nnzT), min(ts.ell, ts.ellT))).sizing_lds
+        if need > LDS_LIMIT:
             raise NotImplementedError(f"tile of {32 * ts.nrb} rows x K={kpad} needs {need} B of LDS (> 160 KiB)")
 
 

@@ -326,13 +326,44 @@ typedef struct dss2_gemm_prop_args {
    * `dmask` (an explicit [N, hout] multiplier tensor, still supported) is applied.                                 */
   const uint64_t* drop_state; uint32_t drop_thr; float drop_scale; int32_t drop_id;
   int32_t b_format;   /* layout of the packed weights: 0 = fp32 fragments; 1 = bf16x3 fragments (dss2_gemm_prop_chain, and
-                         dss2_gemm_prop where dss2_gemm_prop16_supported(...) != 0; kpad is then a multiple of 16) */
+                         dss2_gemm_prop where dss2_gemm_prop_plan answers DSS2_GEMM_BF16X6_KHALF; kpad is then a multiple of 16) */
   int32_t max_tile_rows;   /* 0: unknown (any tile may hold up to 32 * nrb rows); > 0: an upper bound of EVERY tile's row count --
                               the tall-tile chains then leave out the row pieces that are padding in every tile (70-bus graphs in
                               96-row tiles: rows 72..95, a quarter of the hops and of the epilogue) */
 } dss2_gemm_prop_args;
 
 int dss2_gemm_prop(const dss2_gemm_prop_args* args_host, void* stream);
+/* Which kernel a launch of these arguments runs and its geometry: the record the library's own dispatch launches from (gemm_select in
+ * csrc/dss2_gemm_prop.hip).  Narrow layers (args.narrow_h > 0) stream X where nmat * narrow_h <= 8, kpad % 16 == 0, X rows can be read 16
+ * bytes at a time (kreal % 4 == 0, ldx % 4 == 0, X 16-byte aligned) and, for nmat > 1, ELL slices exist; else they take the tile
+ * kernel.  General layers stage the X tile in two K halves where matrix-sequential tall tiles (nmat > 1, nrb * nmat >= 16) would
+ * otherwise leave a column group without its wave; bf16x3 weights (b_format 1) run in that form only.                                   */
+typedef enum dss2_gemm_kernel {
+  DSS2_GEMM_NONE = 0,          /* the launch is refused: see dss2_gemm_prop_plan_t.reason                     */
+  DSS2_GEMM_NARROW_STREAM,     /* narrow, nothing of X staged (gemm_narrow_stream_kernel)                     */
+  DSS2_GEMM_NARROW,            /* narrow, X tile in LDS (gemm_narrow_kernel)                                  */
+  DSS2_GEMM_FP32,              /* gemm_prop_kernel<nrb, nmat>, fp32 MFMAs                                     */
+  DSS2_GEMM_FP32_KHALF,        /* ... with K-halved staging: every column group its wave                      */
+  DSS2_GEMM_BF16X6_KHALF       /* gemm_prop_kernel<nrb, nmat, true, row_split>: bf16x6, K-halved              */
+} dss2_gemm_kernel;
+typedef struct dss2_gemm_prop_plan_t {
+  int32_t kernel;              /* dss2_gemm_kernel                                                            */
+  int32_t reason;              /* kernel == NONE: the code dss2_gemm_prop returns (2: no such kernel for these arguments, 3: the tile
+                                * does not fit LDS)                                                           */
+  int32_t row_split;           /* waves per column group (1; bf16x6: 2 unless DSS2_GEMM_RS=1)                 */
+  int32_t waves;               /* column-group waves (narrow kernels: 4)                                      */
+  int32_t block;               /* threads per workgroup = 64 * waves * row_split                              */
+  int32_t pad_;
+  uint64_t lds_bytes;          /* dynamic LDS of the launch; a K-halved kernel's is the K-halved figure       */
+  uint64_t sizing_lds;         /* what dss2_gemm_prop_lds_bytes answers: the general kernel's LDS WITHOUT K-halving, from the shape
+                                * alone.  Callers size tiles and merged GEMMs by it, and the dispatch's own "tile needs ... B of LDS"
+                                * refusal (reason 3) tests it too -- not lds_bytes: a shape that would fit K-halved only is refused,
+                                * as it always was.  (Narrow launches are refused by the narrow tile kernel's own LDS.)            */
+} dss2_gemm_prop_plan_t;
+/* fills *out from the arguments and the environment alone (no GPU, nothing dereferenced; ntiles is not read).  Arguments that are
+ * errors whatever the kernel (bad kpad / ncg, a missing CSR, prebias or dropout on a narrow launch, ...) are dss2_gemm_prop's to
+ * refuse and are not looked at here.  Returns 0, or 2 for a null pointer.                                                     */
+int dss2_gemm_prop_plan(const dss2_gemm_prop_args* args_host, dss2_gemm_prop_plan_t* out);
 /* Policy constant: 96- / 192-row tiles with ONE column group (hout <= 32) take the split-plane chain -- single-wave workgroups -- only
  * from this many tiles on (a launch with fewer runs the multi-wave chain of that shape, which 192-row tiles do not have); -1: never
  * (DSS2_CHAIN_SP6_NCG1=0).  Applied in one place, dss2_gemm_prop_chain_plan; the *_supported queries below answer for the
@@ -448,7 +479,8 @@ typedef struct dss2_chain_plan_t { dss2_chain_kernel_t fmt[3]; } dss2_chain_plan
 int dss2_gemm_prop_chain_plan(int nrb, int nmat, int hid, int ell_width, int ntiles, int nout, int edge_width, dss2_chain_plan_t* out);
 
 /* != 0: dss2_gemm_prop (one layer) accepts args.b_format = 1 for this shape -- the tall tiles (128 / 192 rows) that run
- * matrix-sequentially with the X tile staged in two K halves; same bf16x6 arithmetic as the chain. */
+ * matrix-sequentially with the X tile staged in two K halves; same bf16x6 arithmetic as the chain.  A reader of dss2_gemm_prop_plan
+ * (operands taken as aligned), like dss2_gemm_prop_lds_bytes below. */
 int dss2_gemm_prop16_supported(int nrb, int nmat, int kreal, int hout, int max_nnz, int ell_width);
 
 /* Diagnostic: the clock the chip holds under the dominant kernel.  probe != NULL (16 uint64 of device memory): every later split-plane

@@ -53,6 +53,56 @@ def test_gemm_linear_matches_matmul(pkg, n_graphs, kdim, hout):
     assert rel_err(Y2, Y.double() @ W.double()) < 2e-6
 
 
+# family -> (grid, graphs, tile height in 32-row blocks, hin, hout, K, b_format, prop_in): the smallest shape that takes each branch of the
+# selection (csrc/dss2_gemm_prop.hip, gemm_select)
+GEMM_FAMILIES = {
+    "NARROW_STREAM": ("cigre14", 3, 2, 32, 2, 2, 0, 0),
+    "NARROW": ("cigre14", 3, 2, 6, 2, 2, 0, 0),            # kreal % 4 != 0: the operands, not a switch, take it off the streaming kernel
+    "FP32": ("cigre14", 3, 2, 32, 32, 2, 0, 0),
+    "FP32-prop_in": ("cigre14", 3, 2, 2, 32, 1, 0, 1),     # the stacked data-gradient form of a 32 -> 2 head: nmat = 1, P^T g appended in LDS
+    "FP32_KHALF": ("ober179", 2, 6, 128, 128, 2, 0, 0),    # four column groups do not get a wave each beside the full X tile
+    "BF16X6_KHALF": ("ober179", 2, 6, 128, 128, 2, 1, 0),
+    "NONE": ("ober179", 2, 6, 256, 256, 2, 1, 0),          # the X tile alone exceeds the LDS: refused on the host, no kernel runs
+}
+
+
+@pytest.mark.parametrize("family", list(GEMM_FAMILIES))
+def test_gemm_prop_families_at_their_smallest_shapes(pkg, family):
+    """One dss2_gemm_prop launch per kernel family of the record (ops.gemm_plan) against the same product and hops in fp64 on the CPU,
+    built from the topology's CSR: out = sum_m P^m (X W_m^T) -- by target, or (prop_in) g W_m through the by-source CSR."""
+    grid, B, nrb, hin, hout, K, fmt, prop_in = GEMM_FAMILIES[family]
+    nw, L = pkg.networks, pkg._lib
+    torch.manual_seed(11)
+    b = pkg.synthetic.make_batch([grid], B, seed=3)
+    N = b["x"].shape[0]
+    topo = pkg.topology.Topology(b["edge_index"].to(DEV), N)
+    ts, nmat, T = topo.tiling, K + 1, bool(prop_in)
+    assert ts.nrb == nrb
+    narrow = hout if nw.is_narrow(nmat, hout) and not prop_in else 0
+    Ws = [torch.randn(*((hin, hout) if T else (hout, hin)), device=DEV) * 0.3 for _ in range(nmat)]      # (prop_in: the head's [2, 32] matrices)
+    kreal, X = (nmat * hin if T else hin), torch.randn(N, hin, device=DEV)
+    p = nw.gemm_plan(ts, 1 if T else nmat, kreal, hout, T, prop_in, narrow, fmt, X=X, ldx=hin)
+    assert p.kernel == getattr(L, "GEMM_" + family.split("-")[0])
+    Y = torch.empty(N, hout, device=DEV)
+    if family == "NONE":
+        assert p.reason == 3
+        with pytest.raises(RuntimeError, match=r"rc=3.*gemm_prop: tile needs \d+ B of LDS"):
+            nw.gemm_prop(topo, X, hin, kreal, torch.empty(8, device=DEV), nmat, hout, Y, b_format=fmt)
+        return
+    plan = nw._PackPlan([Ws], torch.device(DEV), bf16_groups=((0,) if fmt else ()))
+    plan.refresh()
+    Bp = plan.bwd[0] if T else plan.fwd16[0] if fmt else plan.fwd[0]
+    nw.gemm_prop(topo, X, hin, kreal, Bp, 1 if T else nmat, hout, Y, transposed=T, prop_in=prop_in, narrow_h=narrow, b_format=fmt)
+    rowptr, col, w = ((topo.rowptrT, topo.colT, topo.wT) if T else (topo.rowptr, topo.col, topo.w))
+    P = torch.zeros(N, N, dtype=torch.float64)
+    rows = torch.repeat_interleave(torch.arange(N), rowptr.cpu().long().diff())
+    P.index_put_((rows, col.cpu().long()), w.cpu().double(), accumulate=True)
+    ref, Xd = torch.zeros(N, hout, dtype=torch.float64), X.double().cpu()
+    for m in reversed(range(nmat)):      # Horner, as the kernel: T = G_m + P T
+        ref = Xd @ (Ws[m].double().cpu() if T else Ws[m].double().cpu().t()) + P @ ref
+    assert rel_err(Y, ref) < (3e-6 if fmt else TOL_OUT)      # (bf16x6: the single-layer bound of tests/test_gpu_bf16x6.py)
+
+
 @pytest.mark.parametrize("grid,hin,hout,K", [("cigre14", 128, 128, 2), ("cigre14_reswitched", 32, 8, 3),
                                               ("ober_sub", 64, 64, 2), ("cigre14", 128, 2, 2), ("cigre14", 32, 32, 1),
                                               ("ober179", 32, 32, 2)])
