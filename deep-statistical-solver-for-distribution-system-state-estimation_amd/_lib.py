@@ -164,6 +164,26 @@ class AdamaxDesc(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_inf", C.c_void_p), ("n", C.c_int64)]
 
 
+class OptimHyper(C.Structure):
+    """dss2_optim_hyper: rule, flags and hyper-parameters of one optimizer launch; lr_dev overrides lr when set (include/dss2_hip.h)."""
+    _fields_ = ([("rule", C.c_int32), ("flags", C.c_int32)] +
+                [(n, C.c_float) for n in ("lr", "beta1", "beta2", "omb1", "omb2", "eps", "weight_decay", "momentum", "omdamp")] +
+                [("pad_", C.c_int32), ("lr_dev", C.c_void_p)])
+
+
+OPT_ADAM, OPT_RMSPROP, OPT_SGD, OPT_ADAMAX = range(4)                                                   # dss2_optim_rule
+OPT_AMSGRAD, OPT_DECOUPLED_WD, OPT_CENTERED, OPT_MOMENTUM, OPT_NESTEROV = 1, 2, 4, 8, 16          # dss2_optim_flag
+OPTIM_GRAD_CHUNK, OPTIM_MAX_PARTIALS = 192, 256                                                         # dss2_grad_sqsum_partials
+
+
+class OptimDesc(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("s0", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_int64)]
+
+
+class GradDesc(C.Structure):
+    _fields_ = [("grad", C.c_void_p), ("n", C.c_int64)]
+
+
 class CollateDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("chunk", C.c_int32), ("kind", C.c_int32),
                 ("shared", C.c_int32), ("pad_", C.c_int32), ("nodes_per_sample", C.c_int64)]
@@ -427,6 +447,12 @@ _SIGNATURES = {
     "dss2_stack_fold_scratch_floats": (C.c_int64, [C.POINTER(StackDims)]),
     "dss2_adamax_step_flat": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                         C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dss2_optim_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptimHyper), C.c_int, C.c_void_p]),
+    "dss2_optim_step_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptimHyper), C.c_void_p, C.c_void_p]),
+    "dss2_optim_step_flat": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.POINTER(OptimHyper), C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "dss2_grad_sqsum_partials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dss2_grad_clip_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "dss2_gemm_prop_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dss2_wgrad_batched_groups": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dss2_wgrad_y_slices": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -148,6 +148,331 @@ static int dss2_adamax_step_dev_launch(const dss2_adamax_desc* descs_host, int n
   return adamax_launch(descs_host, n_desc, lr, beta1, beta2, eps, weight_decay, 1.f, step_dev, dss2::as_stream(stream));
 }
 
+// ---- Adam / AdamW, RMSprop, SGD, and Adamax with a device-side learning rate (see dss2_hip.h): one multi-tensor kernel templated on
+//      the rule.  The arithmetic is torch's single-tensor path in fp32, fmaf where torch has lerp / addcmul (as adamax_kernel).
+namespace dss2 {
+
+constexpr int OPTIM_CHUNK = 80;       // descriptors per launch, by value in the kernel arguments (80 x 48 B + hyper < 4 KB)
+struct OptimTable { dss2_optim_desc d[OPTIM_CHUNK]; };
+
+// t: this step's 1-based count; bc1 / bc2: 1 - beta^t (from the host, or from the device-side count)
+template <int RULE>
+__device__ __forceinline__ void optim_walk(float* __restrict__ param, const float* __restrict__ grad, float* s0, float* s1, float* s2,
+                                           int64_t n, const dss2_optim_hyper& h, float t, float bc1, float bc2) {
+  const float lr = h.lr_dev ? h.lr_dev[0] : h.lr;
+  const float wd = h.weight_decay;
+  const int flags = h.flags;
+  const float clr = lr / bc1;                     // ADAM / ADAMAX step size
+  const float bc2s = sqrtf(bc2);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float g = grad[i];
+    float p = param[i];
+    if constexpr (RULE == DSS2_OPT_ADAMAX) {      // the operations of adamax_kernel, in its order
+      if (wd != 0.f) g = fmaf(wd, p, g);
+      const float m = fmaf(h.beta1, s0[i], (1.f - h.beta1) * g);
+      const float u = fmaxf(h.beta2 * s1[i], fabsf(g) + h.eps);
+      s0[i] = m;
+      s1[i] = u;
+      param[i] = p - clr * (m / u);
+    } else if constexpr (RULE == DSS2_OPT_ADAM) {
+      if (wd != 0.f) {
+        if (flags & DSS2_OPT_DECOUPLED_WD) p *= 1.f - lr * wd;
+        else g = fmaf(wd, p, g);
+      }
+      const float m = fmaf(h.beta1, s0[i], h.omb1 * g);                // lerp(exp_avg, g, 1-b1)
+      float v = fmaf(h.omb2 * g, g, h.beta2 * s1[i]);                  // mul_(b2).addcmul_(g, g, 1-b2)
+      s0[i] = m;
+      s1[i] = v;
+      if (flags & DSS2_OPT_AMSGRAD) {
+        v = fmaxf(s2[i], v);
+        s2[i] = v;
+      }
+      const float denom = sqrtf(v) / bc2s + h.eps;
+      param[i] = p - clr * (m / denom);
+    } else if constexpr (RULE == DSS2_OPT_RMSPROP) {
+      if (wd != 0.f) g = fmaf(wd, p, g);
+      const float sq = fmaf(h.omb2 * g, g, h.beta2 * s0[i]);           // mul_(alpha).addcmul_(g, g, 1-alpha)
+      s0[i] = sq;
+      float avg;
+      if (flags & DSS2_OPT_CENTERED) {
+        const float ga = fmaf(h.beta2, s2[i], h.omb2 * g);             // lerp(grad_avg, g, 1-alpha)
+        s2[i] = ga;
+        avg = sqrtf(fmaf(-ga, ga, sq));
+      } else {
+        avg = sqrtf(sq);
+      }
+      avg += h.eps;
+      if (flags & DSS2_OPT_MOMENTUM) {
+        const float buf = fmaf(h.momentum, s1[i], g / avg);
+        s1[i] = buf;
+        param[i] = p - lr * buf;
+      } else {
+        param[i] = p - lr * (g / avg);
+      }
+    } else {                                                           // DSS2_OPT_SGD
+      if (wd != 0.f) g = fmaf(wd, p, g);
+      if (flags & DSS2_OPT_MOMENTUM) {
+        const float buf = t == 1.f ? g : fmaf(h.momentum, s0[i], h.omdamp * g);      // torch clones the gradient at the first step
+        s0[i] = buf;
+        g = (flags & DSS2_OPT_NESTEROV) ? fmaf(h.momentum, buf, g) : buf;
+      }
+      param[i] = p - lr * g;
+    }
+  }
+}
+
+template <int RULE>
+__global__ void __launch_bounds__(256) optim_kernel(const OptimTable tab, const dss2_optim_hyper h, float t, float bc1, float bc2,
+                                                    const float* __restrict__ step_dev) {
+  const dss2_optim_desc& d = tab.d[blockIdx.y];
+  if (step_dev) {                                  // (already advanced by adamax_tick_kernel)
+    t = step_dev[0];
+    bc1 = 1.f - powf(h.beta1, t);
+    bc2 = 1.f - powf(h.beta2, t);
+  }
+  optim_walk<RULE>(d.param, d.grad, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2);
+}
+
+template <int RULE>
+__global__ void __launch_bounds__(256) optim_flat_kernel(const dss2_optim_flat_desc* __restrict__ descs, const float* __restrict__ grad_base,
+                                                         const dss2_optim_hyper h, float t, float bc1, float bc2, float* step_dev,
+                                                         unsigned* counter) {
+  const dss2_optim_flat_desc d = descs[blockIdx.y];
+  if (step_dev) {
+    t = step_dev[0] + 1.f;                         // this step's (1-based) count
+    bc1 = 1.f - powf(h.beta1, t);
+    bc2 = 1.f - powf(h.beta2, t);
+  }
+  optim_walk<RULE>(d.param, grad_base + d.grad_off, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2);
+  if (!step_dev) return;
+  // the last workgroup to arrive advances the count: the pattern of adamax_flat_kernel (every workgroup has read the count before the
+  // barrier; nothing is published through memory, so the arrival is a relaxed device-scope atomic without a fence)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.y - 1) {
+      step_dev[0] += 1.f;
+      *counter = 0u;
+    }
+  }
+}
+
+// ---- global-norm gradient clipping: fp64 partial per workgroup, re-added in index order by every workgroup of the second launch
+constexpr int GRAD_CHUNK = 192;       // {pointer, n} descriptors per launch, by value (192 x 16 B = 3 KB)
+constexpr int GRAD_MAX_PARTIALS = 256;
+struct GradTable { dss2_grad_desc d[GRAD_CHUNK]; };
+
+__global__ void __launch_bounds__(256) grad_sqsum_kernel(const GradTable tab, const dss2_grad_flat_desc* __restrict__ flat,
+                                                         const float* __restrict__ grad_base, int n_desc, double* __restrict__ partials) {
+  __shared__ double red[256];
+  double acc = 0.0;
+  for (int j = 0; j < n_desc; ++j) {
+    const float* __restrict__ g = flat ? grad_base + flat[j].grad_off : tab.d[j].grad;
+    const int64_t n = flat ? flat[j].n : tab.d[j].n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+      const double v = (double)g[i];
+      acc = fma(v, v, acc);
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {              // fixed tree: the same bits every run
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(256) grad_clip_scale_kernel(const GradTable tab, const dss2_grad_flat_desc* __restrict__ flat,
+                                                              float* __restrict__ grad_base, int n_desc, const double* __restrict__ partials,
+                                                              int n_partials, float max_norm, float* __restrict__ norm_out) {
+  double sum = 0.0;
+  for (int k = 0; k < n_partials; ++k) sum += partials[k];
+  const float total = (float)sqrt(sum);
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+  const float c = max_norm / (total + 1e-6f);
+  const float coef = c > 1.f ? 1.f : c;            // (a NaN stays a NaN: torch.clamp(max=1.0))
+  if (coef == 1.f) return;                         // g * 1 = g
+  for (int j = 0; j < n_desc; ++j) {
+    float* __restrict__ g = flat ? grad_base + flat[j].grad_off : tab.d[j].grad;
+    const int64_t n = flat ? flat[j].n : tab.d[j].n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) g[i] *= coef;
+  }
+}
+
+}  // namespace dss2
+
+static int optim_hyper_check(const dss2_optim_hyper* h, const char* who) {
+  if (!h) { dss2::set_error("%s: null hyper-parameters", who); return 2; }
+  if (h->rule < DSS2_OPT_ADAM || h->rule > DSS2_OPT_ADAMAX) { dss2::set_error("%s: unknown rule %d", who, h->rule); return 2; }
+  return 0;
+}
+
+// which of the three state slots the rule reads and writes
+static int optim_slot_mask(const dss2_optim_hyper& h) {
+  switch (h.rule) {
+    case DSS2_OPT_ADAM: return 3 | ((h.flags & DSS2_OPT_AMSGRAD) ? 4 : 0);
+    case DSS2_OPT_RMSPROP: return 1 | ((h.flags & DSS2_OPT_MOMENTUM) ? 2 : 0) | ((h.flags & DSS2_OPT_CENTERED) ? 4 : 0);
+    case DSS2_OPT_SGD: return (h.flags & DSS2_OPT_MOMENTUM) ? 1 : 0;
+    default: return 3;
+  }
+}
+
+template <int RULE>
+static void optim_launch_rule(const dss2::OptimTable& tab, dim3 grid, const dss2_optim_hyper& h, float t, float bc1, float bc2,
+                              const float* step_dev, hipStream_t s) {
+  hipLaunchKernelGGL(dss2::optim_kernel<RULE>, grid, dim3(256), 0, s, tab, h, t, bc1, bc2, step_dev);
+}
+
+static int optim_launch(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper& h, float t, float bc1, float bc2,
+                        const float* step_dev, hipStream_t s) {
+  const int mask = optim_slot_mask(h);
+  for (int c0 = 0; c0 < n_desc; c0 += dss2::OPTIM_CHUNK) {
+    const int n = n_desc - c0 < dss2::OPTIM_CHUNK ? n_desc - c0 : dss2::OPTIM_CHUNK;
+    dss2::OptimTable tab = {};
+    int64_t max_n = 0;
+    for (int i = 0; i < n; ++i) {
+      const dss2_optim_desc& d = tab.d[i] = descs_host[c0 + i];
+      if (!d.param || !d.grad || ((mask & 1) && !d.s0) || ((mask & 2) && !d.s1) || ((mask & 4) && !d.s2) || d.n < 0) {
+        dss2::set_error("optim_step: descriptor %d is incomplete", c0 + i);
+        return 2;
+      }
+      if (d.n > max_n) max_n = d.n;
+    }
+    int64_t bx = (max_n + 255) / 256;
+    if (bx > 64) bx = 64;
+    if (bx < 1) bx = 1;
+    const dim3 grid((unsigned)bx, n);
+    switch (h.rule) {
+      case DSS2_OPT_ADAM: optim_launch_rule<DSS2_OPT_ADAM>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
+      case DSS2_OPT_RMSPROP: optim_launch_rule<DSS2_OPT_RMSPROP>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
+      case DSS2_OPT_SGD: optim_launch_rule<DSS2_OPT_SGD>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
+      default: optim_launch_rule<DSS2_OPT_ADAMAX>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
+    }
+  }
+  return dss2::check_launch("optim_step");
+}
+
+static int dss2_optim_step_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, int step, void* stream);
+extern "C" int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, int step, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step")) return rc;
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step](void* s_) { return dss2_optim_step_launch(dss2::plan_ptr(d), n_desc, h, step, s_); });
+  return dss2_optim_step_launch(descs_host, n_desc, *hyper, step, stream);
+}
+static int dss2_optim_step_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, int step, void* stream) {
+  if (n_desc <= 0) return 0;
+  if (!descs_host) { dss2::set_error("optim_step: null descriptor table"); return 2; }
+  if (step < 1) { dss2::set_error("optim_step: step must be >= 1"); return 2; }
+  return optim_launch(descs_host, n_desc, h, (float)step, 1.f - powf(h.beta1, (float)step), 1.f - powf(h.beta2, (float)step), nullptr,
+                      dss2::as_stream(stream));
+}
+
+static int dss2_optim_step_dev_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, float* step_dev, void* stream);
+extern "C" int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step_dev")) return rc;
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step_dev](void* s_) { return dss2_optim_step_dev_launch(dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
+  return dss2_optim_step_dev_launch(descs_host, n_desc, *hyper, step_dev, stream);
+}
+static int dss2_optim_step_dev_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, float* step_dev, void* stream) {
+  if (n_desc <= 0) return 0;
+  if (!descs_host || !step_dev) { dss2::set_error("optim_step_dev: null argument"); return 2; }
+  hipLaunchKernelGGL(dss2::adamax_tick_kernel, dim3(1), dim3(64), 0, dss2::as_stream(stream), step_dev);
+  return optim_launch(descs_host, n_desc, h, 1.f, 1.f, 1.f, step_dev, dss2::as_stream(stream));
+}
+
+template <int RULE>
+static void optim_flat_launch_rule(dim3 grid, const dss2_optim_flat_desc* descs_dev, const float* grad_base, const dss2_optim_hyper& h,
+                                   float t, float bc1, float bc2, float* step_dev, uint32_t* counter, hipStream_t s) {
+  hipLaunchKernelGGL(dss2::optim_flat_kernel<RULE>, grid, dim3(256), 0, s, descs_dev, grad_base, h, t, bc1, bc2, step_dev, counter);
+}
+
+static int dss2_optim_step_flat_launch(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, dss2_optim_hyper h, int step, float* step_dev, uint32_t* counter, void* stream);
+extern "C" int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
+                                    const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step_flat")) return rc;
+  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h = *hyper, step, step_dev, counter](void* s_) { return dss2_optim_step_flat_launch(descs_dev, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
+  return dss2_optim_step_flat_launch(descs_dev, n_desc, max_n, grad_base, *hyper, step, step_dev, counter, stream);
+}
+static int dss2_optim_step_flat_launch(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, dss2_optim_hyper h, int step, float* step_dev, uint32_t* counter, void* stream) {
+  if (n_desc <= 0) return 0;
+  if (!descs_dev || !grad_base || n_desc > 65535) { dss2::set_error("optim_step_flat: bad arguments"); return 2; }
+  if (step < 0 || (step == 0 && (!step_dev || !counter))) { dss2::set_error("optim_step_flat: step >= 1, or step == 0 with step_dev and counter"); return 2; }
+  int64_t bx = (max_n + 4095) / 4096;      // few, fat workgroups, as adamax_step_flat
+  if (bx > 64) bx = 64;
+  if (bx < 1) bx = 1;
+  const dim3 grid((unsigned)bx, n_desc);
+  const float t = step > 0 ? (float)step : 1.f;
+  const float bc1 = step > 0 ? 1.f - powf(h.beta1, t) : 1.f, bc2 = step > 0 ? 1.f - powf(h.beta2, t) : 1.f;
+  float* sd = step > 0 ? nullptr : step_dev;
+  hipStream_t s = dss2::as_stream(stream);
+  switch (h.rule) {
+    case DSS2_OPT_ADAM: optim_flat_launch_rule<DSS2_OPT_ADAM>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
+    case DSS2_OPT_RMSPROP: optim_flat_launch_rule<DSS2_OPT_RMSPROP>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
+    case DSS2_OPT_SGD: optim_flat_launch_rule<DSS2_OPT_SGD>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
+    default: optim_flat_launch_rule<DSS2_OPT_ADAMAX>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
+  }
+  return dss2::check_launch("optim_step_flat");
+}
+
+// by-value chunks of a host table, or the whole device table of a flat bucket, for both clipping launches
+static int grad_args_check(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc,
+                           int n_wg, const void* partials, const char* who) {
+  if ((!descs_host) == (!descs_dev) || (descs_dev && !grad_base) || !partials) { dss2::set_error("%s: a host table, or a device table with its bucket", who); return 2; }
+  const int chunks = descs_dev ? 1 : (n_desc + dss2::GRAD_CHUNK - 1) / dss2::GRAD_CHUNK;
+  if (n_wg < 1 || (int64_t)chunks * n_wg > dss2::GRAD_MAX_PARTIALS) { dss2::set_error("%s: %d launches x %d workgroups exceed %d partials", who, chunks, n_wg, dss2::GRAD_MAX_PARTIALS); return 2; }
+  if (descs_host)
+    for (int i = 0; i < n_desc; ++i)
+      if (!descs_host[i].grad || descs_host[i].n < 0) { dss2::set_error("%s: descriptor %d is incomplete", who, i); return 2; }
+  return 0;
+}
+
+static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc, int n_wg, double* partials, void* stream);
+extern "C" int dss2_grad_sqsum_partials(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base,
+                                        int n_desc, int n_wg, double* partials, void* stream) {
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), host = descs_host != nullptr, descs_dev, grad_base, n_desc, n_wg, partials](void* s_) { return dss2_grad_sqsum_partials_launch(host ? d.data() : nullptr, descs_dev, grad_base, n_desc, n_wg, partials, s_); });
+  return dss2_grad_sqsum_partials_launch(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, stream);
+}
+static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc, int n_wg, double* partials, void* stream) {
+  if (n_desc <= 0) { dss2::set_error("grad_sqsum_partials: no gradients"); return 2; }
+  if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_sqsum_partials")) return rc;
+  hipStream_t s = dss2::as_stream(stream);
+  dss2::GradTable tab = {};
+  if (descs_dev) {
+    hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, tab, descs_dev, grad_base, n_desc, partials);
+  } else {
+    for (int c0 = 0, c = 0; c0 < n_desc; c0 += dss2::GRAD_CHUNK, ++c) {
+      const int n = n_desc - c0 < dss2::GRAD_CHUNK ? n_desc - c0 : dss2::GRAD_CHUNK;
+      for (int i = 0; i < n; ++i) tab.d[i] = descs_host[c0 + i];
+      hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials + (int64_t)c * n_wg);
+    }
+  }
+  return dss2::check_launch("grad_sqsum_partials");
+}
+
+static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc, int n_wg, const double* partials, float max_norm, float* norm_out, void* stream);
+extern "C" int dss2_grad_clip_scale(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc,
+                                    int n_wg, const double* partials, float max_norm, float* norm_out, void* stream) {
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), host = descs_host != nullptr, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out](void* s_) { return dss2_grad_clip_scale_launch(host ? d.data() : nullptr, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out, s_); });
+  return dss2_grad_clip_scale_launch(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out, stream);
+}
+static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc, int n_wg, const double* partials, float max_norm, float* norm_out, void* stream) {
+  if (n_desc <= 0) { dss2::set_error("grad_clip_scale: no gradients"); return 2; }
+  if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_clip_scale")) return rc;
+  if (!norm_out) { dss2::set_error("grad_clip_scale: null norm_out"); return 2; }
+  hipStream_t s = dss2::as_stream(stream);
+  dss2::GradTable tab = {};
+  if (descs_dev) {
+    hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, tab, descs_dev, grad_base, n_desc, partials, n_wg, max_norm, norm_out);
+  } else {
+    const int chunks = (n_desc + dss2::GRAD_CHUNK - 1) / dss2::GRAD_CHUNK;
+    for (int c0 = 0; c0 < n_desc; c0 += dss2::GRAD_CHUNK) {
+      const int n = n_desc - c0 < dss2::GRAD_CHUNK ? n_desc - c0 : dss2::GRAD_CHUNK;
+      for (int i = 0; i < n; ++i) tab.d[i] = descs_host[c0 + i];
+      hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials, chunks * n_wg, max_norm, norm_out);
+    }
+  }
+  return dss2::check_launch("grad_clip_scale");
+}
+
 
 // ---- dropout random state (see dss2_hip.h) -------------------------------------------------------------------------------
 namespace dss2 {

@@ -23,9 +23,11 @@ import torch
 
 from . import data as dss2_data
 from . import networks, synthetic
-from .optim import FusedAdamax
+from . import optim as dss2_optim
 
 REG_COEFS = {"mu_v": 1e-1, "mu_theta": 1e-1, "lam_v": 1e-4, "lam_p": 1e-8, "lam_pf": 1e-6, "lam_reg": 1e2}
+OPTIMIZERS = {"Adamax": dss2_optim.FusedAdamax, "Adam": dss2_optim.FusedAdam, "AdamW": dss2_optim.FusedAdamW,
+              "RMSprop": dss2_optim.FusedRMSprop, "SGD": dss2_optim.FusedSGD}      # the names of dss2_run.py:91's getattr(optim, NAME)
 HYPER = {"dim_nodes": 8, "dim_lines": 6, "dim_out": 2, "dim_hid": 32, "gnn_layers": 8, "K": 2, "dropout_rate": 0.3, "L": 5, "heads": 1}
 
 
@@ -75,8 +77,10 @@ def _fields(data):
     return data.x, data.edge_index, data.edge_attr, data.y, data.num_graphs
 
 
-def train_epoch(model, opt, loader, stats, reg_coefs, group=None) -> float:
+def train_epoch(model, opt, loader, stats, reg_coefs, group=None, max_grad_norm=None) -> float:
+    """``max_grad_norm``: clip the gradients' global 2-norm between backward and the optimizer step (optim.clip_grad_norm_)."""
     model.train()
+    params = list(model.parameters()) if max_grad_norm is not None else None
     total = torch.zeros((), device=stats[0].device)
     for data in loader:                                              # dss2_run.py:134-144
         opt.zero_grad()
@@ -86,6 +90,8 @@ def train_epoch(model, opt, loader, stats, reg_coefs, group=None) -> float:
                                       edge_mean=stats[2], edge_std=stats[3], edge_index=ei, reg_coefs=reg_coefs,
                                       num_samples=num_graphs, node_param=x[:, 8:], edge_param=ea[:, 6:], group=group)
         loss.backward(dss2_data.unit_grad(loss))                      # (= loss.backward(), without autograd's ones_like fill kernel)
+        if max_grad_norm is not None:
+            dss2_optim.clip_grad_norm_(params, max_grad_norm)
         opt.step()
         total += loss.detach()
     return float(total / len(loader))                                # one host sync per epoch (:147)
@@ -97,12 +103,14 @@ class GraphedTrainer:
     step is host-bound (~2.4 ms of Python / autograd dispatch around 0.33 ms of kernels for the SkipPFN line), the replay is
     not.  Valid when every batch of a shape has the SAME graph structure (one topology per dataset, e.g. the reference's
     cigre14 folder): the structure is part of the captured launches, so only x and edge_attr are copied per step.  In-kernel
-    dropout draws new masks on every replay; the optimizer must be ``FusedAdamax(capturable=True)``."""
+    dropout draws new masks on every replay; the optimizer must be a fused one with ``capturable=True`` (``FusedAdamax`` or any other
+    class of optim.py).  ``max_grad_norm``: gradient clipping inside the captured step, between backward and the optimizer."""
 
-    def __init__(self, model, opt, stats, reg_coefs, group=None):
+    def __init__(self, model, opt, stats, reg_coefs, group=None, max_grad_norm=None):
         if not getattr(opt, "capturable", False):
             raise ValueError("GraphedTrainer needs FusedAdamax(capturable=True): the step count must live on the device")
         self.model, self.opt, self.stats, self.reg, self.group = model, opt, stats, reg_coefs, group
+        self.max_grad_norm = max_grad_norm
         self.graphs = {}
         self.params = list(model.parameters())
 
@@ -110,6 +118,7 @@ class GraphedTrainer:
         from .graphs import GraphedStep
         sx, sea, sei = x.clone(), ea.clone(), ei.clone()
         st, reg, model, opt, params, group = self.stats, self.reg, self.model, self.opt, self.params, self.group
+        max_grad_norm = self.max_grad_norm
         eager_losses = []
 
         def step_fn():
@@ -120,6 +129,8 @@ class GraphedTrainer:
                                           edge_mean=st[2], edge_std=st[3], edge_index=sei, reg_coefs=reg, num_samples=None,
                                           node_param=sx[:, 8:], edge_param=sea[:, 6:], group=group)
             loss.backward(dss2_data.unit_grad(loss))
+            if max_grad_norm is not None:
+                dss2_optim.clip_grad_norm_(params, max_grad_norm)
             opt.step()
             if not torch.cuda.is_current_stream_capturing():
                 eager_losses.append(loss.detach().clone())
@@ -163,18 +174,20 @@ class EpochTrainer:
     permutation (on the device) and resetting two words.  Nothing is read back until the caller asks for the epoch's mean loss.
 
     ``mode``: "plan" (graphs.PlannedStep: the library's own launch list, one ``dss2_plan_run`` per step; also at world > 1, where the
-    step's collectives cut it into segments) or "graph" (graphs.GraphedStep: a hipGraph).  Needs ``FusedAdamax(capturable=True)`` and
+    step's collectives cut it into segments) or "graph" (graphs.GraphedStep: a hipGraph).  Needs ``FusedAdamax(capturable=True)`` (or
+    another fused optimizer of optim.py, capturable; ``max_grad_norm`` puts optim.clip_grad_norm_ between backward and its step) and
     either a single-topology ``DeviceDataset`` (the graph structure is then built once, outside the step) or a
     ``dataset.PaddedMixedDataset`` (``MixedDataset.padded()``: samples of several topologies on one bus count, BASELINE config C5 --
     the collation also gathers every slot's edge list and edge count, and the step's second entry is ``Topology.rebuild()``: the
     structure of THIS batch, built on the device inside the step; the loss divides by the batch's real edge count, read on the
     device.  The permutation runs over the union of the parts, the reference loader's uniform shuffle.  Models: MPN, SkipMPN, PFN,
     SkipPFN).  Recording a step runs it (plans:
-    three times, graphs: once), so the model, the optimizer state and the epoch position are saved before and restored after: the first
+    three times, graphs: once), so the model, the optimizer state (every state tensor, the step counts, a tensor ``lr``) and the epoch
+    position are saved before and restored after: the first
     ``train_epoch()`` starts from exactly the state the trainer was given."""
 
     def __init__(self, model, opt, stats, reg_coefs, dataset, batch_size: int, shuffle: bool = True, mode: str = "plan", group=None,
-                 generator=None):
+                 generator=None, max_grad_norm=None):
         from . import _lib
         from . import dataset as dss2_dataset
         self.padded = isinstance(dataset, dss2_dataset.PaddedMixedDataset)
@@ -192,6 +205,7 @@ class EpochTrainer:
         self._lib = _lib
         self.model, self.opt, self.stats, self.reg, self.group = model, opt, stats, reg_coefs, group
         self.ds, self.B, self.shuffle, self.mode, self.generator = dataset, int(batch_size), bool(shuffle), mode, generator
+        self.max_grad_norm = max_grad_norm
         self.params = list(model.parameters())
         dev = dataset.device
         n = len(dataset)
@@ -213,12 +227,18 @@ class EpochTrainer:
     # ---- state that recording a step consumes
     def _state_tensors(self):
         ts = list(self.params)
+        seen = set()
+
+        def add(v):      # (the parameters of a group share one step tensor: once)
+            if torch.is_tensor(v) and id(v) not in seen:
+                seen.add(id(v))
+                ts.append(v)
         for g in self.opt.param_groups:
-            if torch.is_tensor(g.get("_step")):
-                ts.append(g["_step"])
+            add(g.get("_step"))
+            add(g.get("lr"))
             for p in g["params"]:
-                st = self.opt.state.get(p, {})
-                ts += [st[k] for k in ("exp_avg", "exp_inf") if k in st]
+                for v in self.opt.state.get(p, {}).values():
+                    add(v)
         return ts
 
     def _snapshot(self):
@@ -237,7 +257,7 @@ class EpochTrainer:
         dev = ds.device
         sx = torch.empty(nb * ds.n, ds.x.size(2), dtype=torch.float32, device=dev)
         sea = torch.empty(nb * ds.e, ds.edge_attr.size(2), dtype=torch.float32, device=dev)
-        ids, cursor, acc, L = self.ids, self.cursor, self.acc, self._lib
+        ids, cursor, acc, L, max_grad_norm = self.ids, self.cursor, self.acc, self._lib, self.max_grad_norm
         if self.padded:
             # static edge lists and per-slot edge counts, gathered with the features; the structure follows them inside the step
             ei = torch.empty(2, nb * ds.e, dtype=torch.int64, device=dev)
@@ -261,6 +281,8 @@ class EpochTrainer:
                                           edge_mean=st[2], edge_std=st[3], edge_index=ei, reg_coefs=reg, num_samples=None,
                                           node_param=sx[:, 8:], edge_param=sea[:, 6:], group=group)
             loss.backward(dss2_data.unit_grad(loss))
+            if max_grad_norm is not None:
+                dss2_optim.clip_grad_norm_(params, max_grad_norm)
             opt.step()
             L.check(L.lib().dss2_accum_scalar(acc.data_ptr(), loss.data_ptr(), L.stream_ptr(dev)), "dss2_accum_scalar")
             return loss
@@ -320,6 +342,8 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=600)
     ap.add_argument("--lr", type=float, default=3e-3)
+    ap.add_argument("--optimizer", default="Adamax", choices=list(OPTIMIZERS), help="the fused counterpart of torch.optim's class of this name")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the gradients' global 2-norm before every optimizer step")
     hyper_help = {"heads": "GAT_DSSE: attention heads per conv (heads * dim_nodes rounded up to a power of two <= 32: 1 to 4 at 8 "
                            "channels).  Above 1 the model is built with concat=False, the mean over the heads: the only multi-head "
                            "GAT_DSSE the reference can train (its concatenated output fits neither the next conv nor the Linear)"}
@@ -367,20 +391,21 @@ def main(argv=None):
     model = build_model(a.model, hp, gnn_model=a.gnn_model).to(dev)
     single_topology = (not a.data_folder and mixed_train is None) or bool(getattr(train_loader.dataset, "shared_topology", False))
     use_graph = (a.graph == 1) or (a.graph == -1 and single_topology and hp["dim_out"] == 2)
-    opt = FusedAdamax(model.parameters(), lr=a.lr, capturable=use_graph)
+    make_opt, clip = OPTIMIZERS[a.optimizer], a.max_grad_norm
+    opt = make_opt(model.parameters(), lr=a.lr, capturable=use_graph)
     # a device-resident data folder with ONE graph structure: whole epochs without the interpreter (EpochTrainer: the loader's collation is the
     # first launch of the recorded step); pre-collated synthetic batches: the step replayed on copied inputs (GraphedTrainer); else eager
     epoch_trainer = None
     if mixed_train is not None and a.graph != 0 and mixed_train.n is not None and type(model) in (networks.MPN, networks.PFN, networks.SkipPFN):
         use_graph = True
-        opt = FusedAdamax(model.parameters(), lr=a.lr, capturable=True)
-        epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, mixed_train.padded(), a.batch_size, shuffle=True, mode="graph")
+        opt = make_opt(model.parameters(), lr=a.lr, capturable=True)
+        epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, mixed_train.padded(), a.batch_size, shuffle=True, mode="graph", max_grad_norm=clip)
     elif mixed_train is not None:
         use_graph = False                                            # (other models / mixed bus counts: the eager loader, a structure per batch)
-        opt = FusedAdamax(model.parameters(), lr=a.lr)
+        opt = make_opt(model.parameters(), lr=a.lr)
     elif use_graph and a.data_folder and single_topology:
-        epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, train_loader.dataset, a.batch_size, shuffle=True, mode="graph")
-    trainer = GraphedTrainer(model, opt, stats, REG_COEFS) if (use_graph and epoch_trainer is None) else None
+        epoch_trainer = EpochTrainer(model, opt, stats, REG_COEFS, train_loader.dataset, a.batch_size, shuffle=True, mode="graph", max_grad_norm=clip)
+    trainer = GraphedTrainer(model, opt, stats, REG_COEFS, max_grad_norm=clip) if (use_graph and epoch_trainer is None) else None
     how = "whole epochs as replays of one recorded step (EpochTrainer)" if epoch_trainer is not None else ("hipGraph replay" if use_graph else "eager")
     print(f"device:{dev}  train batches {len(train_loader)}  test batches {len(test_loader)}  model {a.model} {hp}  step: {how}")
     for epoch in range(a.epochs):
@@ -389,7 +414,7 @@ def main(argv=None):
             epoch_trainer.train_epoch()
             tl = epoch_trainer.mean_loss()
         else:
-            tl = train_epoch_graphed(trainer, train_loader) if use_graph else train_epoch(model, opt, train_loader, stats, REG_COEFS)
+            tl = train_epoch_graphed(trainer, train_loader) if use_graph else train_epoch(model, opt, train_loader, stats, REG_COEFS, max_grad_norm=clip)
         m = evaluate(model, test_loader, stats) if hp["dim_out"] == 2 else {}
         torch.cuda.synchronize()
         print(f"epoch {epoch:4d}  train_loss {tl:.6g}  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()) +

@@ -875,6 +875,61 @@ int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, in
                           float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev,
                           uint32_t* counter, void* stream);
 
+/* ---- the other optimizers of torch.optim a user puts into the driver's `getattr(optim, NAME)` (dss2_run.py:91-92): Adam / AdamW,
+ * RMSprop, SGD -- and Adamax once more, for a learning rate that lives on the device.  ONE multi-tensor kernel templated on the rule,
+ * the arithmetic of torch's single-tensor path (foreach=False, fused=False) in fp32, in the three forms of the Adamax entry points
+ * above: host table by value (dss2_optim_step, step >= 1 from the host), the same with the step count on the device (dss2_optim_step_dev:
+ * *step_dev is advanced, then used), and the flat-bucket form with a device table (dss2_optim_step_flat: step == 0 -> the count lives in
+ * *step_dev and the launch's last workgroup advances it).  State slots s0 / s1 / s2 (NULL where the rule does not use one):
+ *   ADAM     exp_avg, exp_avg_sq, max_exp_avg_sq (AMSGRAD)        RMSPROP  square_avg, momentum_buffer (MOMENTUM), grad_avg (CENTERED)
+ *   SGD      momentum_buffer (MOMENTUM)                           ADAMAX   exp_avg, exp_inf  (bit for bit dss2_adamax_step*)
+ * lr_dev != NULL: the learning rate is read from the device (a 0-dim fp32 tensor a scheduler fills in place) instead of `lr`, so a
+ * recorded step -- hipGraph or launch plan -- follows a schedule.  A by-value table carries 80 descriptors per launch (80 x 48 B plus
+ * the hyper-parameters stay under 4 KB of kernel arguments). */
+enum dss2_optim_rule { DSS2_OPT_ADAM = 0, DSS2_OPT_RMSPROP = 1, DSS2_OPT_SGD = 2, DSS2_OPT_ADAMAX = 3 };
+enum dss2_optim_flag {
+  DSS2_OPT_AMSGRAD = 1,        /* ADAM: denominators from the running maximum of exp_avg_sq (slot 2) */
+  DSS2_OPT_DECOUPLED_WD = 2,   /* ADAM: AdamW's p *= 1 - lr * wd instead of g += wd * p */
+  DSS2_OPT_CENTERED = 4,       /* RMSPROP: variance around the running mean gradient (slot 2) */
+  DSS2_OPT_MOMENTUM = 8,       /* RMSPROP (slot 1), SGD (slot 0) */
+  DSS2_OPT_NESTEROV = 16       /* SGD */
+};
+typedef struct dss2_optim_hyper {
+  int32_t rule; int32_t flags;
+  float lr;                    /* used when lr_dev == NULL */
+  float beta1, beta2;          /* ADAM / ADAMAX betas; RMSPROP: beta2 = alpha */
+  float omb1, omb2;            /* 1 - beta1, 1 - beta2 as the caller rounds them (torch forms them in double) */
+  float eps, weight_decay;
+  float momentum, omdamp;      /* RMSPROP / SGD momentum; SGD: 1 - dampening */
+  int32_t pad_;
+  const float* lr_dev;
+} dss2_optim_hyper;
+typedef struct dss2_optim_desc {
+  float* param; const float* grad; float* s0; float* s1; float* s2; int64_t n;
+} dss2_optim_desc;
+typedef struct dss2_optim_flat_desc {
+  float* param; int64_t grad_off; float* s0; float* s1; float* s2; int64_t n;
+} dss2_optim_flat_desc;
+int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, int step, void* stream);
+int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream);
+int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
+                         const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream);
+
+/* ---- torch.nn.utils.clip_grad_norm_(parameters, max_norm) (2-norm, error_if_nonfinite=False) in two launches, deterministic.
+ * The gradients are either a HOST table passed by value (descs_host, 192 tensors per launch: more tensors are more launches) or views
+ * of one flat bucket (descs_dev: DEVICE table of {offset, n}, grad_base by value).  dss2_grad_sqsum_partials: workgroup w of n_wg walks
+ * elements w * 256 + t, stride n_wg * 256, of every tensor in table order and writes ONE fp64 partial (chunk c of a by-value table:
+ * partials[c * n_wg + w]); ceil(n_desc / 192) * n_wg <= 256.  dss2_grad_clip_scale: every workgroup re-adds the partials in index order,
+ * total = sqrt(sum), coef = min(1, max_norm / (total + 1e-6)) in fp32 (torch's formula; a non-finite gradient gives a non-finite norm
+ * and coefficient, as in torch), scales its share of the gradients in place, and workgroup 0 writes total to *norm_out.  No float
+ * atomics: two runs give the same bits. */
+typedef struct dss2_grad_desc { float* grad; int64_t n; } dss2_grad_desc;
+typedef struct dss2_grad_flat_desc { int64_t grad_off; int64_t n; } dss2_grad_flat_desc;
+int dss2_grad_sqsum_partials(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc,
+                             int n_wg, double* partials, void* stream);
+int dss2_grad_clip_scale(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc, int n_wg,
+                         const double* partials, float max_norm, float* norm_out, void* stream);
+
 /* ---- shared by the lane-group models GAT_DSSE and GINE_DSSE: the head Linears and the outer-product weight gradients ------- *
  * The head runs inside each model's launches (csrc/dss2_lanegroup.hpp); dss2_lanegroup_wgrad is csrc/dss2_lanegroup.hip.         */
 typedef struct dss2_lanegroup_head {       /* Linear(c, dense) -> Linear(dense, nout) on the last conv's output (or on hin) */
