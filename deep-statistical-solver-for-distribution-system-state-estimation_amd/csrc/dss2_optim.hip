@@ -1,68 +1,15 @@
-// Fused multi-tensor Adamax (torch.optim.Adamax semantics, the optimizer of the reference driver,
-// /root/reference/dss2_run.py:91-92,143): one launch updates every parameter tensor of the model.
+// Fused multi-tensor optimizers: one launch updates every parameter tensor of the model.  The reference driver's is Adamax
+// (torch.optim.Adamax semantics, /root/reference/dss2_run.py:91-92,143):
 //   exp_avg = b1*exp_avg + (1-b1)*g ;  exp_inf = max(b2*exp_inf, |g| + eps) ;
 //   p -= lr / (1 - b1^t) * exp_avg / exp_inf           (weight_decay: g += wd * p first)
+#include <type_traits>
 #include "dss2_weightspace.hpp"
 
 namespace dss2 {
 
-__global__ void adamax_tick_kernel(float* __restrict__ step_dev) {
+// advances the device-side step count in front of the by-value launches of a capturable optimizer (dss2_optim_step_dev)
+__global__ void step_tick_kernel(float* __restrict__ step_dev) {
   if (threadIdx.x == 0 && blockIdx.x == 0) step_dev[0] += 1.f;
-}
-
-// step_dev != NULL: the 1-based step count lives on the device (already advanced by adamax_tick_kernel), so the launch can
-// sit inside a hipGraph and every replay uses the next count; NULL: bias_corr1 was computed by the host.
-constexpr int ADAMAX_CHUNK = 96;      // descriptors per launch, by value in the kernel arguments (96 x 40 B < 4 KB)
-struct AdamaxTable { dss2_adamax_desc d[ADAMAX_CHUNK]; };
-
-__global__ void __launch_bounds__(256) adamax_kernel(const AdamaxTable tab, float lr, float beta1,
-                                                     float beta2, float eps, float weight_decay, float bias_corr1,
-                                                     const float* __restrict__ step_dev) {
-  const dss2_adamax_desc& d = tab.d[blockIdx.y];
-  if (step_dev) bias_corr1 = 1.f - powf(beta1, step_dev[0]);
-  const float clr = lr / bias_corr1;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * blockDim.x) {
-    float g = d.grad[i];
-    const float p = d.param[i];
-    if (weight_decay != 0.f) g = fmaf(weight_decay, p, g);
-    const float m = fmaf(beta1, d.exp_avg[i], (1.f - beta1) * g);        // lerp(exp_avg, g, 1-b1)
-    const float u = fmaxf(beta2 * d.exp_inf[i], fabsf(g) + eps);
-    d.exp_avg[i] = m;
-    d.exp_inf[i] = u;
-    d.param[i] = p - clr * (m / u);
-  }
-}
-
-// One launch for every tensor of a flat gradient bucket (descriptor table in device memory, see dss2_hip.h).
-__global__ void __launch_bounds__(256) adamax_flat_kernel(const dss2_adamax_flat_desc* __restrict__ descs,
-                                                          const float* __restrict__ grad_base, float lr, float beta1, float beta2,
-                                                          float eps, float weight_decay, float bias_corr1, float* step_dev,
-                                                          unsigned* counter) {
-  const dss2_adamax_flat_desc d = descs[blockIdx.y];
-  if (step_dev) bias_corr1 = 1.f - powf(beta1, step_dev[0] + 1.f);      // this step's (1-based) count
-  const float clr = lr / bias_corr1;
-  const float* __restrict__ grad = grad_base + d.grad_off;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * blockDim.x) {
-    float g = grad[i];
-    const float p = d.param[i];
-    if (weight_decay != 0.f) g = fmaf(weight_decay, p, g);
-    const float m = fmaf(beta1, d.exp_avg[i], (1.f - beta1) * g);
-    const float u = fmaxf(beta2 * d.exp_inf[i], fabsf(g) + eps);
-    d.exp_avg[i] = m;
-    d.exp_inf[i] = u;
-    d.param[i] = p - clr * (m / u);
-  }
-  if (!step_dev) return;
-  // The last workgroup to arrive advances the device-side count.  Every workgroup has READ the count before it arrives: the
-  // barrier drains its loads (s_waitcnt vmcnt(0)), and only then is the arrival posted.  Nothing is published through memory, so
-  // a relaxed device-scope atomic is enough -- a release fence here would be an L2 write-back per workgroup on MI355X.
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.y - 1) {
-      step_dev[0] += 1.f;
-      *counter = 0u;
-    }
-  }
 }
 
 // (small_gemm_body / small_gemm_tile: dss2_weightspace.hpp)
@@ -87,89 +34,31 @@ static int dss2_small_gemm_launch(const dss2_sgemm_desc* descs, int n_desc, int 
   return dss2::check_launch("small_gemm");
 }
 
-static int adamax_launch(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps,
-                         float weight_decay, float bc1, const float* step_dev, hipStream_t s) {
-  for (int c0 = 0; c0 < n_desc; c0 += dss2::ADAMAX_CHUNK) {
-    const int n = n_desc - c0 < dss2::ADAMAX_CHUNK ? n_desc - c0 : dss2::ADAMAX_CHUNK;
-    dss2::AdamaxTable tab = {};
-    int64_t max_n = 0;
-    for (int i = 0; i < n; ++i) {
-      tab.d[i] = descs_host[c0 + i];
-      if (!tab.d[i].param || !tab.d[i].grad || !tab.d[i].exp_avg || !tab.d[i].exp_inf) { dss2::set_error("adamax_step: descriptor %d is incomplete", c0 + i); return 2; }
-      if (tab.d[i].n > max_n) max_n = tab.d[i].n;
-    }
-    int64_t bx = (max_n + 255) / 256;
-    if (bx > 64) bx = 64;
-    if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(dss2::adamax_kernel, dim3((unsigned)bx, n), dim3(256), 0, s, tab, lr, beta1, beta2, eps, weight_decay, bc1, step_dev);
-  }
-  return dss2::check_launch("adamax_step");
-}
-
-static int dss2_adamax_step_launch(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
-extern "C" int dss2_adamax_step(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, lr, beta1, beta2, eps, weight_decay, step](void* s_) { return dss2_adamax_step_launch(dss2::plan_ptr(d), n_desc, lr, beta1, beta2, eps, weight_decay, step, s_); });
-  return dss2_adamax_step_launch(descs_host, n_desc, lr, beta1, beta2, eps, weight_decay, step, stream);
-}
-static int dss2_adamax_step_launch(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
-  if (n_desc <= 0) return 0;
-  if (!descs_host) { dss2::set_error("adamax_step: null descriptor table"); return 2; }
-  if (step < 1) { dss2::set_error("adamax_step: step must be >= 1"); return 2; }
-  return adamax_launch(descs_host, n_desc, lr, beta1, beta2, eps, weight_decay, 1.f - powf(beta1, (float)step), nullptr, dss2::as_stream(stream));
-}
-
-static int dss2_adamax_step_flat_launch(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev, uint32_t* counter, void* stream);
-extern "C" int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev, uint32_t* counter, void* stream) {
-  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, lr, beta1, beta2, eps, weight_decay, step, step_dev, counter](void* s_) { return dss2_adamax_step_flat_launch(descs_dev, n_desc, max_n, grad_base, lr, beta1, beta2, eps, weight_decay, step, step_dev, counter, s_); });
-  return dss2_adamax_step_flat_launch(descs_dev, n_desc, max_n, grad_base, lr, beta1, beta2, eps, weight_decay, step, step_dev, counter, stream);
-}
-static int dss2_adamax_step_flat_launch(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev, uint32_t* counter, void* stream) {
-  if (n_desc <= 0) return 0;
-  if (!descs_dev || !grad_base || n_desc > 65535) { dss2::set_error("adamax_step_flat: bad arguments"); return 2; }
-  if (step < 0 || (step == 0 && (!step_dev || !counter))) { dss2::set_error("adamax_step_flat: step >= 1, or step == 0 with step_dev and counter"); return 2; }
-  int64_t bx = (max_n + 4095) / 4096;      // a workgroup walks up to 16 elements per thread: few, fat workgroups (and few
-  if (bx > 64) bx = 64;                    // arrivals at the step counter's word)
-  if (bx < 1) bx = 1;
-  const float bc1 = step > 0 ? 1.f - powf(beta1, (float)step) : 1.f;
-  hipLaunchKernelGGL(dss2::adamax_flat_kernel, dim3((unsigned)bx, n_desc), dim3(256), 0, dss2::as_stream(stream), descs_dev, grad_base,
-                     lr, beta1, beta2, eps, weight_decay, bc1, step > 0 ? nullptr : step_dev, counter);
-  return dss2::check_launch("adamax_step_flat");
-}
-
-static int dss2_adamax_step_dev_launch(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, float* step_dev, void* stream);
-extern "C" int dss2_adamax_step_dev(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, float* step_dev, void* stream) {
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, lr, beta1, beta2, eps, weight_decay, step_dev](void* s_) { return dss2_adamax_step_dev_launch(dss2::plan_ptr(d), n_desc, lr, beta1, beta2, eps, weight_decay, step_dev, s_); });
-  return dss2_adamax_step_dev_launch(descs_host, n_desc, lr, beta1, beta2, eps, weight_decay, step_dev, stream);
-}
-static int dss2_adamax_step_dev_launch(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, float* step_dev, void* stream) {
-  if (n_desc <= 0) return 0;
-  if (!descs_host || !step_dev) { dss2::set_error("adamax_step_dev: null argument"); return 2; }
-  hipLaunchKernelGGL(dss2::adamax_tick_kernel, dim3(1), dim3(64), 0, dss2::as_stream(stream), step_dev);
-  return adamax_launch(descs_host, n_desc, lr, beta1, beta2, eps, weight_decay, 1.f, step_dev, dss2::as_stream(stream));
-}
-
-// ---- Adam / AdamW, RMSprop, SGD, and Adamax with a device-side learning rate (see dss2_hip.h): one multi-tensor kernel templated on
-//      the rule.  The arithmetic is torch's single-tensor path in fp32, fmaf where torch has lerp / addcmul (as adamax_kernel).
+// ---- Adamax, Adam / AdamW, RMSprop, SGD (see dss2_hip.h): one multi-tensor kernel templated on the rule.  The arithmetic is torch's
+//      single-tensor path in fp32, fmaf where torch has lerp / addcmul.
 namespace dss2 {
 
 constexpr int OPTIM_CHUNK = 80;       // descriptors per launch, by value in the kernel arguments (80 x 48 B + hyper < 4 KB)
 struct OptimTable { dss2_optim_desc d[OPTIM_CHUNK]; };
 
-// t: this step's 1-based count; bc1 / bc2: 1 - beta^t (from the host, or from the device-side count)
+// t: this step's 1-based count; bc1 / bc2: 1 - beta^t (from the host, or from the device-side count).  first / stride: this thread's
+// grid-stride walk, formed in the KERNEL bodies: read in here, blockDim.x is not folded to a kernel-argument load and comes from the
+// dispatch packet by a vector load in front of the loop (+0.2 us on the 12 us flat launch of the C2 model).
 template <int RULE>
 __device__ __forceinline__ void optim_walk(float* __restrict__ param, const float* __restrict__ grad, float* s0, float* s1, float* s2,
-                                           int64_t n, const dss2_optim_hyper& h, float t, float bc1, float bc2) {
+                                           int64_t n, const dss2_optim_hyper& h, float t, float bc1, float bc2, int64_t first,
+                                           int64_t stride) {
   const float lr = h.lr_dev ? h.lr_dev[0] : h.lr;
   const float wd = h.weight_decay;
   const int flags = h.flags;
   const float clr = lr / bc1;                     // ADAM / ADAMAX step size
   const float bc2s = sqrtf(bc2);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < n; i += stride) {
     float g = grad[i];
     float p = param[i];
-    if constexpr (RULE == DSS2_OPT_ADAMAX) {      // the operations of adamax_kernel, in its order
+    if constexpr (RULE == DSS2_OPT_ADAMAX) {
       if (wd != 0.f) g = fmaf(wd, p, g);
-      const float m = fmaf(h.beta1, s0[i], (1.f - h.beta1) * g);
+      const float m = fmaf(h.beta1, s0[i], (1.f - h.beta1) * g);       // lerp(exp_avg, g, 1-b1)
       const float u = fmaxf(h.beta2 * s1[i], fabsf(g) + h.eps);
       s0[i] = m;
       s1[i] = u;
@@ -225,28 +114,27 @@ template <int RULE>
 __global__ void __launch_bounds__(256) optim_kernel(const OptimTable tab, const dss2_optim_hyper h, float t, float bc1, float bc2,
                                                     const float* __restrict__ step_dev) {
   const dss2_optim_desc& d = tab.d[blockIdx.y];
-  if (step_dev) {                                  // (already advanced by adamax_tick_kernel)
+  if (step_dev) {                                  // (already advanced by step_tick_kernel)
     t = step_dev[0];
     bc1 = 1.f - powf(h.beta1, t);
     bc2 = 1.f - powf(h.beta2, t);
   }
-  optim_walk<RULE>(d.param, d.grad, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2);
+  optim_walk<RULE>(d.param, d.grad, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2,
+                   (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-template <int RULE>
-__global__ void __launch_bounds__(256) optim_flat_kernel(const dss2_optim_flat_desc* __restrict__ descs, const float* __restrict__ grad_base,
-                                                         const dss2_optim_hyper h, float t, float bc1, float bc2, float* step_dev,
-                                                         unsigned* counter) {
-  const dss2_optim_flat_desc d = descs[blockIdx.y];
-  if (step_dev) {
-    t = step_dev[0] + 1.f;                         // this step's (1-based) count
-    bc1 = 1.f - powf(h.beta1, t);
-    bc2 = 1.f - powf(h.beta2, t);
-  }
-  optim_walk<RULE>(d.param, grad_base + d.grad_off, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2);
-  if (!step_dev) return;
-  // the last workgroup to arrive advances the count: the pattern of adamax_flat_kernel (every workgroup has read the count before the
-  // barrier; nothing is published through memory, so the arrival is a relaxed device-scope atomic without a fence)
+// Descriptor i of a flat-bucket table (in device memory) in either layout: dss2_optim_flat_desc, or the 40-byte dss2_adamax_flat_desc of
+// dss2_adamax_step_flat, which has no third slot.  Workgroup-uniform.
+__device__ __forceinline__ dss2_optim_flat_desc load_flat_desc(const void* __restrict__ descs, int adamax_layout, int i) {
+  if (!adamax_layout) return static_cast<const dss2_optim_flat_desc*>(descs)[i];
+  const dss2_adamax_flat_desc a = static_cast<const dss2_adamax_flat_desc*>(descs)[i];
+  return {a.param, a.grad_off, a.exp_avg, a.exp_inf, nullptr, a.n};
+}
+
+// The last workgroup to arrive advances the device-side count.  Every workgroup has READ the count before it arrives: the
+// barrier drains its loads (s_waitcnt vmcnt(0)), and only then is the arrival posted.  Nothing is published through memory, so
+// a relaxed device-scope atomic is enough -- a release fence here would be an L2 write-back per workgroup on MI355X.
+__device__ __forceinline__ void last_arrival_advances(float* step_dev, unsigned* counter) {
   __syncthreads();
   if (threadIdx.x == 0) {
     if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.y - 1) {
@@ -254,6 +142,22 @@ __global__ void __launch_bounds__(256) optim_flat_kernel(const dss2_optim_flat_d
       *counter = 0u;
     }
   }
+}
+
+// One launch for every tensor of a flat gradient bucket (descriptor table in device memory, see dss2_hip.h).
+template <int RULE>
+__global__ void __launch_bounds__(256) optim_flat_kernel(const void* __restrict__ descs, int adamax_layout, const float* __restrict__ grad_base,
+                                                         const dss2_optim_hyper h, float t, float bc1, float bc2, float* step_dev,
+                                                         unsigned* counter) {
+  const dss2_optim_flat_desc d = load_flat_desc(descs, adamax_layout, blockIdx.y);
+  if (step_dev) {
+    t = step_dev[0] + 1.f;                         // this step's (1-based) count
+    bc1 = 1.f - powf(h.beta1, t);
+    bc2 = 1.f - powf(h.beta2, t);
+  }
+  optim_walk<RULE>(d.param, grad_base + d.grad_off, d.s0, d.s1, d.s2, d.n, h, t, bc1, bc2,
+                   (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+  if (step_dev) last_arrival_advances(step_dev, counter);
 }
 
 // ---- global-norm gradient clipping: fp64 partial per workgroup, re-added in index order by every workgroup of the second launch
@@ -317,103 +221,154 @@ static int optim_slot_mask(const dss2_optim_hyper& h) {
   }
 }
 
-template <int RULE>
-static void optim_launch_rule(const dss2::OptimTable& tab, dim3 grid, const dss2_optim_hyper& h, float t, float bc1, float bc2,
-                              const float* step_dev, hipStream_t s) {
-  hipLaunchKernelGGL(dss2::optim_kernel<RULE>, grid, dim3(256), 0, s, tab, h, t, bc1, bc2, step_dev);
+// h.rule -> the kernel instantiation: f gets the rule as a std::integral_constant, for both the by-value and the flat launch
+template <class F>
+static void optim_for_rule(int rule, F&& f) {
+  switch (rule) {
+    case DSS2_OPT_ADAM: f(std::integral_constant<int, DSS2_OPT_ADAM>{}); break;
+    case DSS2_OPT_RMSPROP: f(std::integral_constant<int, DSS2_OPT_RMSPROP>{}); break;
+    case DSS2_OPT_SGD: f(std::integral_constant<int, DSS2_OPT_SGD>{}); break;
+    default: f(std::integral_constant<int, DSS2_OPT_ADAMAX>{}); break;
+  }
 }
 
-static int optim_launch(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper& h, float t, float bc1, float bc2,
-                        const float* step_dev, hipStream_t s) {
+// workgroups per tensor: one per `per_wg` elements of the largest tensor, 1 .. 64
+static unsigned optim_grid_x(int64_t max_n, int per_wg) {
+  const int64_t bx = (max_n + per_wg - 1) / per_wg;
+  return bx > 64 ? 64u : bx < 1 ? 1u : (unsigned)bx;
+}
+
+// A host table travels to the kernels by value, one TABLE of descriptors per launch: launch(tab, c0, n) gets descriptors c0 .. c0 + n - 1
+// and may refuse them with a nonzero return, which ends the walk.
+template <class TABLE, class DESC, class LAUNCH>
+static int for_each_chunk(const DESC* descs_host, int n_desc, LAUNCH&& launch) {
+  constexpr int CHUNK = (int)std::extent<decltype(TABLE::d)>::value;
+  for (int c0 = 0; c0 < n_desc; c0 += CHUNK) {
+    const int n = n_desc - c0 < CHUNK ? n_desc - c0 : CHUNK;
+    TABLE tab = {};
+    for (int i = 0; i < n; ++i) tab.d[i] = descs_host[c0 + i];
+    if (int rc = launch(tab, c0, n)) return rc;
+  }
+  return 0;
+}
+
+// The launch bodies below serve dss2_optim_step* and their Adamax adapters; `who` is the entry point the caller used, for error texts.
+static int optim_launch(const char* who, const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper& h, float t, float bc1,
+                        float bc2, const float* step_dev, hipStream_t s) {
   const int mask = optim_slot_mask(h);
-  for (int c0 = 0; c0 < n_desc; c0 += dss2::OPTIM_CHUNK) {
-    const int n = n_desc - c0 < dss2::OPTIM_CHUNK ? n_desc - c0 : dss2::OPTIM_CHUNK;
-    dss2::OptimTable tab = {};
+  const int rc = for_each_chunk<dss2::OptimTable>(descs_host, n_desc, [&](const dss2::OptimTable& tab, int c0, int n) {
     int64_t max_n = 0;
     for (int i = 0; i < n; ++i) {
-      const dss2_optim_desc& d = tab.d[i] = descs_host[c0 + i];
+      const dss2_optim_desc& d = tab.d[i];
       if (!d.param || !d.grad || ((mask & 1) && !d.s0) || ((mask & 2) && !d.s1) || ((mask & 4) && !d.s2) || d.n < 0) {
-        dss2::set_error("optim_step: descriptor %d is incomplete", c0 + i);
+        dss2::set_error("%s: descriptor %d is incomplete", who, c0 + i);
         return 2;
       }
       if (d.n > max_n) max_n = d.n;
     }
-    int64_t bx = (max_n + 255) / 256;
-    if (bx > 64) bx = 64;
-    if (bx < 1) bx = 1;
-    const dim3 grid((unsigned)bx, n);
-    switch (h.rule) {
-      case DSS2_OPT_ADAM: optim_launch_rule<DSS2_OPT_ADAM>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
-      case DSS2_OPT_RMSPROP: optim_launch_rule<DSS2_OPT_RMSPROP>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
-      case DSS2_OPT_SGD: optim_launch_rule<DSS2_OPT_SGD>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
-      default: optim_launch_rule<DSS2_OPT_ADAMAX>(tab, grid, h, t, bc1, bc2, step_dev, s); break;
-    }
-  }
-  return dss2::check_launch("optim_step");
+    const dim3 grid(optim_grid_x(max_n, 256), n);
+    optim_for_rule(h.rule, [&](auto rule) {
+      hipLaunchKernelGGL(dss2::optim_kernel<decltype(rule)::value>, grid, dim3(256), 0, s, tab, h, t, bc1, bc2, step_dev);
+    });
+    return 0;
+  });
+  return rc ? rc : dss2::check_launch(who);
 }
 
-static int dss2_optim_step_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, int step, void* stream);
-extern "C" int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, int step, void* stream) {
-  if (int rc = optim_hyper_check(hyper, "optim_step")) return rc;
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step](void* s_) { return dss2_optim_step_launch(dss2::plan_ptr(d), n_desc, h, step, s_); });
-  return dss2_optim_step_launch(descs_host, n_desc, *hyper, step, stream);
-}
-static int dss2_optim_step_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, int step, void* stream) {
+static int optim_step_launch(const char* who, const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper& h, int step, void* stream) {
   if (n_desc <= 0) return 0;
-  if (!descs_host) { dss2::set_error("optim_step: null descriptor table"); return 2; }
-  if (step < 1) { dss2::set_error("optim_step: step must be >= 1"); return 2; }
-  return optim_launch(descs_host, n_desc, h, (float)step, 1.f - powf(h.beta1, (float)step), 1.f - powf(h.beta2, (float)step), nullptr,
+  if (!descs_host) { dss2::set_error("%s: null descriptor table", who); return 2; }
+  if (step < 1) { dss2::set_error("%s: step must be >= 1", who); return 2; }
+  return optim_launch(who, descs_host, n_desc, h, (float)step, 1.f - powf(h.beta1, (float)step), 1.f - powf(h.beta2, (float)step), nullptr,
                       dss2::as_stream(stream));
 }
 
-static int dss2_optim_step_dev_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, float* step_dev, void* stream);
-extern "C" int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream) {
-  if (int rc = optim_hyper_check(hyper, "optim_step_dev")) return rc;
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step_dev](void* s_) { return dss2_optim_step_dev_launch(dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
-  return dss2_optim_step_dev_launch(descs_host, n_desc, *hyper, step_dev, stream);
-}
-static int dss2_optim_step_dev_launch(const dss2_optim_desc* descs_host, int n_desc, dss2_optim_hyper h, float* step_dev, void* stream) {
+static int optim_step_dev_launch(const char* who, const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper& h, float* step_dev, void* stream) {
   if (n_desc <= 0) return 0;
-  if (!descs_host || !step_dev) { dss2::set_error("optim_step_dev: null argument"); return 2; }
-  hipLaunchKernelGGL(dss2::adamax_tick_kernel, dim3(1), dim3(64), 0, dss2::as_stream(stream), step_dev);
-  return optim_launch(descs_host, n_desc, h, 1.f, 1.f, 1.f, step_dev, dss2::as_stream(stream));
+  if (!descs_host || !step_dev) { dss2::set_error("%s: null argument", who); return 2; }
+  hipLaunchKernelGGL(dss2::step_tick_kernel, dim3(1), dim3(64), 0, dss2::as_stream(stream), step_dev);
+  return optim_launch(who, descs_host, n_desc, h, 1.f, 1.f, 1.f, step_dev, dss2::as_stream(stream));
 }
 
-template <int RULE>
-static void optim_flat_launch_rule(dim3 grid, const dss2_optim_flat_desc* descs_dev, const float* grad_base, const dss2_optim_hyper& h,
-                                   float t, float bc1, float bc2, float* step_dev, uint32_t* counter, hipStream_t s) {
-  hipLaunchKernelGGL(dss2::optim_flat_kernel<RULE>, grid, dim3(256), 0, s, descs_dev, grad_base, h, t, bc1, bc2, step_dev, counter);
-}
-
-static int dss2_optim_step_flat_launch(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, dss2_optim_hyper h, int step, float* step_dev, uint32_t* counter, void* stream);
-extern "C" int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
-                                    const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream) {
-  if (int rc = optim_hyper_check(hyper, "optim_step_flat")) return rc;
-  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h = *hyper, step, step_dev, counter](void* s_) { return dss2_optim_step_flat_launch(descs_dev, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
-  return dss2_optim_step_flat_launch(descs_dev, n_desc, max_n, grad_base, *hyper, step, step_dev, counter, stream);
-}
-static int dss2_optim_step_flat_launch(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, dss2_optim_hyper h, int step, float* step_dev, uint32_t* counter, void* stream) {
+// descs_dev: a device table of dss2_optim_flat_desc, or (adamax_layout) of dss2_adamax_flat_desc
+static int optim_step_flat_launch(const char* who, const void* descs_dev, int adamax_layout, int n_desc, int64_t max_n, const float* grad_base,
+                                  const dss2_optim_hyper& h, int step, float* step_dev, uint32_t* counter, void* stream) {
   if (n_desc <= 0) return 0;
-  if (!descs_dev || !grad_base || n_desc > 65535) { dss2::set_error("optim_step_flat: bad arguments"); return 2; }
-  if (step < 0 || (step == 0 && (!step_dev || !counter))) { dss2::set_error("optim_step_flat: step >= 1, or step == 0 with step_dev and counter"); return 2; }
-  int64_t bx = (max_n + 4095) / 4096;      // few, fat workgroups, as adamax_step_flat
-  if (bx > 64) bx = 64;
-  if (bx < 1) bx = 1;
-  const dim3 grid((unsigned)bx, n_desc);
+  if (!descs_dev || !grad_base || n_desc > 65535) { dss2::set_error("%s: bad arguments", who); return 2; }
+  if (step < 0 || (step == 0 && (!step_dev || !counter))) { dss2::set_error("%s: step >= 1, or step == 0 with step_dev and counter", who); return 2; }
+  // a workgroup walks up to 16 elements per thread: few, fat workgroups (and few arrivals at the step counter's word)
+  const dim3 grid(optim_grid_x(max_n, 4096), n_desc);
   const float t = step > 0 ? (float)step : 1.f;
   const float bc1 = step > 0 ? 1.f - powf(h.beta1, t) : 1.f, bc2 = step > 0 ? 1.f - powf(h.beta2, t) : 1.f;
   float* sd = step > 0 ? nullptr : step_dev;
-  hipStream_t s = dss2::as_stream(stream);
-  switch (h.rule) {
-    case DSS2_OPT_ADAM: optim_flat_launch_rule<DSS2_OPT_ADAM>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
-    case DSS2_OPT_RMSPROP: optim_flat_launch_rule<DSS2_OPT_RMSPROP>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
-    case DSS2_OPT_SGD: optim_flat_launch_rule<DSS2_OPT_SGD>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
-    default: optim_flat_launch_rule<DSS2_OPT_ADAMAX>(grid, descs_dev, grad_base, h, t, bc1, bc2, sd, counter, s); break;
-  }
-  return dss2::check_launch("optim_step_flat");
+  optim_for_rule(h.rule, [&](auto rule) {
+    hipLaunchKernelGGL(dss2::optim_flat_kernel<decltype(rule)::value>, grid, dim3(256), 0, dss2::as_stream(stream), descs_dev, adamax_layout,
+                       grad_base, h, t, bc1, bc2, sd, counter);
+  });
+  return dss2::check_launch(who);
 }
 
-// by-value chunks of a host table, or the whole device table of a flat bucket, for both clipping launches
+extern "C" int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, int step, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step")) return rc;
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step](void* s_) { return optim_step_launch("optim_step", dss2::plan_ptr(d), n_desc, h, step, s_); });
+  return optim_step_launch("optim_step", descs_host, n_desc, *hyper, step, stream);
+}
+
+extern "C" int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step_dev")) return rc;
+  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step_dev](void* s_) { return optim_step_dev_launch("optim_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
+  return optim_step_dev_launch("optim_step_dev", descs_host, n_desc, *hyper, step_dev, stream);
+}
+
+extern "C" int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
+                                    const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream) {
+  if (int rc = optim_hyper_check(hyper, "optim_step_flat")) return rc;
+  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h = *hyper, step, step_dev, counter](void* s_) { return optim_step_flat_launch("optim_step_flat", descs_dev, 0, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
+  return optim_step_flat_launch("optim_step_flat", descs_dev, 0, n_desc, max_n, grad_base, *hyper, step, step_dev, counter, stream);
+}
+
+// ---- the Adamax entry points of the header: adapters onto the launch bodies above (rule ADAMAX, learning rate from the host)
+static dss2_optim_hyper adamax_hyper(float lr, float beta1, float beta2, float eps, float weight_decay) {
+  dss2_optim_hyper h = {};
+  h.rule = DSS2_OPT_ADAMAX;
+  h.lr = lr; h.beta1 = beta1; h.beta2 = beta2; h.eps = eps; h.weight_decay = weight_decay;
+  return h;
+}
+
+// (one allocation per call: the converted table is what the launch walks and, when a plan records, what its closure keeps)
+static std::vector<dss2_optim_desc> adamax_descs(const dss2_adamax_desc* descs_host, int n_desc) {
+  std::vector<dss2_optim_desc> d(descs_host && n_desc > 0 ? (size_t)n_desc : 0);
+  for (size_t i = 0; i < d.size(); ++i) {
+    const dss2_adamax_desc& a = descs_host[i];
+    d[i] = {a.param, a.grad, a.exp_avg, a.exp_inf, nullptr, a.n};
+  }
+  return d;
+}
+
+extern "C" int dss2_adamax_step(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
+  const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
+  std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
+  const int rc = optim_step_launch("adamax_step", dss2::plan_ptr(d), n_desc, h, step, stream);
+  DSS2_RECORD([d = std::move(d), n_desc, h, step](void* s_) { return optim_step_launch("adamax_step", dss2::plan_ptr(d), n_desc, h, step, s_); });
+  return rc;
+}
+
+extern "C" int dss2_adamax_step_dev(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, float* step_dev, void* stream) {
+  const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
+  std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
+  const int rc = optim_step_dev_launch("adamax_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, stream);
+  DSS2_RECORD([d = std::move(d), n_desc, h, step_dev](void* s_) { return optim_step_dev_launch("adamax_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
+  return rc;
+}
+
+// (the table is in device memory in the 40-byte layout: the kernel reads it as it is)
+extern "C" int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev, uint32_t* counter, void* stream) {
+  const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
+  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h, step, step_dev, counter](void* s_) { return optim_step_flat_launch("adamax_step_flat", descs_dev, 1, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
+  return optim_step_flat_launch("adamax_step_flat", descs_dev, 1, n_desc, max_n, grad_base, h, step, step_dev, counter, stream);
+}
+
+// ---- gradient clipping: by-value chunks of a host table, or the whole device table of a flat bucket, for both launches
 static int grad_args_check(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc,
                            int n_wg, const void* partials, const char* who) {
   if ((!descs_host) == (!descs_dev) || (descs_dev && !grad_base) || !partials) { dss2::set_error("%s: a host table, or a device table with its bucket", who); return 2; }
@@ -435,15 +390,14 @@ static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, con
   if (n_desc <= 0) { dss2::set_error("grad_sqsum_partials: no gradients"); return 2; }
   if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_sqsum_partials")) return rc;
   hipStream_t s = dss2::as_stream(stream);
-  dss2::GradTable tab = {};
   if (descs_dev) {
-    hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, tab, descs_dev, grad_base, n_desc, partials);
+    hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, dss2::GradTable{}, descs_dev, grad_base, n_desc, partials);
   } else {
-    for (int c0 = 0, c = 0; c0 < n_desc; c0 += dss2::GRAD_CHUNK, ++c) {
-      const int n = n_desc - c0 < dss2::GRAD_CHUNK ? n_desc - c0 : dss2::GRAD_CHUNK;
-      for (int i = 0; i < n; ++i) tab.d[i] = descs_host[c0 + i];
-      hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials + (int64_t)c * n_wg);
-    }
+    int c = 0;                                     // chunk c writes partials[c * n_wg ..]
+    if (int rc = for_each_chunk<dss2::GradTable>(descs_host, n_desc, [&](const dss2::GradTable& tab, int, int n) {
+          hipLaunchKernelGGL(dss2::grad_sqsum_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials + (int64_t)c++ * n_wg);
+          return 0;
+        })) return rc;
   }
   return dss2::check_launch("grad_sqsum_partials");
 }
@@ -459,16 +413,14 @@ static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const d
   if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_clip_scale")) return rc;
   if (!norm_out) { dss2::set_error("grad_clip_scale: null norm_out"); return 2; }
   hipStream_t s = dss2::as_stream(stream);
-  dss2::GradTable tab = {};
   if (descs_dev) {
-    hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, tab, descs_dev, grad_base, n_desc, partials, n_wg, max_norm, norm_out);
+    hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, dss2::GradTable{}, descs_dev, grad_base, n_desc, partials, n_wg, max_norm, norm_out);
   } else {
     const int chunks = (n_desc + dss2::GRAD_CHUNK - 1) / dss2::GRAD_CHUNK;
-    for (int c0 = 0; c0 < n_desc; c0 += dss2::GRAD_CHUNK) {
-      const int n = n_desc - c0 < dss2::GRAD_CHUNK ? n_desc - c0 : dss2::GRAD_CHUNK;
-      for (int i = 0; i < n; ++i) tab.d[i] = descs_host[c0 + i];
-      hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials, chunks * n_wg, max_norm, norm_out);
-    }
+    if (int rc = for_each_chunk<dss2::GradTable>(descs_host, n_desc, [&](const dss2::GradTable& tab, int, int n) {
+          hipLaunchKernelGGL(dss2::grad_clip_scale_kernel, dim3(n_wg), dim3(256), 0, s, tab, nullptr, nullptr, n, partials, chunks * n_wg, max_norm, norm_out);
+          return 0;
+        })) return rc;
   }
   return dss2::check_launch("grad_clip_scale");
 }

@@ -1,7 +1,8 @@
 """Fused optimizers: drop-ins for ``torch.optim.Adamax`` as the reference driver uses it
 (/root/reference/dss2_run.py:91-92 ``getattr(optim, 'Adamax')(model.parameters(), lr=3e-3)``, stepped
 at :143) and for the names a user puts into that line instead -- Adam, AdamW, RMSprop, SGD -- as ONE HIP
-launch over all parameter tensors instead of ~6 ATen launches per tensor.  State keys match torch's, so
+launch over all parameter tensors instead of ~6 ATen launches per tensor: every class here is a rule of the one
+multi-tensor kernel behind ``dss2_optim_step*`` (include/dss2_hip.h).  State keys match torch's, so
 optimizer checkpoints (``optimizer_state_dict`` in dss2_run.py:240-247) load either way.  ``lr`` may be a
 0-dim fp32 device tensor: the launches then read it, so a recorded step (graphs.GraphedStep / PlannedStep)
 follows a ``torch.optim.lr_scheduler`` (the schedulers fill a tensor ``lr`` in place).  ``clip_grad_norm_``
@@ -47,10 +48,6 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _hyper(self, group) -> "_lib.OptimHyper":
         raise NotImplementedError
-
-    def _legacy(self, group) -> bool:
-        """True: the launches are the dss2_adamax_step* entry points with their own table layouts (FusedAdamax with a float lr)."""
-        return False
 
     def _loaded_step(self, ps) -> float:
         known = [self.state[p]["step"] for p in ps if "step" in self.state[p]]
@@ -135,15 +132,14 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if not g.is_contiguous() or g.dtype != torch.float32 or g.untyped_storage().data_ptr() != base:
                 return False
         offs = tuple(p.grad.storage_offset() for p in ps)
-        legacy = self._legacy(group)
-        key = (tuple(p.data_ptr() for p in ps), offs, legacy)
+        key = (tuple(p.data_ptr() for p in ps), offs)
         cached = self._flat_table.get(gi)
         if cached is None or cached[0] != key:
             if torch.cuda.is_current_stream_capturing():
                 return False      # (a table upload cannot be captured: the by-value path below serves this step)
             import numpy as np
-            slots = self._slots(group)[:2] if legacy else self._slots(group)
-            arr = np.zeros((len(ps), 3 + len(slots)), dtype=np.int64)
+            slots = self._slots(group)
+            arr = np.zeros((len(ps), 6), dtype=np.int64)      # dss2_optim_flat_desc
             for i, p in enumerate(ps):
                 stp = self.state[p]
                 arr[i] = (p.data_ptr(), offs[i]) + tuple(stp[k].data_ptr() if k is not None else 0 for k in slots) + (p.numel(),)
@@ -153,14 +149,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
             self.table_builds += 1
         _, tab, max_n, counter = cached
         step_dev = shared.data_ptr() if self.capturable else None
-        if legacy:
-            b1, b2 = group["betas"]
-            _lib.check(_lib.lib().dss2_adamax_step_flat(tab.data_ptr(), len(ps), max_n, base, float(group["lr"]), float(b1), float(b2),
-                                                        float(group["eps"]), float(group["weight_decay"]), int(step),
-                                                        step_dev, counter.data_ptr(), _lib.stream_ptr(dev)), "dss2_adamax_step_flat")
-        else:
-            _lib.check(_lib.lib().dss2_optim_step_flat(tab.data_ptr(), len(ps), max_n, base, C.byref(self._hyper(group)), int(step),
-                                                       step_dev, counter.data_ptr(), _lib.stream_ptr(dev)), "dss2_optim_step_flat")
+        _lib.check(_lib.lib().dss2_optim_step_flat(tab.data_ptr(), len(ps), max_n, base, C.byref(self._hyper(group)), int(step),
+                                                   step_dev, counter.data_ptr(), _lib.stream_ptr(dev)), "dss2_optim_step_flat")
         return True
 
     @torch.no_grad()
@@ -213,16 +203,14 @@ class _FusedOptimizer(torch.optim.Optimizer):
         # host-side descriptor table, passed to the kernels BY VALUE (no device copy to keep alive, capture-safe);
         # parameter and state addresses are written once, the gradient addresses every step (the flat gradient
         # buckets of the backward move)
-        legacy = self._legacy(group)
         cached = self._table.get(gi)
-        pkey = (tuple(p.data_ptr() for p in ps), legacy)
+        pkey = tuple(p.data_ptr() for p in ps)
         if cached is None or cached[1] != pkey:
-            tab = ((_lib.AdamaxDesc if legacy else _lib.OptimDesc) * len(ps))()
-            names = ("exp_avg", "exp_inf") if legacy else ("s0", "s1", "s2")
+            tab = (_lib.OptimDesc * len(ps))()
             for d, p in zip(tab, ps):
                 stp = self.state[p]
                 d.param, d.n = p.data_ptr(), p.numel()
-                for name, k in zip(names, self._slots(group)):
+                for name, k in zip(("s0", "s1", "s2"), self._slots(group)):
                     setattr(d, name, stp[k].data_ptr() if k is not None else None)
             cached = self._table[gi] = (tab, pkey)
             self.table_builds += 1
@@ -230,17 +218,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         for d, g in zip(tab, grads):
             d.grad = g.data_ptr()
         st = _lib.stream_ptr(dev)
-        if legacy:
-            b1, b2 = group["betas"]
-            if self.capturable:
-                _lib.check(_lib.lib().dss2_adamax_step_dev(C.addressof(tab), len(ps), float(group["lr"]), float(b1),
-                                                           float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                           shared.data_ptr(), st), "dss2_adamax_step_dev")
-            else:
-                _lib.check(_lib.lib().dss2_adamax_step(C.addressof(tab), len(ps), float(group["lr"]), float(b1),
-                                                       float(b2), float(group["eps"]), float(group["weight_decay"]), step, st),
-                           "dss2_adamax_step")
-        elif self.capturable:
+        if self.capturable:
             _lib.check(_lib.lib().dss2_optim_step_dev(C.addressof(tab), len(ps), C.byref(self._hyper(group)), shared.data_ptr(), st),
                        "dss2_optim_step_dev")
         else:
@@ -248,19 +226,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
 
 class FusedAdamax(_FusedOptimizer):
+    """``torch.optim.Adamax`` (state: step, exp_avg, exp_inf), the reference driver's optimizer."""
     _HIDE_FRESH = False      # (its checkpoints keep the zero state of init_state(), as they always have)
 
     def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable: bool = False):
         """capturable=True (as in torch's optimizers): the step count lives on the device, so ``step()`` may be captured
-        into a hipGraph together with forward + loss + backward (graphs.GraphedStep) and every replay advances it.
-        A float ``lr`` runs the dss2_adamax_step* launches; a tensor ``lr`` the same arithmetic in the shared kernel."""
+        into a hipGraph together with forward + loss + backward (graphs.GraphedStep) and every replay advances it."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), capturable)
 
     def _slots(self, group):
         return ("exp_avg", "exp_inf", None)
-
-    def _legacy(self, group) -> bool:
-        return not torch.is_tensor(group["lr"])
 
     def _hyper(self, group):
         b1, b2 = group["betas"]

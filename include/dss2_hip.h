@@ -59,7 +59,7 @@ int dss2_topology_probe(const int64_t* edge_index, int64_t n_edges, uint64_t* ou
  * structs and tables -- to the plan; dss2_plan_run(plan, stream) then re-issues the same launches, in order, on `stream`, from ONE  *
  * C call.  Same contract as a hipGraph replay: the recorded device pointers must stay valid (record the step on tensors that        *
  * live as long as the plan, e.g. inside a private memory pool), by-value scalars are frozen (use the device-side step counter of    *
- * dss2_adamax_step_flat / _dev and use_host_seed = 0 of dss2_rng_next, as under capture).  Only launches of this library are         *
+ * dss2_optim_step_flat / _dev and use_host_seed = 0 of dss2_rng_next, as under capture).  Only launches of this library are         *
  * recorded.  One plan records at a time (process-wide).  Every entry point that launches a STEP's work records itself (model, loss, *
  * dss2_get_pflow / dss2_eval_batch, dropout masks, optimizer, dss2_collate / dss2_collate_cursor, dss2_accum_scalar, and            *
  * dss2_csr_build_padded: the structure of a padded batch is a function of device data and part of the step); the entry              *
@@ -776,21 +776,6 @@ int dss2_collate_ragged_multi(const dss2_collate_desc* descs_host, int32_t n_cas
                               const int64_t* const* node_off, const int64_t* const* edge_off, const int64_t* count, int64_t e_total,
                               void* stream);
 
-/* ---- optimizer step (/root/reference/dss2_run.py:91-92,143: Adamax, lr 3e-3) ---
- * torch.optim.Adamax semantics on n_desc tensors, 96 tensors per launch.  descs_host: HOST array, passed to the kernels by
- * value (no descriptor copy, nothing to keep alive, safe inside a hipGraph capture).  `step` is the 1-based step count
- * (bias correction 1 - beta1^step).  grad pointers may be views of the flat gradient bucket the backward produces. */
-typedef struct dss2_adamax_desc {
-  float* param; const float* grad; float* exp_avg; float* exp_inf; int64_t n;
-} dss2_adamax_desc;
-
-int dss2_adamax_step(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps,
-                     float weight_decay, int step, void* stream);
-/* the same with the step count on the device (float, like torch's capturable optimizers): *step_dev is advanced by one and
- * then used for the bias correction, so the launches can be captured into a hipGraph with the rest of the step. */
-int dss2_adamax_step_dev(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps,
-                         float weight_decay, float* step_dev, void* stream);
-
 /* ---- whole-stack kernels ("keep a graph resident in LDS across all L blocks") -------------------
  * /root/reference/networks.py:340-388 (PFN / SkipPFN: PFN-L chained MPN / SkipMPN blocks on the same edge inputs) and
  * :212-338 (one block), for the reference driver's own model line (dss2_run.py:72-88: dim_hid 32, K = 2, 8 layers,
@@ -862,30 +847,27 @@ int dss2_stack_reduce(const dss2_stack_dims* dims, const float* slab, int32_t n_
                       const float* const* params, float* flat, float* fold_scratch, void* stream);
 int64_t dss2_stack_fold_scratch_floats(const dss2_stack_dims* dims);      /* size of fold_scratch (device floats) */
 
-/* The same update as ONE launch for any number of tensors whose gradients are views of ONE flat bucket (what every
- * backward of this library produces: networks._MPNFn / _PFNFn / stack._FusedStackFn): descs_dev is a DEVICE table that
- * holds, per tensor, the element offset of its gradient inside the bucket -- constant from step to step, so the table is
- * written once -- and grad_base, the bucket's address of THIS step, travels by value.  step >= 1: host-side step count;
- * step == 0: the count lives in *step_dev (float) and is advanced by the launch itself (its last workgroup to finish;
- * counter = one device word, zero before the first use), so the launch can be captured into a hipGraph. */
-typedef struct dss2_adamax_flat_desc {
-  float* param; int64_t grad_off; float* exp_avg; float* exp_inf; int64_t n;
-} dss2_adamax_flat_desc;
-int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev,
-                          uint32_t* counter, void* stream);
-
-/* ---- the other optimizers of torch.optim a user puts into the driver's `getattr(optim, NAME)` (dss2_run.py:91-92): Adam / AdamW,
- * RMSprop, SGD -- and Adamax once more, for a learning rate that lives on the device.  ONE multi-tensor kernel templated on the rule,
- * the arithmetic of torch's single-tensor path (foreach=False, fused=False) in fp32, in the three forms of the Adamax entry points
- * above: host table by value (dss2_optim_step, step >= 1 from the host), the same with the step count on the device (dss2_optim_step_dev:
- * *step_dev is advanced, then used), and the flat-bucket form with a device table (dss2_optim_step_flat: step == 0 -> the count lives in
- * *step_dev and the launch's last workgroup advances it).  State slots s0 / s1 / s2 (NULL where the rule does not use one):
+/* ---- optimizer step (/root/reference/dss2_run.py:91-92,143: Adamax, lr 3e-3, and the other optimizers of torch.optim
+ * a user puts into the driver's `getattr(optim, NAME)`: Adam / AdamW, RMSprop, SGD).  ONE multi-tensor kernel templated on the rule, the
+ * arithmetic of torch's single-tensor path (foreach=False, fused=False) in fp32, in three forms:
+ *   dss2_optim_step       descs_host: HOST array, passed to the kernels by value (no descriptor copy, nothing to keep alive, safe inside
+ *                         a hipGraph capture), 80 tensors per launch (80 x 48 B plus the hyper-parameters stay under 4 KB of kernel
+ *                         arguments).  `step` is the 1-based step count (bias corrections 1 - beta^step).  grad pointers may be views of
+ *                         the flat gradient bucket the backward produces.
+ *   dss2_optim_step_dev   the same with the step count on the device (float, like torch's capturable optimizers): *step_dev is advanced
+ *                         by one and then used, so the launches can be captured into a hipGraph with the rest of the step.
+ *   dss2_optim_step_flat  ONE launch for any number of tensors whose gradients are views of ONE flat bucket (what every backward of this
+ *                         library produces: networks._MPNFn / _PFNFn / stack._FusedStackFn): descs_dev is a DEVICE table that holds,
+ *                         per tensor, the element offset of its gradient inside the bucket -- constant from step to step, so the table
+ *                         is written once -- and grad_base, the bucket's address of THIS step, travels by value.  step >= 1: host-side
+ *                         step count; step == 0: the count lives in *step_dev (float) and is advanced by the launch itself (its last
+ *                         workgroup to finish; counter = one device word, zero before the first use), so the launch can be captured.
+ *                         max_n: the largest tensor's element count; n_desc <= 65535.
+ * State slots s0 / s1 / s2 (NULL where the rule does not use one):
  *   ADAM     exp_avg, exp_avg_sq, max_exp_avg_sq (AMSGRAD)        RMSPROP  square_avg, momentum_buffer (MOMENTUM), grad_avg (CENTERED)
- *   SGD      momentum_buffer (MOMENTUM)                           ADAMAX   exp_avg, exp_inf  (bit for bit dss2_adamax_step*)
+ *   SGD      momentum_buffer (MOMENTUM)                           ADAMAX   exp_avg, exp_inf
  * lr_dev != NULL: the learning rate is read from the device (a 0-dim fp32 tensor a scheduler fills in place) instead of `lr`, so a
- * recorded step -- hipGraph or launch plan -- follows a schedule.  A by-value table carries 80 descriptors per launch (80 x 48 B plus
- * the hyper-parameters stay under 4 KB of kernel arguments). */
+ * recorded step -- hipGraph or launch plan -- follows a schedule. */
 enum dss2_optim_rule { DSS2_OPT_ADAM = 0, DSS2_OPT_RMSPROP = 1, DSS2_OPT_SGD = 2, DSS2_OPT_ADAMAX = 3 };
 enum dss2_optim_flag {
   DSS2_OPT_AMSGRAD = 1,        /* ADAM: denominators from the running maximum of exp_avg_sq (slot 2) */
@@ -914,6 +896,26 @@ int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_op
 int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream);
 int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
                          const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream);
+
+/* Adamax with its own argument lists and 40-byte descriptors: ADAPTERS onto the three entry points above (rule DSS2_OPT_ADAMAX, the
+ * hyper-parameters as arguments, lr from the host), same kernels, same results bit for bit, same 80 tensors per by-value launch.
+ * The two by-value forms convert their table to dss2_optim_desc on the host, one allocation per call (a caller that minds it fills
+ * dss2_optim_desc and calls dss2_optim_step*); like there, a descriptor with n < 0 is refused as incomplete.
+ * dss2_adamax_step = dss2_optim_step, dss2_adamax_step_dev = dss2_optim_step_dev, dss2_adamax_step_flat = dss2_optim_step_flat (its
+ * DEVICE table stays in the layout below; the kernel reads either).  Errors name the entry point that was called. */
+typedef struct dss2_adamax_desc {
+  float* param; const float* grad; float* exp_avg; float* exp_inf; int64_t n;
+} dss2_adamax_desc;
+typedef struct dss2_adamax_flat_desc {
+  float* param; int64_t grad_off; float* exp_avg; float* exp_inf; int64_t n;
+} dss2_adamax_flat_desc;
+int dss2_adamax_step(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int step, void* stream);
+int dss2_adamax_step_dev(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float* step_dev, void* stream);
+int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev,
+                          uint32_t* counter, void* stream);
 
 /* ---- torch.nn.utils.clip_grad_norm_(parameters, max_norm) (2-norm, error_if_nonfinite=False) in two launches, deterministic.
  * The gradients are either a HOST table passed by value (descs_host, 192 tensors per launch: more tensors are more launches) or views

@@ -1,15 +1,17 @@
 """GPU: the recordable optimizers (optim.FusedAdam / FusedAdamW / FusedRMSprop / FusedSGD, a device-side learning rate, global-norm
 gradient clipping) -- the names a user puts into the driver's ``getattr(optim, NAME)`` (/root/reference/dss2_run.py:91-92).
 
-* parity over 5 steps against ``torch.optim`` on the CPU in fp64 (``foreach=False``) for 8 configurations x the 4 launch forms
+* parity over 5 steps against ``torch.optim`` on the CPU in fp64 (``foreach=False``) for 10 configurations x the 4 launch forms
   (separate gradients / flat bucket x host / device step count), parameters AND state; every run twice with equal bits;
-* ``FusedAdamax(lr=tensor)`` = ``FusedAdamax(lr=float)`` bit for bit in all forms;
+* ``FusedAdamax(lr=tensor)`` = ``FusedAdamax(lr=float)`` bit for bit in all forms; the ``dss2_adamax_step*`` exports (adapters that Python
+  no longer calls), driven through ctypes with hand-filled tables, = ``FusedAdamax`` bit for bit, and their refusals;
 * a tensor ``lr`` changed between replays of a hipGraph and of a launch plan gives the eager steps with those float rates, bit for bit;
   ``StepLR`` over three ``EpochTrainer`` epochs;
 * ``clip_grad_norm_``: norm and scaled gradients against fp64, untouched bits above the norm, both gradient layouts, more tensors than
   one by-value launch carries, equal bits twice, torch's non-finite behaviour, and a verified launch plan with clip + FusedAdam;
 * ``EpochTrainer`` / ``GraphedTrainer`` with ``max_grad_norm`` = the eager ``train_epoch`` bit for bit; constructing an ``EpochTrainer``
   leaves EVERY optimizer state tensor as it was."""
+import ctypes as C
 import importlib
 
 import pytest
@@ -30,9 +32,11 @@ ZERO_GRAD, TINY_GRAD = 2, 4                                                     
 # the same in all four forms -- torch fp32 / fused kernels:
 #   adam 2.25e-07 / 3.26e-07    adam_wd_amsgrad 2.26e-07 / 2.80e-07    adamw 3.64e-07 / 3.64e-07    rmsprop 1.85e-07 / 1.62e-07
 #   rmsprop_mom_centered_wd 2.75e-07 / 2.51e-07    sgd 1.50e-07 / 1.50e-07    sgd_mom_damp 2.17e-07 / 2.62e-07
-#   sgd_nesterov_wd 3.09e-07 / 2.45e-07
+#   sgd_nesterov_wd 3.09e-07 / 2.45e-07    adamax 1.67e-07 / 3.20e-07    adamax_wd 2.17e-07 / 3.90e-07
 # torch is under 1e-5 everywhere, so the default tolerance holds for every configuration.
 CONFIGS = {
+    "adamax": ("FusedAdamax", "Adamax", {}),
+    "adamax_wd": ("FusedAdamax", "Adamax", dict(weight_decay=0.01)),
     "adam": ("FusedAdam", "Adam", {}),
     "adam_wd_amsgrad": ("FusedAdam", "Adam", dict(weight_decay=0.01, amsgrad=True)),
     "adamw": ("FusedAdamW", "AdamW", dict(weight_decay=0.01)),
@@ -106,8 +110,8 @@ def _reference(cfg):
     return _REF[cfg]
 
 
-def _run_fused(pkg, cls, kw, flat, capturable, steps=STEPS, lr=None):
-    p0, grads = _data()
+def _run_fused(pkg, cls, kw, flat, capturable, steps=STEPS, lr=None, data=None):
+    p0, grads = data or _data()
     ps = [torch.nn.Parameter(p.to(DEV)) for p in p0]
     kw = dict(kw)
     if lr is not None:
@@ -156,6 +160,103 @@ def test_adamax_with_a_tensor_lr_equals_the_float_lr_kernels_bit_for_bit(pkg, fl
     assert len(a) == 3 * len(SHAPES)
     for i, (x, y) in enumerate(zip(a, b)):
         assert torch.equal(x, y), (i, (x - y).abs().max().item())
+
+
+# ---- the Adamax entry points of the header.  FusedAdamax runs dss2_optim_step*, so nothing in Python calls them any more: here they
+#      are called as a C user would, with hand-filled tables in their own 40-byte layouts.
+ADAPTER_SHAPES = [(1,), (3,), (33,), (2049,)] + [(7,)] * 96       # 100 tensors: crosses the by-value chunk of 80 (and the 96 of the former Adamax kernel)
+ADAPTER_STEPS = 3
+ADAPTER_HYPER = (3e-3, 0.9, 0.999, 1e-8, 0.01)                     # lr, beta1, beta2, eps, weight_decay
+_ADAPTER = {}
+
+
+def _adapter_data():
+    if "data" not in _ADAPTER:
+        g = torch.Generator().manual_seed(11)
+        p0 = [torch.randn(s, generator=g) for s in ADAPTER_SHAPES]
+        _ADAPTER["data"] = (p0, [[torch.randn(s, generator=g) for s in ADAPTER_SHAPES] for _ in range(ADAPTER_STEPS)])
+    return _ADAPTER["data"]
+
+
+def _adapter_reference(pkg, flat, capturable):
+    """FusedAdamax on the same data in the same form (the host and the device form their bias corrections separately), once."""
+    if (flat, capturable) not in _ADAPTER:
+        lr, b1, b2, eps, wd = ADAPTER_HYPER
+        _ADAPTER[flat, capturable] = _run_fused(pkg, "FusedAdamax", dict(betas=(b1, b2), eps=eps, weight_decay=wd), flat, capturable,
+                                                steps=ADAPTER_STEPS, lr=lr, data=_adapter_data())
+    return _ADAPTER[flat, capturable]
+
+
+@pytest.mark.parametrize("flat,capturable", FORMS, ids=FORM_IDS)
+def test_the_adamax_exports_equal_fused_adamax_bit_for_bit(pkg, flat, capturable):
+    L, st = pkg._lib.lib(), pkg._lib.stream_ptr(torch.device(DEV))
+    p0, grads = _adapter_data()
+    ps = [p.to(DEV) for p in p0]
+    avg, inf = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    n, sizes = len(ps), [p.numel() for p in ps]
+    step_dev = torch.zeros(1, dtype=torch.float32, device=DEV)
+    counter = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for k in range(ADAPTER_STEPS):
+        if flat:
+            bucket = torch.cat(grads[k]).to(DEV)
+            offs = [sum(sizes[:i]) for i in range(n)]
+            # dss2_adamax_flat_desc: param, grad_off, exp_avg, exp_inf, n
+            tab = torch.tensor([[p.data_ptr(), o, m.data_ptr(), u.data_ptr(), p.numel()] for p, o, m, u in zip(ps, offs, avg, inf)],
+                               dtype=torch.int64).to(DEV)
+            assert tab.shape == (n, 5) and tab.is_contiguous()
+            rc = L.dss2_adamax_step_flat(tab.data_ptr(), n, max(sizes), bucket.data_ptr(), *ADAPTER_HYPER, 0 if capturable else k + 1,
+                                         step_dev.data_ptr() if capturable else None, counter.data_ptr(), st)
+            pkg._lib.check(rc, "dss2_adamax_step_flat")
+        else:
+            gs = [g.to(DEV) for g in grads[k]]
+            tab = (pkg._lib.AdamaxDesc * n)()
+            assert C.sizeof(tab) == 40 * n
+            for d, p, g, m, u in zip(tab, ps, gs, avg, inf):
+                d.param, d.grad, d.exp_avg, d.exp_inf, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), u.data_ptr(), p.numel()
+            if capturable:
+                pkg._lib.check(L.dss2_adamax_step_dev(C.addressof(tab), n, *ADAPTER_HYPER, step_dev.data_ptr(), st), "dss2_adamax_step_dev")
+            else:
+                pkg._lib.check(L.dss2_adamax_step(C.addressof(tab), n, *ADAPTER_HYPER, k + 1, st), "dss2_adamax_step")
+    torch.cuda.synchronize()
+    if capturable:
+        assert float(step_dev) == ADAPTER_STEPS          # advanced by the launches themselves
+        if flat:
+            assert int(counter) == 0                     # the last workgroup to arrive left the arrival word at zero for the next launch
+    got = [p.cpu() for p in ps] + [t.cpu() for m, u in zip(avg, inf) for t in (m, u)]      # _collect's order: exp_avg, exp_inf per tensor
+    want = _adapter_reference(pkg, flat, capturable)
+    assert len(got) == len(want) == 3 * n
+    for i, (x, y) in enumerate(zip(got, want)):
+        assert torch.equal(x, y), (i, (x - y).abs().max().item())
+
+
+def test_the_adamax_exports_refuse_what_they_refused(pkg):
+    L, st = pkg._lib.lib(), pkg._lib.stream_ptr(torch.device(DEV))
+    p, g, m, u = (torch.zeros(4, device=DEV) for _ in range(4))
+    word = torch.zeros(2, dtype=torch.int32, device=DEV)
+    host = (pkg._lib.AdamaxDesc * 1)()
+    host[0].param, host[0].grad, host[0].exp_avg, host[0].exp_inf, host[0].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), u.data_ptr(), 4
+    holed = (pkg._lib.AdamaxDesc * 1)()
+    holed[0].param, holed[0].grad, holed[0].exp_avg, holed[0].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), 4
+    flat = torch.tensor([[p.data_ptr(), 0, m.data_ptr(), u.data_ptr(), 4]], dtype=torch.int64).to(DEV)
+    H, T, G, SD, CT = ADAPTER_HYPER, flat.data_ptr(), g.data_ptr(), word.data_ptr(), word.data_ptr() + 4
+    refused = [
+        ("adamax_step: ", lambda: L.dss2_adamax_step(None, 1, *H, 1, st)),                               # null table
+        ("adamax_step: ", lambda: L.dss2_adamax_step(C.addressof(host), 1, *H, 0, st)),                  # step < 1
+        ("adamax_step: ", lambda: L.dss2_adamax_step(C.addressof(holed), 1, *H, 1, st)),                 # a descriptor without exp_inf
+        ("adamax_step_dev: ", lambda: L.dss2_adamax_step_dev(None, 1, *H, SD, st)),
+        ("adamax_step_dev: ", lambda: L.dss2_adamax_step_dev(C.addressof(host), 1, *H, None, st)),
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(None, 1, 4, G, *H, 1, None, None, st)),
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(T, 1, 4, None, *H, 1, None, None, st)),
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(T, 65536, 4, G, *H, 1, None, None, st)),  # more rows than a grid has
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(T, 1, 4, G, *H, -1, SD, CT, st)),
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(T, 1, 4, G, *H, 0, None, CT, st)),        # step == 0 needs step_dev ...
+        ("adamax_step_flat: ", lambda: L.dss2_adamax_step_flat(T, 1, 4, G, *H, 0, SD, None, st)),        # ... and counter
+    ]
+    for i, (who, call) in enumerate(refused):
+        assert call() == 2, i
+        assert L.dss2_last_error().decode().startswith(who), (i, L.dss2_last_error())
+    torch.cuda.synchronize()
+    assert not p.any() and not m.any() and not u.any() and not word.any()      # nothing was launched
 
 
 # ---- device-side learning rate in recorded steps

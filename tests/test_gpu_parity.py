@@ -549,7 +549,7 @@ def test_hipgraph_replay_matches_eager(pkg, oracle):
 
 
 def test_fused_adamax_matches_torch(pkg):
-    """dss2_adamax_step vs torch.optim.Adamax (the reference's optimizer, dss2_run.py:91-92) on the same
+    """FusedAdamax vs torch.optim.Adamax (the reference's optimizer, dss2_run.py:91-92) on the same
     gradients for three steps; state keys are torch's."""
     torch.manual_seed(0)
     shapes = [(128, 22), (128,), (128, 128), (2, 128), (2,), (1,)]

@@ -4,7 +4,8 @@ B from argv, default 64).  Two modes:
   run   (under rocprofv3 --kernel-trace --output-format csv): builds the step graph and replays it 30 times;
   post <kernel_trace.csv>: prints, for the LAST replay, every kernel with its duration and the idle gap before it, and the
   totals (sum of kernel time, sum of gaps) -- what a launch-count reduction can win at this batch size."""
-import csv, importlib, os, sys
+import csv, importlib, os, re, sys
+OPTIMIZER_KERNELS = re.compile(r"\boptim(_flat)?_kernel\b")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 
 
@@ -49,12 +50,15 @@ def post(path):
     for cand in range(1, 400):        # kernels per step = distance between steps' first rng_next
         if len(idx) > 2 * cand and all(names[idx[-1 - cand] + j] == names[idx[-1 - 2 * cand] + j] for j in range(5)):
             pass
-    # simpler: steps are separated by the largest gaps; take the last 1/40 of the trace between two Adamax kernels
-    ad = [i for i, n in enumerate(names) if "adamax_kernel" in n or "adamax_flat_kernel" in n]
-    a0, a1 = ad[-2], ad[-1]
-    # several adamax launches per step may exist: walk back to the previous step's last adamax
+    # simpler: a step ends with the optimizer's launch (FusedAdamax: a rule of dss2::optim_kernel / optim_flat_kernel); take the
+    # last step, between two of them
+    ad = [i for i, n in enumerate(names) if OPTIMIZER_KERNELS.search(n)]
+    # several optimizer launches per step may exist: walk back to the previous step's last one
     j = len(ad) - 1
     while j > 0 and ad[j] - ad[j - 1] < 5: j -= 1
+    if j < 1:       # (a renamed kernel must not yield an empty or a wrong slice)
+        sys.exit(f"{path}: {len(ad)} launches match {OPTIMIZER_KERNELS.pattern!r}, not the two steps' worth needed to cut out a step; "
+                 f"kernels in the trace: {sorted(set(n.split('(')[0] for n in names))}")
     a1 = ad[-1]; a0 = ad[j - 1]
     step = rows[a0 + 1:a1 + 1]
     t_prev = int(rows[a0]["End_Timestamp"])
