@@ -154,9 +154,7 @@ class DeviceDataset:
                       (self.y, y, self.n * self.y.size(2), 0)], ids, B)
         ei = self.batch_edge_index(B, ids)
         if self.shared_topology:
-            # the batch edge_index of this size is one cached tensor: its structure is built (and attached) once
-            if _topology._last.get((id(ei), "ref")) is None:
-                _topology.register_topology(ei, B * self.n, _topology.Topology(ei, B * self.n, hint=self.hint()))
+            self._attached_structure(ei, B)
         # (samples with individual edge lists: the first graph of the batch decides the doubling rule, which the host
         #  would have to read back; those batches take the cached / probed path of topology.get_topology)
         return Batch(x, ei, ea, y, B)
@@ -193,9 +191,14 @@ class DeviceDataset:
         if not self.shared_topology:
             raise ValueError("batch_structure: the samples have individual edge lists (use DataLoader / PrefetchLoader)")
         ei = self.batch_edge_index(B, self.ids[:1])
-        if _topology._last.get((id(ei), "ref")) is None:
-            _topology.register_topology(ei, B * self.n, _topology.Topology(ei, B * self.n, hint=self.hint()))
-        return ei, _topology.get_topology(ei, B * self.n)
+        return ei, self._attached_structure(ei, B)
+
+    def _attached_structure(self, ei: torch.Tensor, B: int) -> "_topology.Topology":
+        """Single-topology datasets: the batch edge_index of a size is one cached tensor, its structure is built (and attached) once."""
+        topo = _topology.attached_topology(ei, B * self.n)
+        if topo is None:
+            topo = _topology.register_topology(ei, B * self.n, _topology.Topology(ei, B * self.n, hint=self.hint()))
+        return topo
 
     @classmethod
     def from_batch(cls, batch: Dict[str, object], device=None) -> "DeviceDataset":

@@ -256,7 +256,7 @@ def structure(name):
 
 
 def _tiling(o):
-    """topology.Tiling with the oracle's arrays (on the CPU), filled as Topology._build_tiles fills it."""
+    """topology.Tiling with the oracle's arrays (on the CPU), filled as Topology._launch_tiles fills it."""
     if o is None:
         return None
     tm, seg = 32 * o.nrb, [b - a for a, b in zip(o.bounds[:-1], o.bounds[1:])]

@@ -208,6 +208,31 @@ def test_one_launch_build_of_equal_size_graphs_equals_the_oracle(pkg, grids, B, 
         t_bad.stats()
 
 
+@pytest.mark.parametrize("hinted", [True, False], ids=["hint", "walked"])
+def test_alternate_tilings_of_hub_graphs_leave_the_primary_statistics_alone(pkg, hinted):
+    """16 stars of 12 nodes (degree 11: no ELL slices either way), a 96-row primary and alternates of 32, 64 and 192 rows: the 16
+    statistic words stay the PRIMARY's (its 176 entries per tile, not the 352 of the 192-row alternate), its arrays stay what they
+    were, and every tiling is the oracle's at its height.  With a hint the alternates are closed-form and have no ELL launch at all;
+    without one they are walked on a private copy of the words."""
+    ei, N = _stars(16, 11)
+    hint = pkg.topology.TopologyHint(directed=True, nodes_per_graph=12, max_degree=11, max_edges_per_graph=11, edges_per_graph=11) if hinted else None
+    topo = pkg.topology.Topology(ei.to(DEV), N, hint=hint)
+    primary = topo.tiling
+    stats = dict(topo.stats())
+    assert (primary.nrb, stats["max_nnz"], stats["max_nnzT"]) == (3, 176, 176)
+    before = primary.tile_start.clone()
+    tilings = {3: primary, **{h: topo.tiles_for(h) for h in (1, 2, 6)}}
+    torch.cuda.synchronize()
+    assert topo._read_stats(topo._meta) == stats and topo.stats() == stats
+    assert topo.tiling is primary and torch.equal(primary.tile_start, before) and primary.ell_tiles is None and primary.ellT_tiles is None
+    for h, ts in tilings.items():
+        ref = topo_oracle.TopologyOracle(ei, N, nrb=h)
+        assert (ts.global_only, ts.nrb, ts.ntiles, ts.ell, ts.ellT) == (False, ref.nrb, ref.ntiles, 0, 0), h
+        _same(ts.tile_start, ref.tile_start, f"tile_start at nrb {h}")
+        assert ts.max_nnz >= ref.max_nnz and ts.max_nnzT >= ref.max_nnzT, h
+    _check(topo, topo_oracle.TopologyOracle(ei, N))
+
+
 def _padded(pkg, grid, G, slack=1):
     """(padded Topology, unpadded edge_index, N, map of the oracle's ELL entry tiles to the padded slots' ids): every graph of ``grid`` with
     ``slack`` padding slots behind its edges."""
