@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from loss_cases import pinned_branches
 from conftest import ROOT, CASES, LOSS_CASES, case_batch, case_grads, case_state_dict, golden, load_pkg, rel_err, t
 
 pytestmark = pytest.mark.gpu
@@ -378,20 +379,9 @@ def test_baseline_configs_against_oracle(pkg, oracle, grids, B, hid, L):
     # edge forward was exactly this gate, flipped by a 3e-8 change of one theta).  Like the conv gates, the loss's
     # branch decisions -- the four penalty ReLUs and max(I_from, I_to) (data.py:387-388) -- are therefore pinned to
     # the HIP path's own choices, read from the flows the loss kernel exported; all VALUES stay un-pinned.
-    vhv, vlv = b["x"][:, 8].max(), b["x"][:, 8].min()
-    om = out_m.detach().cpu()                                  # (theta already masked in place by the loss)
-    v_m = om[:, 0:1] * b["stats"][1][:1] + b["stats"][0][:1]
-    thij_m = (om[b["edge_index"][0], 1] - om[b["edge_index"][1], 1]).abs()
-    fm = flows_m.cpu()
-    max_pins = iter([fm[:, 6] >= fm[:, 7], fm[:, 6] * vhv >= fm[:, 7] * vlv])
-    relu_pins = iter([v_m > 1.1, v_m < 0.9, thij_m > 0.5, (fm[:, 0] + fm[:, 1]) > 1.5])
-    real_max, real_relu = torch.maximum, torch.relu
-    torch.maximum = lambda a_, b_: torch.where(next(max_pins), a_, b_)
-    torch.relu = lambda t_: t_ * next(relu_pins).to(t_.dtype)
-    try:
+    # (tests/loss_cases.py: pinned_branches; theta of out_m is already masked in place by the loss)
+    with pinned_branches(out_m, flows_m, b["x"], b["stats"], b["edge_index"]):
         loss64 = _referee_loss(oracle, x64, ea64, out64, st64, b["edge_index"])
-    finally:
-        torch.maximum, torch.relu = real_max, real_relu
     with torch.no_grad():
         loss64_unpinned = _referee_loss(oracle, x64, ea64, out64.detach().clone(), st64, b["edge_index"])
     assert abs(loss64.item() - loss64_unpinned.item()) <= 1e-9 * abs(loss64.item())     # the pins only decide near-ties
