@@ -8,6 +8,7 @@ from . import _lib, flags, synthetic, topology  # noqa: F401
 from . import ops, plans, route  # noqa: F401
 from . import networks, data, parallel, graphs, optim, dataset  # noqa: F401
 from .optim import FusedAdamax, FusedAdam, FusedAdamW, FusedRMSprop, FusedSGD  # noqa: F401
+from . import estimator  # noqa: F401
 from . import runner, multi  # noqa: F401
 from .multi import MaskEmbdMPN, MultiMPN, MaskEmbdMultiMPN, MaskEmbdMultiMPN_NoMP, EdgeAggregationGeneral  # noqa: F401
 from .networks import EdgeAggregation, TAGConv, MPN, SkipMPN, PFN, SkipPFN, MessagePassing  # noqa: F401
@@ -16,8 +17,9 @@ from .gine import GINEConv, GINE_DSSE  # noqa: F401
 from .gnn import GCN2Conv, FAConv, gnn_dsse  # noqa: F401
 from .cheb import ChebConv, WrappedMultiConv, MultiConvNet  # noqa: F401
 from .data import gsp_wls_edge, get_pflow  # noqa: F401
+from .estimator import wls_estimate, WLSResult  # noqa: F401
 from .dataset import data_from_pickles, DataLoader, DeviceDataset, MixedDataset  # noqa: F401
 
 __all__ = ["MaskEmbdMPN", "MultiMPN", "MaskEmbdMultiMPN", "MaskEmbdMultiMPN_NoMP", "EdgeAggregationGeneral", "EdgeAggregation", "TAGConv", "MPN", "SkipMPN", "PFN", "SkipPFN", "MessagePassing", "GATv2Conv", "GAT_DSSE", "GINEConv", "GINE_DSSE", "GCN2Conv", "FAConv", "gnn_dsse", "ChebConv", "WrappedMultiConv", "MultiConvNet",
-           "gsp_wls_edge", "get_pflow", "data_from_pickles", "DataLoader", "DeviceDataset", "MixedDataset", "FusedAdamax", "FusedAdam", "FusedAdamW", "FusedRMSprop", "FusedSGD", "dataset", "networks", "data", "parallel", "graphs", "optim", "synthetic",
+           "gsp_wls_edge", "get_pflow", "wls_estimate", "WLSResult", "estimator", "data_from_pickles", "DataLoader", "DeviceDataset", "MixedDataset", "FusedAdamax", "FusedAdam", "FusedAdamW", "FusedRMSprop", "FusedSGD", "dataset", "networks", "data", "parallel", "graphs", "optim", "synthetic",
            "topology", "flags", "ops", "plans", "gat", "gine", "gnn", "cheb"]

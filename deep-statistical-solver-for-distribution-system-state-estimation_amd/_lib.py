@@ -197,6 +197,18 @@ class SgemmDesc(C.Structure):
                 ("accumulate", C.c_int32)]
 
 
+class WlsSolveArgs(C.Structure):
+    """dss2_wls_solve_args (include/dss2_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("edge_attr", C.c_void_p), ("ldea", C.c_int64),
+                ("x_mean", C.c_void_p), ("x_std", C.c_void_p), ("edge_mean", C.c_void_p), ("edge_std", C.c_void_p),
+                ("efrom", C.c_void_p), ("eto", C.c_void_p), ("inc_rowptr", C.c_void_p), ("inc_ent", C.c_void_p),
+                ("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("nodes_per_graph", C.c_int32), ("max_iter", C.c_int32),
+                ("tol", C.c_double), ("w_v", C.c_double), ("w_p", C.c_double), ("w_pf", C.c_double),
+                ("init", C.c_void_p), ("ld_init", C.c_int64), ("state", C.c_void_p), ("objective", C.c_void_p),
+                ("iterations", C.c_void_p), ("status", C.c_void_p), ("last_step", C.c_void_p), ("vminmax", C.c_void_p),
+                ("max_groups", C.c_int32), ("pad_", C.c_int32)]
+
+
 class WlsArgs(C.Structure):
     _fields_ = [("input", C.c_void_p), ("ld_in", C.c_int64),
                 ("edge_input", C.c_void_p), ("ld_ein", C.c_int64),
@@ -418,6 +430,8 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dss2_eval_scratch_doubles": (C.c_int64, []),
+    "dss2_wls_solve": (C.c_int, [C.POINTER(WlsSolveArgs), C.c_void_p]),
+    "dss2_wls_solve_lds_bytes": (C.c_size_t, [C.c_int]),
     "dss2_small_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dss2_measure_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),

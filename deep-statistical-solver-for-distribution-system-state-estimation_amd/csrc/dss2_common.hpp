@@ -199,6 +199,21 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 constexpr int kMaxLdsBytes = 160 * 1024;
 
+// ---- batch-global min / max of vn_kv (csrc/dss2_loss.hip): vminmax_kernel leaves 64 partial (min, max) pairs at vmm[2 + 2 b],
+// vmm[3 + 2 b]; every consumer wave folds them itself with a butterfly -- one coalesced load and twelve cross-lane ops instead
+// of a kernel launch of its own.  All 64 lanes of the wave must be active.
+void launch_vminmax(const float* node_param, int64_t ld_np, int64_t n_nodes, float* vminmax, hipStream_t s);
+__device__ __forceinline__ void vminmax_fold(const float* __restrict__ vmm, float& vlv, float& vhv) {
+  const int lane = threadIdx.x & 63;
+  float lo = vmm[2 + 2 * lane], hi = vmm[3 + 2 * lane];
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  vlv = lo;
+  vhv = hi;
+}
+
 // ---- in-kernel dropout (nn.Dropout between the TAGConv layers, /root/reference/networks.py:268) ---------------------------
 // Counter-based: the keep/drop decision of element (row, col) of layer `id` is a pure function of (seed, offset, id, row,
 // col), so the forward epilogue and the backward epilogue regenerate the same mask instead of storing and re-reading an

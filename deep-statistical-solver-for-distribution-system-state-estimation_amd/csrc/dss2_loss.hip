@@ -80,17 +80,11 @@ __global__ void __launch_bounds__(256) vminmax_kernel(const float* __restrict__ 
   }
 }
 
-// Stage 2 is done by the consumers themselves: every wave folds the VMM_BLOCKS (= 64, one per lane) partial pairs
-// with a butterfly -- one coalesced load and twelve cross-lane ops instead of a kernel launch of its own.
-__device__ __forceinline__ void vminmax_fold(const float* __restrict__ vmm, float& vlv, float& vhv) {
-  const int lane = threadIdx.x & 63;
-  float lo = vmm[2 + 2 * lane], hi = vmm[3 + 2 * lane];
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  vlv = lo;
-  vhv = hi;
+// Stage 2 is done by the consumers themselves (vminmax_fold, dss2_common.hpp).
+
+// stage 1 for consumers in other translation units (csrc/dss2_wls_solve.hip)
+void launch_vminmax(const float* node_param, int64_t ld_np, int64_t n_nodes, float* vminmax, hipStream_t s) {
+  hipLaunchKernelGGL(vminmax_kernel, dim3(VMM_BLOCKS), dim3(256), 0, s, node_param, ld_np, n_nodes, vminmax);
 }
 
 struct NodeMeas { float Z[4], R[4]; };

@@ -281,3 +281,16 @@ def eval_batch(out, y, x, edge_index, edge_attr, x_mean, x_std, acc: torch.Tenso
                                  yhat.data_ptr(), pft.data_ptr(), pfo.data_ptr(), vmm.data_ptr(), scratch.data_ptr(),
                                  acc.data_ptr(), _stream(out)), "dss2_eval_batch")
     return yhat
+
+
+_UNIT_STATS: Dict[str, tuple] = {}
+
+
+def _eval_state_batch(state, y, x, edge_index, edge_attr, acc: torch.Tensor) -> torch.Tensor:
+    """``eval_batch`` for a state that is physical already (v in p.u., theta in rad, 0 at slack buses: what ``estimator.wls_estimate``
+    returns): the same evaluation kernels with the identity in place of the de-normalisation (v * 1 + 0 is exact in fp32)."""
+    key = str(state.device)
+    if key not in _UNIT_STATS:
+        _UNIT_STATS[key] = (torch.zeros(1, dtype=_F32, device=state.device), torch.ones(1, dtype=_F32, device=state.device))
+    zero, one = _UNIT_STATS[key]
+    return eval_batch(state, y, x, edge_index, edge_attr, zero, one, acc)

@@ -332,6 +332,37 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
     return dict(zip(dss2_data.EVAL_METRICS, vals))
 
 
+@torch.no_grad()
+def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, **solver_kw) -> Dict[str, float]:
+    """The classical WLS estimator (``estimator.wls_estimate``) over a loader, scored like ``evaluate``: the ten EVAL_METRICS of its
+    state, averaged over the batches, plus ``wls_mean_iterations`` (Gauss-Newton updates per graph) and ``wls_not_converged`` (graphs
+    that did not end with status 0).  ``model`` None: a flat start, the baseline a learned estimator is compared with; a model: its
+    de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  One device-to-host copy."""
+    from . import estimator
+    dev = stats[0].device
+    acc = torch.zeros(10, dtype=torch.float64, device=dev)
+    tally = torch.zeros(3, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged
+    n = 0
+    if model is not None:
+        model.eval()
+    for data in loader:
+        x, ei, ea, y, _ = _fields(data)
+        init = None
+        if model is not None:
+            out = run_model(model, x[:, :8], ei, ea[:, :6])
+            init = torch.stack([out[:, 0] * stats[1][0] + stats[0][0], out[:, 1]], 1)
+        res = estimator.wls_estimate(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
+        dss2_data._eval_state_batch(res.state, y, x, ei, ea, acc)
+        tally += torch.stack([res.iterations.sum(), torch.tensor(res.iterations.numel(), device=dev), (res.status != 0).sum()]).double()
+        n += 1
+    vals = (acc / max(n, 1)).cpu().tolist()
+    its, graphs, bad = tally.cpu().tolist()
+    m = dict(zip(dss2_data.EVAL_METRICS, vals))
+    m["wls_mean_iterations"] = its / max(graphs, 1.0)
+    m["wls_not_converged"] = int(bad)
+    return m
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", default="cigre14", help="cigre14, cigre14_reswitched, ober_sub or ober179; or a comma-separated list of cases on one "
@@ -354,6 +385,8 @@ def main(argv=None):
     ap.add_argument("--data-folder", default="", help="folder with the reference's pickles (nodes, edges, labels, noise_param)")
     ap.add_argument("--graph", type=int, default=-1, help="1: replay the training step as a hipGraph (GraphedTrainer; needs ONE graph "
                     "structure per batch shape), 0: eager, -1 (default): graph when the data has a single topology")
+    ap.add_argument("--wls-baseline", action="store_true", help="after training, print the evaluation metrics of the classical WLS "
+                    "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); needs one bus count")
     a = ap.parse_args(argv)
     hp = {k: getattr(a, k) for k in HYPER}
     if a.model == "SkipMPN":
@@ -419,6 +452,14 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(f"epoch {epoch:4d}  train_loss {tl:.6g}  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()) +
               f"  ({time.perf_counter() - t0:.2f} s)", flush=True)
+    if a.wls_baseline:
+        ds = getattr(test_loader, "dataset", None)
+        n_bus = getattr(ds, "n", None) if ds is not None else synthetic.load_grid(a.case).n
+        if n_bus is None:
+            raise ValueError("--wls-baseline needs one bus count per graph (the data list mixes bus counts)")
+        for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
+            m = evaluate_wls(test_loader, stats, n_bus, model=start)
+            print(f"wls baseline ({label})  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()), flush=True)
     if a.save:                                                       # dss2_run.py:240-247
         torch.save({"epoch": a.epochs - 1, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},
                    a.save)

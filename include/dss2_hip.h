@@ -694,6 +694,43 @@ int dss2_eval_batch(const float* out, int64_t ldo, const float* y, int64_t ldy, 
                     float* pf_true, float* pf_out, float* vminmax, double* scratch, double* acc, void* stream);
 int64_t dss2_eval_scratch_doubles(void);
 
+/* ---- batched weighted-least-squares state estimation: Gauss-Newton on the normal equations, fp64, ONE launch per solve
+ *      (csrc/dss2_wls_solve.hip).  The measurement model is gsp_wls_edge's: per bus z = (V, theta, P_inj, Q_inj) with weights R^-1
+ *      (x[:, 0:8]), per stored branch (P_from, Q_from) (edge_attr[:, 0:4]), de-normalised in fp64 where the normalised entry is
+ *      non-zero (a de-normalised weight below 0 counts as 0); h(u) as data.py:370-376, 428-435 with shift = 0 and V_lv the batch
+ *      minimum of x[:, 8].  Graph g owns buses [g n, (g + 1) n), n = nodes_per_graph; edges never cross graphs.  Per graph
+ *          J(u) = sum_buses sum_k c_k R^-1 (z - h)^2 + sum_branches sum_k w_pf R_edge^-1 (z_edge - h_edge)^2,  c = (w_v, w_v, w_p, w_p)
+ *      is minimised from `init` [N, 2] = (v in p.u., theta in rad), or from v = 1, theta = 0 (init = NULL); theta at slack buses
+ *      (x[:, 9] != 0) is 0 and stays 0.  Each of at most max_iter iterations forms G = H^T W H and b = H^T W r with the analytic
+ *      Jacobian, replaces the slack angles' rows and columns by the identity, factorises G (Cholesky) and applies du = G^-1 b;
+ *      a pivot <= 0 or not finite, or a step that is not finite, ends the graph with status 2 and the state of the previous
+ *      iterate; max |du| < tol ends it with status 0; status 1 = max_iter reached (tol = 0 never stops early).
+ *      One workgroup per graph with the packed gain matrix in LDS: nodes_per_graph is capped by dss2_wls_solve_lds_bytes(n) <= 160 KiB
+ *      (rc 2 above it).  No atomics and a fixed summation order: two runs agree to the bit.  Allocates nothing, never synchronises. */
+typedef struct dss2_wls_solve_args {
+  const float* x; int64_t ldx;                    /* [N, >= 10] node tensor: 8 measurement columns, vn_kv, slack flag            */
+  const float* edge_attr; int64_t ldea;           /* [E, >= 10] edge tensor: 4 measurement columns, 2 unused, G, B, Gs, Bs       */
+  const float* x_mean; const float* x_std;        /* [8]                                                                          */
+  const float* edge_mean; const float* edge_std;  /* [>= 4]                                                                       */
+  const int32_t* efrom; const int32_t* eto;       /* [E] stored edge endpoints                                                    */
+  const int32_t* inc_rowptr; const int32_t* inc_ent; /* incidence CSR as in dss2_wls_args                                         */
+  int64_t n_nodes; int64_t n_edges;
+  int32_t nodes_per_graph; int32_t max_iter;
+  double tol;
+  double w_v, w_p, w_pf;
+  const float* init; int64_t ld_init;             /* [N, >= 2] start in physical units, or NULL = flat start                      */
+  float* state;                                   /* [N, 2]  (v, theta), contiguous                                               */
+  double* objective;                              /* [G, 2]  bus part and branch part of J at the final fp64 state               */
+  int32_t* iterations;                            /* [G]     updates applied                                                      */
+  int32_t* status;                                /* [G]     0 converged, 1 max_iter reached, 2 factorisation failed             */
+  double* last_step;                              /* [G]     max |du| of the last update applied (0 if none)                      */
+  float* vminmax;                                 /* [130] device scratch                                                         */
+  int32_t max_groups; int32_t pad_;               /* > 0: at most this many workgroups (they stride over the graphs); 0: the library's choice */
+} dss2_wls_solve_args;
+int dss2_wls_solve(const dss2_wls_solve_args* args_host, void* stream);
+/* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic) */
+size_t dss2_wls_solve_lds_bytes(int nodes_per_graph);
+
 /* ---- batched small dense products in weight space (folding the edge MLP's second Linear into conv 0
  *      and the chain rule back): C[M,N] (+)= sum_b op(A_b)[M,K] . op(B_b)[K,N]  (+ u[i] * v[j]).     */
 typedef struct dss2_sgemm_desc {
