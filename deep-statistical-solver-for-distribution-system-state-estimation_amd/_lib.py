@@ -209,6 +209,15 @@ class WlsSolveArgs(C.Structure):
                 ("max_groups", C.c_int32), ("pad_", C.c_int32)]
 
 
+class WlsBadDataArgs(C.Structure):
+    """dss2_wls_bad_data_args (include/dss2_hip.h)."""
+    _fields_ = [("solve", WlsSolveArgs), ("threshold", C.c_double), ("z_p", C.c_double), ("s_min", C.c_double),
+                ("max_removals", C.c_int32), ("pad_", C.c_int32), ("dof", C.c_void_p), ("chi2_limit", C.c_void_p),
+                ("suspect", C.c_void_p), ("removed", C.c_void_p), ("removed_rn", C.c_void_p), ("n_removed", C.c_void_p),
+                ("bus_rn", C.c_void_p), ("bus_sens", C.c_void_p), ("edge_rn", C.c_void_p), ("edge_sens", C.c_void_p),
+                ("state_std", C.c_void_p)]
+
+
 class WlsArgs(C.Structure):
     _fields_ = [("input", C.c_void_p), ("ld_in", C.c_int64),
                 ("edge_input", C.c_void_p), ("ld_ein", C.c_int64),
@@ -432,6 +441,8 @@ _SIGNATURES = {
     "dss2_eval_scratch_doubles": (C.c_int64, []),
     "dss2_wls_solve": (C.c_int, [C.POINTER(WlsSolveArgs), C.c_void_p]),
     "dss2_wls_solve_lds_bytes": (C.c_size_t, [C.c_int]),
+    "dss2_wls_bad_data": (C.c_int, [C.POINTER(WlsBadDataArgs), C.c_void_p]),
+    "dss2_wls_bad_data_lds_bytes": (C.c_size_t, [C.c_int]),
     "dss2_small_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dss2_measure_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,0 +1,363 @@
+// Device functions of the batched fp64 WLS estimator that its kernels share: csrc/dss2_wls_solve.hip (the solve alone) and
+// csrc/dss2_wls_bad_data.hip (the solve, the covariance, normalized residuals and the removal loop).  The LDS layout, the row
+// ownership and the order of every sum are described in the header of dss2_wls_solve.hip; nothing here depends on which kernel runs it.
+//
+// Every function that reads measurements takes a MASK: mask(id) says whether measurement `id` has been removed (its weight is then 0
+// everywhere it enters).  Ids are 4 i + k for bus i (global row), k in V, theta, P, Q, and 4 N + 2 e + k for stored branch e, k in
+// P_from, Q_from.  WsNoMask removes nothing and compiles to nothing; WsRemoved looks the id up in a short list in LDS.
+#pragma once
+#include "dss2_common.hpp"
+
+namespace dss2 {
+
+constexpr int WS_TX = 16;          // trailing update: 16 columns x (T / 16) rows of threads
+
+// LDS carve (bytes from the 16-byte aligned dynamic base), shared by the kernels and dss2_wls_solve_lds_bytes
+__host__ __device__ inline size_t ws_doubles(int n) { const size_t ns = 2 * (size_t)n; return ns * (ns + 1) / 2 + 3 * ns; }
+__host__ __device__ inline size_t ws_ctl_off(int n) { return (ws_doubles(n) * 8 + 15) / 16 * 16; }
+__host__ __device__ inline size_t ws_slk_off(int n) { return ws_ctl_off(n) + 16; }
+__host__ __device__ inline size_t ws_bytes(int n) { return ws_slk_off(n) + ((size_t)n + 15) / 16 * 16; }
+
+struct WsNoMask {
+  __device__ __forceinline__ bool operator()(int) const { return false; }
+};
+struct WsRemoved {                  // the ids removed so far: n of them, in LDS
+  const int* ids;
+  int n;
+  __device__ __forceinline__ bool operator()(int id) const {
+    bool hit = false;
+    for (int q = 0; q < n; ++q) hit = hit || ids[q] == id;
+    return hit;
+  }
+};
+
+// One end's view of a branch: the active and reactive power entering the branch at `self`, and their derivatives with respect to
+// (v_self, theta_self, v_other, theta_other).  With delta = theta_self - theta_other this is data.py:370-373 at the from-end and
+// data.py:374-376 at the to-end (cos is even, sin is odd).
+struct WsBranch { double p, q, dp[4], dq[4]; };
+
+__device__ __forceinline__ WsBranch ws_branch(double vs, double ts, double vo, double to, const float* __restrict__ ep, double kk) {
+  const double G = ep[0], B = ep[1], gg = G + (double)ep[2] / 2.0, bb = B + (double)ep[3] / 2.0;
+  double s, c;
+  sincos(ts - to, &s, &c);
+  const double A = G * c + B * s, Q = -G * s + B * c, vv = vs * vo;
+  WsBranch f;
+  f.p = (-vv * A + gg * (vs * vs)) * kk;
+  f.q = (vv * Q - bb * (vs * vs)) * kk;
+  f.dp[0] = (-vo * A + 2.0 * gg * vs) * kk; f.dp[1] = -vv * Q * kk; f.dp[2] = -vs * A * kk; f.dp[3] = vv * Q * kk;
+  f.dq[0] = (vo * Q - 2.0 * bb * vs) * kk;  f.dq[1] = -vv * A * kk; f.dq[2] = vs * Q * kk;  f.dq[3] = vv * A * kk;
+  return f;
+}
+
+// double(z) * double(std) + double(mean) where the normalised entry is non-zero, else 0; a weight below 0 counts as 0, and so does
+// the weight of a removed measurement (ids id0, id0 + 1, ... in the order of the pairs)
+template <int PAIRS, class Mask>
+__device__ __forceinline__ void ws_meas(const float* __restrict__ in, const float* __restrict__ mean, const float* __restrict__ stdv,
+                                        double (&Z)[PAIRS], double (&R)[PAIRS], const Mask& mask, int id0) {
+#pragma unroll
+  for (int c = 0; c < PAIRS; ++c) {
+    const float z = in[2 * c], r = in[2 * c + 1];
+    Z[c] = (z != 0.f) ? (double)z * (double)stdv[2 * c] + (double)mean[2 * c] : 0.0;
+    const double w = (r != 0.f) ? (double)r * (double)stdv[2 * c + 1] + (double)mean[2 * c + 1] : 0.0;
+    R[c] = w < 0.0 ? 0.0 : w;
+    if (mask(id0 + c)) R[c] = 0.0;
+  }
+}
+__device__ __forceinline__ int ws_bus_id(int64_t gi) { return (int)(4 * gi); }
+__device__ __forceinline__ int ws_edge_id(const dss2_wls_solve_args& a, int e) { return (int)(4 * a.n_nodes + 2 * (int64_t)e); }
+
+struct WsGraph {                    // what the row owners need of the graph being solved
+  int64_t base;                     // first bus
+  int n;
+  double kk;                        // V_lv^2
+  const double* u;                  // LDS state
+  const unsigned char* slk;         // LDS slack flags
+};
+
+// incidence entry k -> stored branch, the other end's LOCAL bus (outside [0, n): an edge that leaves the graph, ignored), orientation
+__device__ __forceinline__ bool ws_slot(const dss2_wls_solve_args& a, const WsGraph& g, int k, int& e, int& lo, bool& is_from) {
+  const int en = a.inc_ent[k];
+  e = en & 0x7fffffff;
+  is_from = en >= 0;
+  lo = (int)((int64_t)(is_from ? a.eto : a.efrom)[e] - g.base);
+  return (unsigned)lo < (unsigned)g.n;
+}
+
+__device__ __forceinline__ void ws_add(double* __restrict__ row, int r, const unsigned char* slk, int c, double v) {
+  if (c <= r && !((c & 1) && slk[c >> 1])) row[c] += v;
+}
+
+// Row r of G and b[r]: every measurement with a non-zero Jacobian entry at state r, in a fixed order.
+template <class Mask>
+__device__ __forceinline__ void ws_accumulate_row(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ Gp, int ns,
+                                                  const Mask& mask) {
+  double* row = Gp + (size_t)r * (r + 1) / 2;
+  double* bvec = Gp + (size_t)ns * (ns + 1) / 2;
+  const int li = r >> 1, c = r & 1;
+  if (c && g.slk[li]) { row[r] = 1.0; bvec[r] = 0.0; return; }     // a slack angle: identity row, held at 0
+  const int64_t gi = g.base + li;
+  double accb = 0.0;
+  {   // the bus's own V (c = 0) or theta (c = 1)
+    double Z[4], R[4];
+    ws_meas(a.x + gi * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gi));
+    const double w = a.w_v * (c ? R[1] : R[0]);
+    row[r] += w;
+    accb += w * ((c ? Z[1] : Z[0]) - g.u[r]);
+  }
+  const int k0 = a.inc_rowptr[gi], k1 = a.inc_rowptr[gi + 1];
+  // the injections of bus i itself (k = k0 - 1) and of every neighbour, and the flow measurement of every incident branch
+  for (int k = k0 - 1; k < k1; ++k) {
+    int lj = li;
+    if (k >= k0) {
+      int e, lo; bool is_from;
+      if (!ws_slot(a, g, k, e, lo, is_from)) continue;
+      lj = lo;
+      if (!(lo == li && !is_from)) {     // (a branch from a bus to itself is listed twice: its flow is taken once)
+        const int lf = is_from ? li : lo, lt = is_from ? lo : li;
+        double Ze[2], Re[2];
+        ws_meas(a.edge_attr + (int64_t)e * a.ldea, a.edge_mean, a.edge_std, Ze, Re, mask, ws_edge_id(a, e));
+        if (Re[0] != 0.0 || Re[1] != 0.0) {
+          const WsBranch f = ws_branch(g.u[2 * lf], g.u[2 * lf + 1], g.u[2 * lt], g.u[2 * lt + 1], a.edge_attr + (int64_t)e * a.ldea + 6, g.kk);
+          double hp = 0.0, hq = 0.0;
+          if (lf == li) { hp += c ? f.dp[1] : f.dp[0]; hq += c ? f.dq[1] : f.dq[0]; }
+          if (lt == li) { hp += c ? f.dp[3] : f.dp[2]; hq += c ? f.dq[3] : f.dq[2]; }
+          const double gp = a.w_pf * Re[0] * hp, gq = a.w_pf * Re[1] * hq;
+          accb += gp * (Ze[0] - f.p) + gq * (Ze[1] - f.q);
+          ws_add(row, r, g.slk, 2 * lf, gp * f.dp[0] + gq * f.dq[0]);
+          ws_add(row, r, g.slk, 2 * lf + 1, gp * f.dp[1] + gq * f.dq[1]);
+          ws_add(row, r, g.slk, 2 * lt, gp * f.dp[2] + gq * f.dq[2]);
+          ws_add(row, r, g.slk, 2 * lt + 1, gp * f.dp[3] + gq * f.dq[3]);
+        }
+      }
+      if (lj == li) continue;            // (bus i's own injections were taken at k = k0 - 1)
+      bool seen = false;                 // parallel branches list a neighbour more than once: its injections are taken at the first
+      for (int q = k0; q < k; ++q) {
+        int e2, lo2; bool f2;
+        if (ws_slot(a, g, q, e2, lo2, f2) && lo2 == lj) seen = true;
+      }
+      if (seen) continue;
+    }
+    const int64_t gj = g.base + lj;
+    double Z[4], R[4];
+    ws_meas(a.x + gj * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gj));
+    const double wP = a.w_p * R[2], wQ = a.w_p * R[3];
+    if (wP == 0.0 && wQ == 0.0) continue;
+    const int j0 = a.inc_rowptr[gj], j1 = a.inc_rowptr[gj + 1];
+    const double vj = g.u[2 * lj], tj = g.u[2 * lj + 1];
+    // pass 1: P_j, Q_j, their derivatives at bus j's own state, and at state r
+    double P = 0.0, Q = 0.0, sP[2] = {0.0, 0.0}, sQ[2] = {0.0, 0.0}, hP = 0.0, hQ = 0.0;
+    for (int q = j0; q < j1; ++q) {
+      int e, lo; bool is_from;
+      if (!ws_slot(a, g, q, e, lo, is_from)) continue;
+      const WsBranch f = ws_branch(vj, tj, g.u[2 * lo], g.u[2 * lo + 1], a.edge_attr + (int64_t)e * a.ldea + 6, g.kk);
+      P -= f.p; Q -= f.q;
+      sP[0] -= f.dp[0]; sP[1] -= f.dp[1]; sQ[0] -= f.dq[0]; sQ[1] -= f.dq[1];
+      if (lo == li) { hP -= c ? f.dp[3] : f.dp[2]; hQ -= c ? f.dq[3] : f.dq[2]; }
+    }
+    if (lj == li) { hP += c ? sP[1] : sP[0]; hQ += c ? sQ[1] : sQ[0]; }
+    const double gP = wP * hP, gQ = wQ * hQ;
+    accb += gP * (Z[2] - P) + gQ * (Z[3] - Q);
+    // pass 2: the columns
+    ws_add(row, r, g.slk, 2 * lj, gP * sP[0] + gQ * sQ[0]);
+    ws_add(row, r, g.slk, 2 * lj + 1, gP * sP[1] + gQ * sQ[1]);
+    for (int q = j0; q < j1; ++q) {
+      int e, lo; bool is_from;
+      if (!ws_slot(a, g, q, e, lo, is_from)) continue;
+      if (2 * lo > r) continue;
+      const WsBranch f = ws_branch(vj, tj, g.u[2 * lo], g.u[2 * lo + 1], a.edge_attr + (int64_t)e * a.ldea + 6, g.kk);
+      ws_add(row, r, g.slk, 2 * lo, -(gP * f.dp[2] + gQ * f.dq[2]));
+      ws_add(row, r, g.slk, 2 * lo + 1, -(gP * f.dp[3] + gQ * f.dq[3]));
+    }
+  }
+  bvec[r] = accb;
+}
+
+// The two parts of J at the state in LDS for bus li: its own four measurements, and the flows of the branches it is the from-end of.
+template <class Mask>
+__device__ __forceinline__ void ws_objective_bus(const dss2_wls_solve_args& a, const WsGraph& g, int li, double& jbus, double& jbranch,
+                                                 const Mask& mask) {
+  const int64_t gi = g.base + li;
+  double Z[4], R[4];
+  ws_meas(a.x + gi * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gi));
+  const double vi = g.u[2 * li], ti = g.u[2 * li + 1];
+  double P = 0.0, Q = 0.0;
+  jbranch = 0.0;
+  const int k0 = a.inc_rowptr[gi], k1 = a.inc_rowptr[gi + 1];
+  for (int k = k0; k < k1; ++k) {
+    int e, lo; bool is_from;
+    if (!ws_slot(a, g, k, e, lo, is_from)) continue;
+    const WsBranch f = ws_branch(vi, ti, g.u[2 * lo], g.u[2 * lo + 1], a.edge_attr + (int64_t)e * a.ldea + 6, g.kk);
+    P -= f.p; Q -= f.q;
+    if (is_from) {
+      double Ze[2], Re[2];
+      ws_meas(a.edge_attr + (int64_t)e * a.ldea, a.edge_mean, a.edge_std, Ze, Re, mask, ws_edge_id(a, e));
+      const double dp = Ze[0] - f.p, dq = Ze[1] - f.q;
+      jbranch += a.w_pf * (Re[0] * dp * dp + Re[1] * dq * dq);
+    }
+  }
+  const double dv = Z[0] - vi, dt = Z[1] - ti, dP = Z[2] - P, dQ = Z[3] - Q;
+  jbus = a.w_v * (R[0] * dv * dv + R[1] * dt * dt) + a.w_p * (R[2] * dP * dP + R[3] * dQ * dQ);
+}
+
+// max that keeps a NaN (either operand), so the result does not depend on the order of the reduction
+__device__ __forceinline__ double ws_nanmax(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmax(x, y)); }
+
+// G, b <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read the packed array before are done with).
+template <int T, class Mask>
+__device__ __forceinline__ void ws_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ Gp, int ns, int tid, const Mask& mask) {
+  const size_t tri = (size_t)ns * (ns + 1) / 2;
+  __syncthreads();
+  for (size_t p = tid; p < tri + ns; p += T) Gp[p] = 0.0;
+  __syncthreads();
+  for (int r = tid; r < ns; r += T) ws_accumulate_row(a, g, r, Gp, ns, mask);
+}
+
+// Cholesky of the packed array WITH the b row (row ns), which leaves as y = L^-1 b.  False: a pivot was <= 0 or not finite (every
+// thread reads the same LDS word: the answer is uniform); the loop runs on to its fixed end.
+template <int T>
+__device__ __forceinline__ bool ws_factor(double* __restrict__ Gp, int ns, int tid) {
+  const int tx = tid % WS_TX, ty = tid / WS_TX;
+  constexpr int TY = T / WS_TX;
+  bool ok = true;
+  for (int j = 0; j < ns; ++j) {
+    __syncthreads();
+    const size_t jj = (size_t)j * (j + 1) / 2 + j;
+    const double d = Gp[jj];
+    const bool good = d > 0.0 && d < INFINITY;
+    ok = ok && good;
+    const double s = good ? sqrt(d) : 1.0;
+    for (int i = j + 1 + tid; i <= ns; i += T) Gp[(size_t)i * (i + 1) / 2 + j] /= s;
+    __syncthreads();
+    if (tid == 0) Gp[jj] = s;
+    for (int i = j + 1 + ty; i <= ns; i += TY) {
+      double* rowi = Gp + (size_t)i * (i + 1) / 2;
+      const double lij = rowi[j];
+      const int kmax = i < ns ? i : ns - 1;
+      for (int k = j + 1 + tx; k <= kmax; k += WS_TX) rowi[k] -= lij * Gp[(size_t)k * (k + 1) / 2 + j];
+    }
+  }
+  return ok;
+}
+
+// L^T du = y, one barrier per column; ends with a barrier
+template <int T>
+__device__ __forceinline__ void ws_back_substitute(const double* __restrict__ Gp, double* __restrict__ bvec, double* __restrict__ du, int ns, int tid) {
+  for (int j = ns - 1; j >= 0; --j) {
+    __syncthreads();
+    const double* rowj = Gp + (size_t)j * (j + 1) / 2;
+    const double xj = bvec[j] / rowj[j];
+    for (int k = tid; k < j; k += T) bvec[k] -= rowj[k] * xj;
+    if (tid == 0) du[j] = xj;
+  }
+  __syncthreads();
+}
+
+struct WsLds {                      // the carve of ws_bytes(n)
+  double* Gp; double* bvec; double* u; double* du; int* ctl; unsigned char* slk;
+};
+__device__ __forceinline__ WsLds ws_carve(unsigned char* smem, int n) {
+  const int ns = 2 * n;
+  WsLds l;
+  l.Gp = reinterpret_cast<double*>(smem);
+  l.bvec = l.Gp + (size_t)ns * (ns + 1) / 2;      // row ns of the packed array
+  l.u = l.bvec + ns;
+  l.du = l.u + ns;
+  l.ctl = reinterpret_cast<int*>(smem + ws_ctl_off(n));
+  l.slk = smem + ws_slk_off(n);
+  return l;
+}
+
+// slack flags and the start (init or flat; a slack angle is 0) of graph g into LDS
+template <int T>
+__device__ __forceinline__ void ws_load_start(const dss2_wls_solve_args& a, const WsGraph& g, const WsLds& l, int tid) {
+  for (int k = tid; k < g.n; k += T) {
+    const int64_t gi = g.base + k;
+    const bool s = a.x[gi * a.ldx + 9] != 0.f;
+    l.slk[k] = s ? 1 : 0;
+    l.u[2 * k] = a.init ? (double)a.init[gi * a.ld_init] : 1.0;
+    l.u[2 * k + 1] = (a.init && !s) ? (double)a.init[gi * a.ld_init + 1] : 0.0;
+  }
+}
+
+struct WsTally { int iters, status; double last; };   // (thread 0's copies are the ones written out)
+
+// Gauss-Newton from the state in LDS: at most a.max_iter iterations (the trip count is fixed; a graph that has stopped skips the body,
+// uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status (1, then 0 or 2) and t.last.  Returns whether the
+// factorisation failed (uniform).  Ends with a barrier.
+template <int T, class Mask>
+__device__ __forceinline__ bool ws_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, const WsLds& l, int ns, int tid,
+                                                const Mask& mask, WsTally& t) {
+  t.status = 1;
+  bool active = true, failed = false;  // uniform over the workgroup
+  for (int it = 0; it < a.max_iter; ++it) {
+    if (active) {
+      ws_form<T>(a, g, l.Gp, ns, tid, mask);      // (its first barrier: u, slk of the start or of the previous iteration; the previous ctl has been read)
+      const bool ok = ws_factor<T>(l.Gp, ns, tid);
+      ws_back_substitute<T>(l.Gp, l.bvec, l.du, ns, tid);
+      // ---- the decision: one thread writes it, all read it after the barrier
+      if (tid < 64) {
+        double m = 0.0;
+        for (int k = tid; k < ns; k += 64) m = ws_nanmax(m, fabs(l.du[k]));
+        for (int o = 32; o > 0; o >>= 1) m = ws_nanmax(m, __shfl_xor(m, o));
+        if (tid == 0) {
+          int stop = 0, apply = 0;
+          if (!ok || !(m < INFINITY)) { t.status = 2; stop = 1; }
+          else {
+            apply = 1; ++t.iters; t.last = m;
+            if (m < a.tol) { t.status = 0; stop = 1; }
+          }
+          l.ctl[0] = stop; l.ctl[1] = apply;
+        }
+      }
+      __syncthreads();
+      if (l.ctl[1]) for (int r = tid; r < ns; r += T) l.u[r] += l.du[r];
+      active = l.ctl[0] == 0;
+      failed = l.ctl[0] != 0 && l.ctl[1] == 0;
+    }
+  }
+  __syncthreads();
+  return failed;
+}
+
+// J at the state in LDS: per-bus parts into the first 2 n words of the packed array, summed by thread 0 in bus order (jb, je are
+// thread 0's).  The packed array is overwritten.  Ends with a barrier.
+template <int T, class Mask>
+__device__ __forceinline__ void ws_objective(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ Gp, int tid, const Mask& mask,
+                                             double& jb, double& je) {
+  for (int k = tid; k < g.n; k += T) {
+    double b, e;
+    ws_objective_bus(a, g, k, b, e, mask);
+    Gp[k] = b; Gp[g.n + k] = e;
+  }
+  __syncthreads();
+  jb = 0.0; je = 0.0;
+  if (tid == 0)
+    for (int k = 0; k < g.n; ++k) { jb += Gp[k]; je += Gp[g.n + k]; }
+  __syncthreads();
+}
+
+constexpr int WS_NARROW_STATES = 64;     // up to 64 states: one wave; above: four
+constexpr int WS_GROUPS_NARROW = 2048, WS_GROUPS_WIDE = 512;
+
+// the argument checks both entries share (`who` names the entry in the message, extra_lds is what its kernel needs beyond ws_bytes); 0 or 2
+inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t extra_lds) {
+  const int n = a.nodes_per_graph;
+  if (a.n_nodes <= 0 || a.n_edges < 0 || n <= 0 || a.n_nodes % n != 0) { set_error("%s: n_nodes must be a positive multiple of nodes_per_graph", who); return 2; }
+  if (n > (1 << 20) || ws_bytes(n) + extra_lds > (size_t)kMaxLdsBytes) {
+    set_error("%s: %d buses per graph need more than the %d bytes of LDS a workgroup has (the gain matrix lives in LDS)", who, n, kMaxLdsBytes);
+    return 2;
+  }
+  if (a.max_iter < 1 || !(a.tol >= 0.0)) { set_error("%s: max_iter must be >= 1 and tol >= 0", who); return 2; }
+  if (!a.x || !a.edge_attr || !a.x_mean || !a.x_std || !a.edge_mean || !a.edge_std || !a.efrom || !a.eto || !a.inc_rowptr || !a.inc_ent ||
+      !a.state || !a.objective || !a.iterations || !a.status || !a.last_step || !a.vminmax) { set_error("%s: null argument", who); return 2; }
+  if (a.ldx < 10 || a.ldea < 10 || (a.init && a.ld_init < 2) || a.max_groups < 0) { set_error("%s: bad leading dimension or max_groups", who); return 2; }
+  return 0;
+}
+inline int64_t ws_grid(const dss2_wls_solve_args& a) {
+  const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
+  int64_t grid = 2 * a.nodes_per_graph <= WS_NARROW_STATES ? WS_GROUPS_NARROW : WS_GROUPS_WIDE;
+  if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
+  return n_graphs < grid ? n_graphs : grid;
+}
+
+}  // namespace dss2

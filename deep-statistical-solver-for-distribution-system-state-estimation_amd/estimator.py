@@ -9,6 +9,11 @@ bus count of a graph: graph g owns rows [g n, (g + 1) n), edges never cross grap
 physical, (v in p.u., theta in rad), the convention of ``eval_batch``'s ``yhat``.  Everything inside is fp64 (the gain matrix of these
 grids has condition number 3e11 .. 3e12: an fp32 Cholesky meets non-positive pivots at the first iteration); one HIP
 launch per solve, csrc/dss2_wls_solve.hip.  No CPU fallback, no host read-back, recordable into a hipGraph or a launch plan.
+
+    wls_bad_data(... same inputs ..., threshold=3.0, max_removals=0, confidence=0.95, s_min=1e-3) -> WLSBadDataResult
+
+The rest of the classical estimator on the same solve and in the same single launch (csrc/dss2_wls_bad_data.hip): the chi-square test
+on J, residual sensitivities and normalized residuals, removal of the largest one followed by a re-solve, the state's standard deviation.
 """
 from __future__ import annotations
 
@@ -98,4 +103,97 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     vmm = torch.empty(130, dtype=_F32, device=dev)
     a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
     _lib.check(_lib.lib().dss2_wls_solve(C.byref(a), _stream(x)), "dss2_wls_solve")
+    return res
+
+
+class WLSBadDataResult(NamedTuple):
+    state: torch.Tensor          # as in WLSResult; of the final solve
+    objective: torch.Tensor      # [G, 2] fp64: J at the final state with the removed measurements' weights at 0
+    iterations: torch.Tensor     # [G] int32: updates applied, summed over all solves
+    status: torch.Tensor         # [G] int32: of the final solve; 2 if any factorisation failed
+    last_step: torch.Tensor      # [G] fp64
+    dof: torch.Tensor            # [G] int32: active measurements - free states
+    chi2_limit: torch.Tensor     # [G] fp64: Wilson-Hilferty quantile of chi2(dof) at `confidence`; +inf for dof <= 0
+    suspect: torch.Tensor        # [G] int32: J > chi2_limit
+    removed: torch.Tensor        # [G, max(max_removals, 1)] int32: ids in the order of removal, -1 in unused slots
+    removed_rn: torch.Tensor     # [G, max(max_removals, 1)] fp64: their normalized residuals at removal
+    n_removed: torch.Tensor      # [G] int32
+    bus_rn: torch.Tensor         # [N, 4] fp64: normalized residuals of (V, theta, P, Q) at the final solve, 0 where inactive
+    edge_rn: torch.Tensor        # [E, 2] fp64: of (P_from, Q_from)
+    bus_sens: torch.Tensor       # [N, 4] fp64: residual sensitivities S_i = w_i Omega_ii
+    edge_sens: torch.Tensor      # [E, 2] fp64
+    state_std: torch.Tensor      # [N, 2] fp64: sqrt(diag (H^T W H)^-1), 0 at slack angles
+
+
+def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                 init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                 weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
+                 confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0) -> WLSBadDataResult:
+    """``wls_estimate`` followed, inside the same launch, by the chi-square test, the largest-normalized-residual test and up to
+    ``max_removals`` removals, each followed by a re-solve from the current state.  A measurement is active if its weight
+    c_k R^-1 is above 0 and it has not been removed; S_i = 1 - w_i h_i Sigma h_i^T, rN_i = |z_i - h_i(u)| sqrt(w_i / S_i) where
+    S_i >= ``s_min`` and 0 below it (critical measurements).  The largest rN above ``threshold`` is removed (ties: the smallest id).
+    Ids: 4 i + k for bus i (row of x), k in V, theta, P, Q; 4 N + 2 e + k for stored branch e, k in P_from, Q_from.
+    With ``max_removals = 0`` the first five fields are ``wls_estimate``'s, bit for bit."""
+    _require_gpu(x, edge_index, edge_attr)
+    n = int(nodes_per_graph)
+    N = x.size(0)
+    if n < 1 or N == 0 or N % n != 0:
+        raise ValueError(f"x has {N} rows: not a positive multiple of nodes_per_graph = {nodes_per_graph}")
+    if int(max_iter) < 1:
+        raise ValueError("max_iter must be at least 1")
+    if not tol >= 0:
+        raise ValueError("tol must be >= 0")
+    if len(weights) != 3:
+        raise ValueError("weights = (w_v, w_p, w_pf)")
+    if not threshold > 0:
+        raise ValueError("threshold must be > 0")
+    if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
+        raise ValueError("max_removals must be an integer in 0 .. 64")
+    if not 0 < confidence < 1:
+        raise ValueError("confidence must be in (0, 1)")
+    if not 0 < s_min < 1:
+        raise ValueError("s_min must be in (0, 1)")
+    if x.dim() != 2 or x.size(1) < 10 or edge_attr.dim() != 2 or edge_attr.size(1) < 10:
+        raise ValueError("x must be the full [N, 11] node tensor and edge_attr the full [E, 13] edge tensor")
+    if init is not None:
+        _require_gpu(init)
+        if init.dim() != 2 or tuple(init.shape) != (N, 2):
+            raise ValueError(f"init must be [N, 2] = ({N}, 2), got {tuple(init.shape)}")
+    L = _lib.lib()
+    if L.dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
+        raise NotImplementedError(f"wls_bad_data keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
+    dev = x.device
+    x2, ldx = _rows(x)
+    ea2, ldea = _rows(edge_attr)
+    topo = get_topology(edge_index, N)
+    G, E, slots = N // n, topo.E, max(int(max_removals), 1)
+    b = _lib.WlsBadDataArgs()
+    a = b.solve
+    a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
+    stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
+    a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
+    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = (t.data_ptr() for t in (topo.efrom, topo.eto, topo.inc_rowptr, topo.inc_ent))
+    a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, E, n, int(max_iter), float(tol)
+    a.w_v, a.w_p, a.w_pf = (float(w) for w in weights)
+    keep = None
+    if init is not None:
+        keep, ld_init = _rows(init.detach())
+        a.init, a.ld_init = keep.data_ptr(), ld_init
+    f64, i32 = torch.float64, torch.int32
+    new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
+    res = WLSBadDataResult(
+        state=new(N, 2, dtype=_F32), objective=new(G, 2), iterations=new(G, dtype=i32), status=new(G, dtype=i32), last_step=new(G),
+        dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
+        n_removed=new(G, dtype=i32), bus_rn=new(N, 4),
+        edge_rn=torch.zeros(E, 2, dtype=f64, device=dev),       # (an edge that leaves its graph is never written)
+        bus_sens=new(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=new(N, 2))
+    a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in res[:5])
+    (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
+     b.state_std) = (t.data_ptr() for t in res[5:])
+    vmm = torch.empty(130, dtype=_F32, device=dev)
+    a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
+    b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
+    b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
+    _lib.check(L.dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
     return res

@@ -333,15 +333,17 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 
 
 @torch.no_grad()
-def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, **solver_kw) -> Dict[str, float]:
+def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None, **solver_kw) -> Dict[str, float]:
     """The classical WLS estimator (``estimator.wls_estimate``) over a loader, scored like ``evaluate``: the ten EVAL_METRICS of its
     state, averaged over the batches, plus ``wls_mean_iterations`` (Gauss-Newton updates per graph) and ``wls_not_converged`` (graphs
     that did not end with status 0).  ``model`` None: a flat start, the baseline a learned estimator is compared with; a model: its
-    de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  One device-to-host copy."""
+    de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  ``bad_data`` = dict(threshold=...,
+    max_removals=..., [confidence, s_min]): the solve is ``estimator.wls_bad_data`` with these, and the metrics gain ``wls_suspect``
+    (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed).  One device-to-host copy."""
     from . import estimator
     dev = stats[0].device
     acc = torch.zeros(10, dtype=torch.float64, device=dev)
-    tally = torch.zeros(3, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged
+    tally = torch.zeros(5, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged, suspect graphs, removals
     n = 0
     if model is not None:
         model.eval()
@@ -351,15 +353,25 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, **solver_kw) -
         if model is not None:
             out = run_model(model, x[:, :8], ei, ea[:, :6])
             init = torch.stack([out[:, 0] * stats[1][0] + stats[0][0], out[:, 1]], 1)
-        res = estimator.wls_estimate(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
+        zero = torch.zeros((), dtype=torch.int64, device=dev)
+        if bad_data is None:
+            res = estimator.wls_estimate(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
+            suspect, removed = zero, zero
+        else:
+            res = estimator.wls_bad_data(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw, **bad_data)
+            suspect, removed = res.suspect.sum(), res.n_removed.sum()
         dss2_data._eval_state_batch(res.state, y, x, ei, ea, acc)
-        tally += torch.stack([res.iterations.sum(), torch.tensor(res.iterations.numel(), device=dev), (res.status != 0).sum()]).double()
+        tally += torch.stack([res.iterations.sum(), torch.tensor(res.iterations.numel(), device=dev), (res.status != 0).sum(),
+                              suspect, removed]).double()
         n += 1
     vals = (acc / max(n, 1)).cpu().tolist()
-    its, graphs, bad = tally.cpu().tolist()
+    its, graphs, bad, n_suspect, n_removed = tally.cpu().tolist()
     m = dict(zip(dss2_data.EVAL_METRICS, vals))
     m["wls_mean_iterations"] = its / max(graphs, 1.0)
     m["wls_not_converged"] = int(bad)
+    if bad_data is not None:
+        m["wls_suspect"] = int(n_suspect)
+        m["wls_removed"] = int(n_removed)
     return m
 
 
@@ -387,6 +399,8 @@ def main(argv=None):
                     "structure per batch shape), 0: eager, -1 (default): graph when the data has a single topology")
     ap.add_argument("--wls-baseline", action="store_true", help="after training, print the evaluation metrics of the classical WLS "
                     "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); needs one bus count")
+    ap.add_argument("--wls-bad-data", type=float, default=None, metavar="THRESHOLD", help="the --wls-baseline lines (implied) through "
+                    "estimator.wls_bad_data: up to 5 measurements per graph are removed while the largest normalized residual exceeds THRESHOLD")
     a = ap.parse_args(argv)
     hp = {k: getattr(a, k) for k in HYPER}
     if a.model == "SkipMPN":
@@ -452,13 +466,14 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(f"epoch {epoch:4d}  train_loss {tl:.6g}  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()) +
               f"  ({time.perf_counter() - t0:.2f} s)", flush=True)
-    if a.wls_baseline:
+    if a.wls_baseline or a.wls_bad_data is not None:
         ds = getattr(test_loader, "dataset", None)
         n_bus = getattr(ds, "n", None) if ds is not None else synthetic.load_grid(a.case).n
         if n_bus is None:
             raise ValueError("--wls-baseline needs one bus count per graph (the data list mixes bus counts)")
         for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
-            m = evaluate_wls(test_loader, stats, n_bus, model=start)
+            bad_data = dict(threshold=a.wls_bad_data, max_removals=5) if a.wls_bad_data is not None else None
+            m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data)
             print(f"wls baseline ({label})  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()), flush=True)
     if a.save:                                                       # dss2_run.py:240-247
         torch.save({"epoch": a.epochs - 1, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},

@@ -270,3 +270,45 @@ def tile_real_batch(batch: Dict[str, object], times: int) -> Dict[str, object]:
     out.update(x=x.repeat(times, 1), edge_index=eis, edge_attr=ea.repeat(times, 1), y=y.repeat(times, 1),
                num_graphs=int(batch["num_graphs"]) * times)
     return out
+
+
+def corrupt_measurements(batch: Dict[str, object], per_graph: int = 1, sigmas: float = 25.0, seed: int = 0,
+                         stats: Optional[Tuple[torch.Tensor, ...]] = None):
+    """Gross errors for the bad-data tests of ``estimator.wls_bad_data``: `per_graph` randomly chosen ACTIVE measurements of every graph
+    (de-normalised weight w = R^-1 above 0, in a column whose normalisation can carry it) are moved by `sigmas` standard deviations, +sigmas / sqrt(w), in physical units, and
+    normalised again.  Returns (the new batch, ids [G, per_graph] int32) with the ids of ``wls_bad_data``: 4 i + k for bus i, k in
+    V, theta, P, Q; 4 N + 2 e + k for stored branch e, k in P_from, Q_from.  Graph boundaries: batch["graph_ptr"], or
+    batch["nodes_per_graph"]; `stats`: the normalisation statistics where the batch does not carry them."""
+    x, ea, ei = batch["x"], batch["edge_attr"], batch["edge_index"]
+    xm, xs, em, es = (np.asarray(t.detach().cpu().double()) for t in (stats if stats is not None else batch["stats"]))
+    N = x.shape[0]
+    if batch.get("graph_ptr") is not None:
+        ptr = np.asarray(batch["graph_ptr"].cpu())
+    else:
+        ptr = np.arange(0, N + 1, int(batch["nodes_per_graph"]))
+    xn, en = np.asarray(x.detach().cpu().double()).copy(), np.asarray(ea.detach().cpu().double()).copy()
+    src = np.asarray(ei[0].cpu())
+    graph_of_bus = np.searchsorted(ptr, np.arange(N), side="right") - 1
+    w_bus = (xn[:, 1:8:2] * xs[1:8:2] + xm[1:8:2]) * (xn[:, 1:8:2] != 0)
+    w_edge = (en[:, 1:4:2] * es[1:4:2] + em[1:4:2]) * (en[:, 1:4:2] != 0)
+    w = np.concatenate([w_bus.reshape(-1), w_edge.reshape(-1)])
+    graph_of = np.concatenate([np.repeat(graph_of_bus, 4), np.repeat(graph_of_bus[src], 2)])
+    rng = np.random.default_rng(seed)
+    ids = np.zeros((len(ptr) - 1, per_graph), dtype=np.int32)
+    scale = np.concatenate([np.tile(xs[0:8:2], N), np.tile(es[0:4:2], en.shape[0])])     # (a column of standard deviation 0 cannot carry an error)
+    active = np.nonzero((w > 0) & (scale != 0))[0]
+    active = active[np.argsort(graph_of[active], kind="stable")]                 # grouped by graph, ids ascending inside a graph
+    first = np.searchsorted(graph_of[active], np.arange(len(ptr)))
+    for g in range(len(ptr) - 1):
+        cand = active[first[g]:first[g + 1]]
+        if len(cand) < per_graph:
+            raise ValueError(f"graph {g} has {len(cand)} active measurements, fewer than per_graph = {per_graph}")
+        ids[g] = rng.choice(cand, size=per_graph, replace=False)
+        for m in ids[g]:
+            t, mean, std, (row, k) = (xn, xm, xs, divmod(int(m), 4)) if m < 4 * N else (en, em, es, divmod(int(m) - 4 * N, 2))
+            z = t[row, 2 * k] * std[2 * k] + mean[2 * k] + sigmas / np.sqrt(w[m])
+            t[row, 2 * k] = (z - mean[2 * k]) / std[2 * k]
+    out = dict(batch)
+    out["x"] = torch.from_numpy(xn).to(dtype=x.dtype, device=x.device)
+    out["edge_attr"] = torch.from_numpy(en).to(dtype=ea.dtype, device=ea.device)
+    return out, torch.from_numpy(ids)

@@ -731,6 +731,42 @@ int dss2_wls_solve(const dss2_wls_solve_args* args_host, void* stream);
 /* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic) */
 size_t dss2_wls_solve_lds_bytes(int nodes_per_graph);
 
+/* ---- the rest of the classical estimator on the same solve, still ONE launch (csrc/dss2_wls_bad_data.hip): the chi-square test on J,
+ *      normalized residuals, removal of the largest one followed by a re-solve, and the state's standard deviation.  Per graph:
+ *        1. Gauss-Newton exactly as dss2_wls_solve (`solve` is its argument block, outputs included), from init / the flat start, later
+ *           from the current state;
+ *        2. at the last iterate G is formed and factorised once more and inverted in place in LDS: Sigma = G^-1;
+ *        3. for every ACTIVE measurement i (effective weight w_i = c_k R^-1 > 0, not removed), with h_i its Jacobian row without the
+ *           slack angles' columns:  S_i = 1 - w_i h_i Sigma h_i^T (the residual sensitivity w_i Omega_ii) and
+ *           rN_i = |z_i - h_i(u)| sqrt(w_i / S_i) where S_i >= s_min, 0 below it (critical measurements: the residual says nothing);
+ *        4. dof = #active - #free states, chi2_limit = dof (1 - 2 / (9 dof) + z_p sqrt(2 / (9 dof)))^3 (Wilson-Hilferty; +inf for
+ *           dof <= 0), suspect = J > chi2_limit with J the objective at the final state;
+ *        5. the arg-max of rN (ties: the smallest id; a NaN wins): if it exceeds `threshold` and fewer than max_removals measurements
+ *           are gone, its id and rN are recorded, its weight is 0 from here on, and the graph goes back to 1.
+ *      A failed factorisation in any solve or in 2. ends the graph with status 2: the state of the previous iterate (in 2.: the last
+ *      one), the removals so far, per-measurement outputs and state_std 0.  Measurement ids (int32): 4 i + k for bus i (global row), k in V, theta, P, Q;
+ *      4 N + 2 e + k for stored branch e, k in P_from, Q_from; rc 2 where 4 N + 2 E does not fit.  iterations counts the updates of
+ *      all solves; status and last_step are the last solve's.  No atomics, one writer per value, fixed summation orders. */
+typedef struct dss2_wls_bad_data_args {
+  dss2_wls_solve_args solve;
+  double threshold;                               /* > 0: the largest normalized residual is removed above it                     */
+  double z_p;                                     /* the standard normal quantile of the test's confidence                        */
+  double s_min;                                   /* in (0, 1): sensitivities below it give rN = 0                                */
+  int32_t max_removals; int32_t pad_;             /* 0 .. 64                                                                      */
+  int32_t* dof;                                   /* [G]                                                                          */
+  double* chi2_limit;                             /* [G]                                                                          */
+  int32_t* suspect;                               /* [G]     J > chi2_limit                                                       */
+  int32_t* removed;                               /* [G, max(max_removals, 1)] ids in the order of removal, -1 in unused slots    */
+  double* removed_rn;                             /* [G, max(max_removals, 1)] their normalized residuals when removed, 0 unused  */
+  int32_t* n_removed;                             /* [G]                                                                          */
+  double* bus_rn; double* bus_sens;               /* [N, 4]  rN and S of the final solve, 0 where inactive                        */
+  double* edge_rn; double* edge_sens;             /* [E, 2]  (an edge that leaves its graph is not written)                       */
+  double* state_std;                              /* [N, 2]  sqrt(Sigma_jj), 0 at slack angles                                    */
+} dss2_wls_bad_data_args;
+int dss2_wls_bad_data(const dss2_wls_bad_data_args* args_host, void* stream);
+/* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic): the solve's plus a fixed block */
+size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph);
+
 /* ---- batched small dense products in weight space (folding the edge MLP's second Linear into conv 0
  *      and the chain rule back): C[M,N] (+)= sum_b op(A_b)[M,K] . op(B_b)[K,N]  (+ u[i] * v[j]).     */
 typedef struct dss2_sgemm_desc {
