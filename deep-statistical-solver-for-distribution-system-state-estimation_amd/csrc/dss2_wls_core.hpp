@@ -348,7 +348,9 @@ inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t e
     return 2;
   }
   if (a.max_iter < 1 || !(a.tol >= 0.0)) { set_error("%s: max_iter must be >= 1 and tol >= 0", who); return 2; }
-  if (!a.x || !a.edge_attr || !a.x_mean || !a.x_std || !a.edge_mean || !a.edge_std || !a.efrom || !a.eto || !a.inc_rowptr || !a.inc_ent ||
+  // (a batch without any branch -- one-bus graphs -- has no edge arrays: every incidence range is empty and nothing reads them)
+  if (!a.x || !a.x_mean || !a.x_std || !a.edge_mean || !a.edge_std || !a.inc_rowptr ||
+      (a.n_edges > 0 && (!a.edge_attr || !a.efrom || !a.eto || !a.inc_ent)) ||
       !a.state || !a.objective || !a.iterations || !a.status || !a.last_step || !a.vminmax) { set_error("%s: null argument", who); return 2; }
   if (a.ldx < 10 || a.ldea < 10 || (a.init && a.ld_init < 2) || a.max_groups < 0) { set_error("%s: bad leading dimension or max_groups", who); return 2; }
   return 0;

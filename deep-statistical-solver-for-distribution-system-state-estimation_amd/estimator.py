@@ -53,6 +53,22 @@ def max_nodes_per_graph() -> int:
     return _MAX_NODES[0]
 
 
+_EDGELESS = {}                   # (device, N) -> the all-zero incidence row pointer of a batch without branches
+
+
+def _incidence(edge_index: torch.Tensor, N: int):
+    """((efrom, eto, inc_rowptr, inc_ent) as device addresses, the stored edge count).  A batch without any branch (one-bus graphs) has
+    no Topology: every bus's incidence range is empty, and the kernels touch no edge array then.  Like a Topology, the row pointer is
+    kept (a recorded launch replays with its address)."""
+    if edge_index.dim() == 2 and edge_index.size(0) == 2 and edge_index.size(1) == 0:
+        key = (edge_index.device, N)
+        if key not in _EDGELESS:
+            _EDGELESS[key] = torch.zeros(N + 1, dtype=torch.int32, device=edge_index.device)
+        return (None, None, _EDGELESS[key].data_ptr(), None), 0
+    topo = get_topology(edge_index, N)
+    return tuple(t.data_ptr() for t in (topo.efrom, topo.eto, topo.inc_rowptr, topo.inc_ent)), topo.E
+
+
 def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                  init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
                  weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
@@ -83,14 +99,14 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     dev = x.device
     x2, ldx = _rows(x)
     ea2, ldea = _rows(edge_attr)
-    topo = get_topology(edge_index, N)
+    incidence, E = _incidence(edge_index, N)
     G = N // n
     a = _lib.WlsSolveArgs()
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
-    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = (t.data_ptr() for t in (topo.efrom, topo.eto, topo.inc_rowptr, topo.inc_ent))
-    a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, topo.E, n, int(max_iter), float(tol)
+    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = incidence
+    a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, E, n, int(max_iter), float(tol)
     a.w_v, a.w_p, a.w_pf = (float(w) for w in weights)
     keep = None
     if init is not None:
@@ -166,14 +182,14 @@ def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     dev = x.device
     x2, ldx = _rows(x)
     ea2, ldea = _rows(edge_attr)
-    topo = get_topology(edge_index, N)
-    G, E, slots = N // n, topo.E, max(int(max_removals), 1)
+    incidence, E = _incidence(edge_index, N)
+    G, slots = N // n, max(int(max_removals), 1)
     b = _lib.WlsBadDataArgs()
     a = b.solve
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
-    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = (t.data_ptr() for t in (topo.efrom, topo.eto, topo.inc_rowptr, topo.inc_ent))
+    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = incidence
     a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, E, n, int(max_iter), float(tol)
     a.w_v, a.w_p, a.w_pf = (float(w) for w in weights)
     keep = None

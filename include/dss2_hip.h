@@ -714,7 +714,7 @@ typedef struct dss2_wls_solve_args {
   const float* edge_mean; const float* edge_std;  /* [>= 4]                                                                       */
   const int32_t* efrom; const int32_t* eto;       /* [E] stored edge endpoints                                                    */
   const int32_t* inc_rowptr; const int32_t* inc_ent; /* incidence CSR as in dss2_wls_args                                         */
-  int64_t n_nodes; int64_t n_edges;
+  int64_t n_nodes; int64_t n_edges;               /* n_edges = 0 (one-bus graphs): inc_rowptr all 0; edge_attr, efrom, eto, inc_ent may be NULL */
   int32_t nodes_per_graph; int32_t max_iter;
   double tol;
   double w_v, w_p, w_pf;
