@@ -218,6 +218,11 @@ class WlsBadDataArgs(C.Structure):
                 ("state_std", C.c_void_p)]
 
 
+class WlsLargeArgs(C.Structure):
+    """dss2_wls_large_args (include/dss2_hip.h)."""
+    _fields_ = [("solve", WlsSolveArgs), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
 class WlsArgs(C.Structure):
     _fields_ = [("input", C.c_void_p), ("ld_in", C.c_int64),
                 ("edge_input", C.c_void_p), ("ld_ein", C.c_int64),
@@ -443,6 +448,11 @@ _SIGNATURES = {
     "dss2_wls_solve_lds_bytes": (C.c_size_t, [C.c_int]),
     "dss2_wls_bad_data": (C.c_int, [C.POINTER(WlsBadDataArgs), C.c_void_p]),
     "dss2_wls_bad_data_lds_bytes": (C.c_size_t, [C.c_int]),
+    "dss2_wls_solve_large": (C.c_int, [C.POINTER(WlsLargeArgs), C.c_void_p]),
+    "dss2_wls_large_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "dss2_wls_large_groups": (C.c_int64, [C.POINTER(WlsSolveArgs)]),
+    "dss2_wls_large_max_nodes": (C.c_int, []),
+    "dss2_wls_large_lds_bytes": (C.c_size_t, [C.c_int]),
     "dss2_small_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dss2_measure_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),

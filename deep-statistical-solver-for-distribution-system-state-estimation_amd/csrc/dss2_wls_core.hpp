@@ -87,12 +87,11 @@ __device__ __forceinline__ void ws_add(double* __restrict__ row, int r, const un
   if (c <= r && !((c & 1) && slk[c >> 1])) row[c] += v;
 }
 
-// Row r of G and b[r]: every measurement with a non-zero Jacobian entry at state r, in a fixed order.
+// Row r of G and b[r]: every measurement with a non-zero Jacobian entry at state r, in a fixed order.  `row` is the zeroed row r
+// (columns 0 .. r, contiguous, LDS or global memory), `bvec` the right-hand side (entry r is written).
 template <class Mask>
-__device__ __forceinline__ void ws_accumulate_row(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ Gp, int ns,
-                                                  const Mask& mask) {
-  double* row = Gp + (size_t)r * (r + 1) / 2;
-  double* bvec = Gp + (size_t)ns * (ns + 1) / 2;
+__device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ row,
+                                                     double* __restrict__ bvec, const Mask& mask) {
   const int li = r >> 1, c = r & 1;
   if (c && g.slk[li]) { row[r] = 1.0; bvec[r] = 0.0; return; }     // a slack angle: identity row, held at 0
   const int64_t gi = g.base + li;
@@ -170,6 +169,12 @@ __device__ __forceinline__ void ws_accumulate_row(const dss2_wls_solve_args& a, 
     }
   }
   bvec[r] = accb;
+}
+// ... in the packed lower triangle with the b row (the LDS kernels' layout)
+template <class Mask>
+__device__ __forceinline__ void ws_accumulate_row(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ Gp, int ns,
+                                                  const Mask& mask) {
+  ws_accumulate_row_at(a, g, r, Gp + (size_t)r * (r + 1) / 2, Gp + (size_t)ns * (ns + 1) / 2, mask);
 }
 
 // The two parts of J at the state in LDS for bus li: its own four measurements, and the flows of the branches it is the from-end of.
@@ -281,6 +286,26 @@ __device__ __forceinline__ void ws_load_start(const dss2_wls_solve_args& a, cons
 
 struct WsTally { int iters, status; double last; };   // (thread 0's copies are the ones written out)
 
+// The decision of an iteration from the step in du and `ok` (the factorisation's answer): wave 0 forms max |du|, thread 0 writes
+// ctl = {stop, apply} and its tallies.  The caller's barrier comes next.
+__device__ __forceinline__ void ws_decide(const dss2_wls_solve_args& a, const double* __restrict__ du, int* __restrict__ ctl, int ns, int tid,
+                                          bool ok, WsTally& t) {
+  if (tid < 64) {
+    double m = 0.0;
+    for (int k = tid; k < ns; k += 64) m = ws_nanmax(m, fabs(du[k]));
+    for (int o = 32; o > 0; o >>= 1) m = ws_nanmax(m, __shfl_xor(m, o));
+    if (tid == 0) {
+      int stop = 0, apply = 0;
+      if (!ok || !(m < INFINITY)) { t.status = 2; stop = 1; }
+      else {
+        apply = 1; ++t.iters; t.last = m;
+        if (m < a.tol) { t.status = 0; stop = 1; }
+      }
+      ctl[0] = stop; ctl[1] = apply;
+    }
+  }
+}
+
 // Gauss-Newton from the state in LDS: at most a.max_iter iterations (the trip count is fixed; a graph that has stopped skips the body,
 // uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status (1, then 0 or 2) and t.last.  Returns whether the
 // factorisation failed (uniform).  Ends with a barrier.
@@ -295,20 +320,7 @@ __device__ __forceinline__ bool ws_gauss_newton(const dss2_wls_solve_args& a, co
       const bool ok = ws_factor<T>(l.Gp, ns, tid);
       ws_back_substitute<T>(l.Gp, l.bvec, l.du, ns, tid);
       // ---- the decision: one thread writes it, all read it after the barrier
-      if (tid < 64) {
-        double m = 0.0;
-        for (int k = tid; k < ns; k += 64) m = ws_nanmax(m, fabs(l.du[k]));
-        for (int o = 32; o > 0; o >>= 1) m = ws_nanmax(m, __shfl_xor(m, o));
-        if (tid == 0) {
-          int stop = 0, apply = 0;
-          if (!ok || !(m < INFINITY)) { t.status = 2; stop = 1; }
-          else {
-            apply = 1; ++t.iters; t.last = m;
-            if (m < a.tol) { t.status = 0; stop = 1; }
-          }
-          l.ctl[0] = stop; l.ctl[1] = apply;
-        }
-      }
+      ws_decide(a, l.du, l.ctl, ns, tid, ok, t);
       __syncthreads();
       if (l.ctl[1]) for (int r = tid; r < ns; r += T) l.u[r] += l.du[r];
       active = l.ctl[0] == 0;
@@ -339,14 +351,13 @@ __device__ __forceinline__ void ws_objective(const dss2_wls_solve_args& a, const
 constexpr int WS_NARROW_STATES = 64;     // up to 64 states: one wave; above: four
 constexpr int WS_GROUPS_NARROW = 2048, WS_GROUPS_WIDE = 512;
 
-// the argument checks both entries share (`who` names the entry in the message, extra_lds is what its kernel needs beyond ws_bytes); 0 or 2
-inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t extra_lds) {
+// The argument checks the entries share, in two parts around each entry's own size limit (`who` names the entry in the message); 0 or 2
+inline int ws_check_batch(const dss2_wls_solve_args& a, const char* who) {
   const int n = a.nodes_per_graph;
   if (a.n_nodes <= 0 || a.n_edges < 0 || n <= 0 || a.n_nodes % n != 0) { set_error("%s: n_nodes must be a positive multiple of nodes_per_graph", who); return 2; }
-  if (n > (1 << 20) || ws_bytes(n) + extra_lds > (size_t)kMaxLdsBytes) {
-    set_error("%s: %d buses per graph need more than the %d bytes of LDS a workgroup has (the gain matrix lives in LDS)", who, n, kMaxLdsBytes);
-    return 2;
-  }
+  return 0;
+}
+inline int ws_check_rest(const dss2_wls_solve_args& a, const char* who) {
   if (a.max_iter < 1 || !(a.tol >= 0.0)) { set_error("%s: max_iter must be >= 1 and tol >= 0", who); return 2; }
   // (a batch without any branch -- one-bus graphs -- has no edge arrays: every incidence range is empty and nothing reads them)
   if (!a.x || !a.x_mean || !a.x_std || !a.edge_mean || !a.edge_std || !a.inc_rowptr ||
@@ -354,6 +365,16 @@ inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t e
       !a.state || !a.objective || !a.iterations || !a.status || !a.last_step || !a.vminmax) { set_error("%s: null argument", who); return 2; }
   if (a.ldx < 10 || a.ldea < 10 || (a.init && a.ld_init < 2) || a.max_groups < 0) { set_error("%s: bad leading dimension or max_groups", who); return 2; }
   return 0;
+}
+// ... for the kernels that keep the gain matrix in LDS (extra_lds is what the kernel needs beyond ws_bytes)
+inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t extra_lds) {
+  if (int rc = ws_check_batch(a, who)) return rc;
+  const int n = a.nodes_per_graph;
+  if (n > (1 << 20) || ws_bytes(n) + extra_lds > (size_t)kMaxLdsBytes) {
+    set_error("%s: %d buses per graph need more than the %d bytes of LDS a workgroup has (the gain matrix lives in LDS)", who, n, kMaxLdsBytes);
+    return 2;
+  }
+  return ws_check_rest(a, who);
 }
 inline int64_t ws_grid(const dss2_wls_solve_args& a) {
   const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;

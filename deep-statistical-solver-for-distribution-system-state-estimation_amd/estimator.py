@@ -9,6 +9,12 @@ bus count of a graph: graph g owns rows [g n, (g + 1) n), edges never cross grap
 physical, (v in p.u., theta in rad), the convention of ``eval_batch``'s ``yhat``.  Everything inside is fp64 (the gain matrix of these
 grids has condition number 3e11 .. 3e12: an fp32 Cholesky meets non-positive pivots at the first iteration); one HIP
 launch per solve, csrc/dss2_wls_solve.hip.  No CPU fallback, no host read-back, recordable into a hipGraph or a launch plan.
+It keeps the gain matrix in LDS and serves up to ``max_nodes_per_graph()`` = 99 buses per graph.
+
+    wls_estimate_large(... same arguments ...) -> WLSResult
+
+The same estimator for up to ``max_nodes_per_graph_large()`` = 256 buses per graph (ober179): the gain matrix in a workspace in global
+memory, a blocked Cholesky, csrc/dss2_wls_large.hip.
 
     wls_bad_data(... same inputs ..., threshold=3.0, max_removals=0, confidence=0.95, s_min=1e-3) -> WLSBadDataResult
 
@@ -76,6 +82,31 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     c = (w_v, w_v, w_p, w_p), ``weights`` = (w_v, w_p, w_pf): (1, 1, 1) is the classical WLS, (lam_v, lam_p, lam_pf) the training
     loss's relative weighting.  Start: ``init`` [N, 2] (physical), or flat (v = 1, theta = 0); theta at slack buses is 0 and stays 0.
     ``tol = 0`` never stops early.  ``max_groups`` > 0 caps the number of workgroups (they stride over the graphs)."""
+    return _estimate(False, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                     max_groups)
+
+
+def max_nodes_per_graph_large() -> int:
+    """The largest bus count of a graph ``wls_estimate_large`` serves."""
+    return int(_lib.lib().dss2_wls_large_max_nodes())
+
+
+_WORKSPACES = {}                 # (device, bytes) -> the gain matrices' workspace of wls_estimate_large, kept (a recorded launch replays
+                                 # with its address); calls on one stream run one after the other, and no call needs its contents
+
+
+def wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                       init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                       weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
+    """``wls_estimate`` -- the same inputs, iteration, result and decisions -- for graphs of up to ``max_nodes_per_graph_large()``
+    buses, small ones included: the gain matrix lives in a workspace in global memory (one slice per workgroup, allocated once per
+    device and size) and is factorised in blocks, csrc/dss2_wls_large.hip.  Still one launch per solve, recordable."""
+    return _estimate(True, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                     max_groups)
+
+
+def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+              max_groups) -> WLSResult:
     _require_gpu(x, edge_index, edge_attr)
     n = int(nodes_per_graph)
     N = x.size(0)
@@ -93,7 +124,10 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
         _require_gpu(init)
         if init.dim() != 2 or tuple(init.shape) != (N, 2):
             raise ValueError(f"init must be [N, 2] = ({N}, 2), got {tuple(init.shape)}")
-    if n > max_nodes_per_graph():
+    if large and n > max_nodes_per_graph_large():
+        raise NotImplementedError(f"wls_estimate_large keeps a block column's panel of the gain matrix in LDS: at most "
+                                  f"{max_nodes_per_graph_large()} buses per graph, got {n}")
+    if not large and n > max_nodes_per_graph():
         raise NotImplementedError(f"wls_estimate keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
                                   f"got {n}")
     dev = x.device
@@ -101,7 +135,8 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     ea2, ldea = _rows(edge_attr)
     incidence, E = _incidence(edge_index, N)
     G = N // n
-    a = _lib.WlsSolveArgs()
+    big = _lib.WlsLargeArgs() if large else None
+    a = big.solve if large else _lib.WlsSolveArgs()
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
@@ -118,7 +153,15 @@ def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in res)
     vmm = torch.empty(130, dtype=_F32, device=dev)
     a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
-    _lib.check(_lib.lib().dss2_wls_solve(C.byref(a), _stream(x)), "dss2_wls_solve")
+    L = _lib.lib()
+    if not large:
+        _lib.check(L.dss2_wls_solve(C.byref(a), _stream(x)), "dss2_wls_solve")
+        return res
+    need = int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a))))
+    if (dev, need) not in _WORKSPACES:
+        _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    big.workspace, big.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
+    _lib.check(L.dss2_wls_solve_large(C.byref(big), _stream(x)), "dss2_wls_solve_large")
     return res
 
 

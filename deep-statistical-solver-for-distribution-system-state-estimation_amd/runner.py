@@ -334,12 +334,13 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 
 @torch.no_grad()
 def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None, **solver_kw) -> Dict[str, float]:
-    """The classical WLS estimator (``estimator.wls_estimate``) over a loader, scored like ``evaluate``: the ten EVAL_METRICS of its
+    """The classical WLS estimator (``estimator.wls_estimate``; ``wls_estimate_large`` above its bus count) over a loader, scored like ``evaluate``: the ten EVAL_METRICS of its
     state, averaged over the batches, plus ``wls_mean_iterations`` (Gauss-Newton updates per graph) and ``wls_not_converged`` (graphs
     that did not end with status 0).  ``model`` None: a flat start, the baseline a learned estimator is compared with; a model: its
     de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  ``bad_data`` = dict(threshold=...,
     max_removals=..., [confidence, s_min]): the solve is ``estimator.wls_bad_data`` with these, and the metrics gain ``wls_suspect``
-    (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed).  One device-to-host copy."""
+    (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed; ``wls_bad_data`` has no large form:
+    above ``estimator.max_nodes_per_graph()`` buses it refuses).  One device-to-host copy."""
     from . import estimator
     dev = stats[0].device
     acc = torch.zeros(10, dtype=torch.float64, device=dev)
@@ -355,7 +356,8 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
             init = torch.stack([out[:, 0] * stats[1][0] + stats[0][0], out[:, 1]], 1)
         zero = torch.zeros((), dtype=torch.int64, device=dev)
         if bad_data is None:
-            res = estimator.wls_estimate(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
+            solve = estimator.wls_estimate if nodes_per_graph <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
+            res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
             suspect, removed = zero, zero
         else:
             res = estimator.wls_bad_data(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw, **bad_data)

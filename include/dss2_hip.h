@@ -767,6 +767,27 @@ int dss2_wls_bad_data(const dss2_wls_bad_data_args* args_host, void* stream);
 /* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic): the solve's plus a fixed block */
 size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph);
 
+/* ---- dss2_wls_solve for graphs beyond its LDS cap (csrc/dss2_wls_large.hip): the same estimator, algorithm, outputs and decisions,
+ *      still ONE launch and one workgroup per graph, with the gain matrix in a caller-provided workspace in global memory and a blocked
+ *      Cholesky (16-column blocks: the diagonal block factorised by one wave, the panel below it solved by its rows' owners and kept in
+ *      LDS, the trailing update on 8 x 8 register tiles) and a blocked back substitution.  It serves every bus count from 1 to
+ *      dss2_wls_large_max_nodes() (256: 512 states); above it rc 2.  The workgroups stride over the graphs, each in its own slice of
+ *      the workspace: dss2_wls_large_workspace_bytes(nodes_per_graph, dss2_wls_large_groups(&solve)) bytes, 16-byte aligned, contents
+ *      irrelevant before and after.  No atomics, fixed summation orders: runs, batch positions and group counts agree to the bit.
+ *      rc 2 with a message for a null argument, a null, misaligned or short workspace, N not a multiple of n, n above the cap.  */
+typedef struct dss2_wls_large_args {
+  dss2_wls_solve_args solve;                      /* as for dss2_wls_solve                                                        */
+  void* workspace; uint64_t workspace_bytes;
+} dss2_wls_large_args;
+int dss2_wls_solve_large(const dss2_wls_large_args* args_host, void* stream);
+/* bytes of workspace `groups` workgroups need for graphs of nodes_per_graph buses (pure host arithmetic; 0 for a bus count not served) */
+size_t dss2_wls_large_workspace_bytes(int nodes_per_graph, int64_t groups);
+/* the number of workgroups dss2_wls_solve_large will launch for these arguments (max_groups honoured); 0 for arguments it refuses */
+int64_t dss2_wls_large_groups(const dss2_wls_solve_args* solve);
+int dss2_wls_large_max_nodes(void);
+/* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic) */
+size_t dss2_wls_large_lds_bytes(int nodes_per_graph);
+
 /* ---- batched small dense products in weight space (folding the edge MLP's second Linear into conv 0
  *      and the chain rule back): C[M,N] (+)= sum_b op(A_b)[M,K] . op(B_b)[K,N]  (+ u[i] * v[j]).     */
 typedef struct dss2_sgemm_desc {
