@@ -223,6 +223,13 @@ class WlsLargeArgs(C.Structure):
     _fields_ = [("solve", WlsSolveArgs), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
 
 
+class WlsRobustArgs(C.Structure):
+    """dss2_wls_robust_args (include/dss2_hip.h)."""
+    _fields_ = [("solve", WlsSolveArgs), ("gamma", C.c_double), ("plain_iters", C.c_int32), ("pad_", C.c_int32),
+                ("bus_q", C.c_void_p), ("edge_q", C.c_void_p), ("n_downweighted", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
 class WlsArgs(C.Structure):
     _fields_ = [("input", C.c_void_p), ("ld_in", C.c_int64),
                 ("edge_input", C.c_void_p), ("ld_ein", C.c_int64),
@@ -453,6 +460,8 @@ _SIGNATURES = {
     "dss2_wls_large_groups": (C.c_int64, [C.POINTER(WlsSolveArgs)]),
     "dss2_wls_large_max_nodes": (C.c_int, []),
     "dss2_wls_large_lds_bytes": (C.c_size_t, [C.c_int]),
+    "dss2_wls_robust": (C.c_int, [C.POINTER(WlsRobustArgs), C.c_void_p]),
+    "dss2_wls_robust_large": (C.c_int, [C.POINTER(WlsRobustArgs), C.c_void_p]),
     "dss2_small_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dss2_measure_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),

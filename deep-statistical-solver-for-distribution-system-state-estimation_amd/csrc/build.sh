@@ -14,8 +14,8 @@ NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
 NOPK_SRCS="${DSS2_NOPK_SRCS-dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_stack dss2_edge16}"      # (DSS2_NOPK_SRCS="" builds the diagnostic library WITH packed ops everywhere)
 mkdir -p "$OBJ"
 pids=()
-for src in dss2_api dss2_lanegroup dss2_gat dss2_gine dss2_gnn dss2_cheb dss2_stack dss2_gemm_prop dss2_gemm_chain dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_edge dss2_edge16 dss2_wgrad dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_loss dss2_wls_solve dss2_wls_bad_data dss2_wls_large dss2_optim dss2_dataset dss2_topology; do
-  if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_common.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_gemm_chain_kernel.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_weightspace.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wgrad_batch.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge16_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_lanegroup.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wls_core.hpp" -nt "$OBJ/$src.o" ] || { [ "$src" = dss2_wls_bad_data ] && [ "$HERE/dss2_wls_bad_data_core.hpp" -nt "$OBJ/$src.o" ]; } || [ "$ROOT/include/dss2_hip.h" -nt "$OBJ/$src.o" ]; then
+for src in dss2_api dss2_lanegroup dss2_gat dss2_gine dss2_gnn dss2_cheb dss2_stack dss2_gemm_prop dss2_gemm_chain dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_edge dss2_edge16 dss2_wgrad dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_loss dss2_wls_solve dss2_wls_bad_data dss2_wls_large dss2_wls_robust dss2_optim dss2_dataset dss2_topology; do
+  if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_common.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_gemm_chain_kernel.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_weightspace.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wgrad_batch.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge16_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_lanegroup.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wls_core.hpp" -nt "$OBJ/$src.o" ] || { [ "$src" = dss2_wls_bad_data ] && [ "$HERE/dss2_wls_bad_data_core.hpp" -nt "$OBJ/$src.o" ]; } || { { [ "$src" = dss2_wls_large ] || [ "$src" = dss2_wls_robust ]; } && [ "$HERE/dss2_wls_large_core.hpp" -nt "$OBJ/$src.o" ]; } || [ "$ROOT/include/dss2_hip.h" -nt "$OBJ/$src.o" ]; then
     extra=""; case " $NOPK_SRCS " in *" $src "*) extra="$NOPK";; esac
     $HIPCC $FLAGS $extra "$@" -c "$HERE/$src.hip" -o "$OBJ/$src.o" 2> >(grep -v "is not a recognized feature for this target" >&2) &
     pids+=($!)

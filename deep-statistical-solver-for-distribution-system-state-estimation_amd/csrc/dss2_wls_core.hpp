@@ -5,6 +5,11 @@
 // Every function that reads measurements takes a MASK: mask(id) says whether measurement `id` has been removed (its weight is then 0
 // everywhere it enters).  Ids are 4 i + k for bus i (global row), k in V, theta, P, Q, and 4 N + 2 e + k for stored branch e, k in
 // P_from, Q_from.  WsNoMask removes nothing and compiles to nothing; WsRemoved looks the id up in a short list in LDS.
+//
+// Beside it they take a WEIGHTING: a factor q on a measurement's weight that depends on its own residual at the state in LDS.
+// WsNoWeight (the default: the callers that know nothing of it) has none and compiles to nothing; WsHuber is the M-estimator's
+// q = gamma / t where t = sqrt(w) |r| > gamma (csrc/dss2_wls_robust.hip).  Whoever visits a measurement forms its q from the same
+// inputs in the same order: the same bits everywhere, nothing stored during the solve.
 #pragma once
 #include "dss2_common.hpp"
 
@@ -29,6 +34,28 @@ struct WsRemoved {                  // the ids removed so far: n of them, in LDS
     for (int q = 0; q < n; ++q) hit = hit || ids[q] == id;
     return hit;
   }
+};
+
+struct WsNoWeight {
+  static constexpr bool robust = false;
+  __device__ __forceinline__ WsNoWeight at(int) const { return *this; }
+};
+struct WsHuber {
+  static constexpr bool robust = true;
+  double gamma;
+  int plain_iters;                  // the iterations before this one run with q = 1
+  bool on;
+  double* bus_q; double* edge_q;    // [N, 4], [E, 2]: written by the objective pass (not read before)
+  int* cnt;                         // n ints of workgroup scratch for the objective pass's counts of q < 1
+  int* n_down;                      // this graph's count (thread 0 writes it)
+  __device__ __forceinline__ WsHuber at(int it) const { WsHuber h = *this; h.on = it >= plain_iters; return h; }
+  // q of a measurement of weight w and residual r.  Not t > gamma -- a NaN, a weight of 0 -- keeps 1.
+  __device__ __forceinline__ double factor(double w, double r) const {
+    const double t = sqrt(w) * fabs(r);
+    return (on && t > gamma) ? gamma / t : 1.0;
+  }
+  // rho(t) - t^2 above gamma, rho(t) = 2 gamma t - gamma^2: what a measurement with factor(w, r) < 1 adds to the plain sum w r^2
+  __device__ __forceinline__ double excess(double w, double r) const { return 2.0 * gamma * (sqrt(w) * fabs(r)) - gamma * gamma - w * r * r; }
 };
 
 // One end's view of a branch: the active and reactive power entering the branch at `self`, and their derivatives with respect to
@@ -89,9 +116,9 @@ __device__ __forceinline__ void ws_add(double* __restrict__ row, int r, const un
 
 // Row r of G and b[r]: every measurement with a non-zero Jacobian entry at state r, in a fixed order.  `row` is the zeroed row r
 // (columns 0 .. r, contiguous, LDS or global memory), `bvec` the right-hand side (entry r is written).
-template <class Mask>
+template <class Mask, class Wt = WsNoWeight>
 __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ row,
-                                                     double* __restrict__ bvec, const Mask& mask) {
+                                                     double* __restrict__ bvec, const Mask& mask, const Wt& wt = Wt()) {
   const int li = r >> 1, c = r & 1;
   if (c && g.slk[li]) { row[r] = 1.0; bvec[r] = 0.0; return; }     // a slack angle: identity row, held at 0
   const int64_t gi = g.base + li;
@@ -99,7 +126,8 @@ __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& 
   {   // the bus's own V (c = 0) or theta (c = 1)
     double Z[4], R[4];
     ws_meas(a.x + gi * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gi));
-    const double w = a.w_v * (c ? R[1] : R[0]);
+    double w = a.w_v * (c ? R[1] : R[0]);
+    if constexpr (Wt::robust) w *= wt.factor(w, (c ? Z[1] : Z[0]) - g.u[r]);
     row[r] += w;
     accb += w * ((c ? Z[1] : Z[0]) - g.u[r]);
   }
@@ -120,8 +148,11 @@ __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& 
           double hp = 0.0, hq = 0.0;
           if (lf == li) { hp += c ? f.dp[1] : f.dp[0]; hq += c ? f.dq[1] : f.dq[0]; }
           if (lt == li) { hp += c ? f.dp[3] : f.dp[2]; hq += c ? f.dq[3] : f.dq[2]; }
-          const double gp = a.w_pf * Re[0] * hp, gq = a.w_pf * Re[1] * hq;
-          accb += gp * (Ze[0] - f.p) + gq * (Ze[1] - f.q);
+          double wp = a.w_pf * Re[0], wq = a.w_pf * Re[1];
+          const double rp = Ze[0] - f.p, rq = Ze[1] - f.q;
+          if constexpr (Wt::robust) { wp *= wt.factor(wp, rp); wq *= wt.factor(wq, rq); }
+          const double gp = wp * hp, gq = wq * hq;
+          accb += gp * rp + gq * rq;
           ws_add(row, r, g.slk, 2 * lf, gp * f.dp[0] + gq * f.dq[0]);
           ws_add(row, r, g.slk, 2 * lf + 1, gp * f.dp[1] + gq * f.dq[1]);
           ws_add(row, r, g.slk, 2 * lt, gp * f.dp[2] + gq * f.dq[2]);
@@ -139,7 +170,7 @@ __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& 
     const int64_t gj = g.base + lj;
     double Z[4], R[4];
     ws_meas(a.x + gj * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gj));
-    const double wP = a.w_p * R[2], wQ = a.w_p * R[3];
+    double wP = a.w_p * R[2], wQ = a.w_p * R[3];
     if (wP == 0.0 && wQ == 0.0) continue;
     const int j0 = a.inc_rowptr[gj], j1 = a.inc_rowptr[gj + 1];
     const double vj = g.u[2 * lj], tj = g.u[2 * lj + 1];
@@ -154,8 +185,10 @@ __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& 
       if (lo == li) { hP -= c ? f.dp[3] : f.dp[2]; hQ -= c ? f.dq[3] : f.dq[2]; }
     }
     if (lj == li) { hP += c ? sP[1] : sP[0]; hQ += c ? sQ[1] : sQ[0]; }
+    const double rP = Z[2] - P, rQ = Z[3] - Q;
+    if constexpr (Wt::robust) { wP *= wt.factor(wP, rP); wQ *= wt.factor(wQ, rQ); }
     const double gP = wP * hP, gQ = wQ * hQ;
-    accb += gP * (Z[2] - P) + gQ * (Z[3] - Q);
+    accb += gP * rP + gQ * rQ;
     // pass 2: the columns
     ws_add(row, r, g.slk, 2 * lj, gP * sP[0] + gQ * sQ[0]);
     ws_add(row, r, g.slk, 2 * lj + 1, gP * sP[1] + gQ * sQ[1]);
@@ -171,22 +204,27 @@ __device__ __forceinline__ void ws_accumulate_row_at(const dss2_wls_solve_args& 
   bvec[r] = accb;
 }
 // ... in the packed lower triangle with the b row (the LDS kernels' layout)
-template <class Mask>
+template <class Mask, class Wt = WsNoWeight>
 __device__ __forceinline__ void ws_accumulate_row(const dss2_wls_solve_args& a, const WsGraph& g, int r, double* __restrict__ Gp, int ns,
-                                                  const Mask& mask) {
-  ws_accumulate_row_at(a, g, r, Gp + (size_t)r * (r + 1) / 2, Gp + (size_t)ns * (ns + 1) / 2, mask);
+                                                  const Mask& mask, const Wt& wt = Wt()) {
+  ws_accumulate_row_at(a, g, r, Gp + (size_t)r * (r + 1) / 2, Gp + (size_t)ns * (ns + 1) / 2, mask, wt);
 }
 
 // The two parts of J at the state in LDS for bus li: its own four measurements, and the flows of the branches it is the from-end of.
-template <class Mask>
-__device__ __forceinline__ void ws_objective_bus(const dss2_wls_solve_args& a, const WsGraph& g, int li, double& jbus, double& jbranch,
-                                                 const Mask& mask) {
+// With a weighting the sums are formed by the very same statements -- without any q < 1 they are the plain ones to the bit -- and a
+// measurement with q < 1 then trades its term for rho's tail (`excess`); its q is written, and the number of q < 1 among the bus's own
+// is returned.
+template <class Mask, class Wt = WsNoWeight>
+__device__ __forceinline__ int ws_objective_bus(const dss2_wls_solve_args& a, const WsGraph& g, int li, double& jbus, double& jbranch,
+                                                const Mask& mask, const Wt& wt = Wt()) {
   const int64_t gi = g.base + li;
   double Z[4], R[4];
   ws_meas(a.x + gi * a.ldx, a.x_mean, a.x_std, Z, R, mask, ws_bus_id(gi));
   const double vi = g.u[2 * li], ti = g.u[2 * li + 1];
   double P = 0.0, Q = 0.0;
   jbranch = 0.0;
+  double corr_e = 0.0, corr_b = 0.0;     // (with a weighting only)
+  int down = 0;
   const int k0 = a.inc_rowptr[gi], k1 = a.inc_rowptr[gi + 1];
   for (int k = k0; k < k1; ++k) {
     int e, lo; bool is_from;
@@ -198,23 +236,44 @@ __device__ __forceinline__ void ws_objective_bus(const dss2_wls_solve_args& a, c
       ws_meas(a.edge_attr + (int64_t)e * a.ldea, a.edge_mean, a.edge_std, Ze, Re, mask, ws_edge_id(a, e));
       const double dp = Ze[0] - f.p, dq = Ze[1] - f.q;
       jbranch += a.w_pf * (Re[0] * dp * dp + Re[1] * dq * dq);
+      if constexpr (Wt::robust) {
+        const double rr[2] = {dp, dq};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const double w = a.w_pf * Re[c], q = wt.factor(w, rr[c]);
+          wt.edge_q[2 * (int64_t)e + c] = q;
+          if (q < 1.0) { ++down; corr_e += wt.excess(w, rr[c]); }
+        }
+      }
     }
   }
   const double dv = Z[0] - vi, dt = Z[1] - ti, dP = Z[2] - P, dQ = Z[3] - Q;
   jbus = a.w_v * (R[0] * dv * dv + R[1] * dt * dt) + a.w_p * (R[2] * dP * dP + R[3] * dQ * dQ);
+  if constexpr (Wt::robust) {
+    const double rr[4] = {dv, dt, dP, dQ};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const double w = (c < 2 ? a.w_v : a.w_p) * R[c], q = wt.factor(w, rr[c]);
+      wt.bus_q[4 * gi + c] = q;
+      if (q < 1.0) { ++down; corr_b += wt.excess(w, rr[c]); }
+    }
+    jbus += corr_b; jbranch += corr_e;
+  }
+  return down;
 }
 
 // max that keeps a NaN (either operand), so the result does not depend on the order of the reduction
 __device__ __forceinline__ double ws_nanmax(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmax(x, y)); }
 
 // G, b <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read the packed array before are done with).
-template <int T, class Mask>
-__device__ __forceinline__ void ws_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ Gp, int ns, int tid, const Mask& mask) {
+template <int T, class Mask, class Wt = WsNoWeight>
+__device__ __forceinline__ void ws_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ Gp, int ns, int tid, const Mask& mask,
+                                        const Wt& wt = Wt()) {
   const size_t tri = (size_t)ns * (ns + 1) / 2;
   __syncthreads();
   for (size_t p = tid; p < tri + ns; p += T) Gp[p] = 0.0;
   __syncthreads();
-  for (int r = tid; r < ns; r += T) ws_accumulate_row(a, g, r, Gp, ns, mask);
+  for (int r = tid; r < ns; r += T) ws_accumulate_row(a, g, r, Gp, ns, mask, wt);
 }
 
 // Cholesky of the packed array WITH the b row (row ns), which leaves as y = L^-1 b.  False: a pivot was <= 0 or not finite (every
@@ -309,14 +368,15 @@ __device__ __forceinline__ void ws_decide(const dss2_wls_solve_args& a, const do
 // Gauss-Newton from the state in LDS: at most a.max_iter iterations (the trip count is fixed; a graph that has stopped skips the body,
 // uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status (1, then 0 or 2) and t.last.  Returns whether the
 // factorisation failed (uniform).  Ends with a barrier.
-template <int T, class Mask>
+// wt.at(it) is the weighting of iteration `it`.
+template <int T, class Mask, class Wt = WsNoWeight>
 __device__ __forceinline__ bool ws_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, const WsLds& l, int ns, int tid,
-                                                const Mask& mask, WsTally& t) {
+                                                const Mask& mask, WsTally& t, const Wt& wt = Wt()) {
   t.status = 1;
   bool active = true, failed = false;  // uniform over the workgroup
   for (int it = 0; it < a.max_iter; ++it) {
     if (active) {
-      ws_form<T>(a, g, l.Gp, ns, tid, mask);      // (its first barrier: u, slk of the start or of the previous iteration; the previous ctl has been read)
+      ws_form<T>(a, g, l.Gp, ns, tid, mask, wt.at(it));      // (its first barrier: u, slk of the start or of the previous iteration; the previous ctl has been read)
       const bool ok = ws_factor<T>(l.Gp, ns, tid);
       ws_back_substitute<T>(l.Gp, l.bvec, l.du, ns, tid);
       // ---- the decision: one thread writes it, all read it after the barrier
@@ -332,19 +392,27 @@ __device__ __forceinline__ bool ws_gauss_newton(const dss2_wls_solve_args& a, co
 }
 
 // J at the state in LDS: per-bus parts into the first 2 n words of the packed array, summed by thread 0 in bus order (jb, je are
-// thread 0's).  The packed array is overwritten.  Ends with a barrier.
-template <int T, class Mask>
+// thread 0's).  The packed array is overwritten.  Ends with a barrier.  With a weighting the per-bus counts of q < 1 go through
+// wt.cnt and thread 0 writes their sum to wt.n_down: no atomics.
+template <int T, class Mask, class Wt = WsNoWeight>
 __device__ __forceinline__ void ws_objective(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ Gp, int tid, const Mask& mask,
-                                             double& jb, double& je) {
+                                             double& jb, double& je, const Wt& wt = Wt()) {
   for (int k = tid; k < g.n; k += T) {
     double b, e;
-    ws_objective_bus(a, g, k, b, e, mask);
+    const int down = ws_objective_bus(a, g, k, b, e, mask, wt);
     Gp[k] = b; Gp[g.n + k] = e;
+    if constexpr (Wt::robust) wt.cnt[k] = down;
   }
   __syncthreads();
   jb = 0.0; je = 0.0;
-  if (tid == 0)
+  if (tid == 0) {
     for (int k = 0; k < g.n; ++k) { jb += Gp[k]; je += Gp[g.n + k]; }
+    if constexpr (Wt::robust) {
+      int down = 0;
+      for (int k = 0; k < g.n; ++k) down += wt.cnt[k];
+      *wt.n_down = down;
+    }
+  }
   __syncthreads();
 }
 

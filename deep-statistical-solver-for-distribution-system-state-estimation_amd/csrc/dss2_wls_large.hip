@@ -30,221 +30,10 @@
 // another of the same workgroup is separated by a barrier (all waves of a workgroup share their CU's vector cache).
 // No atomics, one writer per value, fixed summation orders; a slice's contents before a graph do not matter (A is zeroed, Pt, Ld are
 // written before they are read; what is read from Pt beyond row ns only reaches tile entries that are not stored).
-#include "dss2_wls_core.hpp"
+// The device functions live in dss2_wls_large_core.hpp, which csrc/dss2_wls_robust.hip shares.
+#include "dss2_wls_large_core.hpp"
 
 namespace dss2 {
-
-constexpr int WL_T = 256;                // threads of a workgroup
-constexpr int WL_NB = 16;                // columns of a block column
-constexpr int WL_TILE = 8;               // the trailing update's register tile is WL_TILE x WL_TILE
-constexpr int WL_MAX_NODES = 256;        // two workgroups of the largest graph share the LDS of a CU
-constexpr int WL_GROUPS = 512;
-
-typedef double wl_d2 __attribute__((ext_vector_type(2)));
-
-__host__ __device__ constexpr size_t wl_row_off(int r) {
-  return (size_t)(WL_NB * WL_NB) * ((size_t)(r / WL_NB) * (r / WL_NB + 1) / 2) + (size_t)(r % WL_NB) * WL_NB * (r / WL_NB + 1);
-}
-__host__ __device__ constexpr size_t wl_graph_doubles(int n) {       // block rows of ns + 1 rows, the lower triangle of blocks
-  return (size_t)(WL_NB * WL_NB) * ((size_t)((2 * n + WL_NB) / WL_NB) * ((2 * n + WL_NB) / WL_NB + 1) / 2);
-}
-__host__ __device__ constexpr int wl_pstride(int n) { return (2 * n + 1 + WL_TILE - 1) / WL_TILE * WL_TILE; }
-__host__ __device__ constexpr size_t wl_lds_doubles(int n) { return (size_t)WL_NB * wl_pstride(n) + WL_NB * WL_NB + WL_NB + 4 * (size_t)n; }
-__host__ __device__ constexpr size_t wl_lds_bytes(int n) { return wl_lds_doubles(n) * 8 + 16 + ((size_t)n + 15) / 16 * 16; }
-static_assert(2 * wl_lds_bytes(WL_MAX_NODES) <= (size_t)kMaxLdsBytes, "two workgroups of the largest graph per CU");
-static_assert(WL_NB == 16 && WL_TILE == 8 && WL_NB % WL_TILE == 0, "the unrolled loops and the readlane indices assume 16 and 8");
-
-struct WlLds { double* Pt; double* Ld; double* invd; double* u; double* du; int* ctl; unsigned char* slk; int S; };
-__device__ __forceinline__ WlLds wl_carve(unsigned char* smem, int n) {
-  WlLds l;
-  l.S = wl_pstride(n);
-  l.Pt = reinterpret_cast<double*>(smem);
-  l.Ld = l.Pt + (size_t)WL_NB * l.S;
-  l.invd = l.Ld + WL_NB * WL_NB;
-  l.u = l.invd + WL_NB;
-  l.du = l.u + 2 * n;
-  l.ctl = reinterpret_cast<int*>(smem + wl_lds_doubles(n) * 8);
-  l.slk = smem + wl_lds_doubles(n) * 8 + 16;
-  return l;
-}
-
-// lane `lane`'s x in every lane (`lane` is a constant after unrolling: two v_readlane_b32)
-__device__ __forceinline__ double wl_lane(double x, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane), __builtin_amdgcn_readlane(__double2loint(x), lane));
-}
-
-// A <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read A before are done with).
-__device__ __forceinline__ void wl_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, int ns, int tid) {
-  const size_t pairs = wl_graph_doubles(g.n) / 2;
-  __syncthreads();
-  for (size_t p = tid; p < pairs; p += WL_T) reinterpret_cast<wl_d2*>(A)[p] = wl_d2{0.0, 0.0};
-  __syncthreads();
-  for (int r = tid; r < ns; r += WL_T) ws_accumulate_row_at(a, g, r, A + wl_row_off(r), A + wl_row_off(ns), WsNoMask());
-}
-
-// Wave 0: the diagonal block at (j0, j0), w columns wide, factorised in registers; lane i < w holds row i.  Returns whether every pivot
-// was > 0 and finite (uniform over the wave).
-__device__ __forceinline__ bool wl_factor_diag(double* __restrict__ A, const WlLds& l, int j0, int w, int lane) {
-  const bool mine = lane < w;
-  double* grow = A + wl_row_off(j0 + (mine ? lane : 0)) + j0;
-  double row[WL_NB];
-#pragma unroll
-  for (int k = 0; k < WL_NB; ++k) row[k] = (mine && k <= lane) ? grow[k] : 0.0;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < WL_NB; ++j) {
-    const double d = wl_lane(row[j], j);
-    const bool good = d > 0.0 && d < INFINITY;
-    if (j < w) ok = ok && good;
-    const double s = good ? sqrt(d) : 1.0;
-    row[j] = lane == j ? s : row[j] / s;              // (0 in the lanes above the diagonal)
-#pragma unroll
-    for (int k = j + 1; k < WL_NB; ++k) {
-      const double lkj = wl_lane(row[j], k);
-      if (lane >= k) row[k] -= row[j] * lkj;
-    }
-  }
-  if (lane < WL_NB) {
-    double dg = 1.0;
-#pragma unroll
-    for (int k = 0; k < WL_NB; ++k) {
-      const bool in = mine && k <= lane;
-      l.Ld[lane * WL_NB + k] = in ? row[k] : 0.0;
-      if (in) grow[k] = row[k];
-      if (k == lane) dg = row[k];
-    }
-    l.invd[lane] = 1.0 / dg;                          // (1 beyond the block's width)
-  }
-  return ok;
-}
-
-// The panel below the diagonal block: thread i solves row i (j1 .. ns, the b row included) against Ld.  Beyond the block's width
-// (the last block column only) A holds zeros and Ld is 0: those entries stay 0.
-__device__ __forceinline__ void wl_panel(double* __restrict__ A, const WlLds& l, int j0, int w, int ns, int tid) {
-  for (int i = j0 + w + tid; i <= ns; i += WL_T) {
-    wl_d2* prow = reinterpret_cast<wl_d2*>(A + wl_row_off(i) + j0);
-    double x[WL_NB];
-#pragma unroll
-    for (int k = 0; k < WL_NB / 2; ++k) { const wl_d2 v = prow[k]; x[2 * k] = v.x; x[2 * k + 1] = v.y; }
-#pragma unroll
-    for (int j = 0; j < WL_NB; ++j) {
-      x[j] *= l.invd[j];
-#pragma unroll
-      for (int m = j + 1; m < WL_NB; ++m) x[m] -= x[j] * l.Ld[m * WL_NB + j];
-    }
-#pragma unroll
-    for (int k = 0; k < WL_NB / 2; ++k) prow[k] = wl_d2{x[2 * k], x[2 * k + 1]};
-#pragma unroll
-    for (int k = 0; k < WL_NB; ++k) l.Pt[(size_t)k * l.S + i] = x[k];
-  }
-}
-
-// A[i, c] -= sum_j Pt[j][i] Pt[j][c] for j1 <= c <= i <= ns, c < ns, on 8 x 8 tiles: tile p = ti (ti + 1) / 2 + tj, tj <= ti
-__device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds& l, int j1, int ns, int tid) {
-  const int ntr = (ns + 1 - j1 + WL_TILE - 1) / WL_TILE, ntiles = ntr * (ntr + 1) / 2;
-  for (int p = tid; p < ntiles; p += WL_T) {
-    int ti = (int)((sqrtf(8.f * (float)p + 1.f) - 1.f) * 0.5f);
-    while (ti * (ti + 1) / 2 > p) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= p) ++ti;
-    const int tj = p - ti * (ti + 1) / 2;
-    const int i0 = j1 + WL_TILE * ti, c0 = j1 + WL_TILE * tj;
-    double acc[WL_TILE][WL_TILE];
-#pragma unroll
-    for (int q = 0; q < WL_TILE; ++q)
-#pragma unroll
-      for (int c = 0; c < WL_TILE; ++c) acc[q][c] = 0.0;
-#pragma unroll 4
-    for (int j = 0; j < WL_NB; ++j) {
-      const wl_d2* pr2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + i0);
-      const wl_d2* pc2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + c0);
-      double pr[WL_TILE], pc[WL_TILE];
-#pragma unroll
-      for (int q = 0; q < WL_TILE / 2; ++q) {
-        const wl_d2 v = pr2[q], c = pc2[q];
-        pr[2 * q] = v.x; pr[2 * q + 1] = v.y; pc[2 * q] = c.x; pc[2 * q + 1] = c.y;
-      }
-#pragma unroll
-      for (int q = 0; q < WL_TILE; ++q)
-#pragma unroll
-        for (int c = 0; c < WL_TILE; ++c) acc[q][c] += pr[q] * pc[c];
-    }
-    if (tj < ti && i0 + WL_TILE - 1 <= ns) {            // a whole tile below the diagonal
-#pragma unroll
-      for (int q = 0; q < WL_TILE; ++q) {
-        wl_d2* arow = reinterpret_cast<wl_d2*>(A + wl_row_off(i0 + q) + c0);
-#pragma unroll
-        for (int c = 0; c < WL_TILE / 2; ++c) {
-          wl_d2 v = arow[c];
-          v.x -= acc[q][2 * c]; v.y -= acc[q][2 * c + 1];
-          arow[c] = v;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < WL_TILE; ++q) {
-        const int i = i0 + q;
-        if (i > ns) continue;
-        double* arow = A + wl_row_off(i);
-#pragma unroll
-        for (int c = 0; c < WL_TILE; ++c)
-          if (c0 + c <= i && c0 + c < ns) arow[c0 + c] -= acc[q][c];
-      }
-    }
-  }
-}
-
-// Cholesky of A WITH the b row (row ns), which leaves as y = L^-1 b.  Wave 0's return value says whether every pivot was good.
-__device__ __forceinline__ bool wl_factor(double* __restrict__ A, const WlLds& l, int ns, int tid) {
-  bool ok = true;
-  for (int j0 = 0; j0 < ns; j0 += WL_NB) {
-    const int w = ns - j0 < WL_NB ? ns - j0 : WL_NB;
-    __syncthreads();                                   // the rows' owners, or the previous trailing update, have written the block
-    if (tid < 64) ok = wl_factor_diag(A, l, j0, w, tid) && ok;
-    __syncthreads();
-    wl_panel(A, l, j0, w, ns, tid);
-    __syncthreads();
-    if (j0 + w < ns) wl_trailing(A, l, j0 + w, ns, tid);
-  }
-  return ok;
-}
-
-// L^T du = y, block column by block column from the last; starts and ends with a barrier
-__device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A, const WlLds& l, int ns, int tid) {
-  __syncthreads();
-  const double* y = A + wl_row_off(ns);
-  for (int c = tid; c < ns; c += WL_T) l.du[c] = y[c];
-  __syncthreads();
-  for (int j0 = (ns - 1) / WL_NB * WL_NB; j0 >= 0; j0 -= WL_NB) {
-    const int w = ns - j0 < WL_NB ? ns - j0 : WL_NB;
-    if (tid < 64) {                                    // the diagonal block: lane c owns column c of it and du[j0 + c]
-      const bool mine = tid < w;
-      double Lc[WL_NB], dg = 1.0;
-#pragma unroll
-      for (int j = 0; j < WL_NB; ++j) {
-        Lc[j] = (mine && j >= tid && j < w) ? A[wl_row_off(j0 + j) + j0 + tid] : 0.0;
-        if (mine && j == tid) dg = Lc[j];
-      }
-      const double inv = 1.0 / dg;
-      double yv = mine ? l.du[j0 + tid] : 0.0;
-#pragma unroll
-      for (int j = WL_NB - 1; j >= 0; --j) {
-        if (j < w) {
-          const double xj = wl_lane(yv * inv, j);
-          if (tid < j) yv -= Lc[j] * xj;
-          else if (tid == j) yv = xj;
-        }
-      }
-      if (mine) l.du[j0 + tid] = yv;
-    }
-    __syncthreads();
-    for (int c = tid; c < j0; c += WL_T) {             // the columns left of the block: rows of A, coalesced over c
-      double s = l.du[c];
-      for (int j = 0; j < w; ++j) s -= A[wl_row_off(j0 + j) + c] * l.du[j0 + j];
-      l.du[c] = s;
-    }
-    __syncthreads();
-  }
-}
 
 __global__ void __launch_bounds__(WL_T) wls_large_kernel(const dss2_wls_large_args b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wl_smem[];
@@ -286,21 +75,6 @@ __global__ void __launch_bounds__(WL_T) wls_large_kernel(const dss2_wls_large_ar
   }
 }
 
-static int64_t wl_grid(const dss2_wls_solve_args& a) {
-  const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
-  int64_t grid = WL_GROUPS;
-  if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
-  return n_graphs < grid ? n_graphs : grid;
-}
-static int wl_check_size(const dss2_wls_solve_args& a) {
-  if (int rc = ws_check_batch(a, "wls_solve_large")) return rc;
-  if (a.nodes_per_graph > WL_MAX_NODES) {
-    set_error("wls_solve_large: %d buses per graph: at most %d (a block column's panel of the gain matrix lives in LDS)", a.nodes_per_graph, WL_MAX_NODES);
-    return 2;
-  }
-  return 0;
-}
-
 }  // namespace dss2
 
 using namespace dss2;
@@ -309,12 +83,9 @@ extern "C" int dss2_wls_large_max_nodes(void) { return WL_MAX_NODES; }
 extern "C" size_t dss2_wls_large_lds_bytes(int nodes_per_graph) {
   return nodes_per_graph > 0 && nodes_per_graph <= WL_MAX_NODES ? wl_lds_bytes(nodes_per_graph) : 0;
 }
-extern "C" size_t dss2_wls_large_workspace_bytes(int nodes_per_graph, int64_t groups) {
-  if (nodes_per_graph <= 0 || nodes_per_graph > WL_MAX_NODES || groups <= 0) return 0;
-  return (size_t)groups * wl_graph_doubles(nodes_per_graph) * 8;
-}
+extern "C" size_t dss2_wls_large_workspace_bytes(int nodes_per_graph, int64_t groups) { return wl_workspace_bytes(nodes_per_graph, groups); }
 extern "C" int64_t dss2_wls_large_groups(const dss2_wls_solve_args* ap) {
-  if (!ap || wl_check_size(*ap) != 0 || ap->max_groups < 0) return 0;
+  if (!ap || wl_check_size(*ap, "wls_solve_large") != 0 || ap->max_groups < 0) return 0;
   return wl_grid(*ap);
 }
 
@@ -327,22 +98,12 @@ extern "C" int dss2_wls_solve_large(const dss2_wls_large_args* bp, void* stream)
 static int dss2_wls_large_launch(const dss2_wls_large_args* bp, void* stream) {
   const dss2_wls_large_args& b = *bp;
   const dss2_wls_solve_args& a = b.solve;
-  if (int rc = wl_check_size(a)) return rc;
-  if (a.max_groups < 0) { set_error("wls_solve_large: bad leading dimension or max_groups"); return 2; }
-  const int n = a.nodes_per_graph;
-  const int64_t grid = wl_grid(a);
-  const size_t need = dss2_wls_large_workspace_bytes(n, grid);
-  if (!b.workspace || (reinterpret_cast<uintptr_t>(b.workspace) & 15) != 0) { set_error("wls_solve_large: the workspace is null or not 16-byte aligned"); return 2; }
-  if (b.workspace_bytes < need) {
-    set_error("wls_solve_large: the workspace has %llu bytes, %lld workgroups of %d buses need %llu", (unsigned long long)b.workspace_bytes,
-              (long long)grid, n, (unsigned long long)need);
-    return 2;
-  }
-  if (int rc = ws_check_rest(a, "wls_solve_large")) return rc;
+  if (int rc = wl_check_size(a, "wls_solve_large")) return rc;
+  if (int rc = wl_check_workspace(a, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;
   hipStream_t s = as_stream(stream);
   static std::atomic<uint32_t> done{0};
   if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&wls_large_kernel), done, "wls_solve_large")) return rc;
   launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
-  hipLaunchKernelGGL(wls_large_kernel, dim3((unsigned)grid), dim3(WL_T), wl_lds_bytes(n), s, b);
+  hipLaunchKernelGGL(wls_large_kernel, dim3((unsigned)wl_grid(a)), dim3(WL_T), wl_lds_bytes(a.nodes_per_graph), s, b);
   return check_launch("wls_solve_large");
 }

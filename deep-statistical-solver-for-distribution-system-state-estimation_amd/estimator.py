@@ -20,6 +20,12 @@ memory, a blocked Cholesky, csrc/dss2_wls_large.hip.
 
 The rest of the classical estimator on the same solve and in the same single launch (csrc/dss2_wls_bad_data.hip): the chi-square test
 on J, residual sensitivities and normalized residuals, removal of the largest one followed by a re-solve, the state's standard deviation.
+It inverts the gain matrix in LDS: up to 99 buses per graph.
+
+    wls_robust(... same inputs ..., gamma=3.0, plain_iters=1, large=None) -> WLSRobustResult
+
+The second classical answer to gross errors, for every bus count up to 256: the Huber M-estimator by iteratively re-weighted
+Gauss-Newton on the kernels of ``wls_estimate`` and ``wls_estimate_large`` (csrc/dss2_wls_robust.hip).  No covariance, one launch.
 """
 from __future__ import annotations
 
@@ -106,7 +112,9 @@ def wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_
 
 
 def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-              max_groups) -> WLSResult:
+              max_groups, robust=None):
+    """The plain solve (``robust`` None -> WLSResult) or the Huber one (``robust`` = (gamma, plain_iters) -> WLSRobustResult) on the LDS
+    kernel or on the blocked one (``large``)."""
     _require_gpu(x, edge_index, edge_attr)
     n = int(nodes_per_graph)
     N = x.size(0)
@@ -124,19 +132,23 @@ def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_st
         _require_gpu(init)
         if init.dim() != 2 or tuple(init.shape) != (N, 2):
             raise ValueError(f"init must be [N, 2] = ({N}, 2), got {tuple(init.shape)}")
+    who = ("wls_estimate_large" if large else "wls_estimate") if robust is None else f"wls_robust (large={large})"
     if large and n > max_nodes_per_graph_large():
-        raise NotImplementedError(f"wls_estimate_large keeps a block column's panel of the gain matrix in LDS: at most "
+        raise NotImplementedError(f"{who} keeps a block column's panel of the gain matrix in LDS: at most "
                                   f"{max_nodes_per_graph_large()} buses per graph, got {n}")
     if not large and n > max_nodes_per_graph():
-        raise NotImplementedError(f"wls_estimate keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
+        raise NotImplementedError(f"{who} keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
                                   f"got {n}")
     dev = x.device
     x2, ldx = _rows(x)
     ea2, ldea = _rows(edge_attr)
     incidence, E = _incidence(edge_index, N)
     G = N // n
-    big = _lib.WlsLargeArgs() if large else None
-    a = big.solve if large else _lib.WlsSolveArgs()
+    if robust is not None:
+        big = _lib.WlsRobustArgs()
+    else:
+        big = _lib.WlsLargeArgs() if large else None
+    a = big.solve if big is not None else _lib.WlsSolveArgs()
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
@@ -154,15 +166,55 @@ def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_st
     vmm = torch.empty(130, dtype=_F32, device=dev)
     a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
     L = _lib.lib()
-    if not large:
-        _lib.check(L.dss2_wls_solve(C.byref(a), _stream(x)), "dss2_wls_solve")
-        return res
-    need = int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a))))
-    if (dev, need) not in _WORKSPACES:
-        _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    big.workspace, big.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
-    _lib.check(L.dss2_wls_solve_large(C.byref(big), _stream(x)), "dss2_wls_solve_large")
+    if robust is not None:
+        res = WLSRobustResult(*res, bus_q=torch.empty(N, 4, dtype=torch.float64, device=dev),
+                              edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
+                              n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
+        big.gamma, big.plain_iters = robust
+        big.bus_q, big.edge_q, big.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
+    if large:
+        need = int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a))))
+        if (dev, need) not in _WORKSPACES:
+            _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        big.workspace, big.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
+    name = ("dss2_wls_robust" if robust is not None else "dss2_wls_solve") + ("_large" if large else "")
+    _lib.check(getattr(L, name)(C.byref(a if big is None else big), _stream(x)), name)
     return res
+
+
+class WLSRobustResult(NamedTuple):
+    state: torch.Tensor          # as in WLSResult
+    objective: torch.Tensor      # [G, 2] fp64: bus part and branch part of the Huber cost at the final fp64 state
+    iterations: torch.Tensor
+    status: torch.Tensor
+    last_step: torch.Tensor
+    bus_q: torch.Tensor          # [N, 4] fp64: the weight factors of (V, theta, P, Q) at the final state, 1 where not down-weighted
+    edge_q: torch.Tensor         # [E, 2] fp64: of (P_from, Q_from)
+    n_downweighted: torch.Tensor  # [G] int32: measurements with q < 1
+
+
+def wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+               init: Optional[torch.Tensor] = None, max_iter: int = 20, tol: float = 1e-6,
+               weights: Sequence[float] = (1.0, 1.0, 1.0), gamma: float = 3.0, plain_iters: int = 1,
+               large: Optional[bool] = None, max_groups: int = 0) -> WLSRobustResult:
+    """The Huber M-estimator on ``wls_estimate``'s measurement model, by iteratively re-weighted Gauss-Newton: with w_i = c_k R^-1 the
+    weight of measurement i, r_i its residual and t_i = sqrt(w_i) |r_i| at the current iterate, every iteration from number
+    ``plain_iters`` on (counted from 0) is ``wls_estimate``'s with w_i q_i in place of w_i, q_i = gamma / t_i where t_i > gamma and
+    1 elsewhere; the first ``plain_iters`` are plain (the default, 1, moves a flat start next to the solution before residuals are
+    judged).  Start, slack angles, failure, decision, statuses and ``max_groups`` are ``wls_estimate``'s, and ``gamma = inf`` gives its
+    result to the bit.  Reported at the final state: the Huber cost (t^2 up to gamma, 2 gamma t - gamma^2 above), every q, and the count
+    of q < 1 per graph.  ``large`` None: the LDS kernel up to ``max_nodes_per_graph()`` buses, the blocked kernel above (up to
+    ``max_nodes_per_graph_large()``); True / False force one.  gamma = 3 is the default for a reason: at 1.5, on ober179 (condition
+    number 2.4e13), three to four measurements per graph are down-weighted and the state is worse than plain WLS."""
+    gamma = float(gamma)
+    if not gamma > 0:
+        raise ValueError("gamma must be > 0")
+    if int(plain_iters) != plain_iters or plain_iters < 0:
+        raise ValueError("plain_iters must be an integer >= 0")
+    if large is None:
+        large = int(nodes_per_graph) > max_nodes_per_graph()
+    return _estimate(bool(large), x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                     max_groups, robust=(gamma, int(plain_iters)))
 
 
 class WLSBadDataResult(NamedTuple):

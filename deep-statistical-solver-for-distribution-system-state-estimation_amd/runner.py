@@ -340,11 +340,17 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
     de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  ``bad_data`` = dict(threshold=...,
     max_removals=..., [confidence, s_min]): the solve is ``estimator.wls_bad_data`` with these, and the metrics gain ``wls_suspect``
     (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed; ``wls_bad_data`` has no large form:
-    above ``estimator.max_nodes_per_graph()`` buses it refuses).  One device-to-host copy."""
+    above ``estimator.max_nodes_per_graph()`` buses it refuses).  The keyword ``robust`` = dict(gamma=..., [plain_iters]) (taken out of
+    ``solver_kw``): the solve is ``estimator.wls_robust`` with these, the Huber M-estimator, for every bus count up to
+    ``estimator.max_nodes_per_graph_large()``, and the metrics gain ``wls_downweighted`` (measurements with a weight factor below 1 at the
+    solution); not together with ``bad_data``.  One device-to-host copy."""
     from . import estimator
+    robust = solver_kw.pop("robust", None)
+    if bad_data is not None and robust is not None:
+        raise ValueError("evaluate_wls: bad_data and robust are two answers to gross errors: give one of them")
     dev = stats[0].device
     acc = torch.zeros(10, dtype=torch.float64, device=dev)
-    tally = torch.zeros(5, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged, suspect graphs, removals
+    tally = torch.zeros(5, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged, suspect graphs, removals (robust: down-weighted measurements)
     n = 0
     if model is not None:
         model.eval()
@@ -355,7 +361,10 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
             out = run_model(model, x[:, :8], ei, ea[:, :6])
             init = torch.stack([out[:, 0] * stats[1][0] + stats[0][0], out[:, 1]], 1)
         zero = torch.zeros((), dtype=torch.int64, device=dev)
-        if bad_data is None:
+        if robust is not None:
+            res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw, **robust)
+            suspect, removed = zero, res.n_downweighted.sum()
+        elif bad_data is None:
             solve = estimator.wls_estimate if nodes_per_graph <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
             res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
             suspect, removed = zero, zero
@@ -374,6 +383,8 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
     if bad_data is not None:
         m["wls_suspect"] = int(n_suspect)
         m["wls_removed"] = int(n_removed)
+    if robust is not None:
+        m["wls_downweighted"] = int(n_removed)
     return m
 
 
@@ -403,7 +414,12 @@ def main(argv=None):
                     "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); needs one bus count")
     ap.add_argument("--wls-bad-data", type=float, default=None, metavar="THRESHOLD", help="the --wls-baseline lines (implied) through "
                     "estimator.wls_bad_data: up to 5 measurements per graph are removed while the largest normalized residual exceeds THRESHOLD")
+    ap.add_argument("--wls-robust", type=float, default=None, metavar="GAMMA", help="the --wls-baseline lines (implied) through "
+                    "estimator.wls_robust, the Huber M-estimator with threshold GAMMA (3.0 is the usual choice); any bus count up to 256; "
+                    "not together with --wls-bad-data")
     a = ap.parse_args(argv)
+    if a.wls_robust is not None and a.wls_bad_data is not None:
+        ap.error("--wls-robust and --wls-bad-data are exclusive")
     hp = {k: getattr(a, k) for k in HYPER}
     if a.model == "SkipMPN":
         hp["dim_out"] = hp["dim_nodes"]
@@ -468,14 +484,15 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(f"epoch {epoch:4d}  train_loss {tl:.6g}  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()) +
               f"  ({time.perf_counter() - t0:.2f} s)", flush=True)
-    if a.wls_baseline or a.wls_bad_data is not None:
+    if a.wls_baseline or a.wls_bad_data is not None or a.wls_robust is not None:
         ds = getattr(test_loader, "dataset", None)
         n_bus = getattr(ds, "n", None) if ds is not None else synthetic.load_grid(a.case).n
         if n_bus is None:
             raise ValueError("--wls-baseline needs one bus count per graph (the data list mixes bus counts)")
         for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
             bad_data = dict(threshold=a.wls_bad_data, max_removals=5) if a.wls_bad_data is not None else None
-            m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data)
+            robust = dict(gamma=a.wls_robust) if a.wls_robust is not None else None
+            m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data, robust=robust)
             print(f"wls baseline ({label})  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()), flush=True)
     if a.save:                                                       # dss2_run.py:240-247
         torch.save({"epoch": a.epochs - 1, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},

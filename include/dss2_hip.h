@@ -788,6 +788,29 @@ int dss2_wls_large_max_nodes(void);
 /* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic) */
 size_t dss2_wls_large_lds_bytes(int nodes_per_graph);
 
+/* ---- the Huber M-estimator on the same kernels (csrc/dss2_wls_robust.hip): iteratively re-weighted Gauss-Newton, ONE launch.  With
+ *      w_i = c_k R^-1 the weight dss2_wls_solve gives measurement i, r_i = z_i - h_i(u) and t_i = sqrt(w_i) |r_i| at the current
+ *      iterate, the factor q_i is gamma / t_i where t_i > gamma and the iteration's number (from 0) is >= plain_iters, and 1 elsewhere
+ *      (a NaN and a weight of 0 keep 1); an iteration is dss2_wls_solve's with w_i q_i in place of w_i in G and b.  Start, slack
+ *      angles, pivot test, decision, statuses and max_groups are dss2_wls_solve's; gamma = +inf gives its five outputs to the bit.
+ *      At the final state, with weighting on: solve.objective is the Huber cost sum rho(t_i), rho = t^2 (dss2_wls_solve's term) up to
+ *      gamma and 2 gamma t - gamma^2 above, split into bus part and branch part; q per measurement; the count of q < 1 per graph.
+ *      dss2_wls_robust keeps the gain matrix in LDS (dss2_wls_solve's size limit; workspace unused); dss2_wls_robust_large is the
+ *      blocked form with dss2_wls_solve_large's workspace (dss2_wls_large_workspace_bytes, dss2_wls_large_groups) and size limit.
+ *      No atomics, fixed summation orders.  rc 2 with a message for what the plain entries refuse, gamma not > 0 (a NaN included),
+ *      plain_iters < 0, a null output. */
+typedef struct dss2_wls_robust_args {
+  dss2_wls_solve_args solve;                      /* as for dss2_wls_solve; objective is the Huber cost                           */
+  double gamma;                                   /* > 0; +inf: the plain estimator                                               */
+  int32_t plain_iters; int32_t pad_;              /* >= 0: the first plain_iters iterations run with q = 1                        */
+  double* bus_q;                                  /* [N, 4]  q of (V, theta, P, Q) at the final state                             */
+  double* edge_q;                                 /* [E, 2]  q of (P_from, Q_from) (an edge that leaves its graph is not written) */
+  int32_t* n_downweighted;                        /* [G]     measurements with q < 1                                              */
+  void* workspace; uint64_t workspace_bytes;      /* dss2_wls_robust_large only                                                   */
+} dss2_wls_robust_args;
+int dss2_wls_robust(const dss2_wls_robust_args* args_host, void* stream);
+int dss2_wls_robust_large(const dss2_wls_robust_args* args_host, void* stream);
+
 /* ---- batched small dense products in weight space (folding the edge MLP's second Linear into conv 0
  *      and the chain rule back): C[M,N] (+)= sum_b op(A_b)[M,K] . op(B_b)[K,N]  (+ u[i] * v[j]).     */
 typedef struct dss2_sgemm_desc {
