@@ -1,7 +1,8 @@
 // Bad-data detection and removal on the batched WLS estimator, fp64, gfx950: the solve of dss2_wls_solve.hip, then the covariance,
 // residual sensitivities, normalized residuals, the chi-square test and the removal of the largest normalized residual, repeated --
 // all inside ONE launch, one workgroup per graph, the launch geometry of wls_solve.  The device functions of the solve are those of
-// dss2_wls_core.hpp, with a mask that gives a removed measurement the weight 0 everywhere it enters; the measurement pass, the arg-max,
+// dss2_wls_core.hpp, with a mask that gives a removed measurement the weight 0 everywhere it enters, and so are a graph's prologue,
+// the state store, the launch path and the entry wrapper (ws_graph, ws_store_state, ws_launch, ws_entry); the measurement pass, the arg-max,
 // the decision and the outputs are those of dss2_wls_bad_data_core.hpp, with Sigma addressed on the packed triangle (BdPacked).
 //
 //   LDS   the solve's carve (packed G with the b row, u, du, ctl, slack flags), then a fixed block:
@@ -71,8 +72,7 @@ __global__ void __launch_bounds__(T) wls_bad_data_kernel(const dss2_wls_bad_data
   vminmax_fold(a.vminmax, vlv, vhv);
   const int64_t n_graphs = a.n_nodes / n;
   for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
-    WsGraph g;
-    g.base = gr * n; g.n = n; g.kk = (double)vlv * (double)vlv; g.u = l.u; g.slk = l.slk;
+    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
     ws_load_start<T>(a, g, l, tid);
     WsTally t = {0, 1, 0.0};
     int nrem = 0, n_active = 0;          // nrem is uniform; n_active is thread 0's
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(T) wls_bad_data_kernel(const dss2_wls_bad_data
       }
     }
     // ---- outputs: the state in fp32, J at the fp64 state with the final weights, the test, the tallies
-    for (int q = tid; q < ns; q += T) a.state[(g.base + (q >> 1)) * 2 + (q & 1)] = (float)l.u[q];
+    ws_store_state<T>(a, g, ns, tid);
     double jb, je;
     ws_objective<T>(a, g, l.Gp, tid, WsRemoved{r.rem, nrem}, jb, je);
     if (tid == 0) bd_finish(b, gr, t, jb, je, n_active, nrem, slots, l.slk, n);
@@ -116,30 +116,13 @@ extern "C" size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph) {
   return nodes_per_graph > 0 ? bd_bytes(nodes_per_graph) : 0;
 }
 
-static int dss2_wls_bad_data_launch(const dss2_wls_bad_data_args* bp, void* stream);
-extern "C" int dss2_wls_bad_data(const dss2_wls_bad_data_args* bp, void* stream) {
-  if (!bp) { dss2::set_error("dss2_wls_bad_data: null argument"); return 2; }
-  DSS2_RECORD([b = *bp](void* s_) { return dss2_wls_bad_data_launch(&b, s_); });
-  return dss2_wls_bad_data_launch(bp, stream);
-}
-static int dss2_wls_bad_data_launch(const dss2_wls_bad_data_args* bp, void* stream) {
-  const dss2_wls_bad_data_args& b = *bp;
-  const dss2_wls_solve_args& a = b.solve;
-  if (int rc = ws_check_args(a, "wls_bad_data", BD_EXTRA_BYTES)) return rc;
-  const int n = a.nodes_per_graph;
-  const bool narrow = 2 * n <= WS_NARROW_STATES;
+static int wls_bad_data_launch(const dss2_wls_bad_data_args& b, void* stream) {
+  if (int rc = ws_check_args(b.solve, "wls_bad_data", BD_EXTRA_BYTES)) return rc;
+  const int n = b.solve.nodes_per_graph;
   if (2 * n > 256) { set_error("wls_bad_data: %d states do not fit the workgroup that owns the covariance's rows", 2 * n); return 2; }
   if (int rc = bd_check_params(b, "wls_bad_data")) return rc;
-  hipStream_t s = as_stream(stream);
-  const int64_t grid = ws_grid(a);
-  const size_t lds = bd_bytes(n);
-  launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
-  if (narrow) {
-    hipLaunchKernelGGL(wls_bad_data_kernel<64>, dim3((unsigned)grid), dim3(64), lds, s, b);
-  } else {
-    static std::atomic<uint32_t> done{0};
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&wls_bad_data_kernel<256>), done, "wls_bad_data")) return rc;
-    hipLaunchKernelGGL(wls_bad_data_kernel<256>, dim3((unsigned)grid), dim3(256), lds, s, b);
-  }
-  return check_launch("wls_bad_data");
+  return ws_launch<wls_bad_data_kernel<64>, wls_bad_data_kernel<256>>(b, bd_bytes(n), "wls_bad_data", as_stream(stream));
+}
+extern "C" int dss2_wls_bad_data(const dss2_wls_bad_data_args* bp, void* stream) {
+  return ws_entry(bp, stream, "dss2_wls_bad_data", wls_bad_data_launch);
 }

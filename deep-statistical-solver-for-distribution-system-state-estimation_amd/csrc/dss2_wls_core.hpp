@@ -1,6 +1,14 @@
-// Device functions of the batched fp64 WLS estimator that its kernels share: csrc/dss2_wls_solve.hip (the solve alone) and
-// csrc/dss2_wls_bad_data.hip (the solve, the covariance, normalized residuals and the removal loop).  The LDS layout, the row
-// ownership and the order of every sum are described in the header of dss2_wls_solve.hip; nothing here depends on which kernel runs it.
+// What every kernel of the batched fp64 WLS estimator shares.  All four WLS translation units include it, directly or through
+// dss2_wls_large_core.hpp and dss2_wls_bad_data_core.hpp: csrc/dss2_wls_solve.hip (the solve alone), csrc/dss2_wls_bad_data.hip (the solve, the covariance,
+// normalized residuals and the removal loop), csrc/dss2_wls_large.hip (the solve on a blocked gain matrix in global memory) and
+// csrc/dss2_wls_robust.hip (the Huber M-estimator, on both storage forms).  Here live
+//   - the device functions: measurements, the row owners' assembly, the packed Cholesky, the decision, the objective;
+//   - a graph's prologue (ws_graph) and the plain epilogue (ws_store_state, ws_finish), once for every kernel;
+//   - wls_lds_kernel, the ONE kernel body with the gain matrix in LDS: the plain and the Huber estimator are two instantiations of it;
+//   - the host side: the argument checks, ws_launch (the launch path of every kernel on the LDS carve) and ws_entry (the null check
+//     and the launch plan's record of every entry).
+// The LDS layout, the row ownership and the order of every sum are described in the header of dss2_wls_solve.hip; nothing here
+// depends on which kernel runs it.
 //
 // Every function that reads measurements takes a MASK: mask(id) says whether measurement `id` has been removed (its weight is then 0
 // everywhere it enters).  Ids are 4 i + k for bus i (global row), k in V, theta, P, Q, and 4 N + 2 e + k for stored branch e, k in
@@ -58,6 +66,17 @@ struct WsHuber {
   __device__ __forceinline__ double excess(double w, double r) const { return 2.0 * gamma * (sqrt(w) * fabs(r)) - gamma * gamma - w * r * r; }
 };
 
+// What a kernel body that is a template on its argument struct asks of it: the `solve` block and the weighting.  (cnt and n_down of
+// a WsHuber are the kernel's to set: where its scratch lies, which graph it is at.)
+__host__ __device__ __forceinline__ const dss2_wls_solve_args& ws_solve_block(const dss2_wls_solve_args& a) { return a; }
+template <class Args>
+__host__ __device__ __forceinline__ const dss2_wls_solve_args& ws_solve_block(const Args& b) { return b.solve; }
+__device__ __forceinline__ WsNoWeight ws_weighting(const dss2_wls_solve_args&) { return WsNoWeight(); }
+__device__ __forceinline__ WsNoWeight ws_weighting(const dss2_wls_large_args&) { return WsNoWeight(); }
+__device__ __forceinline__ WsHuber ws_weighting(const dss2_wls_robust_args& b) {
+  return WsHuber{b.gamma, b.plain_iters, true, b.bus_q, b.edge_q, nullptr, nullptr};
+}
+
 // One end's view of a branch: the active and reactive power entering the branch at `self`, and their derivatives with respect to
 // (v_self, theta_self, v_other, theta_other).  With delta = theta_self - theta_other this is data.py:370-373 at the from-end and
 // data.py:374-376 at the to-end (cos is even, sin is odd).
@@ -100,6 +119,12 @@ struct WsGraph {                    // what the row owners need of the graph bei
   const double* u;                  // LDS state
   const unsigned char* slk;         // LDS slack flags
 };
+// graph gr of a batch of n-bus graphs (vlv: vminmax_fold's low-voltage base)
+__device__ __forceinline__ WsGraph ws_graph(int64_t gr, int n, float vlv, const double* u, const unsigned char* slk) {
+  WsGraph g;
+  g.base = gr * n; g.n = n; g.kk = (double)vlv * (double)vlv; g.u = u; g.slk = slk;
+  return g;
+}
 
 // incidence entry k -> stored branch, the other end's LOCAL bus (outside [0, n): an edge that leaves the graph, ignored), orientation
 __device__ __forceinline__ bool ws_slot(const dss2_wls_solve_args& a, const WsGraph& g, int k, int& e, int& lo, bool& is_from) {
@@ -416,6 +441,51 @@ __device__ __forceinline__ void ws_objective(const dss2_wls_solve_args& a, const
   __syncthreads();
 }
 
+// The state in LDS, in fp32
+template <int T>
+__device__ __forceinline__ void ws_store_state(const dss2_wls_solve_args& a, const WsGraph& g, int ns, int tid) {
+  for (int r = tid; r < ns; r += T) a.state[(g.base + (r >> 1)) * 2 + (r & 1)] = (float)g.u[r];
+}
+// The plain epilogue of graph gr: the state in fp32, J at the fp64 state (ws_objective through `scratch`: 2 n doubles that are idle
+// by now), thread 0's tallies.  Ends with ws_objective's barrier: the next graph of this workgroup may reuse the LDS.
+template <int T, class Wt>
+__device__ __forceinline__ void ws_finish(const dss2_wls_solve_args& a, const WsGraph& g, int64_t gr, double* __restrict__ scratch, int ns,
+                                          int tid, const WsTally& t, const Wt& wt) {
+  ws_store_state<T>(a, g, ns, tid);
+  double jb, je;
+  ws_objective<T>(a, g, scratch, tid, WsNoMask(), jb, je, wt);
+  if (tid == 0) {
+    a.objective[2 * gr] = jb; a.objective[2 * gr + 1] = je;
+    a.iterations[gr] = t.iters; a.status[gr] = t.status; a.last_step[gr] = t.last;
+  }
+}
+
+// The kernel with the gain matrix in LDS: one workgroup of T threads per graph, the workgroups stride over the graphs.  Args is
+// dss2_wls_solve_args (the plain estimator) or dss2_wls_robust_args (the Huber one: ws_weighting gives its WsHuber); the two differ
+// in the weighting alone, and WsNoWeight's part of every statement compiles to nothing.
+template <int T, class Args>
+__global__ void __launch_bounds__(T) wls_lds_kernel(const Args b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];
+  const dss2_wls_solve_args& a = ws_solve_block(b);
+  const int n = a.nodes_per_graph, ns = 2 * n;
+  const WsLds l = ws_carve(ws_smem, n);
+  const int tid = threadIdx.x;
+  float vlv, vhv;
+  vminmax_fold(a.vminmax, vlv, vhv);
+  auto wt = ws_weighting(b);
+  using Wt = decltype(wt);
+  if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Gp + 2 * n);   // behind the objective's 2 n per-bus parts: n ints, inside the packed array
+  const int64_t n_graphs = a.n_nodes / n;
+  for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
+    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
+    ws_load_start<T>(a, g, l, tid);
+    WsTally t = {0, 1, 0.0};
+    ws_gauss_newton<T>(a, g, l, ns, tid, WsNoMask(), t, wt);
+    if constexpr (Wt::robust) wt.n_down = b.n_downweighted + gr;
+    ws_finish<T>(a, g, gr, l.Gp, ns, tid, t, wt);
+  }
+}
+
 constexpr int WS_NARROW_STATES = 64;     // up to 64 states: one wave; above: four
 constexpr int WS_GROUPS_NARROW = 2048, WS_GROUPS_WIDE = 512;
 
@@ -449,6 +519,32 @@ inline int64_t ws_grid(const dss2_wls_solve_args& a) {
   int64_t grid = 2 * a.nodes_per_graph <= WS_NARROW_STATES ? WS_GROUPS_NARROW : WS_GROUPS_WIDE;
   if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
   return n_graphs < grid ? n_graphs : grid;
+}
+
+// The launch of a kernel on the LDS carve, after the entry's checks: K64 for one wave (up to WS_NARROW_STATES states), K256 above;
+// `lds` is the kernel's dynamic LDS.  K256 may need more than the 64 KiB a kernel gets unasked: the once-per-device flag of that
+// request is a static of this template, so every kernel pair has its own.
+template <auto K64, auto K256, class Args>
+inline int ws_launch(const Args& b, size_t lds, const char* who, hipStream_t s) {
+  const dss2_wls_solve_args& a = ws_solve_block(b);
+  const int64_t grid = ws_grid(a);
+  launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
+  if (2 * a.nodes_per_graph <= WS_NARROW_STATES) {
+    hipLaunchKernelGGL(K64, dim3((unsigned)grid), dim3(64), lds, s, b);
+  } else {
+    static std::atomic<uint32_t> done{0};
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(K256), done, who)) return rc;
+    hipLaunchKernelGGL(K256, dim3((unsigned)grid), dim3(256), lds, s, b);
+  }
+  return check_launch(who);
+}
+
+// An extern "C" entry: the null check, the launch plan's record (a closure over a COPY of the arguments), the launch body
+template <class Args>
+inline int ws_entry(const Args* bp, void* stream, const char* name, int (*launch)(const Args&, void*)) {
+  if (!bp) { set_error("%s: null argument", name); return 2; }
+  DSS2_RECORD([b = *bp, launch](void* s_) { return launch(b, s_); });
+  return launch(*bp, stream);
 }
 
 }  // namespace dss2

@@ -30,52 +30,9 @@
 // another of the same workgroup is separated by a barrier (all waves of a workgroup share their CU's vector cache).
 // No atomics, one writer per value, fixed summation orders; a slice's contents before a graph do not matter (A is zeroed, Pt, Ld are
 // written before they are read; what is read from Pt beyond row ns only reaches tile entries that are not stored).
-// The device functions live in dss2_wls_large_core.hpp, which csrc/dss2_wls_robust.hip shares.
+// The kernel body (wls_blocked_kernel), its device functions and the launch path live in dss2_wls_large_core.hpp, which
+// csrc/dss2_wls_robust.hip shares; this file instantiates the plain estimator.
 #include "dss2_wls_large_core.hpp"
-
-namespace dss2 {
-
-__global__ void __launch_bounds__(WL_T) wls_large_kernel(const dss2_wls_large_args b) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wl_smem[];
-  const dss2_wls_solve_args& a = b.solve;
-  const int n = a.nodes_per_graph, ns = 2 * n;
-  const WlLds l = wl_carve(wl_smem, n);
-  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wl_graph_doubles(n);
-  const int tid = threadIdx.x;
-  float vlv, vhv;
-  vminmax_fold(a.vminmax, vlv, vhv);
-  const int64_t n_graphs = a.n_nodes / n;
-  for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
-    WsGraph g;
-    g.base = gr * n; g.n = n; g.kk = (double)vlv * (double)vlv; g.u = l.u; g.slk = l.slk;
-    const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
-    ws_load_start<WL_T>(a, g, start, tid);
-    WsTally t = {0, 1, 0.0};
-    bool active = true;                                // uniform over the workgroup
-    for (int it = 0; it < a.max_iter; ++it) {
-      if (active) {
-        wl_form(a, g, A, ns, tid);
-        const bool ok = wl_factor(A, l, ns, tid);
-        wl_back_substitute(A, l, ns, tid);
-        ws_decide(a, l.du, l.ctl, ns, tid, ok, t);
-        __syncthreads();
-        if (l.ctl[1]) for (int r = tid; r < ns; r += WL_T) l.u[r] += l.du[r];
-        active = l.ctl[0] == 0;
-      }
-    }
-    __syncthreads();
-    // ---- outputs, as wls_solve_kernel's (the objective's per-bus parts go through du)
-    for (int r = tid; r < ns; r += WL_T) a.state[(g.base + (r >> 1)) * 2 + (r & 1)] = (float)l.u[r];
-    double jb, je;
-    ws_objective<WL_T>(a, g, l.du, tid, WsNoMask(), jb, je);      // (its last barrier: the next graph of this workgroup reuses the LDS)
-    if (tid == 0) {
-      a.objective[2 * gr] = jb; a.objective[2 * gr + 1] = je;
-      a.iterations[gr] = t.iters; a.status[gr] = t.status; a.last_step[gr] = t.last;
-    }
-  }
-}
-
-}  // namespace dss2
 
 using namespace dss2;
 
@@ -89,21 +46,11 @@ extern "C" int64_t dss2_wls_large_groups(const dss2_wls_solve_args* ap) {
   return wl_grid(*ap);
 }
 
-static int dss2_wls_large_launch(const dss2_wls_large_args* bp, void* stream);
-extern "C" int dss2_wls_solve_large(const dss2_wls_large_args* bp, void* stream) {
-  if (!bp) { dss2::set_error("dss2_wls_solve_large: null argument"); return 2; }
-  DSS2_RECORD([b = *bp](void* s_) { return dss2_wls_large_launch(&b, s_); });
-  return dss2_wls_large_launch(bp, stream);
+static int wls_solve_large_launch(const dss2_wls_large_args& b, void* stream) {
+  if (int rc = wl_check_size(b.solve, "wls_solve_large")) return rc;
+  if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;
+  return wl_launch<wls_blocked_kernel<dss2_wls_large_args>>(b, "wls_solve_large", as_stream(stream));
 }
-static int dss2_wls_large_launch(const dss2_wls_large_args* bp, void* stream) {
-  const dss2_wls_large_args& b = *bp;
-  const dss2_wls_solve_args& a = b.solve;
-  if (int rc = wl_check_size(a, "wls_solve_large")) return rc;
-  if (int rc = wl_check_workspace(a, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;
-  hipStream_t s = as_stream(stream);
-  static std::atomic<uint32_t> done{0};
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(&wls_large_kernel), done, "wls_solve_large")) return rc;
-  launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
-  hipLaunchKernelGGL(wls_large_kernel, dim3((unsigned)wl_grid(a)), dim3(WL_T), wl_lds_bytes(a.nodes_per_graph), s, b);
-  return check_launch("wls_solve_large");
+extern "C" int dss2_wls_solve_large(const dss2_wls_large_args* bp, void* stream) {
+  return ws_entry(bp, stream, "dss2_wls_solve_large", wls_solve_large_launch);
 }

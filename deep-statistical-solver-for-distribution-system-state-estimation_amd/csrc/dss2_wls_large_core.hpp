@@ -1,7 +1,9 @@
-// Device functions of the blocked fp64 WLS solve with the gain matrix in global memory, shared by csrc/dss2_wls_large.hip (the plain
-// estimator) and csrc/dss2_wls_robust.hip (the Huber M-estimator's large form): the workspace layout, the LDS carve, the rows' assembly,
-// the blocked Cholesky and back substitution, and the entries' size check, grid and workspace check.  The layout and every step are
-// described in the header of dss2_wls_large.hip; nothing here depends on which kernel runs it.
+// The blocked fp64 WLS solve with the gain matrix in global memory, shared by csrc/dss2_wls_large.hip (the plain estimator) and
+// csrc/dss2_wls_robust.hip (the Huber M-estimator's large form): the workspace layout, the LDS carve, the rows' assembly, the blocked
+// Cholesky and back substitution, the Gauss-Newton loop (wl_gauss_newton), the ONE kernel body on this layout (wls_blocked_kernel: the
+// two estimators are two instantiations of it), and the host side -- the entries' size check, grid and workspace check, and their
+// launch path (wl_launch).  The layout and every step are described in the header of dss2_wls_large.hip; nothing here depends on which
+// kernel runs it.
 #pragma once
 #include "dss2_wls_core.hpp"
 
@@ -220,6 +222,55 @@ __device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A,
   }
 }
 
+// ws_gauss_newton's counterpart on this layout: Gauss-Newton from the state in LDS, at most a.max_iter iterations (the trip count is
+// fixed; a graph that has stopped skips the body, uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status
+// (1, then 0 or 2) and t.last.  wt.at(it) is the weighting of iteration `it`.  Ends with a barrier.
+template <class Wt>
+__device__ __forceinline__ void wl_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, const WlLds& l, int ns,
+                                                int tid, WsTally& t, const Wt& wt) {
+  t.status = 1;
+  bool active = true;                                  // uniform over the workgroup
+  for (int it = 0; it < a.max_iter; ++it) {
+    if (active) {
+      wl_form(a, g, A, ns, tid, wt.at(it));
+      const bool ok = wl_factor(A, l, ns, tid);
+      wl_back_substitute(A, l, ns, tid);
+      ws_decide(a, l.du, l.ctl, ns, tid, ok, t);
+      __syncthreads();
+      if (l.ctl[1]) for (int r = tid; r < ns; r += WL_T) l.u[r] += l.du[r];
+      active = l.ctl[0] == 0;
+    }
+  }
+  __syncthreads();
+}
+
+// The kernel on this layout: one workgroup of WL_T threads per graph and workspace slice, the workgroups stride over the graphs.
+// Args is dss2_wls_large_args (the plain estimator) or dss2_wls_robust_args (the Huber one), as for wls_lds_kernel.
+template <class Args>
+__global__ void __launch_bounds__(WL_T) wls_blocked_kernel(const Args b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char wl_smem[];
+  const dss2_wls_solve_args& a = ws_solve_block(b);
+  const int n = a.nodes_per_graph, ns = 2 * n;
+  const WlLds l = wl_carve(wl_smem, n);
+  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wl_graph_doubles(n);
+  const int tid = threadIdx.x;
+  float vlv, vhv;
+  vminmax_fold(a.vminmax, vlv, vhv);
+  auto wt = ws_weighting(b);
+  using Wt = decltype(wt);
+  if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Pt);   // the panel is idle after the last factorisation: n ints of its 16 (2 n + 1) doubles
+  const int64_t n_graphs = a.n_nodes / n;
+  for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
+    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
+    const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
+    ws_load_start<WL_T>(a, g, start, tid);
+    WsTally t = {0, 1, 0.0};
+    wl_gauss_newton(a, g, A, l, ns, tid, t, wt);
+    if constexpr (Wt::robust) wt.n_down = b.n_downweighted + gr;
+    ws_finish<WL_T>(a, g, gr, l.du, ns, tid, t, wt);   // (the objective's per-bus parts go through du)
+  }
+}
+
 // ---- host side: the grid and the size check of the entries that run on this layout (`who` names the entry in the message)
 inline int64_t wl_grid(const dss2_wls_solve_args& a) {
   const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
@@ -252,6 +303,16 @@ inline int wl_check_workspace(const dss2_wls_solve_args& a, const void* workspac
     return 2;
   }
   return ws_check_rest(a, who);
+}
+// The launch of kernel K on this layout, after the entry's checks (ws_launch's counterpart; the flag is K's own here too)
+template <auto K, class Args>
+inline int wl_launch(const Args& b, const char* who, hipStream_t s) {
+  const dss2_wls_solve_args& a = b.solve;
+  static std::atomic<uint32_t> done{0};
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(K), done, who)) return rc;
+  launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
+  hipLaunchKernelGGL(K, dim3((unsigned)wl_grid(a)), dim3(WL_T), wl_lds_bytes(a.nodes_per_graph), s, b);
+  return check_launch(who);
 }
 
 }  // namespace dss2

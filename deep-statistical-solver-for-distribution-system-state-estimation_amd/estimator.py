@@ -111,10 +111,13 @@ def wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_
                      max_groups)
 
 
-def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-              max_groups, robust=None):
-    """The plain solve (``robust`` None -> WLSResult) or the Huber one (``robust`` = (gamma, plain_iters) -> WLSRobustResult) on the LDS
-    kernel or on the blocked one (``large``)."""
+def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                 max_groups, refuse_size, check_own=None):
+    """Validates the arguments every estimator here shares and fills ``a``, the ``WlsSolveArgs`` of its launch -- outputs included.
+    The caller's own checks run at their place among these: ``check_own()`` (its ValueErrors) after the scalars', ``refuse_size(n)``
+    (its NotImplementedError) after every ValueError.  Returns (keep, out, N, E, G): ``keep`` is what ``a`` points into and nothing
+    else holds -- the row views, the statistics vectors, the kept ``init``, the vminmax buffer -- to be held until the launch has been
+    issued; ``out`` is the WLSResult of fresh tensors that ``a`` writes."""
     _require_gpu(x, edge_index, edge_attr)
     n = int(nodes_per_graph)
     N = x.size(0)
@@ -126,59 +129,74 @@ def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_st
         raise ValueError("tol must be >= 0")
     if len(weights) != 3:
         raise ValueError("weights = (w_v, w_p, w_pf)")
+    if check_own is not None:
+        check_own()
     if x.dim() != 2 or x.size(1) < 10 or edge_attr.dim() != 2 or edge_attr.size(1) < 10:
         raise ValueError("x must be the full [N, 11] node tensor and edge_attr the full [E, 13] edge tensor")
     if init is not None:
         _require_gpu(init)
         if init.dim() != 2 or tuple(init.shape) != (N, 2):
             raise ValueError(f"init must be [N, 2] = ({N}, 2), got {tuple(init.shape)}")
-    who = ("wls_estimate_large" if large else "wls_estimate") if robust is None else f"wls_robust (large={large})"
-    if large and n > max_nodes_per_graph_large():
-        raise NotImplementedError(f"{who} keeps a block column's panel of the gain matrix in LDS: at most "
-                                  f"{max_nodes_per_graph_large()} buses per graph, got {n}")
-    if not large and n > max_nodes_per_graph():
-        raise NotImplementedError(f"{who} keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
-                                  f"got {n}")
+    refuse_size(n)
     dev = x.device
     x2, ldx = _rows(x)
     ea2, ldea = _rows(edge_attr)
     incidence, E = _incidence(edge_index, N)
     G = N // n
-    if robust is not None:
-        big = _lib.WlsRobustArgs()
-    else:
-        big = _lib.WlsLargeArgs() if large else None
-    a = big.solve if big is not None else _lib.WlsSolveArgs()
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
     a.efrom, a.eto, a.inc_rowptr, a.inc_ent = incidence
     a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, E, n, int(max_iter), float(tol)
     a.w_v, a.w_p, a.w_pf = (float(w) for w in weights)
-    keep = None
+    kept_init = None
     if init is not None:
-        keep, ld_init = _rows(init.detach())
-        a.init, a.ld_init = keep.data_ptr(), ld_init
-    res = WLSResult(torch.empty(N, 2, dtype=_F32, device=dev), torch.empty(G, 2, dtype=torch.float64, device=dev),
+        kept_init, ld_init = _rows(init.detach())
+        a.init, a.ld_init = kept_init.data_ptr(), ld_init
+    out = WLSResult(torch.empty(N, 2, dtype=_F32, device=dev), torch.empty(G, 2, dtype=torch.float64, device=dev),
                     torch.empty(G, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev),
                     torch.empty(G, dtype=torch.float64, device=dev))
-    a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in res)
+    a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in out)
     vmm = torch.empty(130, dtype=_F32, device=dev)
     a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
+    return (x2, ea2, stats, kept_init, vmm), out, N, E, G
+
+
+def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+              max_groups, robust=None):
+    """The plain solve (``robust`` None -> WLSResult) or the Huber one (``robust`` = (gamma, plain_iters) -> WLSRobustResult) on the LDS
+    kernel or on the blocked one (``large``)."""
+    who = ("wls_estimate_large" if large else "wls_estimate") if robust is None else f"wls_robust (large={large})"
+
+    def refuse_size(n):
+        if large and n > max_nodes_per_graph_large():
+            raise NotImplementedError(f"{who} keeps a block column's panel of the gain matrix in LDS: at most "
+                                      f"{max_nodes_per_graph_large()} buses per graph, got {n}")
+        if not large and n > max_nodes_per_graph():
+            raise NotImplementedError(f"{who} keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
+                                      f"got {n}")
+
+    # the one place that picks the struct: plain LDS -> the solve block itself; every other form carries it as .solve
+    args = _lib.WlsRobustArgs() if robust is not None else _lib.WlsLargeArgs() if large else _lib.WlsSolveArgs()
+    a = getattr(args, "solve", args)
+    keep, res, N, E, G = _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter,
+                                      tol, weights, max_groups, refuse_size)
+    n, dev = a.nodes_per_graph, x.device
     L = _lib.lib()
     if robust is not None:
         res = WLSRobustResult(*res, bus_q=torch.empty(N, 4, dtype=torch.float64, device=dev),
                               edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
                               n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
-        big.gamma, big.plain_iters = robust
-        big.bus_q, big.edge_q, big.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
+        args.gamma, args.plain_iters = robust
+        args.bus_q, args.edge_q, args.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
     if large:
         need = int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a))))
         if (dev, need) not in _WORKSPACES:
             _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        big.workspace, big.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
+        args.workspace, args.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
     name = ("dss2_wls_robust" if robust is not None else "dss2_wls_solve") + ("_large" if large else "")
-    _lib.check(getattr(L, name)(C.byref(a if big is None else big), _stream(x)), name)
+    _lib.check(getattr(L, name)(C.byref(args), _stream(x)), name)
+    del keep                     # (held until here: the launch has been issued)
     return res
 
 
@@ -246,65 +264,36 @@ def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     S_i >= ``s_min`` and 0 below it (critical measurements).  The largest rN above ``threshold`` is removed (ties: the smallest id).
     Ids: 4 i + k for bus i (row of x), k in V, theta, P, Q; 4 N + 2 e + k for stored branch e, k in P_from, Q_from.
     With ``max_removals = 0`` the first five fields are ``wls_estimate``'s, bit for bit."""
-    _require_gpu(x, edge_index, edge_attr)
-    n = int(nodes_per_graph)
-    N = x.size(0)
-    if n < 1 or N == 0 or N % n != 0:
-        raise ValueError(f"x has {N} rows: not a positive multiple of nodes_per_graph = {nodes_per_graph}")
-    if int(max_iter) < 1:
-        raise ValueError("max_iter must be at least 1")
-    if not tol >= 0:
-        raise ValueError("tol must be >= 0")
-    if len(weights) != 3:
-        raise ValueError("weights = (w_v, w_p, w_pf)")
-    if not threshold > 0:
-        raise ValueError("threshold must be > 0")
-    if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
-        raise ValueError("max_removals must be an integer in 0 .. 64")
-    if not 0 < confidence < 1:
-        raise ValueError("confidence must be in (0, 1)")
-    if not 0 < s_min < 1:
-        raise ValueError("s_min must be in (0, 1)")
-    if x.dim() != 2 or x.size(1) < 10 or edge_attr.dim() != 2 or edge_attr.size(1) < 10:
-        raise ValueError("x must be the full [N, 11] node tensor and edge_attr the full [E, 13] edge tensor")
-    if init is not None:
-        _require_gpu(init)
-        if init.dim() != 2 or tuple(init.shape) != (N, 2):
-            raise ValueError(f"init must be [N, 2] = ({N}, 2), got {tuple(init.shape)}")
-    L = _lib.lib()
-    if L.dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
-        raise NotImplementedError(f"wls_bad_data keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
-    dev = x.device
-    x2, ldx = _rows(x)
-    ea2, ldea = _rows(edge_attr)
-    incidence, E = _incidence(edge_index, N)
-    G, slots = N // n, max(int(max_removals), 1)
+    def check_own():
+        if not threshold > 0:
+            raise ValueError("threshold must be > 0")
+        if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
+            raise ValueError("max_removals must be an integer in 0 .. 64")
+        if not 0 < confidence < 1:
+            raise ValueError("confidence must be in (0, 1)")
+        if not 0 < s_min < 1:
+            raise ValueError("s_min must be in (0, 1)")
+
+    def refuse_size(n):
+        if _lib.lib().dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
+            raise NotImplementedError(f"wls_bad_data keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
+
     b = _lib.WlsBadDataArgs()
-    a = b.solve
-    a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
-    stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
-    a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
-    a.efrom, a.eto, a.inc_rowptr, a.inc_ent = incidence
-    a.n_nodes, a.n_edges, a.nodes_per_graph, a.max_iter, a.tol = N, E, n, int(max_iter), float(tol)
-    a.w_v, a.w_p, a.w_pf = (float(w) for w in weights)
-    keep = None
-    if init is not None:
-        keep, ld_init = _rows(init.detach())
-        a.init, a.ld_init = keep.data_ptr(), ld_init
+    keep, solved, N, E, G = _solve_block(b.solve, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init,
+                                         max_iter, tol, weights, max_groups, refuse_size, check_own)
+    dev, slots = x.device, max(int(max_removals), 1)
     f64, i32 = torch.float64, torch.int32
     new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
     res = WLSBadDataResult(
-        state=new(N, 2, dtype=_F32), objective=new(G, 2), iterations=new(G, dtype=i32), status=new(G, dtype=i32), last_step=new(G),
+        *solved,
         dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
         n_removed=new(G, dtype=i32), bus_rn=new(N, 4),
         edge_rn=torch.zeros(E, 2, dtype=f64, device=dev),       # (an edge that leaves its graph is never written)
         bus_sens=new(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=new(N, 2))
-    a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in res[:5])
     (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
      b.state_std) = (t.data_ptr() for t in res[5:])
-    vmm = torch.empty(130, dtype=_F32, device=dev)
-    a.vminmax, a.max_groups = vmm.data_ptr(), int(max_groups)
     b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
     b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
-    _lib.check(L.dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
+    _lib.check(_lib.lib().dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
+    del keep                     # (held until here: the launch has been issued)
     return res
