@@ -206,7 +206,7 @@ class WlsSolveArgs(C.Structure):
                 ("tol", C.c_double), ("w_v", C.c_double), ("w_p", C.c_double), ("w_pf", C.c_double),
                 ("init", C.c_void_p), ("ld_init", C.c_int64), ("state", C.c_void_p), ("objective", C.c_void_p),
                 ("iterations", C.c_void_p), ("status", C.c_void_p), ("last_step", C.c_void_p), ("vminmax", C.c_void_p),
-                ("max_groups", C.c_int32), ("pad_", C.c_int32)]
+                ("max_groups", C.c_int32), ("pad_", C.c_int32), ("graph_ptr", C.c_void_p), ("n_graphs", C.c_int64)]
 
 
 class WlsBadDataArgs(C.Structure):

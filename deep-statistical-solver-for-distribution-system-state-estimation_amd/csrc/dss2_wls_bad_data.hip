@@ -63,16 +63,21 @@ template <int T>
 __global__ void __launch_bounds__(T) wls_bad_data_kernel(const dss2_wls_bad_data_args b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bd_smem[];
   const dss2_wls_solve_args& a = b.solve;
-  const int n = a.nodes_per_graph, ns = 2 * n;
-  const WsLds l = ws_carve(bd_smem, n);
-  const BdLds r = bd_carve(bd_smem + ws_bytes(n));
+  const BdLds r = bd_carve(bd_smem + ws_bytes(a.nodes_per_graph));   // behind the carve of the largest graph this launch can hold
   const int tid = threadIdx.x;
   const int slots = b.max_removals > 1 ? b.max_removals : 1;
   float vlv, vhv;
   vminmax_fold(a.vminmax, vlv, vhv);
-  const int64_t n_graphs = a.n_nodes / n;
+  const int64_t n_graphs = ws_n_graphs(a);
   for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
-    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
+    const WsRange rg = ws_range(a, gr);
+    if (!rg.ok) {                        // uniform over the workgroup
+      if (tid == 0) bd_refuse(b, gr, slots);
+      continue;
+    }
+    const int n = rg.n, ns = 2 * n;      // (2 n <= 2 nodes_per_graph <= T: a thread per row of Sigma)
+    const WsLds l = ws_carve(bd_smem, n);
+    const WsGraph g = ws_graph(rg.base, n, vlv, l.u, l.slk);
     ws_load_start<T>(a, g, l, tid);
     WsTally t = {0, 1, 0.0};
     int nrem = 0, n_active = 0;          // nrem is uniform; n_active is thread 0's

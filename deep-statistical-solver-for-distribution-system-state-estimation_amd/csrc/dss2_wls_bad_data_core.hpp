@@ -187,6 +187,13 @@ __device__ __forceinline__ void bd_finish(const dss2_wls_bad_data_args& b, int64
   for (int q = nrem; q < slots; ++q) { b.removed[gr * slots + q] = -1; b.removed_rn[gr * slots + q] = 0.0; }
 }
 
+// Thread 0's outputs of a graph that ws_range refused: the solve's, and the test's at their "failed graph" values
+__device__ __forceinline__ void bd_refuse(const dss2_wls_bad_data_args& b, int64_t gr, int slots) {
+  ws_refuse(b.solve, gr);
+  b.dof[gr] = 0; b.chi2_limit[gr] = INFINITY; b.suspect[gr] = 0; b.n_removed[gr] = 0;
+  for (int q = 0; q < slots; ++q) { b.removed[gr * slots + q] = -1; b.removed_rn[gr * slots + q] = 0.0; }
+}
+
 // The parameter checks of a bad-data entry beyond the solve's (`who` names the entry in the message); 0 or 2
 inline int bd_check_params(const dss2_wls_bad_data_args& b, const char* who) {
   const dss2_wls_solve_args& a = b.solve;

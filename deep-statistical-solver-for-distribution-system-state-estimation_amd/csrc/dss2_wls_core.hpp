@@ -3,7 +3,8 @@
 // normalized residuals and the removal loop), csrc/dss2_wls_large.hip (the solve on a blocked gain matrix in global memory) and
 // csrc/dss2_wls_robust.hip (the Huber M-estimator, on both storage forms).  Here live
 //   - the device functions: measurements, the row owners' assembly, the packed Cholesky, the decision, the objective;
-//   - a graph's prologue (ws_graph) and the plain epilogue (ws_store_state, ws_finish), once for every kernel;
+//   - a graph's range (ws_range: the uniform layout, or graph_ptr with nodes_per_graph as a bound, and the guard of the latter), its
+//     prologue (ws_graph) and the plain epilogue (ws_store_state, ws_finish), once for every kernel;
 //   - wls_lds_kernel, the ONE kernel body with the gain matrix in LDS: the plain and the Huber estimator are two instantiations of it;
 //   - the host side: the argument checks, ws_launch (the launch path of every kernel on the LDS carve) and ws_entry (the null check
 //     and the launch plan's record of every entry).
@@ -119,11 +120,52 @@ struct WsGraph {                    // what the row owners need of the graph bei
   const double* u;                  // LDS state
   const unsigned char* slk;         // LDS slack flags
 };
-// graph gr of a batch of n-bus graphs (vlv: vminmax_fold's low-voltage base)
-__device__ __forceinline__ WsGraph ws_graph(int64_t gr, int n, float vlv, const double* u, const unsigned char* slk) {
+// the graph of n buses from row `base` on (vlv: vminmax_fold's low-voltage base)
+__device__ __forceinline__ WsGraph ws_graph(int64_t base, int n, float vlv, const double* u, const unsigned char* slk) {
   WsGraph g;
-  g.base = gr * n; g.n = n; g.kk = (double)vlv * (double)vlv; g.u = u; g.slk = slk;
+  g.base = base; g.n = n; g.kk = (double)vlv * (double)vlv; g.u = u; g.slk = slk;
   return g;
+}
+
+// Which rows graph gr owns.  Without a graph_ptr: [gr n, (gr + 1) n), n = nodes_per_graph.  With one: [graph_ptr[gr], graph_ptr[gr + 1]),
+// and nodes_per_graph is only the BOUND everything was sized by on the host.  The two words are read once per graph and made wave-uniform
+// (every wave of the workgroup reads the same two: n is the same in every thread, and so is every trip count derived from it).
+// ok = false: the pointer does not describe a graph this launch can hold -- n < 1, n above the bound, rows outside [0, n_nodes) -- and the
+// graph is refused (ws_refuse) before anything of it touches LDS or memory.
+__host__ __device__ __forceinline__ int64_t ws_n_graphs(const dss2_wls_solve_args& a) {
+  return a.graph_ptr ? a.n_graphs : a.n_nodes / a.nodes_per_graph;
+}
+struct WsRange { int64_t base; int n; bool ok; };
+__device__ __forceinline__ int64_t ws_uniform(int64_t v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v), hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ WsRange ws_range(const dss2_wls_solve_args& a, int64_t gr) {
+  WsRange r;
+  if (a.graph_ptr) {
+    const int64_t b0 = ws_uniform(a.graph_ptr[gr]), cnt = ws_uniform(a.graph_ptr[gr + 1]) - b0;
+    r.ok = cnt >= 1 && cnt <= (int64_t)a.nodes_per_graph && b0 >= 0 && b0 <= a.n_nodes - cnt;
+    r.base = b0; r.n = r.ok ? (int)cnt : 0;
+  } else {
+    r.base = gr * a.nodes_per_graph; r.n = a.nodes_per_graph; r.ok = true;
+  }
+  return r;
+}
+// The range as a kernel body's template parameter, in the style of WsNoMask / WsNoWeight.  WsAnyRange -- the default of every body --
+// decides per launch, by the uniform branch of ws_range.  WsUniformRange knows that the launch has no graph_ptr: it is there for the
+// one instantiation whose uniform launches measurably slowed with the branch in the body (the wide Huber kernel).
+struct WsAnyRange {
+  __device__ static __forceinline__ int64_t n_graphs(const dss2_wls_solve_args& a) { return ws_n_graphs(a); }
+  __device__ static __forceinline__ WsRange at(const dss2_wls_solve_args& a, int64_t gr) { return ws_range(a, gr); }
+};
+struct WsUniformRange {
+  __device__ static __forceinline__ int64_t n_graphs(const dss2_wls_solve_args& a) { return a.n_nodes / a.nodes_per_graph; }
+  __device__ static __forceinline__ WsRange at(const dss2_wls_solve_args& a, int64_t gr) { return WsRange{gr * a.nodes_per_graph, a.nodes_per_graph, true}; }
+};
+// The five plain outputs of a refused graph (one thread calls it): status 2, nothing done.  No state row is written.
+__device__ __forceinline__ void ws_refuse(const dss2_wls_solve_args& a, int64_t gr) {
+  a.objective[2 * gr] = 0.0; a.objective[2 * gr + 1] = 0.0;
+  a.iterations[gr] = 0; a.status[gr] = 2; a.last_step[gr] = 0.0;
 }
 
 // incidence entry k -> stored branch, the other end's LOCAL bus (outside [0, n): an edge that leaves the graph, ignored), orientation
@@ -460,24 +502,35 @@ __device__ __forceinline__ void ws_finish(const dss2_wls_solve_args& a, const Ws
   }
 }
 
-// The kernel with the gain matrix in LDS: one workgroup of T threads per graph, the workgroups stride over the graphs.  Args is
+// The kernel with the gain matrix in LDS: one workgroup of T threads per graph, the workgroups stride over the graphs.  A graph's
+// n (ws_range) sets its carve, its trip counts and its scratch; the LDS was allocated for the bound, and the carve of a smaller graph
+// lies inside it.  Nothing is carried from one graph to the next: slk, u, ctl and the packed array are written before they are read,
+// and a graph ends with a barrier.  Args is
 // dss2_wls_solve_args (the plain estimator) or dss2_wls_robust_args (the Huber one: ws_weighting gives its WsHuber); the two differ
 // in the weighting alone, and WsNoWeight's part of every statement compiles to nothing.
-template <int T, class Args>
+template <int T, class Args, class Range = WsAnyRange>
 __global__ void __launch_bounds__(T) wls_lds_kernel(const Args b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];
   const dss2_wls_solve_args& a = ws_solve_block(b);
-  const int n = a.nodes_per_graph, ns = 2 * n;
-  const WsLds l = ws_carve(ws_smem, n);
   const int tid = threadIdx.x;
   float vlv, vhv;
   vminmax_fold(a.vminmax, vlv, vhv);
   auto wt = ws_weighting(b);
   using Wt = decltype(wt);
-  if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Gp + 2 * n);   // behind the objective's 2 n per-bus parts: n ints, inside the packed array
-  const int64_t n_graphs = a.n_nodes / n;
+  const int64_t n_graphs = Range::n_graphs(a);
   for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
-    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
+    const WsRange rg = Range::at(a, gr);
+    if (!rg.ok) {                         // uniform over the workgroup
+      if (tid == 0) {
+        ws_refuse(a, gr);
+        if constexpr (Wt::robust) b.n_downweighted[gr] = 0;
+      }
+      continue;
+    }
+    const int n = rg.n, ns = 2 * n;
+    const WsLds l = ws_carve(ws_smem, n);
+    if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Gp + 2 * n);   // behind the objective's 2 n per-bus parts: n ints, inside the packed array
+    const WsGraph g = ws_graph(rg.base, n, vlv, l.u, l.slk);
     ws_load_start<T>(a, g, l, tid);
     WsTally t = {0, 1, 0.0};
     ws_gauss_newton<T>(a, g, l, ns, tid, WsNoMask(), t, wt);
@@ -492,6 +545,10 @@ constexpr int WS_GROUPS_NARROW = 2048, WS_GROUPS_WIDE = 512;
 // The argument checks the entries share, in two parts around each entry's own size limit (`who` names the entry in the message); 0 or 2
 inline int ws_check_batch(const dss2_wls_solve_args& a, const char* who) {
   const int n = a.nodes_per_graph;
+  if (a.graph_ptr) {                     // n is a bound on a graph's bus count: the kernel checks every graph against it
+    if (a.n_nodes <= 0 || a.n_edges < 0 || n <= 0 || a.n_graphs < 1) { set_error("%s: with a graph_ptr n_nodes, nodes_per_graph (the bound) and n_graphs must be positive", who); return 2; }
+    return 0;
+  }
   if (a.n_nodes <= 0 || a.n_edges < 0 || n <= 0 || a.n_nodes % n != 0) { set_error("%s: n_nodes must be a positive multiple of nodes_per_graph", who); return 2; }
   return 0;
 }
@@ -515,7 +572,7 @@ inline int ws_check_args(const dss2_wls_solve_args& a, const char* who, size_t e
   return ws_check_rest(a, who);
 }
 inline int64_t ws_grid(const dss2_wls_solve_args& a) {
-  const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
+  const int64_t n_graphs = ws_n_graphs(a);
   int64_t grid = 2 * a.nodes_per_graph <= WS_NARROW_STATES ? WS_GROUPS_NARROW : WS_GROUPS_WIDE;
   if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
   return n_graphs < grid ? n_graphs : grid;

@@ -245,23 +245,33 @@ __device__ __forceinline__ void wl_gauss_newton(const dss2_wls_solve_args& a, co
 }
 
 // The kernel on this layout: one workgroup of WL_T threads per graph and workspace slice, the workgroups stride over the graphs.
+// A graph's n (ws_range) sets its carve, its panel stride and every trip count; LDS and the slice were sized for the bound.
 // Args is dss2_wls_large_args (the plain estimator) or dss2_wls_robust_args (the Huber one), as for wls_lds_kernel.
 template <class Args>
 __global__ void __launch_bounds__(WL_T) wls_blocked_kernel(const Args b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wl_smem[];
   const dss2_wls_solve_args& a = ws_solve_block(b);
-  const int n = a.nodes_per_graph, ns = 2 * n;
-  const WlLds l = wl_carve(wl_smem, n);
-  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wl_graph_doubles(n);
+  // the slice is sized by nodes_per_graph (with a graph_ptr: the bound); a graph uses the rows 0 .. 2 n of it, whose offsets depend on the row alone
+  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wl_graph_doubles(a.nodes_per_graph);
   const int tid = threadIdx.x;
   float vlv, vhv;
   vminmax_fold(a.vminmax, vlv, vhv);
   auto wt = ws_weighting(b);
   using Wt = decltype(wt);
-  if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Pt);   // the panel is idle after the last factorisation: n ints of its 16 (2 n + 1) doubles
-  const int64_t n_graphs = a.n_nodes / n;
+  const int64_t n_graphs = ws_n_graphs(a);
   for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
-    const WsGraph g = ws_graph(gr, n, vlv, l.u, l.slk);
+    const WsRange rg = ws_range(a, gr);
+    if (!rg.ok) {                                      // uniform over the workgroup
+      if (tid == 0) {
+        ws_refuse(a, gr);
+        if constexpr (Wt::robust) b.n_downweighted[gr] = 0;
+      }
+      continue;
+    }
+    const int n = rg.n, ns = 2 * n;
+    const WlLds l = wl_carve(wl_smem, n);
+    if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(l.Pt);   // the panel is idle after the last factorisation: n ints of its 16 (2 n + 1) doubles
+    const WsGraph g = ws_graph(rg.base, n, vlv, l.u, l.slk);
     const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
     ws_load_start<WL_T>(a, g, start, tid);
     WsTally t = {0, 1, 0.0};
@@ -273,7 +283,7 @@ __global__ void __launch_bounds__(WL_T) wls_blocked_kernel(const Args b) {
 
 // ---- host side: the grid and the size check of the entries that run on this layout (`who` names the entry in the message)
 inline int64_t wl_grid(const dss2_wls_solve_args& a) {
-  const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
+  const int64_t n_graphs = ws_n_graphs(a);
   int64_t grid = WL_GROUPS;
   if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
   return n_graphs < grid ? n_graphs : grid;

@@ -35,6 +35,9 @@ static int wls_robust_launch(const dss2_wls_robust_args& b, void* stream) {
   using B = dss2_wls_robust_args;
   if (int rc = ws_check_args(b.solve, "wls_robust", 0)) return rc;
   if (int rc = wr_check_params(b, "wls_robust")) return rc;
+  // (the wide kernel's uniform launches keep an instantiation without the graph_ptr branch: with it they measured 2.5 % slower)
+  if (!b.solve.graph_ptr)
+    return ws_launch<wls_lds_kernel<64, B>, wls_lds_kernel<256, B, WsUniformRange>>(b, ws_bytes(b.solve.nodes_per_graph), "wls_robust", as_stream(stream));
   return ws_launch<wls_lds_kernel<64, B>, wls_lds_kernel<256, B>>(b, ws_bytes(b.solve.nodes_per_graph), "wls_robust", as_stream(stream));
 }
 extern "C" int dss2_wls_robust(const dss2_wls_robust_args* bp, void* stream) { return ws_entry(bp, stream, "dss2_wls_robust", wls_robust_launch); }

@@ -58,10 +58,13 @@ def masked_zscore(t: torch.Tensor, num_feat: int):
 
 
 class Batch:
-    """What the driver reads from a PyG batch (dss2_run.py:134-141)."""
+    """What the driver reads from a PyG batch (dss2_run.py:134-141).  A batch whose graphs differ in bus count also carries
+    ``graph_ptr`` ([num_graphs + 1] int64 on the device: graph g owns rows [graph_ptr[g], graph_ptr[g + 1])) and ``max_nodes``
+    (the largest bus count a graph of it can have, a host int): what ``estimator``'s functions take as graph_ptr and as the bound."""
 
-    def __init__(self, x, edge_index, edge_attr, y, num_graphs):
+    def __init__(self, x, edge_index, edge_attr, y, num_graphs, graph_ptr=None, max_nodes=None):
         self.x, self.edge_index, self.edge_attr, self.y, self.num_graphs = x, edge_index, edge_attr, y, num_graphs
+        self.graph_ptr, self.max_nodes = graph_ptr, max_nodes
 
     def to(self, device):
         if torch.device(device).type != "cuda":
@@ -445,6 +448,8 @@ class MixedDataset:
             base += tab.size
         ptr_at = base
         pieces.append(edge_off)
+        if self.n is None:       # the graphs' node offsets ride along: the batch's graph_ptr (the WLS estimators' row pointer)
+            pieces.append(node_off)
         table = self._upload(np.concatenate(pieces).reshape(1, -1), dev).reshape(-1)
         edge_ptr = table[ptr_at:ptr_at + B + 1]
         if n_parts <= 4:
@@ -479,7 +484,7 @@ class MixedDataset:
                 _lib.check(L.dss2_collate_ragged(C.addressof(descs), 4, t0, t0 + 8 * c, t0 + 16 * c, c, E, st), "dss2_collate_ragged")
         if self.n is None:       # different bus counts: no closed-form tiles, the general (statistics-reading) build
             _topology.register_topology(ei, Ntot, _topology.Topology(ei, Ntot))
-            return Batch(x, ei, ea, y, B)
+            return Batch(x, ei, ea, y, B, graph_ptr=table[ptr_at + B + 1:ptr_at + 2 * B + 2], max_nodes=max(p.n for p in self.parts))
         n = self.n
         first = self.parts[int(part[0])]
         # (edge_ptr: the batch's own prefix sum of the graphs' edge counts, uploaded with the tables above: with it the structure is one

@@ -26,10 +26,22 @@ It inverts the gain matrix in LDS: up to 99 buses per graph.
 
 The second classical answer to gross errors, for every bus count up to 256: the Huber M-estimator by iteratively re-weighted
 Gauss-Newton on the kernels of ``wls_estimate`` and ``wls_estimate_large`` (csrc/dss2_wls_robust.hip).  No covariance, one launch.
+
+Batches that mix bus counts: all four take the keyword ``graph_ptr`` (``_public`` at the end of the module adds it: the parameter lists
+above are pinned by callers and tests, and ``inspect.signature`` goes on reporting them), a contiguous int64 device tensor [G + 1] of row offsets (what
+``synthetic.make_batch`` returns for a list of grids and ``dataset.MixedDataset`` puts on its batches).  Graph g then owns rows
+[graph_ptr[g], graph_ptr[g + 1]) and ``nodes_per_graph`` is an UPPER BOUND on a graph's bus count, known on the host: the kernel choice,
+LDS, workspace and every size refusal go by it, N need not be a multiple of it, and outputs per graph are [G, ...].  Nothing is read back:
+the kernel checks every graph against the bound and against [0, N), and a graph that fails the check ends with status 2, 0 iterations,
+objective 0 and no row written (its rows of ``state`` and of the per-measurement outputs keep the value they were allocated with: 0, and
+1 for the q factors), while the others are solved.  Measurement ids stay global (4 i + k for row i of x, 4 N + 2 e + k for stored branch
+e), and V_lv is the minimum of vn_kv over the WHOLE batch, as the training loss has it.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -81,15 +93,18 @@ def _incidence(edge_index: torch.Tensor, N: int):
     return tuple(t.data_ptr() for t in (topo.efrom, topo.eto, topo.inc_rowptr, topo.inc_ent)), topo.E
 
 
-def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+def _wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                  init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
-                 weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
+                 weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
+                 graph_ptr: Optional[torch.Tensor] = None) -> WLSResult:
     """Gauss-Newton on J_g(u) = sum_buses sum_k c_k R^-1 (Z - h)^2 + sum_branches sum_k w_pf R_edge^-1 (edge_Z - h_edge)^2 per graph,
     c = (w_v, w_v, w_p, w_p), ``weights`` = (w_v, w_p, w_pf): (1, 1, 1) is the classical WLS, (lam_v, lam_p, lam_pf) the training
     loss's relative weighting.  Start: ``init`` [N, 2] (physical), or flat (v = 1, theta = 0); theta at slack buses is 0 and stays 0.
-    ``tol = 0`` never stops early.  ``max_groups`` > 0 caps the number of workgroups (they stride over the graphs)."""
+    ``tol = 0`` never stops early.  ``max_groups`` > 0 caps the number of workgroups (they stride over the graphs).
+    ``graph_ptr`` [G + 1] (int64, device): the batch mixes bus counts, graph g owns rows [graph_ptr[g], graph_ptr[g + 1]) and
+    ``nodes_per_graph`` is an upper bound on a graph's bus count (the module docstring: the bound, the ids, V_lv)."""
     return _estimate(False, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups)
+                     max_groups, graph_ptr=graph_ptr)
 
 
 def max_nodes_per_graph_large() -> int:
@@ -101,27 +116,37 @@ _WORKSPACES = {}                 # (device, bytes) -> the gain matrices' workspa
                                  # with its address); calls on one stream run one after the other, and no call needs its contents
 
 
-def wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+def _wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                        init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
-                       weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
+                       weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
+                       graph_ptr: Optional[torch.Tensor] = None) -> WLSResult:
     """``wls_estimate`` -- the same inputs, iteration, result and decisions -- for graphs of up to ``max_nodes_per_graph_large()``
     buses, small ones included: the gain matrix lives in a workspace in global memory (one slice per workgroup, allocated once per
-    device and size) and is factorised in blocks, csrc/dss2_wls_large.hip.  Still one launch per solve, recordable."""
+    device and size) and is factorised in blocks, csrc/dss2_wls_large.hip.  Still one launch per solve, recordable.
+    ``graph_ptr`` as for ``wls_estimate``: with it ``nodes_per_graph`` is an upper bound, and the workspace is sized by the bound."""
     return _estimate(True, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups)
+                     max_groups, graph_ptr=graph_ptr)
 
 
 def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                 max_groups, refuse_size, check_own=None):
+                 max_groups, refuse_size, check_own=None, graph_ptr=None):
     """Validates the arguments every estimator here shares and fills ``a``, the ``WlsSolveArgs`` of its launch -- outputs included.
     The caller's own checks run at their place among these: ``check_own()`` (its ValueErrors) after the scalars', ``refuse_size(n)``
     (its NotImplementedError) after every ValueError.  Returns (keep, out, N, E, G): ``keep`` is what ``a`` points into and nothing
     else holds -- the row views, the statistics vectors, the kept ``init``, the vminmax buffer -- to be held until the launch has been
-    issued; ``out`` is the WLSResult of fresh tensors that ``a`` writes."""
+    issued; ``out`` is the WLSResult of fresh tensors that ``a`` writes.  With a ``graph_ptr`` n is the bound, G its length less one,
+    and ``state`` is zero-filled (a graph the kernel refuses writes no row)."""
     _require_gpu(x, edge_index, edge_attr)
     n = int(nodes_per_graph)
     N = x.size(0)
-    if n < 1 or N == 0 or N % n != 0:
+    if graph_ptr is not None:
+        _require_gpu(graph_ptr)
+        if graph_ptr.dtype != torch.int64 or graph_ptr.dim() != 1 or graph_ptr.numel() < 2 or not graph_ptr.is_contiguous():
+            raise ValueError("graph_ptr must be a contiguous 1-D int64 tensor of at least 2 elements (G + 1 row offsets)")
+        if n < 1 or N == 0:
+            raise ValueError(f"with a graph_ptr nodes_per_graph = {nodes_per_graph} is the bound on a graph's bus count: at least 1, "
+                             f"and x must have rows")
+    elif n < 1 or N == 0 or N % n != 0:
         raise ValueError(f"x has {N} rows: not a positive multiple of nodes_per_graph = {nodes_per_graph}")
     if int(max_iter) < 1:
         raise ValueError("max_iter must be at least 1")
@@ -142,7 +167,9 @@ def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std
     x2, ldx = _rows(x)
     ea2, ldea = _rows(edge_attr)
     incidence, E = _incidence(edge_index, N)
-    G = N // n
+    G = N // n if graph_ptr is None else graph_ptr.numel() - 1
+    if graph_ptr is not None:
+        a.graph_ptr, a.n_graphs = graph_ptr.data_ptr(), G
     a.x, a.ldx, a.edge_attr, a.ldea = x2.data_ptr(), ldx, ea2.data_ptr(), ldea
     stats = (_vec(x_mean, 8, dev), _vec(x_std, 8, dev), _vec(edge_mean, 4, dev), _vec(edge_std, 4, dev))
     a.x_mean, a.x_std, a.edge_mean, a.edge_std = (s.data_ptr() for s in stats)
@@ -153,7 +180,7 @@ def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std
     if init is not None:
         kept_init, ld_init = _rows(init.detach())
         a.init, a.ld_init = kept_init.data_ptr(), ld_init
-    out = WLSResult(torch.empty(N, 2, dtype=_F32, device=dev), torch.empty(G, 2, dtype=torch.float64, device=dev),
+    out = WLSResult((torch.empty if graph_ptr is None else torch.zeros)(N, 2, dtype=_F32, device=dev), torch.empty(G, 2, dtype=torch.float64, device=dev),
                     torch.empty(G, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev),
                     torch.empty(G, dtype=torch.float64, device=dev))
     a.state, a.objective, a.iterations, a.status, a.last_step = (t.data_ptr() for t in out)
@@ -163,7 +190,7 @@ def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std
 
 
 def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-              max_groups, robust=None):
+              max_groups, robust=None, graph_ptr=None):
     """The plain solve (``robust`` None -> WLSResult) or the Huber one (``robust`` = (gamma, plain_iters) -> WLSRobustResult) on the LDS
     kernel or on the blocked one (``large``)."""
     who = ("wls_estimate_large" if large else "wls_estimate") if robust is None else f"wls_robust (large={large})"
@@ -180,11 +207,11 @@ def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_st
     args = _lib.WlsRobustArgs() if robust is not None else _lib.WlsLargeArgs() if large else _lib.WlsSolveArgs()
     a = getattr(args, "solve", args)
     keep, res, N, E, G = _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter,
-                                      tol, weights, max_groups, refuse_size)
+                                      tol, weights, max_groups, refuse_size, graph_ptr=graph_ptr)
     n, dev = a.nodes_per_graph, x.device
     L = _lib.lib()
     if robust is not None:
-        res = WLSRobustResult(*res, bus_q=torch.empty(N, 4, dtype=torch.float64, device=dev),
+        res = WLSRobustResult(*res, bus_q=(torch.empty if graph_ptr is None else torch.ones)(N, 4, dtype=torch.float64, device=dev),
                               edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
                               n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
         args.gamma, args.plain_iters = robust
@@ -211,10 +238,10 @@ class WLSRobustResult(NamedTuple):
     n_downweighted: torch.Tensor  # [G] int32: measurements with q < 1
 
 
-def wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+def _wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                init: Optional[torch.Tensor] = None, max_iter: int = 20, tol: float = 1e-6,
                weights: Sequence[float] = (1.0, 1.0, 1.0), gamma: float = 3.0, plain_iters: int = 1,
-               large: Optional[bool] = None, max_groups: int = 0) -> WLSRobustResult:
+               large: Optional[bool] = None, max_groups: int = 0, graph_ptr: Optional[torch.Tensor] = None) -> WLSRobustResult:
     """The Huber M-estimator on ``wls_estimate``'s measurement model, by iteratively re-weighted Gauss-Newton: with w_i = c_k R^-1 the
     weight of measurement i, r_i its residual and t_i = sqrt(w_i) |r_i| at the current iterate, every iteration from number
     ``plain_iters`` on (counted from 0) is ``wls_estimate``'s with w_i q_i in place of w_i, q_i = gamma / t_i where t_i > gamma and
@@ -223,7 +250,8 @@ def wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nod
     result to the bit.  Reported at the final state: the Huber cost (t^2 up to gamma, 2 gamma t - gamma^2 above), every q, and the count
     of q < 1 per graph.  ``large`` None: the LDS kernel up to ``max_nodes_per_graph()`` buses, the blocked kernel above (up to
     ``max_nodes_per_graph_large()``); True / False force one.  gamma = 3 is the default for a reason: at 1.5, on ober179 (condition
-    number 2.4e13), three to four measurements per graph are down-weighted and the state is worse than plain WLS."""
+    number 2.4e13), three to four measurements per graph are down-weighted and the state is worse than plain WLS.
+    ``graph_ptr`` as for ``wls_estimate``: ``nodes_per_graph`` is then an upper bound, and ``large`` None routes by the bound."""
     gamma = float(gamma)
     if not gamma > 0:
         raise ValueError("gamma must be > 0")
@@ -232,7 +260,7 @@ def wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nod
     if large is None:
         large = int(nodes_per_graph) > max_nodes_per_graph()
     return _estimate(bool(large), x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups, robust=(gamma, int(plain_iters)))
+                     max_groups, robust=(gamma, int(plain_iters)), graph_ptr=graph_ptr)
 
 
 class WLSBadDataResult(NamedTuple):
@@ -254,16 +282,19 @@ class WLSBadDataResult(NamedTuple):
     state_std: torch.Tensor      # [N, 2] fp64: sqrt(diag (H^T W H)^-1), 0 at slack angles
 
 
-def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                  init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
                  weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
-                 confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0) -> WLSBadDataResult:
+                 confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0,
+                 graph_ptr: Optional[torch.Tensor] = None) -> WLSBadDataResult:
     """``wls_estimate`` followed, inside the same launch, by the chi-square test, the largest-normalized-residual test and up to
     ``max_removals`` removals, each followed by a re-solve from the current state.  A measurement is active if its weight
     c_k R^-1 is above 0 and it has not been removed; S_i = 1 - w_i h_i Sigma h_i^T, rN_i = |z_i - h_i(u)| sqrt(w_i / S_i) where
     S_i >= ``s_min`` and 0 below it (critical measurements).  The largest rN above ``threshold`` is removed (ties: the smallest id).
     Ids: 4 i + k for bus i (row of x), k in V, theta, P, Q; 4 N + 2 e + k for stored branch e, k in P_from, Q_from.
-    With ``max_removals = 0`` the first five fields are ``wls_estimate``'s, bit for bit."""
+    With ``max_removals = 0`` the first five fields are ``wls_estimate``'s, bit for bit.
+    ``graph_ptr`` as for ``wls_estimate``: ``nodes_per_graph`` is then an upper bound (a bound above 99 is refused as 100 buses are),
+    and the ids -- ``removed`` among them -- stay the global ones above."""
     def check_own():
         if not threshold > 0:
             raise ValueError("threshold must be > 0")
@@ -280,16 +311,17 @@ def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
 
     b = _lib.WlsBadDataArgs()
     keep, solved, N, E, G = _solve_block(b.solve, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init,
-                                         max_iter, tol, weights, max_groups, refuse_size, check_own)
+                                         max_iter, tol, weights, max_groups, refuse_size, check_own, graph_ptr=graph_ptr)
     dev, slots = x.device, max(int(max_removals), 1)
     f64, i32 = torch.float64, torch.int32
     new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
+    rows = new if graph_ptr is None else lambda *shape: torch.zeros(*shape, dtype=f64, device=dev)   # (a refused graph writes no row)
     res = WLSBadDataResult(
         *solved,
         dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
-        n_removed=new(G, dtype=i32), bus_rn=new(N, 4),
+        n_removed=new(G, dtype=i32), bus_rn=rows(N, 4),
         edge_rn=torch.zeros(E, 2, dtype=f64, device=dev),       # (an edge that leaves its graph is never written)
-        bus_sens=new(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=new(N, 2))
+        bus_sens=rows(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=rows(N, 2))
     (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
      b.state_std) = (t.data_ptr() for t in res[5:])
     b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
@@ -297,3 +329,54 @@ def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
     _lib.check(_lib.lib().dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
     del keep                     # (held until here: the launch has been issued)
     return res
+
+
+def _public(impl):
+    """The public form of an estimator function: the parameters it has always had -- what ``inspect.signature`` reports, and what callers
+    and tests have pinned -- plus the keyword ``graph_ptr`` of the module docstring, which the wrapper takes off before the call and
+    hands to ``impl``, the same function with ``graph_ptr`` as its last parameter.  Without it the call is the old one, untouched."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(*args, graph_ptr=None, **kw):
+            if graph_ptr is None:
+                return fn(*args, **kw)
+            bound = sig.bind(*args, **kw)
+            return impl(*bound.args, **bound.kwargs, graph_ptr=graph_ptr)
+        call.__doc__ = impl.__doc__
+        return call
+    return deco
+
+
+@_public(_wls_estimate)
+def wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                 init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                 weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
+    return _wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, max_groups)
+
+
+@_public(_wls_estimate_large)
+def wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                       init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                       weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0) -> WLSResult:
+    return _wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                               max_groups)
+
+
+@_public(_wls_robust)
+def wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+               init: Optional[torch.Tensor] = None, max_iter: int = 20, tol: float = 1e-6,
+               weights: Sequence[float] = (1.0, 1.0, 1.0), gamma: float = 3.0, plain_iters: int = 1,
+               large: Optional[bool] = None, max_groups: int = 0) -> WLSRobustResult:
+    return _wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, gamma,
+                       plain_iters, large, max_groups)
+
+
+@_public(_wls_bad_data)
+def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                 init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                 weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
+                 confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0) -> WLSBadDataResult:
+    return _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, threshold,
+                         max_removals, confidence, s_min, max_groups)

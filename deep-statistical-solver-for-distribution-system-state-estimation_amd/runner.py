@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import argparse
 import time
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -333,7 +333,7 @@ def evaluate(model, loader, stats) -> Dict[str, float]:
 
 
 @torch.no_grad()
-def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None, **solver_kw) -> Dict[str, float]:
+def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=None, bad_data=None, **solver_kw) -> Dict[str, float]:
     """The classical WLS estimator (``estimator.wls_estimate``; ``wls_estimate_large`` above its bus count) over a loader, scored like ``evaluate``: the ten EVAL_METRICS of its
     state, averaged over the batches, plus ``wls_mean_iterations`` (Gauss-Newton updates per graph) and ``wls_not_converged`` (graphs
     that did not end with status 0).  ``model`` None: a flat start, the baseline a learned estimator is compared with; a model: its
@@ -343,7 +343,10 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
     above ``estimator.max_nodes_per_graph()`` buses it refuses).  The keyword ``robust`` = dict(gamma=..., [plain_iters]) (taken out of
     ``solver_kw``): the solve is ``estimator.wls_robust`` with these, the Huber M-estimator, for every bus count up to
     ``estimator.max_nodes_per_graph_large()``, and the metrics gain ``wls_downweighted`` (measurements with a weight factor below 1 at the
-    solution); not together with ``bad_data``.  One device-to-host copy."""
+    solution); not together with ``bad_data``.  A batch that carries a ``graph_ptr`` (a dict key or an attribute: ``synthetic.make_batch``,
+    ``dataset.MixedDataset`` on parts of different bus counts) is solved with it and with its ``max_nodes`` -- else ``nodes_per_graph``,
+    which may be None where every batch says its own -- as the bound on a graph's bus count: a data list may mix grids.  The kernel
+    (LDS or blocked) is chosen by that bound.  One device-to-host copy."""
     from . import estimator
     robust = solver_kw.pop("robust", None)
     if bad_data is not None and robust is not None:
@@ -361,15 +364,22 @@ def evaluate_wls(loader, stats, nodes_per_graph: int, model=None, bad_data=None,
             out = run_model(model, x[:, :8], ei, ea[:, :6])
             init = torch.stack([out[:, 0] * stats[1][0] + stats[0][0], out[:, 1]], 1)
         zero = torch.zeros((), dtype=torch.int64, device=dev)
+        get = data.get if isinstance(data, dict) else lambda k: getattr(data, k, None)
+        graph_ptr, bound, kw = get("graph_ptr"), nodes_per_graph, solver_kw
+        if graph_ptr is not None:
+            kw = dict(solver_kw, graph_ptr=graph_ptr)
+            bound = get("max_nodes") or nodes_per_graph
+        if bound is None:
+            raise ValueError("evaluate_wls: nodes_per_graph is None and the batch carries no graph_ptr with max_nodes")
         if robust is not None:
-            res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw, **robust)
+            res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **robust)
             suspect, removed = zero, res.n_downweighted.sum()
         elif bad_data is None:
-            solve = estimator.wls_estimate if nodes_per_graph <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
-            res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw)
+            solve = estimator.wls_estimate if bound <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
+            res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw)
             suspect, removed = zero, zero
         else:
-            res = estimator.wls_bad_data(x, ei, ea, stats[0], stats[1], stats[2], stats[3], nodes_per_graph, init=init, **solver_kw, **bad_data)
+            res = estimator.wls_bad_data(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **bad_data)
             suspect, removed = res.suspect.sum(), res.n_removed.sum()
         dss2_data._eval_state_batch(res.state, y, x, ei, ea, acc)
         tally += torch.stack([res.iterations.sum(), torch.tensor(res.iterations.numel(), device=dev), (res.status != 0).sum(),
@@ -411,7 +421,7 @@ def main(argv=None):
     ap.add_argument("--graph", type=int, default=-1, help="1: replay the training step as a hipGraph (GraphedTrainer; needs ONE graph "
                     "structure per batch shape), 0: eager, -1 (default): graph when the data has a single topology")
     ap.add_argument("--wls-baseline", action="store_true", help="after training, print the evaluation metrics of the classical WLS "
-                    "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); needs one bus count")
+                    "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); a data list may mix bus counts")
     ap.add_argument("--wls-bad-data", type=float, default=None, metavar="THRESHOLD", help="the --wls-baseline lines (implied) through "
                     "estimator.wls_bad_data: up to 5 measurements per graph are removed while the largest normalized residual exceeds THRESHOLD")
     ap.add_argument("--wls-robust", type=float, default=None, metavar="GAMMA", help="the --wls-baseline lines (implied) through "
@@ -487,8 +497,8 @@ def main(argv=None):
     if a.wls_baseline or a.wls_bad_data is not None or a.wls_robust is not None:
         ds = getattr(test_loader, "dataset", None)
         n_bus = getattr(ds, "n", None) if ds is not None else synthetic.load_grid(a.case).n
-        if n_bus is None:
-            raise ValueError("--wls-baseline needs one bus count per graph (the data list mixes bus counts)")
+        if n_bus is None:                                            # a data list that mixes bus counts: its batches carry graph_ptr; the bound is the largest part's
+            n_bus = max(p.n for p in ds.parts)
         for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
             bad_data = dict(threshold=a.wls_bad_data, max_removals=5) if a.wls_bad_data is not None else None
             robust = dict(gamma=a.wls_robust) if a.wls_robust is not None else None

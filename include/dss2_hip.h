@@ -698,7 +698,8 @@ int64_t dss2_eval_scratch_doubles(void);
  *      (csrc/dss2_wls_solve.hip).  The measurement model is gsp_wls_edge's: per bus z = (V, theta, P_inj, Q_inj) with weights R^-1
  *      (x[:, 0:8]), per stored branch (P_from, Q_from) (edge_attr[:, 0:4]), de-normalised in fp64 where the normalised entry is
  *      non-zero (a de-normalised weight below 0 counts as 0); h(u) as data.py:370-376, 428-435 with shift = 0 and V_lv the batch
- *      minimum of x[:, 8].  Graph g owns buses [g n, (g + 1) n), n = nodes_per_graph; edges never cross graphs.  Per graph
+ *      minimum of x[:, 8].  Graph g owns buses [g n, (g + 1) n), n = nodes_per_graph -- or, with graph_ptr (the end of the struct),
+ *      [graph_ptr[g], graph_ptr[g + 1]) with n an upper bound; edges never cross graphs.  Per graph
  *          J(u) = sum_buses sum_k c_k R^-1 (z - h)^2 + sum_branches sum_k w_pf R_edge^-1 (z_edge - h_edge)^2,  c = (w_v, w_v, w_p, w_p)
  *      is minimised from `init` [N, 2] = (v in p.u., theta in rad), or from v = 1, theta = 0 (init = NULL); theta at slack buses
  *      (x[:, 9] != 0) is 0 and stays 0.  Each of at most max_iter iterations forms G = H^T W H and b = H^T W r with the analytic
@@ -726,6 +727,14 @@ typedef struct dss2_wls_solve_args {
   double* last_step;                              /* [G]     max |du| of the last update applied (0 if none)                      */
   float* vminmax;                                 /* [130] device scratch                                                         */
   int32_t max_groups; int32_t pad_;               /* > 0: at most this many workgroups (they stride over the graphs); 0: the library's choice */
+  /* Batches that mix bus counts (every entry that takes this block).  graph_ptr = NULL: the uniform layout above.  Otherwise graph g
+   * owns buses [graph_ptr[g], graph_ptr[g + 1]) and nodes_per_graph is an UPPER BOUND on a graph's bus count: LDS, workspace, the
+   * workgroup's width, the grid and every size refusal go by it, and n_nodes need not be a multiple of it.  The kernel reads the two
+   * words once per graph and refuses a graph with fewer than 1 or more than nodes_per_graph buses or with rows outside [0, n_nodes):
+   * status 2, iterations 0, last_step 0, objective (0, 0), n_downweighted / n_removed / dof / suspect 0, chi2_limit +inf, removed -1,
+   * no state or per-measurement row written; the other graphs are solved.  Measurement ids stay global; V_lv is the batch's.  */
+  const int64_t* graph_ptr;                       /* [n_graphs + 1] device memory, or NULL                                        */
+  int64_t n_graphs;                               /* ignored when graph_ptr is NULL                                               */
 } dss2_wls_solve_args;
 int dss2_wls_solve(const dss2_wls_solve_args* args_host, void* stream);
 /* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic) */
