@@ -180,8 +180,21 @@ class OptimDesc(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("s0", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_int64)]
 
 
+class OptimFlatDesc(C.Structure):
+    """dss2_optim_flat_desc: a row of the DEVICE table of dss2_optim_step_flat (optim.py builds it through numpy)."""
+    _fields_ = [("param", C.c_void_p), ("grad_off", C.c_int64), ("s0", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_int64)]
+
+
+class AdamaxFlatDesc(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad_off", C.c_int64), ("exp_avg", C.c_void_p), ("exp_inf", C.c_void_p), ("n", C.c_int64)]
+
+
 class GradDesc(C.Structure):
     _fields_ = [("grad", C.c_void_p), ("n", C.c_int64)]
+
+
+class GradFlatDesc(C.Structure):
+    _fields_ = [("grad_off", C.c_int64), ("n", C.c_int64)]
 
 
 class CollateDesc(C.Structure):
@@ -386,6 +399,27 @@ class ChebEdgeArgs(C.Structure):
                 ("pmax", C.c_void_p), ("parg", C.c_void_p), ("psum", C.c_void_p), ("dwh", C.c_void_p), ("ddn", C.c_void_p),
                 ("dw", C.c_void_p), ("dz1", C.c_void_p), ("a1", C.c_void_p)]
 
+
+# Every struct type of include/dss2_hip.h (the opaque dss2_plan aside) and its mirror.  A field carries the C member's name (lambda_:
+# `lambda` is a Python keyword) and every upper-case integer constant X of this module is the header's DSS2_X: tests/test_abi_cpu.py
+# compiles the header and holds layouts, field types, the signatures below and the constants to it.
+C_STRUCTS = {
+    "dss2_csr_build_args": CsrBuildArgs, "dss2_ell_build_args": EllBuildArgs, "dss2_padded_build_args": PaddedBuildArgs,
+    "dss2_pack_desc": PackDesc, "dss2_edge_args": EdgeArgs, "dss2_edge_pass_t": EdgePass, "dss2_edge_plan_t": EdgePlan,
+    "dss2_gemm_prop_args": GemmPropArgs, "dss2_gemm_prop_plan_t": GemmPlan, "dss2_chain_layer": ChainLayer,
+    "dss2_chain_edge": ChainEdge, "dss2_chain_head": ChainHead, "dss2_chain_kernel_t": ChainKernel, "dss2_chain_plan_t": ChainPlan,
+    "dss2_csr_axpy_args": CsrAxpyArgs, "dss2_wgrad_args": WgradArgs, "dss2_wgrad_plan_t": WgradPlan, "dss2_reduce_desc": ReduceDesc,
+    "dss2_wls_args": WlsArgs, "dss2_wls_solve_args": WlsSolveArgs, "dss2_wls_bad_data_args": WlsBadDataArgs,
+    "dss2_wls_large_args": WlsLargeArgs, "dss2_wls_robust_args": WlsRobustArgs, "dss2_sgemm_desc": SgemmDesc,
+    "dss2_collate_desc": CollateDesc, "dss2_stack_dims": StackDims, "dss2_stack_args": StackArgs, "dss2_optim_hyper": OptimHyper,
+    "dss2_optim_desc": OptimDesc, "dss2_optim_flat_desc": OptimFlatDesc, "dss2_adamax_desc": AdamaxDesc,
+    "dss2_adamax_flat_desc": AdamaxFlatDesc, "dss2_grad_desc": GradDesc, "dss2_grad_flat_desc": GradFlatDesc,
+    "dss2_lanegroup_head": LanegroupHead, "dss2_lanegroup_wgrad_job": LanegroupWgradJob, "dss2_lanegroup_wgrad_args": LanegroupWgradArgs,
+    "dss2_gat_graph": GatGraph, "dss2_gat_conv": GatConv, "dss2_gat_args": GatArgs,
+    "dss2_gine_graph": GineGraph, "dss2_gine_conv": GineConv, "dss2_gine_args": GineArgs,
+    "dss2_gnn_graph": GnnGraph, "dss2_gnn_conv": GnnConv, "dss2_gnn_args": GnnArgs,
+    "dss2_cheb_graph": ChebGraph, "dss2_cheb_layer": ChebLayer, "dss2_cheb_args": ChebArgs, "dss2_cheb_edge_args": ChebEdgeArgs,
+}
 
 _SIGNATURES = {
     # name: (restype, argtypes)

@@ -13,15 +13,27 @@ FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -I$ROOT/include -I$HERE -Wall 
 NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
 NOPK_SRCS="${DSS2_NOPK_SRCS-dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_stack dss2_edge16}"      # (DSS2_NOPK_SRCS="" builds the diagnostic library WITH packed ops everywhere)
 mkdir -p "$OBJ"
+SRCS="dss2_api dss2_lanegroup dss2_gat dss2_gine dss2_gnn dss2_cheb dss2_stack dss2_gemm_prop dss2_gemm_chain dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_edge dss2_edge16 dss2_wgrad dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_loss dss2_wls_solve dss2_wls_bad_data dss2_wls_large dss2_wls_robust dss2_optim dss2_dataset dss2_topology"
+# An object is rebuilt when it or its depfile is missing, or when the depfile -- written by the compiler (-MMD): the source and every
+# header it includes -- names a file that is newer than the object or no longer exists.
+stale() {
+  local o="$OBJ/$1.o" d="$OBJ/$1.d" f
+  [ -f "$o" ] && [ -f "$d" ] || return 0
+  for f in $(sed -e 's/^[^:]*: *//' -e 's/ *\\$//' "$d"); do
+    [ -e "$f" ] && ! [ "$f" -nt "$o" ] || return 0
+  done
+  return 1
+}
 pids=()
-for src in dss2_api dss2_lanegroup dss2_gat dss2_gine dss2_gnn dss2_cheb dss2_stack dss2_gemm_prop dss2_gemm_chain dss2_gemm_chain16 dss2_gemm_chain_sp dss2_gemm_chain_sp6 dss2_edge dss2_edge16 dss2_wgrad dss2_wgrad16 dss2_wgrad16h dss2_wgrad16th dss2_loss dss2_wls_solve dss2_wls_bad_data dss2_wls_large dss2_wls_robust dss2_optim dss2_dataset dss2_topology; do
-  if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_common.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_gemm_chain_kernel.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_weightspace.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wgrad_batch.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_edge16_tile.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_lanegroup.hpp" -nt "$OBJ/$src.o" ] || [ "$HERE/dss2_wls_core.hpp" -nt "$OBJ/$src.o" ] || { [ "$src" = dss2_wls_bad_data ] && [ "$HERE/dss2_wls_bad_data_core.hpp" -nt "$OBJ/$src.o" ]; } || { { [ "$src" = dss2_wls_large ] || [ "$src" = dss2_wls_robust ]; } && [ "$HERE/dss2_wls_large_core.hpp" -nt "$OBJ/$src.o" ]; } || [ "$ROOT/include/dss2_hip.h" -nt "$OBJ/$src.o" ]; then
+for src in $SRCS; do
+  if stale "$src"; then
     extra=""; case " $NOPK_SRCS " in *" $src "*) extra="$NOPK";; esac
-    $HIPCC $FLAGS $extra "$@" -c "$HERE/$src.hip" -o "$OBJ/$src.o" 2> >(grep -v "is not a recognized feature for this target" >&2) &
+    $HIPCC $FLAGS $extra "$@" -MMD -MF "$OBJ/$src.d" -c "$HERE/$src.hip" -o "$OBJ/$src.o" 2> >(grep -v "is not a recognized feature for this target" >&2) &
     pids+=($!)
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
+echo "compiled ${#pids[@]} of $(echo $SRCS | wc -w) translation units"
 # The NOPK translation units must really be free of packed fp32 VALU ops: the flag is passed with -Xclang and the host
 # pass's "not a recognized feature" line is filtered above, so a toolchain that silently ignored it on the DEVICE pass
 # would give no other signal.  Disassemble the gfx950 code objects and fail the build if one v_pk_*_f32 is left.

@@ -161,8 +161,8 @@ __global__ void __launch_bounds__(256) optim_flat_kernel(const void* __restrict_
 }
 
 // ---- global-norm gradient clipping: fp64 partial per workgroup, re-added in index order by every workgroup of the second launch
-constexpr int GRAD_CHUNK = 192;       // {pointer, n} descriptors per launch, by value (192 x 16 B = 3 KB)
-constexpr int GRAD_MAX_PARTIALS = 256;
+constexpr int GRAD_CHUNK = DSS2_OPTIM_GRAD_CHUNK;       // {pointer, n} descriptors per launch, by value (192 x 16 B = 3 KB)
+constexpr int GRAD_MAX_PARTIALS = DSS2_OPTIM_MAX_PARTIALS;
 struct GradTable { dss2_grad_desc d[GRAD_CHUNK]; };
 
 __global__ void __launch_bounds__(256) grad_sqsum_kernel(const GradTable tab, const dss2_grad_flat_desc* __restrict__ flat,

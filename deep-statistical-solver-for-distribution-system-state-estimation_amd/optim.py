@@ -139,11 +139,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 return False      # (a table upload cannot be captured: the by-value path below serves this step)
             import numpy as np
             slots = self._slots(group)
-            arr = np.zeros((len(ps), 6), dtype=np.int64)      # dss2_optim_flat_desc
+            arr = np.zeros(len(ps), dtype=np.dtype(_lib.OptimFlatDesc))
             for i, p in enumerate(ps):
                 stp = self.state[p]
                 arr[i] = (p.data_ptr(), offs[i]) + tuple(stp[k].data_ptr() if k is not None else 0 for k in slots) + (p.numel(),)
-            tab = torch.from_numpy(arr).to(dev)
+            tab = torch.from_numpy(arr.view(np.uint8)).to(dev)
             cached = self._flat_table[gi] = (key, tab, max(p.numel() for p in ps),
                                              torch.zeros(1, dtype=torch.int32, device=dev))
             self.table_builds += 1

@@ -15,13 +15,8 @@ from .ops import _F32, _ncg, _round8, _round16, is_narrow, prep_weights
 # ------------------------------------------------------------------------------------------
 # weight packing plans
 # ------------------------------------------------------------------------------------------
-_DESC_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("ld", "<i4"),
-                        ("transpose", "<i4"), ("koff", "<i4"), ("kpad", "<i4"), ("ncg", "<i4"), ("joff", "<i4")])
-
-
-_SG_DTYPE = np.dtype([("A", "<u8", (4,)), ("B", "<u8", (4,)), ("C", "<u8"), ("u", "<u8"), ("v", "<u8"), ("c_off", "<i8"),
-                      ("M", "<i4"), ("N", "<i4"), ("K", "<i4"), ("lda", "<i4"), ("ldb", "<i4"), ("ldc", "<i4"),
-                      ("transA", "<i4"), ("transB", "<i4"), ("nbatch", "<i4"), ("accumulate", "<i4")])
+_DESC_DTYPE = np.dtype(_lib.PackDesc)      # the device tables' rows are laid out by the mirrors of their C structs
+_SG_DTYPE = np.dtype(_lib.SgemmDesc)
 
 
 def _sg(A, B, M, N, K, lda, ldb, ldc, C=0, c_off=-1, tA=0, tB=0, u=0, v=0):

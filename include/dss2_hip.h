@@ -1051,6 +1051,8 @@ int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, in
  * total = sqrt(sum), coef = min(1, max_norm / (total + 1e-6)) in fp32 (torch's formula; a non-finite gradient gives a non-finite norm
  * and coefficient, as in torch), scales its share of the gradients in place, and workgroup 0 writes total to *norm_out.  No float
  * atomics: two runs give the same bits. */
+#define DSS2_OPTIM_GRAD_CHUNK 192      /* tensors of a by-value table per launch */
+#define DSS2_OPTIM_MAX_PARTIALS 256    /* launches x n_wg at most: the length of `partials` */
 typedef struct dss2_grad_desc { float* grad; int64_t n; } dss2_grad_desc;
 typedef struct dss2_grad_flat_desc { int64_t grad_off; int64_t n; } dss2_grad_flat_desc;
 int dss2_grad_sqsum_partials(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc,

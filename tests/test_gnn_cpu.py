@@ -2,11 +2,8 @@
 (tests/golden/case_gnn_*.npz), strict loads of the goldens' state_dicts in their key order, gnn_dsse's construction (the reference's networks.py:11-69
 attributes and state_dict keys through PyG's Sequential naming), the options the kernels refuse, the driver wiring and the
 ctypes mirrors of the new structs."""
-import ctypes
 import json
 import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -183,32 +180,5 @@ def test_runner_builds_the_driver_line_and_the_cli_accepts_it(pkg):
 
 
 def test_struct_layouts_match_the_header_sizes(pkg):
-    """sizeof / offsetof of the new structs compiled from include/dss2_hip.h against the ctypes mirrors."""
-    L = pkg._lib
-    structs = {"dss2_gnn_graph": L.GnnGraph, "dss2_gnn_conv": L.GnnConv, "dss2_gnn_args": L.GnnArgs}
-    lines = ["#include <stdio.h>", "#include <stddef.h>", "#include <stdint.h>", '#include "dss2_hip.h"', "int main(void) {"]
-    want = []
-    for cname, cls in structs.items():
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(ctypes.sizeof(cls))
-        for f, _ in cls._fields_:
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {f}));')
-            want.append(getattr(cls, f).offset)
-    lines += ["return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        with open(c, "w") as fh:
-            fh.write("\n".join(lines))
-        exe = os.path.join(d, "t")
-        cc = None
-        for cand in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang"):
-            r = subprocess.run(["bash", "-c", f"command -v {cand}"], capture_output=True, text=True)
-            if r.returncode == 0:
-                cc = cand
-                break
-        if cc is None:
-            pytest.fail("no C compiler to check the header layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == want
-    assert L.GNN_MAX_K == 4
+    """DSS2_GNN_MAX_K (tests/test_abi_cpu.py holds the mirrors of the new structs to the header)."""
+    assert pkg._lib.GNN_MAX_K == 4

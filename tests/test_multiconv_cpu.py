@@ -1,17 +1,14 @@
 """CPU: the MultiConvNet / ChebConv oracle (tests/cheb_oracle.py) against the reference goldens (tests/golden/case_multiconv_*.npz),
 a hand-derived ChebConv answer, the models' construction (the reference's networks.py:737-835 attributes and state_dict keys), strict
 loads of the goldens' state_dicts, the options the kernels refuse and the ctypes mirrors of the new structs."""
-import ctypes
 import os
-import subprocess
-import tempfile
 import types
 
 import pytest
 import torch
 
 import cheb_oracle as cor
-from conftest import ROOT, load_pkg
+from conftest import load_pkg
 
 
 def _rel(a, b):
@@ -125,16 +122,8 @@ def test_cpu_tensors_raise():
 
 
 def test_struct_layouts_match_the_header_sizes():
-    """ctypes mirrors of the new C structs: same sizes as the C compiler's layout (probe compiled with gcc)."""
-    pkg = load_pkg()
-    src = ('#include <stdio.h>\n#include "dss2_hip.h"\nint main(){printf("%zu %zu %zu %zu %d %d\\n", sizeof(dss2_cheb_graph), '
-           'sizeof(dss2_cheb_layer), sizeof(dss2_cheb_args), sizeof(dss2_cheb_edge_args), DSS2_CHEB_MAX_K, DSS2_CHEB_MAX_CONVS);return 0;}\n')
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "p.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "p.c"), "-o", os.path.join(d, "p")])
-        sizes = [int(v) for v in subprocess.check_output([os.path.join(d, "p")]).split()]
-    L = pkg._lib
-    assert sizes == [ctypes.sizeof(L.ChebGraph), ctypes.sizeof(L.ChebLayer), ctypes.sizeof(L.ChebArgs), ctypes.sizeof(L.ChebEdgeArgs),
-                     L.CHEB_MAX_K, L.CHEB_MAX_CONVS]
+    """The DSS2_CHEB_MAX_* values and the exported entries (tests/test_abi_cpu.py holds the mirrors to the header)."""
+    L = load_pkg()._lib
+    assert (L.CHEB_MAX_K, L.CHEB_MAX_CONVS) == (4, 4)
     for name in ("dss2_cheb_forward", "dss2_cheb_backward", "dss2_cheb_edge_forward", "dss2_cheb_edge_backward"):
         assert name in L.EXPORTED_SYMBOLS

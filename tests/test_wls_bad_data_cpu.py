@@ -8,12 +8,8 @@ Two fp64 routes to the sensitivities -- the leverages of a QR of sqrt(W) H (the 
              8 x STATE_STD_ROUTES = 3.44e-9
   rN         3.8e-4 relative where S is about 1e-6: that is why s_min exists; 2.0e-7 at worst, in units of max(rN, 1), where S >= 2 s_min
 """
-import ctypes
 import functools
 import inspect
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -21,7 +17,7 @@ import torch
 import wls_bad_data_oracle as bo
 import wls_cases as wc
 import wls_oracle as wo
-from conftest import ROOT, load_pkg
+from conftest import load_pkg
 
 S_MIN = 1e-3
 STATE_STD_ROUTES = 4.3e-10     # the worst state_std difference between the fp64 routes (measured 4.24e-10), rounded up; asserted below
@@ -153,29 +149,10 @@ def test_ober_sub_largest_sensitivity_is_a_decoupled_slack_angle():
 
 
 def test_struct_layout_matches_the_header():
-    """sizeof / offsetof of dss2_wls_bad_data_args compiled from include/dss2_hip.h against the ctypes mirror; the solve's block is
-    embedded unchanged."""
+    """The solve's block is embedded unchanged, at offset 0 (tests/test_abi_cpu.py holds every field to the header)."""
     lib = load_pkg()._lib
     cls = lib.WlsBadDataArgs
     assert cls._fields_[0] == ("solve", lib.WlsSolveArgs) and cls.solve.offset == 0
-    lines = ["#include <stdio.h>", "#include <stddef.h>", "#include <stdint.h>", '#include "dss2_hip.h"', "int main(void) {",
-             'printf("%zu\\n", sizeof(dss2_wls_bad_data_args));', 'printf("%zu\\n", sizeof(dss2_wls_solve_args));']
-    want = [ctypes.sizeof(cls), ctypes.sizeof(lib.WlsSolveArgs)]
-    for f, _ in cls._fields_:
-        lines.append(f'printf("%zu\\n", offsetof(dss2_wls_bad_data_args, {f}));')
-        want.append(getattr(cls, f).offset)
-    lines += ["return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        with open(c, "w") as fh:
-            fh.write("\n".join(lines))
-        cc = next((cand for cand in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")
-                   if subprocess.run(["bash", "-c", f"command -v {cand}"], capture_output=True).returncode == 0), None)
-        if cc is None:
-            pytest.fail("no C compiler to check the header layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "t")], check=True)
-        got = [int(v) for v in subprocess.run([os.path.join(d, "t")], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == want
 
 
 def test_lds_helper_admits_every_bus_count_the_solve_serves():

@@ -19,9 +19,6 @@
   * dss2_wls_solve_args' two new fields, graph_ptr and n_graphs, in the ctypes mirrors of all four argument structs against the header.
 """
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -30,7 +27,7 @@ import wls_bad_data_oracle as bo
 import wls_mixed_cases as mc
 import wls_oracle as wo
 import wls_robust_oracle as ro
-from conftest import ROOT, load_pkg
+from conftest import load_pkg
 
 Q_BOUND, SENS_BOUND, RN_BOUND, STD_BOUND, S_MIN, LEAD = 1e-9, 2e-7, 1e-4, 8 * 4.3e-10, 1e-3, 1e-3
 
@@ -140,38 +137,14 @@ def test_the_bad_data_mix_removes_the_injected_errors_clearly():
 
 
 def test_struct_layout_of_the_two_new_fields_matches_the_header():
+    """Where the two fields sit in the mirror and that all three nested structs embed it at offset 0 (tests/test_abi_cpu.py holds every
+    field of the four to the header)."""
     lib = load_pkg()._lib
-    nested = {"dss2_wls_bad_data_args": lib.WlsBadDataArgs, "dss2_wls_large_args": lib.WlsLargeArgs, "dss2_wls_robust_args": lib.WlsRobustArgs}
     S = lib.WlsSolveArgs
     assert [f for f, _ in S._fields_][-2:] == ["graph_ptr", "n_graphs"] and S.n_graphs.offset == S.graph_ptr.offset + 8
     assert S.graph_ptr.offset == S.max_groups.offset + 8 and ctypes.sizeof(S) == S.n_graphs.offset + 8
-    lines = ["#include <stdio.h>", "#include <stddef.h>", "#include <stdint.h>", '#include "dss2_hip.h"', "int main(void) {",
-             'printf("%zu\\n", sizeof(dss2_wls_solve_args));', 'printf("%zu\\n", offsetof(dss2_wls_solve_args, graph_ptr));',
-             'printf("%zu\\n", offsetof(dss2_wls_solve_args, n_graphs));',
-             'printf("%zu\\n", sizeof(((dss2_wls_solve_args*)0)->graph_ptr));', 'printf("%zu\\n", sizeof(((dss2_wls_solve_args*)0)->n_graphs));']
-    want = [ctypes.sizeof(S), S.graph_ptr.offset, S.n_graphs.offset, S.graph_ptr.size, S.n_graphs.size]
-    for cname, cls in nested.items():
+    for cls in (lib.WlsBadDataArgs, lib.WlsLargeArgs, lib.WlsRobustArgs):
         assert cls._fields_[0] == ("solve", S) and cls.solve.offset == 0
-        lines.append(f'printf("%zu\\n", sizeof({cname}));')
-        want.append(ctypes.sizeof(cls))
-        for f in ("graph_ptr", "n_graphs"):
-            lines.append(f'printf("%zu\\n", offsetof({cname}, solve.{f}));')
-            want.append(cls.solve.offset + getattr(S, f).offset)
-        for f, _ in cls._fields_[1:]:          # what follows the solve block moved with it
-            lines.append(f'printf("%zu\\n", offsetof({cname}, {f}));')
-            want.append(getattr(cls, f).offset)
-    lines += ["return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        with open(c, "w") as fh:
-            fh.write("\n".join(lines))
-        cc = next((cand for cand in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")
-                   if subprocess.run(["bash", "-c", f"command -v {cand}"], capture_output=True).returncode == 0), None)
-        if cc is None:
-            pytest.fail("no C compiler to check the header layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "t")], check=True)
-        got = [int(v) for v in subprocess.run([os.path.join(d, "t")], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == want
 
 
 def test_the_python_side_takes_graph_ptr_everywhere():

@@ -1,6 +1,6 @@
 """CPU: what tests/test_gpu_wls_robust.py relies on, without a GPU.
 
-(a) the ctypes mirror of dss2_wls_robust_args against include/dss2_hip.h, the exported entries, wls_robust's signature and the refusals
+(a) the ctypes mirror of dss2_wls_robust_args against the header, the exported entries, wls_robust's signature and the refusals
     that need no device;
 (b) the oracle of tests/wls_robust_oracle.py against tests/wls_oracle.py where the two must coincide exactly (gamma = inf; every iteration
     plain), and on uncorrupted batches at gamma = 3 (nothing is down-weighted, the plain solution within 2e-7);
@@ -17,9 +17,6 @@
 """
 import ctypes
 import inspect
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -29,33 +26,16 @@ import wls_edge_cases as ec
 import wls_large_cases as lc
 import wls_oracle as wo
 import wls_robust_oracle as ro
-from conftest import ROOT, load_pkg
+from conftest import load_pkg
 
 TABLE = ["cigre14", "ober_sub", "n33", "ober179"]
 
 
 def test_struct_layout_matches_the_header():
+    """The solve's block at offset 0 and what follows it (tests/test_abi_cpu.py holds every field to the header)."""
     lib = load_pkg()._lib
     cls = lib.WlsRobustArgs
     assert cls._fields_[0] == ("solve", lib.WlsSolveArgs) and cls.solve.offset == 0
-    lines = ["#include <stdio.h>", "#include <stddef.h>", "#include <stdint.h>", '#include "dss2_hip.h"', "int main(void) {",
-             'printf("%zu\\n", sizeof(dss2_wls_robust_args));', 'printf("%zu\\n", sizeof(dss2_wls_solve_args));']
-    want = [ctypes.sizeof(cls), ctypes.sizeof(lib.WlsSolveArgs)]
-    for f, _ in cls._fields_:
-        lines.append(f'printf("%zu\\n", offsetof(dss2_wls_robust_args, {f}));')
-        want.append(getattr(cls, f).offset)
-    lines += ["return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        with open(c, "w") as fh:
-            fh.write("\n".join(lines))
-        cc = next((cand for cand in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")
-                   if subprocess.run(["bash", "-c", f"command -v {cand}"], capture_output=True).returncode == 0), None)
-        if cc is None:
-            pytest.fail("no C compiler to check the header layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "t")], check=True)
-        got = [int(v) for v in subprocess.run([os.path.join(d, "t")], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == want
     assert ctypes.sizeof(cls) == ctypes.sizeof(lib.WlsSolveArgs) + 56
 
 
