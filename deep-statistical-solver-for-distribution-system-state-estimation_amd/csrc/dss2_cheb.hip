@@ -505,17 +505,17 @@ static int dss2_cheb_edge_backward_launch(const dss2_cheb_edge_args* ap, void* s
 }
 
 extern "C" int dss2_cheb_forward(const dss2_cheb_args* ap, void* stream) {
-  return run_entry(dss2_cheb_forward_launch, ap, stream, "dss2_cheb_forward");
+  return dss2::entry(dss2_cheb_forward_launch, stream, dss2::copied(ap, "dss2_cheb_forward"));
 }
 
 extern "C" int dss2_cheb_backward(const dss2_cheb_args* ap, void* stream) {
-  return run_entry(dss2_cheb_backward_launch, ap, stream, "dss2_cheb_backward");
+  return dss2::entry(dss2_cheb_backward_launch, stream, dss2::copied(ap, "dss2_cheb_backward"));
 }
 
 extern "C" int dss2_cheb_edge_forward(const dss2_cheb_edge_args* ap, void* stream) {
-  return run_entry(dss2_cheb_edge_forward_launch, ap, stream, "dss2_cheb_edge_forward");
+  return dss2::entry(dss2_cheb_edge_forward_launch, stream, dss2::copied(ap, "dss2_cheb_edge_forward"));
 }
 
 extern "C" int dss2_cheb_edge_backward(const dss2_cheb_edge_args* ap, void* stream) {
-  return run_entry(dss2_cheb_edge_backward_launch, ap, stream, "dss2_cheb_edge_backward");
+  return dss2::entry(dss2_cheb_edge_backward_launch, stream, dss2::copied(ap, "dss2_cheb_edge_backward"));
 }

@@ -9,13 +9,12 @@
 #include <string.h>
 
 #include "dss2_hip.h"
+#include "dss2_entry.hpp"      // set_error, the plan hooks, dss2::entry
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace dss2 {
-
-void set_error(const char* fmt, ...);
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
@@ -30,12 +29,9 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 // ---- launch plans (dss2_plan_*, dss2_api.hip): while a plan records, every launch entry point of the library appends a closure --
 // its own launch function bound to COPIES of its host-side arguments -- and dss2_plan_run re-issues the closures in order from ONE C
-// call.  DSS2_RECORD sits in the extern "C" wrapper of an entry point, in front of the call of its *_launch body.
-bool plan_recording();
-void plan_record(std::function<int(void*)> op);
-template <class T> inline std::vector<T> plan_keep(const T* p, size_t n) { return p ? std::vector<T>(p, p + n) : std::vector<T>(); }
-template <class T> inline const T* plan_ptr(const std::vector<T>& v) { return v.empty() ? nullptr : v.data(); }
-#define DSS2_RECORD(...) do { if (dss2::plan_recording()) dss2::plan_record(__VA_ARGS__); } while (0)
+// call.  Every extern "C" entry that takes a stream is one call of dss2::entry (dss2_entry.hpp: the record, then the launch, with
+// copied() / kept() around host structs and host tables) after its *_launch body, or refuses with DSS2_NOT_IN_PLAN
+// (tests/test_entry_cpu.py checks that each does one or the other, and that nothing else calls plan_record).
 // Entry points that are NOT part of a step (structure build, measurement model, z-score: they size their outputs from host-side
 // facts of the batch) refuse to run while a plan records: a plan that silently skipped them would replay on stale structure.
 #define DSS2_NOT_IN_PLAN(name) do { if (dss2::plan_recording()) { dss2::set_error(name ": not available while a launch plan records (it is not a launch of a training step; build it before dss2_plan_begin)"); return 3; } } while (0)

@@ -321,8 +321,7 @@ extern "C" int dss2_collate(const dss2_collate_desc* descs_host, int32_t n_desc,
   if (batch <= 0 || n_desc <= 0) return 0;
   CollateTable tab;
   if (int rc = collate_table(descs_host, n_desc, &tab)) return rc;
-  DSS2_RECORD([tab, n_desc, sample_ids, batch](void* s_) { return collate_launch(tab, n_desc, sample_ids, batch, nullptr, 0, s_); });
-  return collate_launch(tab, n_desc, sample_ids, batch, nullptr, 0, stream);
+  return dss2::entry(collate_launch, stream, tab, n_desc, sample_ids, batch, nullptr, 0);
 }
 
 extern "C" int dss2_collate_cursor(const dss2_collate_desc* descs_host, int32_t n_desc, const int64_t* sample_ids, int64_t* cursor,
@@ -331,8 +330,7 @@ extern "C" int dss2_collate_cursor(const dss2_collate_desc* descs_host, int32_t 
   if (!sample_ids || !cursor) { set_error("collate_cursor: null argument"); return 2; }
   CollateTable tab;
   if (int rc = collate_table(descs_host, n_desc, &tab)) return rc;
-  DSS2_RECORD([tab, n_desc, sample_ids, batch, cursor, advance](void* s_) { return collate_launch(tab, n_desc, sample_ids, batch, cursor, advance, s_); });
-  return collate_launch(tab, n_desc, sample_ids, batch, cursor, advance, stream);
+  return dss2::entry(collate_launch, stream, tab, n_desc, sample_ids, batch, cursor, advance);
 }
 
 extern "C" int dss2_collate_ragged_multi(const dss2_collate_desc* descs_host, int32_t n_cases, int32_t n_desc, const int64_t* const* samp,
@@ -367,8 +365,7 @@ static int accum_scalar_launch(double* acc, const float* value, void* stream) {
 }
 extern "C" int dss2_accum_scalar(double* acc, const float* value, void* stream) {
   if (!acc || !value) { set_error("accum_scalar: null argument"); return 2; }
-  DSS2_RECORD([acc, value](void* s_) { return accum_scalar_launch(acc, value, s_); });
-  return accum_scalar_launch(acc, value, stream);
+  return dss2::entry(accum_scalar_launch, stream, acc, value);
 }
 
 extern "C" int dss2_collate_ragged(const dss2_collate_desc* descs_host, int32_t n_desc, const int64_t* samp,

@@ -905,11 +905,7 @@ static int dss2_edge_fwd_launch(const dss2_edge_args* ap, void* stream) {
   if (a.ell_ent ? a.ntiles <= 0 : a.n_nodes <= 0) return 0;
   return edge_launch(a, edge_select(a.h, a.nrb, a.ell_ent ? a.ell_width : 0, 0, a.bwd_with_u != 0).fwd, false, stream);
 }
-extern "C" int dss2_edge_fwd(const dss2_edge_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_edge_fwd: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_edge_fwd_launch(&a, s_); });
-  return dss2_edge_fwd_launch(ap, stream);
-}
+extern "C" int dss2_edge_fwd(const dss2_edge_args* ap, void* stream) { return dss2::entry(dss2_edge_fwd_launch, stream, dss2::copied(ap, "dss2_edge_fwd")); }
 
 static int dss2_edge_bwd_launch(const dss2_edge_args* ap, void* stream) {
   const dss2_edge_args& a = *ap;
@@ -919,17 +915,8 @@ static int dss2_edge_bwd_launch(const dss2_edge_args* ap, void* stream) {
   const dss2_edge_plan_t p = edge_select(a.h, a.nrb, width, width, a.U != nullptr);
   return edge_launch(a, a.by_source ? p.bwd_src : p.bwd, true, stream);
 }
-extern "C" int dss2_edge_bwd(const dss2_edge_args* ap, void* stream) {
-  if (!ap) { set_error("dss2_edge_bwd: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_edge_bwd_launch(&a, s_); });
-  return dss2_edge_bwd_launch(ap, stream);
-}
+extern "C" int dss2_edge_bwd(const dss2_edge_args* ap, void* stream) { return dss2::entry(dss2_edge_bwd_launch, stream, dss2::copied(ap, "dss2_edge_bwd")); }
 
-static int dss2_edge_combine_fwd_launch(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fe, void* stream);
-extern "C" int dss2_edge_combine_fwd(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fe, void* stream) {
-  DSS2_RECORD([AB, ldab, ea, ldea, W1c, ldw, b1, rowptr, col, ent, S, n_nodes, h, fe](void* s_) { return dss2_edge_combine_fwd_launch(AB, ldab, ea, ldea, W1c, ldw, b1, rowptr, col, ent, S, n_nodes, h, fe, s_); });
-  return dss2_edge_combine_fwd_launch(AB, ldab, ea, ldea, W1c, ldw, b1, rowptr, col, ent, S, n_nodes, h, fe, stream);
-}
 static int dss2_edge_combine_fwd_launch(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fe, void* stream) {
   if (h <= 0 || fe < 0 || fe > EC_MAXFE) { set_error("edge_combine_fwd: h=%d / fe=%d (0..32) unsupported", h, fe); return 2; }
   if (n_nodes <= 0) return 0;
@@ -948,12 +935,10 @@ static int dss2_edge_combine_fwd_launch(const float* AB, int64_t ldab, const flo
   }
   return check_launch("edge_combine_fwd");
 }
-
-static int dss2_edge_combine_bwd_launch(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* dAB, float* slab, int n_slabs, int64_t n_nodes, int h, int fe, int by_source, void* stream);
-extern "C" int dss2_edge_combine_bwd(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* dAB, float* slab, int n_slabs, int64_t n_nodes, int h, int fe, int by_source, void* stream) {
-  DSS2_RECORD([AB, ldab, ea, ldea, W1c, ldw, b1, dS, rowptr, col, ent, dAB, slab, n_slabs, n_nodes, h, fe, by_source](void* s_) { return dss2_edge_combine_bwd_launch(AB, ldab, ea, ldea, W1c, ldw, b1, dS, rowptr, col, ent, dAB, slab, n_slabs, n_nodes, h, fe, by_source, s_); });
-  return dss2_edge_combine_bwd_launch(AB, ldab, ea, ldea, W1c, ldw, b1, dS, rowptr, col, ent, dAB, slab, n_slabs, n_nodes, h, fe, by_source, stream);
+extern "C" int dss2_edge_combine_fwd(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* S, int64_t n_nodes, int h, int fe, void* stream) {
+  return dss2::entry(dss2_edge_combine_fwd_launch, stream, AB, ldab, ea, ldea, W1c, ldw, b1, rowptr, col, ent, S, n_nodes, h, fe);
 }
+
 static int dss2_edge_combine_bwd_launch(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* dAB, float* slab, int n_slabs, int64_t n_nodes, int h, int fe, int by_source, void* stream) {
   if (h <= 0 || fe < 0 || fe > EC_MAXFE) { set_error("edge_combine_bwd: h=%d / fe=%d (0..32) unsupported", h, fe); return 2; }
   if (!by_source && (!slab || n_slabs <= 0)) { set_error("edge_combine_bwd: slab missing"); return 2; }
@@ -973,13 +958,10 @@ static int dss2_edge_combine_bwd_launch(const float* AB, int64_t ldab, const flo
   }
   return check_launch("edge_combine_bwd");
 }
-
-static int dss2_csr_axpy_launch(const dss2_csr_axpy_args* ap, void* stream);
-extern "C" int dss2_csr_axpy(const dss2_csr_axpy_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_csr_axpy: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_csr_axpy_launch(&a, s_); });
-  return dss2_csr_axpy_launch(ap, stream);
+extern "C" int dss2_edge_combine_bwd(const float* AB, int64_t ldab, const float* ea, int64_t ldea, const float* W1c, int64_t ldw, const float* b1, const float* dS, const int32_t* rowptr, const int32_t* col, const int32_t* ent, float* dAB, float* slab, int n_slabs, int64_t n_nodes, int h, int fe, int by_source, void* stream) {
+  return dss2::entry(dss2_edge_combine_bwd_launch, stream, AB, ldab, ea, ldea, W1c, ldw, b1, dS, rowptr, col, ent, dAB, slab, n_slabs, n_nodes, h, fe, by_source);
 }
+
 static int dss2_csr_axpy_launch(const dss2_csr_axpy_args* ap, void* stream) {
   const dss2_csr_axpy_args& a = *ap;
   if (a.n_rows <= 0) return 0;
@@ -997,12 +979,8 @@ static int dss2_csr_axpy_launch(const dss2_csr_axpy_args* ap, void* stream) {
   else hipLaunchKernelGGL(csr_axpy_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), k);
   return check_launch("csr_axpy");
 }
+extern "C" int dss2_csr_axpy(const dss2_csr_axpy_args* ap, void* stream) { return dss2::entry(dss2_csr_axpy_launch, stream, dss2::copied(ap, "dss2_csr_axpy")); }
 
-static int dss2_segment_sum_launch(const float* msg, int64_t ldm, const int32_t* rowptr, const int32_t* ent, float* out, int64_t ldo, int64_t n_rows, int h, void* stream);
-extern "C" int dss2_segment_sum(const float* msg, int64_t ldm, const int32_t* rowptr, const int32_t* ent, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
-  DSS2_RECORD([msg, ldm, rowptr, ent, out, ldo, n_rows, h](void* s_) { return dss2_segment_sum_launch(msg, ldm, rowptr, ent, out, ldo, n_rows, h, s_); });
-  return dss2_segment_sum_launch(msg, ldm, rowptr, ent, out, ldo, n_rows, h, stream);
-}
 static int dss2_segment_sum_launch(const float* msg, int64_t ldm, const int32_t* rowptr, const int32_t* ent, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
   if (h <= 0) { set_error("segment_sum: h=%d", h); return 2; }
   if (n_rows <= 0) return 0;
@@ -1022,12 +1000,10 @@ static int dss2_segment_sum_launch(const float* msg, int64_t ldm, const int32_t*
                      out, ldo, n_rows, h);
   return check_launch("segment_sum");
 }
-
-static int dss2_gather_rows_launch(const float* src, int64_t lds, const int32_t* idx, float* out, int64_t ldo, int64_t n_rows, int h, void* stream);
-extern "C" int dss2_gather_rows(const float* src, int64_t lds, const int32_t* idx, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
-  DSS2_RECORD([src, lds, idx, out, ldo, n_rows, h](void* s_) { return dss2_gather_rows_launch(src, lds, idx, out, ldo, n_rows, h, s_); });
-  return dss2_gather_rows_launch(src, lds, idx, out, ldo, n_rows, h, stream);
+extern "C" int dss2_segment_sum(const float* msg, int64_t ldm, const int32_t* rowptr, const int32_t* ent, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
+  return dss2::entry(dss2_segment_sum_launch, stream, msg, ldm, rowptr, ent, out, ldo, n_rows, h);
 }
+
 static int dss2_gather_rows_launch(const float* src, int64_t lds, const int32_t* idx, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
   if (h <= 0) { set_error("gather_rows: h=%d", h); return 2; }
   if (n_rows <= 0) return 0;
@@ -1039,12 +1015,10 @@ static int dss2_gather_rows_launch(const float* src, int64_t lds, const int32_t*
   else hipLaunchKernelGGL(gather_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), src, lds, idx, out, ldo, n_rows, h);
   return check_launch("gather_rows");
 }
-
-static int dss2_reduce_slabs_launch(const float* slab, int n_slabs, int64_t stride, float* out, int64_t len, void* stream);
-extern "C" int dss2_reduce_slabs(const float* slab, int n_slabs, int64_t stride, float* out, int64_t len, void* stream) {
-  DSS2_RECORD([slab, n_slabs, stride, out, len](void* s_) { return dss2_reduce_slabs_launch(slab, n_slabs, stride, out, len, s_); });
-  return dss2_reduce_slabs_launch(slab, n_slabs, stride, out, len, stream);
+extern "C" int dss2_gather_rows(const float* src, int64_t lds, const int32_t* idx, float* out, int64_t ldo, int64_t n_rows, int h, void* stream) {
+  return dss2::entry(dss2_gather_rows_launch, stream, src, lds, idx, out, ldo, n_rows, h);
 }
+
 static int dss2_reduce_slabs_launch(const float* slab, int n_slabs, int64_t stride, float* out, int64_t len, void* stream) {
   if (len <= 0) return 0;
   if (stride % 4 == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && n_slabs > 0) {
@@ -1058,12 +1032,10 @@ static int dss2_reduce_slabs_launch(const float* slab, int n_slabs, int64_t stri
                      n_slabs, stride, out, len);
   return check_launch("reduce_slabs");
 }
-
-static int dss2_reduce_slabs_multi_launch(const dss2_reduce_desc* descs_host, int n_desc, void* stream);
-extern "C" int dss2_reduce_slabs_multi(const dss2_reduce_desc* descs_host, int n_desc, void* stream) {
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc](void* s_) { return dss2_reduce_slabs_multi_launch(dss2::plan_ptr(d), n_desc, s_); });
-  return dss2_reduce_slabs_multi_launch(descs_host, n_desc, stream);
+extern "C" int dss2_reduce_slabs(const float* slab, int n_slabs, int64_t stride, float* out, int64_t len, void* stream) {
+  return dss2::entry(dss2_reduce_slabs_launch, stream, slab, n_slabs, stride, out, len);
 }
+
 static int dss2_reduce_slabs_multi_launch(const dss2_reduce_desc* descs_host, int n_desc, void* stream) {
   if (n_desc <= 0) return 0;
   if (!descs_host || n_desc > REDUCE_MAX_DESC) { set_error("reduce_slabs_multi: 1..%d descriptors, got %d", REDUCE_MAX_DESC, n_desc); return 2; }
@@ -1085,4 +1057,7 @@ static int dss2_reduce_slabs_multi_launch(const dss2_reduce_desc* descs_host, in
   hipLaunchKernelGGL(reduce_slabs_multi_v4_kernel, dim3((unsigned)blocks, (unsigned)n_desc), dim3(256), 0,
                      as_stream(stream), tab);
   return check_launch("reduce_slabs_multi");
+}
+extern "C" int dss2_reduce_slabs_multi(const dss2_reduce_desc* descs_host, int n_desc, void* stream) {
+  return dss2::entry(dss2_reduce_slabs_multi_launch, stream, dss2::kept(descs_host, n_desc), n_desc);
 }

@@ -422,9 +422,9 @@ static int dss2_gat_backward_launch(const dss2_gat_args* ap, void* stream) {
 }
 
 extern "C" int dss2_gat_forward(const dss2_gat_args* ap, void* stream) {
-  return run_entry(dss2_gat_forward_launch, ap, stream, "dss2_gat_forward");
+  return dss2::entry(dss2_gat_forward_launch, stream, dss2::copied(ap, "dss2_gat_forward"));
 }
 
 extern "C" int dss2_gat_backward(const dss2_gat_args* ap, void* stream) {
-  return run_entry(dss2_gat_backward_launch, ap, stream, "dss2_gat_backward");
+  return dss2::entry(dss2_gat_backward_launch, stream, dss2::copied(ap, "dss2_gat_backward"));
 }

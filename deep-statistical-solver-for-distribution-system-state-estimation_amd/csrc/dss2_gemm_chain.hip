@@ -120,23 +120,13 @@ static dss2_chain_plan_t chain_plan_of(const dss2_gemm_prop_args& a, const dss2_
 }
 static int chain_impl(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, const dss2_chain_plan_t& p, void* stream);
 
-static int dss2_gemm_prop_chain_launch(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, void* stream);
-extern "C" int dss2_gemm_prop_chain(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, void* stream) {
-  if (!ap) { dss2::set_error("dss2_gemm_prop_chain: null argument"); return 2; }
-  DSS2_RECORD([a = *ap, l = dss2::plan_keep(layers, (size_t)(n_layers > 0 ? n_layers : 0)), n_layers](void* s_) { return dss2_gemm_prop_chain_launch(&a, dss2::plan_ptr(l), n_layers, s_); });
-  return dss2_gemm_prop_chain_launch(ap, layers, n_layers, stream);
-}
 static int dss2_gemm_prop_chain_launch(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, void* stream) {
   return chain_impl(ap, layers, n_layers, nullptr, chain_plan_of(*ap, nullptr), stream);
 }
-
-static int dss2_gemm_prop_chain_head_launch(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream);
-extern "C" int dss2_gemm_prop_chain_head(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream) {
-  if (!ap) { dss2::set_error("dss2_gemm_prop_chain_head: null argument"); return 2; }
-  if (!head) { dss2::set_error("dss2_gemm_prop_chain_head: head is NULL"); return 2; }
-  DSS2_RECORD([a = *ap, l = dss2::plan_keep(layers, (size_t)(n_layers > 0 ? n_layers : 0)), n_layers, h = *head](void* s_) { return dss2_gemm_prop_chain_head_launch(&a, dss2::plan_ptr(l), n_layers, &h, s_); });
-  return dss2_gemm_prop_chain_head_launch(ap, layers, n_layers, head, stream);
+extern "C" int dss2_gemm_prop_chain(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, void* stream) {
+  return dss2::entry(dss2_gemm_prop_chain_launch, stream, dss2::copied(ap, "dss2_gemm_prop_chain"), dss2::kept(layers, n_layers), n_layers);
 }
+
 static int dss2_gemm_prop_chain_head_launch(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream) {
   using namespace dss2;
   if (!head || (head->mode != 1 && head->mode != 2)) { set_error("gemm_prop_chain_head: head.mode must be 1 or 2"); return 2; }
@@ -169,6 +159,10 @@ static int dss2_gemm_prop_chain_head_launch(const dss2_gemm_prop_args* ap, const
     }
   }
   return chain_impl(ap, layers, n_layers, head, p, stream);
+}
+extern "C" int dss2_gemm_prop_chain_head(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, void* stream) {
+  if (ap && !head) { dss2::set_error("dss2_gemm_prop_chain_head: head is NULL"); return 2; }      // (a null ap: entry()'s "null argument" comes first)
+  return dss2::entry(dss2_gemm_prop_chain_head_launch, stream, dss2::copied(ap, "dss2_gemm_prop_chain_head"), dss2::kept(layers, n_layers), n_layers, dss2::copied(head));
 }
 
 static int chain_impl(const dss2_gemm_prop_args* ap, const dss2_chain_layer* layers, int n_layers, const dss2_chain_head* head, const dss2_chain_plan_t& p, void* stream) {

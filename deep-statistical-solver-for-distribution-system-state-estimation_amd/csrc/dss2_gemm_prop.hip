@@ -1000,24 +1000,16 @@ extern "C" int dss2_gemm_prop16_supported(int nrb, int nmat, int kreal, int hout
   return gemm_shape_plan(nrb, nmat, kreal, (kreal + 15) / 16 * 16, hout, (hout + 31) / 32, max_nnz, ell_width, 1).kernel == DSS2_GEMM_BF16X6_KHALF;
 }
 
-static int dss2_pack_weights_launch(const dss2_pack_desc* descs, int n_desc, int max_elems, void* stream);
-extern "C" int dss2_pack_weights(const dss2_pack_desc* descs, int n_desc, int max_elems, void* stream) {
-  DSS2_RECORD([descs, n_desc, max_elems](void* s_) { return dss2_pack_weights_launch(descs, n_desc, max_elems, s_); });
-  return dss2_pack_weights_launch(descs, n_desc, max_elems, stream);
-}
 static int dss2_pack_weights_launch(const dss2_pack_desc* descs, int n_desc, int max_elems, void* stream) {
   if (n_desc <= 0) return 0;
   dim3 grid((max_elems + 255) / 256, n_desc);
   hipLaunchKernelGGL(dss2::pack_weights_kernel, grid, dim3(256), 0, dss2::as_stream(stream), descs);
   return dss2::check_launch("pack_weights");
 }
-
-static int dss2_gemm_prop_launch(const dss2_gemm_prop_args* ap, void* stream);
-extern "C" int dss2_gemm_prop(const dss2_gemm_prop_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_gemm_prop: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_gemm_prop_launch(&a, s_); });
-  return dss2_gemm_prop_launch(ap, stream);
+extern "C" int dss2_pack_weights(const dss2_pack_desc* descs, int n_desc, int max_elems, void* stream) {
+  return dss2::entry(dss2_pack_weights_launch, stream, descs, n_desc, max_elems);      // (descs: a DEVICE table)
 }
+
 static int dss2_gemm_prop_launch(const dss2_gemm_prop_args* ap, void* stream) {
   using namespace dss2;
   dss2_gemm_prop_args a = *ap;
@@ -1046,3 +1038,4 @@ static int dss2_gemm_prop_launch(const dss2_gemm_prop_args* ap, void* stream) {
   a.relu = (a.relu & ~(1 << 24)) | (p.kernel == DSS2_GEMM_FP32_KHALF || p.kernel == DSS2_GEMM_BF16X6_KHALF ? 1 << 24 : 0);      // bit 24: K-halved staging, the record's alone
   return gemm_launcher(p.kernel, a.nrb, a.nmat, p.row_split)(a, as_stream(stream), p);      // (non-null: gemm_select asked)
 }
+extern "C" int dss2_gemm_prop(const dss2_gemm_prop_args* ap, void* stream) { return dss2::entry(dss2_gemm_prop_launch, stream, dss2::copied(ap, "dss2_gemm_prop")); }

@@ -229,9 +229,9 @@ static int dss2_gine_backward_launch(const dss2_gine_args* ap, void* stream) {
 }
 
 extern "C" int dss2_gine_forward(const dss2_gine_args* ap, void* stream) {
-  return run_entry(dss2_gine_forward_launch, ap, stream, "dss2_gine_forward");
+  return dss2::entry(dss2_gine_forward_launch, stream, dss2::copied(ap, "dss2_gine_forward"));
 }
 
 extern "C" int dss2_gine_backward(const dss2_gine_args* ap, void* stream) {
-  return run_entry(dss2_gine_backward_launch, ap, stream, "dss2_gine_backward");
+  return dss2::entry(dss2_gine_backward_launch, stream, dss2::copied(ap, "dss2_gine_backward"));
 }

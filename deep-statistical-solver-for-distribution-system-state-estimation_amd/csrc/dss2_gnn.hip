@@ -412,14 +412,13 @@ static int dss2_gnn_dis_launch(const int32_t* rowptr, const int32_t* col, int64_
 }
 
 extern "C" int dss2_gnn_forward(const dss2_gnn_args* ap, void* stream) {
-  return run_entry(dss2_gnn_forward_launch, ap, stream, "dss2_gnn_forward");
+  return dss2::entry(dss2_gnn_forward_launch, stream, dss2::copied(ap, "dss2_gnn_forward"));
 }
 
 extern "C" int dss2_gnn_backward(const dss2_gnn_args* ap, void* stream) {
-  return run_entry(dss2_gnn_backward_launch, ap, stream, "dss2_gnn_backward");
+  return dss2::entry(dss2_gnn_backward_launch, stream, dss2::copied(ap, "dss2_gnn_backward"));
 }
 
 extern "C" int dss2_gnn_dis(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int mode, float* dis, void* stream) {
-  DSS2_RECORD([rowptr, col, n_nodes, mode, dis](void* s_) { return dss2_gnn_dis_launch(rowptr, col, n_nodes, mode, dis, s_); });
-  return dss2_gnn_dis_launch(rowptr, col, n_nodes, mode, dis, stream);
+  return dss2::entry(dss2_gnn_dis_launch, stream, rowptr, col, n_nodes, mode, dis);
 }

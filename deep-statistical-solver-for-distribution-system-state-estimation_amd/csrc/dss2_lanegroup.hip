@@ -39,5 +39,5 @@ static int dss2_lanegroup_wgrad_launch(const dss2_lanegroup_wgrad_args* ap, void
 }
 
 extern "C" int dss2_lanegroup_wgrad(const dss2_lanegroup_wgrad_args* ap, void* stream) {
-  return run_entry(dss2_lanegroup_wgrad_launch, ap, stream, "dss2_lanegroup_wgrad");
+  return dss2::entry(dss2_lanegroup_wgrad_launch, stream, dss2::copied(ap, "dss2_lanegroup_wgrad"));
 }

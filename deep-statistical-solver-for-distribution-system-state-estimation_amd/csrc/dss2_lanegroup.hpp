@@ -147,12 +147,4 @@ inline int launch_group(void (*k8)(Args), void (*k16)(Args), void (*k32)(Args), 
   return check_launch(what);
 }
 
-// the body of an extern "C" entry point: null check, a copy of the args into the recording plan, the launch
-template <class Args>
-inline int run_entry(int (*launch)(const Args*, void*), const Args* ap, void* stream, const char* what) {
-  if (!ap) { set_error("%s: null argument", what); return 2; }
-  DSS2_RECORD([launch, a = *ap](void* s_) { return launch(&a, s_); });
-  return launch(ap, stream);
-}
-
 }  // namespace dss2

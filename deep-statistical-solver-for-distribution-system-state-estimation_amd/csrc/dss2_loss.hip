@@ -533,12 +533,6 @@ __global__ void eval_finish_kernel(const double* __restrict__ partials, int nb, 
 
 using namespace dss2;
 
-static int dss2_wls_loss_partials_launch(const dss2_wls_args* ap, void* stream);
-extern "C" int dss2_wls_loss_partials(const dss2_wls_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_wls_loss_partials: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_wls_loss_partials_launch(&a, s_); });
-  return dss2_wls_loss_partials_launch(ap, stream);
-}
 static int dss2_wls_loss_partials_launch(const dss2_wls_args* ap, void* stream) {
   const dss2_wls_args& a = *ap;
   if (a.n_nodes <= 0 || a.n_edges <= 0) { set_error("wls_loss: empty batch"); return 2; }
@@ -553,25 +547,15 @@ static int dss2_wls_loss_partials_launch(const dss2_wls_args* ap, void* stream) 
                        (double)a.n_edges, a.lam_reg, a.loss, a.edge_count);
   return check_launch("wls_loss_partials");
 }
+extern "C" int dss2_wls_loss_partials(const dss2_wls_args* ap, void* stream) { return dss2::entry(dss2_wls_loss_partials_launch, stream, dss2::copied(ap, "dss2_wls_loss_partials")); }
 
-static int dss2_wls_loss_value_launch(const dss2_wls_args* ap, void* stream);
-extern "C" int dss2_wls_loss_value(const dss2_wls_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_wls_loss_value: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_wls_loss_value_launch(&a, s_); });
-  return dss2_wls_loss_value_launch(ap, stream);
-}
 static int dss2_wls_loss_value_launch(const dss2_wls_args* ap, void* stream) {
   if (!ap->sums || !ap->loss) { set_error("wls_loss_value: null argument"); return 2; }
   hipLaunchKernelGGL(wls_value_kernel, dim3(1), dim3(64), 0, as_stream(stream), ap->sums, ap->lam_reg, ap->loss);
   return check_launch("wls_loss_value");
 }
+extern "C" int dss2_wls_loss_value(const dss2_wls_args* ap, void* stream) { return dss2::entry(dss2_wls_loss_value_launch, stream, dss2::copied(ap, "dss2_wls_loss_value")); }
 
-static int dss2_wls_loss_grad_launch(const dss2_wls_args* ap, void* stream);
-extern "C" int dss2_wls_loss_grad(const dss2_wls_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_wls_loss_grad: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_wls_loss_grad_launch(&a, s_); });
-  return dss2_wls_loss_grad_launch(ap, stream);
-}
 static int dss2_wls_loss_grad_launch(const dss2_wls_args* ap, void* stream) {
   const dss2_wls_args& a = *ap;
   if (a.n_nodes <= 0) { set_error("wls_loss: empty batch"); return 2; }
@@ -579,17 +563,8 @@ static int dss2_wls_loss_grad_launch(const dss2_wls_args* ap, void* stream) {
   hipLaunchKernelGGL(wls_grad_kernel, dim3((unsigned)nb), dim3(LB), 0, as_stream(stream), a);
   return check_launch("wls_loss_grad");
 }
+extern "C" int dss2_wls_loss_grad(const dss2_wls_args* ap, void* stream) { return dss2::entry(dss2_wls_loss_grad_launch, stream, dss2::copied(ap, "dss2_wls_loss_grad")); }
 
-static int dss2_get_pflow_launch(const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
-                                 const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
-                                 int64_t n_nodes, int64_t n_edges, float* vminmax, float* pflow, int apply_shift, void* stream);
-extern "C" int dss2_get_pflow(const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
-                              const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
-                              int64_t n_nodes, int64_t n_edges, float* vminmax, float* pflow, int apply_shift,
-                              void* stream) {
-  DSS2_RECORD([=](void* s_) { return dss2_get_pflow_launch(y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges, vminmax, pflow, apply_shift, s_); });
-  return dss2_get_pflow_launch(y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges, vminmax, pflow, apply_shift, stream);
-}
 static int dss2_get_pflow_launch(const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
                                  const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
                                  int64_t n_nodes, int64_t n_edges, float* vminmax, float* pflow, int apply_shift, void* stream) {
@@ -601,22 +576,15 @@ static int dss2_get_pflow_launch(const float* y, int64_t ldy, const float* node_
                      efrom, eto, n_edges, vminmax, pflow, apply_shift);
   return check_launch("get_pflow");
 }
+extern "C" int dss2_get_pflow(const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
+                              const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
+                              int64_t n_nodes, int64_t n_edges, float* vminmax, float* pflow, int apply_shift,
+                              void* stream) {
+  return dss2::entry(dss2_get_pflow_launch, stream, y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges, vminmax, pflow, apply_shift);
+}
 
 extern "C" int64_t dss2_eval_scratch_doubles(void) { return 256 * dss2::EV_SUMS; }
 
-static int dss2_eval_batch_launch(const float* out, int64_t ldo, const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
-                                  const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
-                                  int64_t n_nodes, int64_t n_edges, const float* x_mean, const float* x_std, float* yhat,
-                                  float* pf_true, float* pf_out, float* vminmax, double* scratch, double* acc, void* stream);
-extern "C" int dss2_eval_batch(const float* out, int64_t ldo, const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
-                               const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
-                               int64_t n_nodes, int64_t n_edges, const float* x_mean, const float* x_std, float* yhat,
-                               float* pf_true, float* pf_out, float* vminmax, double* scratch, double* acc, void* stream) {
-  DSS2_RECORD([=](void* s_) { return dss2_eval_batch_launch(out, ldo, y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges,
-                                                            x_mean, x_std, yhat, pf_true, pf_out, vminmax, scratch, acc, s_); });
-  return dss2_eval_batch_launch(out, ldo, y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges, x_mean, x_std, yhat,
-                                pf_true, pf_out, vminmax, scratch, acc, stream);
-}
 static int dss2_eval_batch_launch(const float* out, int64_t ldo, const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
                                   const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
                                   int64_t n_nodes, int64_t n_edges, const float* x_mean, const float* x_std, float* yhat,
@@ -636,4 +604,11 @@ static int dss2_eval_batch_launch(const float* out, int64_t ldo, const float* y,
   hipLaunchKernelGGL(eval_partials_kernel, dim3(nb), dim3(256), 0, s, yhat, y, ldy, pf_true, pf_out, n_nodes, n_edges, scratch);
   hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(64), 0, s, scratch, nb, (double)n_nodes, acc);
   return check_launch("eval_batch");
+}
+extern "C" int dss2_eval_batch(const float* out, int64_t ldo, const float* y, int64_t ldy, const float* node_param, int64_t ld_np,
+                               const float* edge_param, int64_t ld_ep, const int32_t* efrom, const int32_t* eto,
+                               int64_t n_nodes, int64_t n_edges, const float* x_mean, const float* x_std, float* yhat,
+                               float* pf_true, float* pf_out, float* vminmax, double* scratch, double* acc, void* stream) {
+  return dss2::entry(dss2_eval_batch_launch, stream, out, ldo, y, ldy, node_param, ld_np, edge_param, ld_ep, efrom, eto, n_nodes, n_edges, x_mean, x_std, yhat,
+                     pf_true, pf_out, vminmax, scratch, acc);
 }

@@ -21,17 +21,15 @@ __global__ void __launch_bounds__(256) small_gemm_kernel(const dss2_sgemm_desc* 
 
 }  // namespace dss2
 
-static int dss2_small_gemm_launch(const dss2_sgemm_desc* descs, int n_desc, int max_tiles, float* base_out, void* stream);
-extern "C" int dss2_small_gemm(const dss2_sgemm_desc* descs, int n_desc, int max_tiles, float* base_out, void* stream) {
-  DSS2_RECORD([descs, n_desc, max_tiles, base_out](void* s_) { return dss2_small_gemm_launch(descs, n_desc, max_tiles, base_out, s_); });
-  return dss2_small_gemm_launch(descs, n_desc, max_tiles, base_out, stream);
-}
 static int dss2_small_gemm_launch(const dss2_sgemm_desc* descs, int n_desc, int max_tiles, float* base_out, void* stream) {
   if (n_desc <= 0) return 0;
   if (max_tiles <= 0) { dss2::set_error("small_gemm: max_tiles must be positive"); return 2; }
   hipLaunchKernelGGL(dss2::small_gemm_kernel, dim3(max_tiles, n_desc), dim3(256), 0, dss2::as_stream(stream),
                      descs, base_out);
   return dss2::check_launch("small_gemm");
+}
+extern "C" int dss2_small_gemm(const dss2_sgemm_desc* descs, int n_desc, int max_tiles, float* base_out, void* stream) {
+  return dss2::entry(dss2_small_gemm_launch, stream, descs, n_desc, max_tiles, base_out);      // (descs: a DEVICE table)
 }
 
 // ---- Adamax, Adam / AdamW, RMSprop, SGD (see dss2_hip.h): one multi-tensor kernel templated on the rule.  The arithmetic is torch's
@@ -310,21 +308,18 @@ static int optim_step_flat_launch(const char* who, const void* descs_dev, int ad
 
 extern "C" int dss2_optim_step(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, int step, void* stream) {
   if (int rc = optim_hyper_check(hyper, "optim_step")) return rc;
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step](void* s_) { return optim_step_launch("optim_step", dss2::plan_ptr(d), n_desc, h, step, s_); });
-  return optim_step_launch("optim_step", descs_host, n_desc, *hyper, step, stream);
+  return dss2::entry(optim_step_launch, stream, "optim_step", dss2::kept(descs_host, n_desc), n_desc, *hyper, step);
 }
 
 extern "C" int dss2_optim_step_dev(const dss2_optim_desc* descs_host, int n_desc, const dss2_optim_hyper* hyper, float* step_dev, void* stream) {
   if (int rc = optim_hyper_check(hyper, "optim_step_dev")) return rc;
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), n_desc, h = *hyper, step_dev](void* s_) { return optim_step_dev_launch("optim_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
-  return optim_step_dev_launch("optim_step_dev", descs_host, n_desc, *hyper, step_dev, stream);
+  return dss2::entry(optim_step_dev_launch, stream, "optim_step_dev", dss2::kept(descs_host, n_desc), n_desc, *hyper, step_dev);
 }
 
 extern "C" int dss2_optim_step_flat(const dss2_optim_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base,
                                     const dss2_optim_hyper* hyper, int step, float* step_dev, uint32_t* counter, void* stream) {
   if (int rc = optim_hyper_check(hyper, "optim_step_flat")) return rc;
-  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h = *hyper, step, step_dev, counter](void* s_) { return optim_step_flat_launch("optim_step_flat", descs_dev, 0, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
-  return optim_step_flat_launch("optim_step_flat", descs_dev, 0, n_desc, max_n, grad_base, *hyper, step, step_dev, counter, stream);
+  return dss2::entry(optim_step_flat_launch, stream, "optim_step_flat", descs_dev, 0, n_desc, max_n, grad_base, *hyper, step, step_dev, counter);
 }
 
 // ---- the Adamax entry points of the header: adapters onto the launch bodies above (rule ADAMAX, learning rate from the host)
@@ -335,7 +330,7 @@ static dss2_optim_hyper adamax_hyper(float lr, float beta1, float beta2, float e
   return h;
 }
 
-// (one allocation per call: the converted table is what the launch walks and, when a plan records, what its closure keeps)
+// (one allocation per call: the converted table is what the launch walks and, when a plan records, what its closure copies)
 static std::vector<dss2_optim_desc> adamax_descs(const dss2_adamax_desc* descs_host, int n_desc) {
   std::vector<dss2_optim_desc> d(descs_host && n_desc > 0 ? (size_t)n_desc : 0);
   for (size_t i = 0; i < d.size(); ++i) {
@@ -347,25 +342,20 @@ static std::vector<dss2_optim_desc> adamax_descs(const dss2_adamax_desc* descs_h
 
 extern "C" int dss2_adamax_step(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
   const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
-  std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
-  const int rc = optim_step_launch("adamax_step", dss2::plan_ptr(d), n_desc, h, step, stream);
-  DSS2_RECORD([d = std::move(d), n_desc, h, step](void* s_) { return optim_step_launch("adamax_step", dss2::plan_ptr(d), n_desc, h, step, s_); });
-  return rc;
+  const std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
+  return dss2::entry(optim_step_launch, stream, "adamax_step", dss2::kept(d.data(), d.size()), n_desc, h, step);
 }
 
 extern "C" int dss2_adamax_step_dev(const dss2_adamax_desc* descs_host, int n_desc, float lr, float beta1, float beta2, float eps, float weight_decay, float* step_dev, void* stream) {
   const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
-  std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
-  const int rc = optim_step_dev_launch("adamax_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, stream);
-  DSS2_RECORD([d = std::move(d), n_desc, h, step_dev](void* s_) { return optim_step_dev_launch("adamax_step_dev", dss2::plan_ptr(d), n_desc, h, step_dev, s_); });
-  return rc;
+  const std::vector<dss2_optim_desc> d = adamax_descs(descs_host, n_desc);
+  return dss2::entry(optim_step_dev_launch, stream, "adamax_step_dev", dss2::kept(d.data(), d.size()), n_desc, h, step_dev);
 }
 
 // (the table is in device memory in the 40-byte layout: the kernel reads it as it is)
 extern "C" int dss2_adamax_step_flat(const dss2_adamax_flat_desc* descs_dev, int n_desc, int64_t max_n, const float* grad_base, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* step_dev, uint32_t* counter, void* stream) {
   const dss2_optim_hyper h = adamax_hyper(lr, beta1, beta2, eps, weight_decay);
-  DSS2_RECORD([descs_dev, n_desc, max_n, grad_base, h, step, step_dev, counter](void* s_) { return optim_step_flat_launch("adamax_step_flat", descs_dev, 1, n_desc, max_n, grad_base, h, step, step_dev, counter, s_); });
-  return optim_step_flat_launch("adamax_step_flat", descs_dev, 1, n_desc, max_n, grad_base, h, step, step_dev, counter, stream);
+  return dss2::entry(optim_step_flat_launch, stream, "adamax_step_flat", descs_dev, 1, n_desc, max_n, grad_base, h, step, step_dev, counter);
 }
 
 // ---- gradient clipping: by-value chunks of a host table, or the whole device table of a flat bucket, for both launches
@@ -380,12 +370,7 @@ static int grad_args_check(const dss2_grad_desc* descs_host, const dss2_grad_fla
   return 0;
 }
 
-static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc, int n_wg, double* partials, void* stream);
-extern "C" int dss2_grad_sqsum_partials(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base,
-                                        int n_desc, int n_wg, double* partials, void* stream) {
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), host = descs_host != nullptr, descs_dev, grad_base, n_desc, n_wg, partials](void* s_) { return dss2_grad_sqsum_partials_launch(host ? d.data() : nullptr, descs_dev, grad_base, n_desc, n_wg, partials, s_); });
-  return dss2_grad_sqsum_partials_launch(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, stream);
-}
+// (both bodies refuse n_desc <= 0 before they choose between the tables, so kept()'s null for an empty host table decides nothing)
 static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base, int n_desc, int n_wg, double* partials, void* stream) {
   if (n_desc <= 0) { dss2::set_error("grad_sqsum_partials: no gradients"); return 2; }
   if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_sqsum_partials")) return rc;
@@ -401,13 +386,11 @@ static int dss2_grad_sqsum_partials_launch(const dss2_grad_desc* descs_host, con
   }
   return dss2::check_launch("grad_sqsum_partials");
 }
-
-static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc, int n_wg, const double* partials, float max_norm, float* norm_out, void* stream);
-extern "C" int dss2_grad_clip_scale(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc,
-                                    int n_wg, const double* partials, float max_norm, float* norm_out, void* stream) {
-  DSS2_RECORD([d = dss2::plan_keep(descs_host, (size_t)(n_desc > 0 ? n_desc : 0)), host = descs_host != nullptr, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out](void* s_) { return dss2_grad_clip_scale_launch(host ? d.data() : nullptr, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out, s_); });
-  return dss2_grad_clip_scale_launch(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out, stream);
+extern "C" int dss2_grad_sqsum_partials(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, const float* grad_base,
+                                        int n_desc, int n_wg, double* partials, void* stream) {
+  return dss2::entry(dss2_grad_sqsum_partials_launch, stream, dss2::kept(descs_host, n_desc), descs_dev, grad_base, n_desc, n_wg, partials);
 }
+
 static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc, int n_wg, const double* partials, float max_norm, float* norm_out, void* stream) {
   if (n_desc <= 0) { dss2::set_error("grad_clip_scale: no gradients"); return 2; }
   if (int rc = grad_args_check(descs_host, descs_dev, grad_base, n_desc, n_wg, partials, "grad_clip_scale")) return rc;
@@ -423,6 +406,10 @@ static int dss2_grad_clip_scale_launch(const dss2_grad_desc* descs_host, const d
         })) return rc;
   }
   return dss2::check_launch("grad_clip_scale");
+}
+extern "C" int dss2_grad_clip_scale(const dss2_grad_desc* descs_host, const dss2_grad_flat_desc* descs_dev, float* grad_base, int n_desc,
+                                    int n_wg, const double* partials, float max_norm, float* norm_out, void* stream) {
+  return dss2::entry(dss2_grad_clip_scale_launch, stream, dss2::kept(descs_host, n_desc), descs_dev, grad_base, n_desc, n_wg, partials, max_norm, norm_out);
 }
 
 
@@ -449,17 +436,15 @@ __global__ void __launch_bounds__(256) dropout_mask_kernel(const uint64_t* __res
 }
 }  // namespace dss2
 
-static int dss2_rng_next_launch(uint64_t* state, uint64_t* snapshot, uint64_t host_seed, int use_host_seed, void* stream);
-extern "C" int dss2_rng_next(uint64_t* state, uint64_t* snapshot, uint64_t host_seed, int use_host_seed, void* stream) {
-  DSS2_RECORD([state, snapshot, host_seed, use_host_seed](void* s_) { return dss2_rng_next_launch(state, snapshot, host_seed, use_host_seed, s_); });
-  return dss2_rng_next_launch(state, snapshot, host_seed, use_host_seed, stream);
-}
 static int dss2_rng_next_launch(uint64_t* state, uint64_t* snapshot, uint64_t host_seed, int use_host_seed, void* stream) {
   if (!snapshot || (!use_host_seed && !state)) { dss2::set_error("rng_next: null argument"); return 2; }
   hipLaunchKernelGGL(dss2::rng_next_kernel, dim3(1), dim3(64), 0, dss2::as_stream(stream),
                      reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(snapshot),
                      (unsigned long long)host_seed, use_host_seed);
   return dss2::check_launch("rng_next");
+}
+extern "C" int dss2_rng_next(uint64_t* state, uint64_t* snapshot, uint64_t host_seed, int use_host_seed, void* stream) {
+  return dss2::entry(dss2_rng_next_launch, stream, state, snapshot, host_seed, use_host_seed);
 }
 
 // p -> (threshold, scale) exactly as the Python side computes them for the kernels (one definition: this one)
@@ -473,12 +458,6 @@ extern "C" void dss2_dropout_params(float p, uint32_t* thr, float* scale) {
   }
 }
 
-static int dss2_dropout_mask_launch(const uint64_t* snapshot, int32_t drop_id, float p, int64_t n_rows, int h, float* out, int64_t ldo, void* stream);
-extern "C" int dss2_dropout_mask(const uint64_t* snapshot, int32_t drop_id, float p, int64_t n_rows, int h, float* out,
-                                 int64_t ldo, void* stream) {
-  DSS2_RECORD([=](void* s_) { return dss2_dropout_mask_launch(snapshot, drop_id, p, n_rows, h, out, ldo, s_); });
-  return dss2_dropout_mask_launch(snapshot, drop_id, p, n_rows, h, out, ldo, stream);
-}
 static int dss2_dropout_mask_launch(const uint64_t* snapshot, int32_t drop_id, float p, int64_t n_rows, int h, float* out, int64_t ldo, void* stream) {
   if (!snapshot || !out || drop_id <= 0 || h <= 0) { dss2::set_error("dropout_mask: bad arguments"); return 2; }
   if (n_rows <= 0) return 0;
@@ -489,6 +468,10 @@ static int dss2_dropout_mask_launch(const uint64_t* snapshot, int32_t drop_id, f
   hipLaunchKernelGGL(dss2::dropout_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, dss2::as_stream(stream), snapshot,
                      (uint32_t)drop_id, thr, scale, n_rows, h, out, ldo);
   return dss2::check_launch("dropout_mask");
+}
+extern "C" int dss2_dropout_mask(const uint64_t* snapshot, int32_t drop_id, float p, int64_t n_rows, int h, float* out,
+                                 int64_t ldo, void* stream) {
+  return dss2::entry(dss2_dropout_mask_launch, stream, snapshot, drop_id, p, n_rows, h, out, ldo);
 }
 
 
@@ -516,11 +499,6 @@ __global__ void __launch_bounds__(256) gate_grad_kernel(const float* __restrict_
 }
 }  // namespace dss2
 
-static int dss2_gate_grad_launch(const float* g, const float* y, float* out, int64_t n_rows, int h, const uint64_t* snapshot, int32_t drop_id, float p, int relu, void* stream);
-extern "C" int dss2_gate_grad(const float* g, const float* y, float* out, int64_t n_rows, int h, const uint64_t* snapshot, int32_t drop_id, float p, int relu, void* stream) {
-  DSS2_RECORD([g, y, out, n_rows, h, snapshot, drop_id, p, relu](void* s_) { return dss2_gate_grad_launch(g, y, out, n_rows, h, snapshot, drop_id, p, relu, s_); });
-  return dss2_gate_grad_launch(g, y, out, n_rows, h, snapshot, drop_id, p, relu, stream);
-}
 static int dss2_gate_grad_launch(const float* g, const float* y, float* out, int64_t n_rows, int h, const uint64_t* snapshot, int32_t drop_id, float p, int relu, void* stream) {
   if (!g || !out || (relu && !y) || h <= 0) { dss2::set_error("gate_grad: bad arguments"); return 2; }
   if (n_rows <= 0) return 0;
@@ -531,4 +509,7 @@ static int dss2_gate_grad_launch(const float* g, const float* y, float* out, int
   hipLaunchKernelGGL(dss2::gate_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, dss2::as_stream(stream), g, y, out, n_rows, h,
                      snapshot, (uint32_t)drop_id, thr, scale, relu);
   return dss2::check_launch("gate_grad");
+}
+extern "C" int dss2_gate_grad(const float* g, const float* y, float* out, int64_t n_rows, int h, const uint64_t* snapshot, int32_t drop_id, float p, int relu, void* stream) {
+  return dss2::entry(dss2_gate_grad_launch, stream, g, y, out, n_rows, h, snapshot, drop_id, p, relu);
 }

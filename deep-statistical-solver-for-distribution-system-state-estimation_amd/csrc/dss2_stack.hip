@@ -1163,12 +1163,6 @@ extern "C" int dss2_stack_supported(const dss2_stack_dims* d, int hid, int nmat,
           ell_width <= S_MAX_ELL && ellT_width >= 1 && ellT_width <= S_MAX_ELL) ? 1 : 0;
 }
 
-static int dss2_stack_pack_launch(const dss2_stack_dims* d, const float* const* params, uint32_t* wpack, uint64_t* rng_state, uint64_t* rng_snapshot, uint64_t host_seed, int use_host_seed, float* tick, const dss2_stack_args* tiles, void* stream);
-extern "C" int dss2_stack_pack(const dss2_stack_dims* d, const float* const* params, uint32_t* wpack, uint64_t* rng_state, uint64_t* rng_snapshot, uint64_t host_seed, int use_host_seed, float* tick, const dss2_stack_args* tiles, void* stream) {
-  if (!d) { dss2::set_error("dss2_stack_pack: null argument"); return 2; }
-  DSS2_RECORD([dd = *d, params, wpack, rng_state, rng_snapshot, host_seed, use_host_seed, tick, has_t = tiles != nullptr, tt = tiles ? *tiles : dss2_stack_args{}](void* s_) { return dss2_stack_pack_launch(&dd, params, wpack,      /* (params: a DEVICE table of pointers) */ rng_state, rng_snapshot, host_seed, use_host_seed, tick, has_t ? &tt : nullptr, s_); });
-  return dss2_stack_pack_launch(d, params, wpack, rng_state, rng_snapshot, host_seed, use_host_seed, tick, tiles, stream);
-}
 static int dss2_stack_pack_launch(const dss2_stack_dims* d, const float* const* params, uint32_t* wpack, uint64_t* rng_state, uint64_t* rng_snapshot, uint64_t host_seed, int use_host_seed, float* tick, const dss2_stack_args* tiles, void* stream) {
   if (!dims_ok(*d) || !params || !wpack) { set_error("stack_pack: bad arguments"); return 2; }
   if (rng_snapshot && !use_host_seed && !rng_state) { set_error("stack_pack: rng_state missing"); return 2; }
@@ -1184,6 +1178,9 @@ static int dss2_stack_pack_launch(const dss2_stack_dims* d, const float* const* 
                      (unsigned long long)host_seed, use_host_seed, tick, ep);
   return check_launch("stack_pack");
 }
+extern "C" int dss2_stack_pack(const dss2_stack_dims* d, const float* const* params, uint32_t* wpack, uint64_t* rng_state, uint64_t* rng_snapshot, uint64_t host_seed, int use_host_seed, float* tick, const dss2_stack_args* tiles, void* stream) {
+  return dss2::entry(dss2_stack_pack_launch, stream, dss2::copied(d, "dss2_stack_pack"), params /* (a DEVICE table of pointers) */, wpack, rng_state, rng_snapshot, host_seed, use_host_seed, tick, dss2::copied(tiles));
+}
 
 static int stack_args_ok(const dss2_stack_args& a, const char* what) {
   if (!dims_ok(a.dims)) { set_error("%s: unsupported dimensions", what); return 2; }
@@ -1195,12 +1192,6 @@ static int stack_args_ok(const dss2_stack_args& a, const char* what) {
   return 0;
 }
 
-static int dss2_stack_forward_launch(const dss2_stack_args* ap, void* stream);
-extern "C" int dss2_stack_forward(const dss2_stack_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_stack_forward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_stack_forward_launch(&a, s_); });
-  return dss2_stack_forward_launch(ap, stream);
-}
 static int dss2_stack_forward_launch(const dss2_stack_args* ap, void* stream) {
   const dss2_stack_args& a = *ap;
   if (a.ntiles <= 0) return 0;
@@ -1212,13 +1203,8 @@ static int dss2_stack_forward_launch(const dss2_stack_args* ap, void* stream) {
   hipLaunchKernelGGL(stack_fwd_kernel, dim3(a.ntiles), dim3(512), stack_fwd_lds(a.ell_width), as_stream(stream), a);
   return check_launch("stack_forward");
 }
+extern "C" int dss2_stack_forward(const dss2_stack_args* ap, void* stream) { return dss2::entry(dss2_stack_forward_launch, stream, dss2::copied(ap, "dss2_stack_forward")); }
 
-static int dss2_stack_backward_launch(const dss2_stack_args* ap, void* stream);
-extern "C" int dss2_stack_backward(const dss2_stack_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_stack_backward: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_stack_backward_launch(&a, s_); });
-  return dss2_stack_backward_launch(ap, stream);
-}
 static int dss2_stack_backward_launch(const dss2_stack_args* ap, void* stream) {
   const dss2_stack_args& a = *ap;
   if (a.ntiles <= 0) return 0;
@@ -1231,13 +1217,8 @@ static int dss2_stack_backward_launch(const dss2_stack_args* ap, void* stream) {
   hipLaunchKernelGGL(stack_bwd_kernel, dim3(a.n_wg), dim3(512), stack_bwd_lds(a.ell_width, a.ellT_width), as_stream(stream), a);
   return check_launch("stack_backward");
 }
+extern "C" int dss2_stack_backward(const dss2_stack_args* ap, void* stream) { return dss2::entry(dss2_stack_backward_launch, stream, dss2::copied(ap, "dss2_stack_backward")); }
 
-static int dss2_stack_reduce_launch(const dss2_stack_dims* d, const float* slab, int32_t n_slabs, int64_t slab_stride, const float* const* params, float* flat, float* fold_scratch, void* stream);
-extern "C" int dss2_stack_reduce(const dss2_stack_dims* d, const float* slab, int32_t n_slabs, int64_t slab_stride, const float* const* params, float* flat, float* fold_scratch, void* stream) {
-  if (!d) { dss2::set_error("dss2_stack_reduce: null argument"); return 2; }
-  DSS2_RECORD([dd = *d, slab, n_slabs, slab_stride, params, flat, fold_scratch](void* s_) { return dss2_stack_reduce_launch(&dd, slab, n_slabs, slab_stride, params, flat, fold_scratch, s_); });
-  return dss2_stack_reduce_launch(d, slab, n_slabs, slab_stride, params, flat, fold_scratch, stream);
-}
 static int dss2_stack_reduce_launch(const dss2_stack_dims* d, const float* slab, int32_t n_slabs, int64_t slab_stride, const float* const* params, float* flat, float* fold_scratch, void* stream) {
   if (!dims_ok(*d) || !slab || !params || !flat || !fold_scratch || n_slabs < 1 || (slab_stride & 3)) { set_error("stack_reduce: bad arguments"); return 2; }
   const int64_t total = dss2_stack_flat_floats(d);
@@ -1246,4 +1227,7 @@ static int dss2_stack_reduce_launch(const dss2_stack_dims* d, const float* slab,
                      fold_scratch, fl_block(d->n_hh, d->dout_inner), d->n_blocks);
   hipLaunchKernelGGL(stack_fold_bwd_kernel, dim3(d->n_blocks * 4), dim3(256), 0, s, *d, params, fold_scratch, flat);
   return check_launch("stack_reduce");
+}
+extern "C" int dss2_stack_reduce(const dss2_stack_dims* d, const float* slab, int32_t n_slabs, int64_t slab_stride, const float* const* params, float* flat, float* fold_scratch, void* stream) {
+  return dss2::entry(dss2_stack_reduce_launch, stream, dss2::copied(d, "dss2_stack_reduce"), slab, n_slabs, slab_stride, params, flat, fold_scratch);
 }

@@ -775,7 +775,25 @@ extern "C" int dss2_csr_build_graphs(const dss2_csr_build_args* ap, int32_t node
   return check_launch("csr_build_graphs");
 }
 
-static int ell_tiles_launch(const dss2_ell_build_args& b, void* stream);
+// (the tilings' ELL tables: dss2_ell_tiles_build, and the closed-form tilings of dss2_csr_build_padded)
+static int ell_tiles_launch(const dss2_ell_build_args& b, void* stream) {
+  if (b.ntiles <= 0 || b.tm <= 0) { set_error("ell_tiles_build: bad arguments"); return 2; }
+  EllArgs a = {};
+  a.rowptr[0] = b.rowptr; a.col[0] = b.col; a.ent[0] = b.ent; a.w[0] = b.w;
+  a.rowptr[1] = b.rowptrT; a.col[1] = b.colT; a.ent[1] = b.entT; a.w[1] = b.wT;
+  a.ell_w[0] = reinterpret_cast<int2*>(b.ell_tiles); a.ell_e[0] = reinterpret_cast<int2*>(b.ell_ent_tiles);
+  a.ell_w[1] = reinterpret_cast<int2*>(b.ellT_tiles); a.ell_e[1] = reinterpret_cast<int2*>(b.ellT_ent_tiles);
+  a.D[0] = b.ell_width; a.D[1] = b.ellT_width;
+  a.tile_start = b.tile_start; a.ntiles = b.ntiles; a.TM = b.tm; a.meta = b.meta;
+  a.uniform_rows = b.uniform_rows; a.N = b.n_nodes; a.tile_start_w = const_cast<int32_t*>(b.tile_start);
+  if (b.uniform_rows < 0 || (b.uniform_rows > 0 && (b.n_nodes <= 0 || b.uniform_rows > b.tm || (int64_t)b.uniform_rows * b.ntiles < b.n_nodes))) {
+    set_error("ell_tiles_build: uniform_rows / n_nodes do not describe ntiles tiles of <= tm rows"); return 2;
+  }
+  if ((a.D[0] > 0 && (!a.ell_w[0] || !a.ell_e[0])) || (a.D[1] > 0 && (!a.ell_w[1] || !a.ell_e[1]))) { set_error("ell_tiles_build: null output"); return 2; }
+  hipLaunchKernelGGL(ell_tiles_kernel, dim3(b.ntiles, 2), dim3(256), 0, as_stream(stream), a);
+  return check_launch("ell_tiles_build");
+}
+
 static int csr_build_padded_launch(const dss2_padded_build_args& q, void* stream) {
   const dss2_csr_build_args& a = q.csr;
   hipStream_t s = as_stream(stream);
@@ -819,8 +837,7 @@ extern "C" int dss2_csr_build_padded(const dss2_padded_build_args* qp, void* str
   if (q.n_ell < 0 || q.n_ell > DSS2_PADDED_MAX_TILINGS) { set_error("csr_build_padded: 0..%d tilings", DSS2_PADDED_MAX_TILINGS); return 2; }
   for (int i = 0; i < q.n_ell; ++i)
     if (q.ell[i].uniform_rows <= 0) { set_error("csr_build_padded: tiling %d is not closed-form (uniform_rows > 0 expected)", i); return 2; }
-  DSS2_RECORD([q](void* s_) { return csr_build_padded_launch(q, s_); });
-  return csr_build_padded_launch(q, stream);
+  return dss2::entry(csr_build_padded_launch, stream, q);
 }
 
 extern "C" int dss2_tiles_uniform(int32_t* tile_start, int32_t ntiles, int32_t rows_per_tile, int64_t n_nodes, void* stream) {
@@ -845,23 +862,6 @@ extern "C" int dss2_tiles_walk(const int32_t* lastcut, int64_t n_nodes, const in
 extern "C" int dss2_ell_tiles_build(const dss2_ell_build_args* ap, void* stream) {
   DSS2_NOT_IN_PLAN("dss2_ell_tiles_build");
   return ell_tiles_launch(*ap, stream);
-}
-static int ell_tiles_launch(const dss2_ell_build_args& b, void* stream) {
-  if (b.ntiles <= 0 || b.tm <= 0) { set_error("ell_tiles_build: bad arguments"); return 2; }
-  EllArgs a = {};
-  a.rowptr[0] = b.rowptr; a.col[0] = b.col; a.ent[0] = b.ent; a.w[0] = b.w;
-  a.rowptr[1] = b.rowptrT; a.col[1] = b.colT; a.ent[1] = b.entT; a.w[1] = b.wT;
-  a.ell_w[0] = reinterpret_cast<int2*>(b.ell_tiles); a.ell_e[0] = reinterpret_cast<int2*>(b.ell_ent_tiles);
-  a.ell_w[1] = reinterpret_cast<int2*>(b.ellT_tiles); a.ell_e[1] = reinterpret_cast<int2*>(b.ellT_ent_tiles);
-  a.D[0] = b.ell_width; a.D[1] = b.ellT_width;
-  a.tile_start = b.tile_start; a.ntiles = b.ntiles; a.TM = b.tm; a.meta = b.meta;
-  a.uniform_rows = b.uniform_rows; a.N = b.n_nodes; a.tile_start_w = const_cast<int32_t*>(b.tile_start);
-  if (b.uniform_rows < 0 || (b.uniform_rows > 0 && (b.n_nodes <= 0 || b.uniform_rows > b.tm || (int64_t)b.uniform_rows * b.ntiles < b.n_nodes))) {
-    set_error("ell_tiles_build: uniform_rows / n_nodes do not describe ntiles tiles of <= tm rows"); return 2;
-  }
-  if ((a.D[0] > 0 && (!a.ell_w[0] || !a.ell_e[0])) || (a.D[1] > 0 && (!a.ell_w[1] || !a.ell_e[1]))) { set_error("ell_tiles_build: null output"); return 2; }
-  hipLaunchKernelGGL(ell_tiles_kernel, dim3(b.ntiles, 2), dim3(256), 0, as_stream(stream), a);
-  return check_launch("ell_tiles_build");
 }
 
 extern "C" int dss2_deg_pows(const int32_t* rowptr, const int32_t* col, const float* w, const float* deg, int64_t n_nodes,

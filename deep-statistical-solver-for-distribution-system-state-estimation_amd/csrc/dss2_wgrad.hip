@@ -900,23 +900,12 @@ static int wgrad_dispatch(const dss2_wgrad_args& a, void* stream, const dss2::Wg
   return wgrad_launcher(a.nrb, a.narrow ? 1 : a.nmat, p.nb)(a, s, wb, p);      // (narrow: the matrices are columns of ONE pass; non-null: wgrad_select asked)
 }
 
-static int dss2_wgrad_launch(const dss2_wgrad_args* ap, void* stream);
-extern "C" int dss2_wgrad(const dss2_wgrad_args* ap, void* stream) {
-  if (!ap) { dss2::set_error("dss2_wgrad: null argument"); return 2; }
-  DSS2_RECORD([a = *ap](void* s_) { return dss2_wgrad_launch(&a, s_); });
-  return dss2_wgrad_launch(ap, stream);
-}
 static int dss2_wgrad_launch(const dss2_wgrad_args* ap, void* stream) {
   dss2::WgradBatch wb = {};
   return wgrad_dispatch(*ap, stream, wb);
 }
+extern "C" int dss2_wgrad(const dss2_wgrad_args* ap, void* stream) { return dss2::entry(dss2_wgrad_launch, stream, dss2::copied(ap, "dss2_wgrad")); }
 
-static int dss2_wgrad_batched_launch(const dss2_wgrad_args* ap, const float* const* Gs, const float* const* Xs, float* const* slabs, const float* const* rowscale2s, int64_t slab_stride, int n_layers, void* stream);
-extern "C" int dss2_wgrad_batched(const dss2_wgrad_args* ap, const float* const* Gs, const float* const* Xs, float* const* slabs, const float* const* rowscale2s, int64_t slab_stride, int n_layers, void* stream) {
-  if (!ap) { dss2::set_error("dss2_wgrad_batched: null argument"); return 2; }
-  DSS2_RECORD([a = *ap, g = dss2::plan_keep(Gs, (size_t)(n_layers > 0 ? n_layers : 0)), x = dss2::plan_keep(Xs, (size_t)(n_layers > 0 ? n_layers : 0)), sl = dss2::plan_keep(slabs, (size_t)(n_layers > 0 ? n_layers : 0)), r = dss2::plan_keep(rowscale2s, (size_t)(rowscale2s && n_layers > 0 ? n_layers : 0)), slab_stride, n_layers](void* s_) { return dss2_wgrad_batched_launch(&a, dss2::plan_ptr(g), dss2::plan_ptr(x), dss2::plan_ptr(sl), dss2::plan_ptr(r), slab_stride, n_layers, s_); });
-  return dss2_wgrad_batched_launch(ap, Gs, Xs, slabs, rowscale2s, slab_stride, n_layers, stream);
-}
 static int dss2_wgrad_batched_launch(const dss2_wgrad_args* ap, const float* const* Gs, const float* const* Xs, float* const* slabs, const float* const* rowscale2s, int64_t slab_stride, int n_layers, void* stream) {
   if (n_layers < 1 || n_layers > dss2::WGRAD_MAX_BATCH) { dss2::set_error("wgrad_batched: 1..%d layers, got %d", dss2::WGRAD_MAX_BATCH, n_layers); return 2; }
   if (!Gs || !Xs || !slabs) { dss2::set_error("wgrad_batched: null pointer table"); return 2; }
@@ -933,6 +922,10 @@ static int dss2_wgrad_batched_launch(const dss2_wgrad_args* ap, const float* con
   a.G = Gs[0]; a.X = Xs[0]; a.slab = slabs[0];
   a.rowscale2 = nullptr;   // per layer, from the table
   return wgrad_dispatch(a, stream, wb);
+}
+extern "C" int dss2_wgrad_batched(const dss2_wgrad_args* ap, const float* const* Gs, const float* const* Xs, float* const* slabs, const float* const* rowscale2s, int64_t slab_stride, int n_layers, void* stream) {
+  return dss2::entry(dss2_wgrad_batched_launch, stream, dss2::copied(ap, "dss2_wgrad_batched"), dss2::kept(Gs, n_layers), dss2::kept(Xs, n_layers), dss2::kept(slabs, n_layers),
+                     dss2::kept(rowscale2s, n_layers), slab_stride, n_layers);
 }
 
 #ifdef DSS2_STAMPS

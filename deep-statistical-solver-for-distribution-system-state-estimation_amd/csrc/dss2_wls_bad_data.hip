@@ -2,7 +2,7 @@
 // residual sensitivities, normalized residuals, the chi-square test and the removal of the largest normalized residual, repeated --
 // all inside ONE launch, one workgroup per graph, the launch geometry of wls_solve.  The device functions of the solve are those of
 // dss2_wls_core.hpp, with a mask that gives a removed measurement the weight 0 everywhere it enters, and so are a graph's prologue,
-// the state store, the launch path and the entry wrapper (ws_graph, ws_store_state, ws_launch, ws_entry); the measurement pass, the arg-max,
+// the state store and the launch path (ws_graph, ws_store_state, ws_launch); the measurement pass, the arg-max,
 // the decision and the outputs are those of dss2_wls_bad_data_core.hpp, with Sigma addressed on the packed triangle (BdPacked).
 //
 //   LDS   the solve's carve (packed G with the b row, u, du, ctl, slack flags), then a fixed block:
@@ -121,7 +121,8 @@ extern "C" size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph) {
   return nodes_per_graph > 0 ? bd_bytes(nodes_per_graph) : 0;
 }
 
-static int wls_bad_data_launch(const dss2_wls_bad_data_args& b, void* stream) {
+static int wls_bad_data_launch(const dss2_wls_bad_data_args* bp, void* stream) {
+  const dss2_wls_bad_data_args& b = *bp;
   if (int rc = ws_check_args(b.solve, "wls_bad_data", BD_EXTRA_BYTES)) return rc;
   const int n = b.solve.nodes_per_graph;
   if (2 * n > 256) { set_error("wls_bad_data: %d states do not fit the workgroup that owns the covariance's rows", 2 * n); return 2; }
@@ -129,5 +130,5 @@ static int wls_bad_data_launch(const dss2_wls_bad_data_args& b, void* stream) {
   return ws_launch<wls_bad_data_kernel<64>, wls_bad_data_kernel<256>>(b, bd_bytes(n), "wls_bad_data", as_stream(stream));
 }
 extern "C" int dss2_wls_bad_data(const dss2_wls_bad_data_args* bp, void* stream) {
-  return ws_entry(bp, stream, "dss2_wls_bad_data", wls_bad_data_launch);
+  return dss2::entry(wls_bad_data_launch, stream, dss2::copied(bp, "dss2_wls_bad_data"));
 }

@@ -6,8 +6,7 @@
 //   - a graph's range (ws_range: the uniform layout, or graph_ptr with nodes_per_graph as a bound, and the guard of the latter), its
 //     prologue (ws_graph) and the plain epilogue (ws_store_state, ws_finish), once for every kernel;
 //   - wls_lds_kernel, the ONE kernel body with the gain matrix in LDS: the plain and the Huber estimator are two instantiations of it;
-//   - the host side: the argument checks, ws_launch (the launch path of every kernel on the LDS carve) and ws_entry (the null check
-//     and the launch plan's record of every entry).
+//   - the host side: the argument checks and ws_launch (the launch path of every kernel on the LDS carve).
 // The LDS layout, the row ownership and the order of every sum are described in the header of dss2_wls_solve.hip; nothing here
 // depends on which kernel runs it.
 //
@@ -594,14 +593,6 @@ inline int ws_launch(const Args& b, size_t lds, const char* who, hipStream_t s) 
     hipLaunchKernelGGL(K256, dim3((unsigned)grid), dim3(256), lds, s, b);
   }
   return check_launch(who);
-}
-
-// An extern "C" entry: the null check, the launch plan's record (a closure over a COPY of the arguments), the launch body
-template <class Args>
-inline int ws_entry(const Args* bp, void* stream, const char* name, int (*launch)(const Args&, void*)) {
-  if (!bp) { set_error("%s: null argument", name); return 2; }
-  DSS2_RECORD([b = *bp, launch](void* s_) { return launch(b, s_); });
-  return launch(*bp, stream);
 }
 
 }  // namespace dss2

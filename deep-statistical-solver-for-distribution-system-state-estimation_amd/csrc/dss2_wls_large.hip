@@ -46,11 +46,12 @@ extern "C" int64_t dss2_wls_large_groups(const dss2_wls_solve_args* ap) {
   return wl_grid(*ap);
 }
 
-static int wls_solve_large_launch(const dss2_wls_large_args& b, void* stream) {
+static int wls_solve_large_launch(const dss2_wls_large_args* bp, void* stream) {
+  const dss2_wls_large_args& b = *bp;
   if (int rc = wl_check_size(b.solve, "wls_solve_large")) return rc;
   if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;
   return wl_launch<wls_blocked_kernel<dss2_wls_large_args>>(b, "wls_solve_large", as_stream(stream));
 }
 extern "C" int dss2_wls_solve_large(const dss2_wls_large_args* bp, void* stream) {
-  return ws_entry(bp, stream, "dss2_wls_solve_large", wls_solve_large_launch);
+  return dss2::entry(wls_solve_large_launch, stream, dss2::copied(bp, "dss2_wls_solve_large"));
 }

@@ -31,8 +31,9 @@ static int wr_check_params(const dss2_wls_robust_args& b, const char* who) {
   return 0;
 }
 
-static int wls_robust_launch(const dss2_wls_robust_args& b, void* stream) {
+static int wls_robust_launch(const dss2_wls_robust_args* bp, void* stream) {
   using B = dss2_wls_robust_args;
+  const B& b = *bp;
   if (int rc = ws_check_args(b.solve, "wls_robust", 0)) return rc;
   if (int rc = wr_check_params(b, "wls_robust")) return rc;
   // (the wide kernel's uniform launches keep an instantiation without the graph_ptr branch: with it they measured 2.5 % slower)
@@ -40,14 +41,15 @@ static int wls_robust_launch(const dss2_wls_robust_args& b, void* stream) {
     return ws_launch<wls_lds_kernel<64, B>, wls_lds_kernel<256, B, WsUniformRange>>(b, ws_bytes(b.solve.nodes_per_graph), "wls_robust", as_stream(stream));
   return ws_launch<wls_lds_kernel<64, B>, wls_lds_kernel<256, B>>(b, ws_bytes(b.solve.nodes_per_graph), "wls_robust", as_stream(stream));
 }
-extern "C" int dss2_wls_robust(const dss2_wls_robust_args* bp, void* stream) { return ws_entry(bp, stream, "dss2_wls_robust", wls_robust_launch); }
+extern "C" int dss2_wls_robust(const dss2_wls_robust_args* bp, void* stream) { return dss2::entry(wls_robust_launch, stream, dss2::copied(bp, "dss2_wls_robust")); }
 
-static int wls_robust_large_launch(const dss2_wls_robust_args& b, void* stream) {
+static int wls_robust_large_launch(const dss2_wls_robust_args* bp, void* stream) {
+  const dss2_wls_robust_args& b = *bp;
   if (int rc = wl_check_size(b.solve, "wls_robust_large")) return rc;
   if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_robust_large")) return rc;
   if (int rc = wr_check_params(b, "wls_robust_large")) return rc;
   return wl_launch<wls_blocked_kernel<dss2_wls_robust_args>>(b, "wls_robust_large", as_stream(stream));
 }
 extern "C" int dss2_wls_robust_large(const dss2_wls_robust_args* bp, void* stream) {
-  return ws_entry(bp, stream, "dss2_wls_robust_large", wls_robust_large_launch);
+  return dss2::entry(wls_robust_large_launch, stream, dss2::copied(bp, "dss2_wls_robust_large"));
 }

@@ -37,9 +37,10 @@ extern "C" size_t dss2_wls_solve_lds_bytes(int nodes_per_graph) {
   return nodes_per_graph > 0 ? ws_bytes(nodes_per_graph) : 0;
 }
 
-static int wls_solve_launch(const dss2_wls_solve_args& a, void* stream) {
+static int wls_solve_launch(const dss2_wls_solve_args* ap, void* stream) {
   using A = dss2_wls_solve_args;
+  const A& a = *ap;
   if (int rc = ws_check_args(a, "wls_solve", 0)) return rc;
   return ws_launch<wls_lds_kernel<64, A>, wls_lds_kernel<256, A>>(a, ws_bytes(a.nodes_per_graph), "wls_solve", as_stream(stream));
 }
-extern "C" int dss2_wls_solve(const dss2_wls_solve_args* ap, void* stream) { return ws_entry(ap, stream, "dss2_wls_solve", wls_solve_launch); }
+extern "C" int dss2_wls_solve(const dss2_wls_solve_args* ap, void* stream) { return dss2::entry(wls_solve_launch, stream, dss2::copied(ap, "dss2_wls_solve")); }

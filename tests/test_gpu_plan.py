@@ -5,6 +5,7 @@ every launch; the reference runs its loop from Python, /root/reference/dss2_run.
 * replaying the plan gives bit for bit the eager step: loss, outputs, every parameter gradient -- MPN on the chained kernels (the C2
   model), the C1 configuration on the whole-stack kernels, a SkipPFN with in-kernel dropout (device-side random state);
 * N planned training steps with the fused Adamax (capturable: device-side step count) = N eager steps, bit for bit in every parameter;
+* a recorded op owns copies of its host table and of its argument struct: the caller's are zeroed before the replay (dss2::entry);
 * a plan that is still recording cannot be run; recording twice at once is refused;
 * tensors allocated between two replays are not written by the second one (every thread's allocations of the recorded step stay in the plan's pool).
 """
@@ -101,6 +102,64 @@ def test_planned_training_steps_with_fused_adamax_equal_eager_steps(pkg):
     torch.cuda.synchronize()
     for a, b in zip(p1, p2):
         assert torch.equal(a, b), (a - b).abs().max().item()
+
+
+def test_a_recorded_op_owns_its_host_table_and_its_argument_struct(pkg):
+    """The two argument wrappers of dss2::entry (csrc/dss2_entry.hpp) on the device path, through direct ctypes calls: kept() around the
+    HOST descriptor table of dss2_reduce_slabs_multi, copied() around the argument struct of dss2_csr_axpy.  Both are zeroed in place
+    after the recording; the replay must still give the eager results bit for bit."""
+    M, L = pkg._lib, pkg._lib.lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator().manual_seed(5)
+    slab_a, slab_b = torch.randn(3, 16, generator=gen).to(DEV), torch.randn(2, 20, generator=gen).to(DEV)      # (20: no multiple of 16)
+    out_a, out_b = torch.empty(16, device=DEV), torch.empty(20, device=DEV)
+    rowptr = torch.tensor([0, 2, 3, 3, 5, 6], dtype=torch.int32, device=DEV)                                    # 5 rows, one of them empty
+    col = torch.tensor([1, 4, 0, 2, 3, 0], dtype=torch.int32, device=DEV)
+    w, T = torch.randn(6, generator=gen).to(DEV), torch.randn(5, 4, generator=gen).to(DEV)
+    out_c = torch.empty(5, 4, device=DEV)
+    outs = (out_a, out_b, out_c)
+
+    def fresh():
+        descs = (M.ReduceDesc * 2)(M.ReduceDesc(slab_a.data_ptr(), out_a.data_ptr(), 16, 16, 3, 0),
+                                   M.ReduceDesc(slab_b.data_ptr(), out_b.data_ptr(), 20, 20, 2, 0))
+        a = M.CsrAxpyArgs(rowptr=rowptr.data_ptr(), col=col.data_ptr(), w=w.data_ptr(), T=T.data_ptr(), ldt=4, out=out_c.data_ptr(), ldo=4,
+                          n_rows=5, h=4)
+        return descs, a
+
+    def launch(descs, a):
+        M.check(L.dss2_reduce_slabs_multi(descs, 2, stream), "dss2_reduce_slabs_multi")
+        M.check(L.dss2_csr_axpy(C.byref(a), stream), "dss2_csr_axpy")
+
+    for o in outs:
+        o.fill_(float("nan"))
+    launch(*fresh())
+    torch.cuda.synchronize()
+    eager = [o.clone() for o in outs]
+    assert torch.allclose(eager[0], slab_a.sum(0), atol=1e-5) and torch.allclose(eager[1], slab_b.sum(0), atol=1e-5)
+    ref_c = torch.zeros(5, 4, device=DEV).index_add_(0, torch.repeat_interleave(torch.arange(5, device=DEV), rowptr.diff().long()),
+                                                      w[:, None] * T[col.long()])
+    assert torch.allclose(eager[2], ref_c, atol=1e-5)
+
+    h = C.c_void_p()
+    assert L.dss2_plan_begin(C.byref(h)) == 0
+    try:
+        descs, a = fresh()
+        launch(descs, a)
+    finally:
+        assert L.dss2_plan_end(h) == 0
+    try:
+        assert L.dss2_plan_size(h) == 2
+        C.memset(descs, 0, C.sizeof(descs))          # the caller's table and struct are the caller's again
+        C.memset(C.byref(a), 0, C.sizeof(a))
+        for _ in range(2):                           # (a plan is reusable)
+            for o in outs:
+                o.fill_(float("nan"))
+            M.check(L.dss2_plan_run(h, stream), "dss2_plan_run")
+            torch.cuda.synchronize()
+            for o, e in zip(outs, eager):
+                assert torch.equal(o, e)
+    finally:
+        L.dss2_plan_destroy(h)
 
 
 def test_plan_api_refuses_misuse(pkg):
