@@ -228,7 +228,7 @@ class WlsBadDataArgs(C.Structure):
                 ("max_removals", C.c_int32), ("pad_", C.c_int32), ("dof", C.c_void_p), ("chi2_limit", C.c_void_p),
                 ("suspect", C.c_void_p), ("removed", C.c_void_p), ("removed_rn", C.c_void_p), ("n_removed", C.c_void_p),
                 ("bus_rn", C.c_void_p), ("bus_sens", C.c_void_p), ("edge_rn", C.c_void_p), ("edge_sens", C.c_void_p),
-                ("state_std", C.c_void_p)]
+                ("state_std", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
 
 
 class WlsLargeArgs(C.Structure):

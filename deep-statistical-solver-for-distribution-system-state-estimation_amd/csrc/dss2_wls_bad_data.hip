@@ -25,7 +25,16 @@
 //
 // Every __syncthreads() sits in control flow that is uniform over the workgroup (failed, the round's flag and ok are uniform: every
 // thread derives them from the same LDS words).  The thread that owns a row of Sigma is its index: 2 n <= T is checked at the entry.
+//
+// THE BLOCKED FORM (wls_bad_data_blocked_kernel; args.workspace != NULL): the same rounds for 1 to 256 buses per graph on the layout of
+// csrc/dss2_wls_large.hip -- G on block rows in the workgroup's slice of a workspace in global memory, a block column's panel in LDS,
+// 256 threads, the large solve's grid.  Per round: wl_gauss_newton with the removal mask; G at the last iterate formed and factorised
+// once more (wl_form, wl_factor); the inversion in place on the block rows (wl_invert, dss2_wls_large_invert.hpp: blocked in 16 rows,
+// the owner of a COLUMN in place of the owner of a row, since 2 n may exceed the workgroup); then steps 3 and 4 above by the same bd_*
+// functions with Sigma addressed on the block rows (BdBlockRows).  LDS is the large solve's carve of the bound, then the same fixed
+// block (red, rem).  Everything after the rounds is the LDS kernel's; the objective's per-bus parts go through du.
 #include "dss2_wls_bad_data_core.hpp"
+#include "dss2_wls_large_invert.hpp"
 
 namespace dss2 {
 
@@ -113,6 +122,81 @@ __global__ void __launch_bounds__(T) wls_bad_data_kernel(const dss2_wls_bad_data
   }
 }
 
+struct BdBlockRows {                     // Sigma on the block rows of dss2_wls_large_core.hpp (the blocked kernel)
+  const double* Sg;
+  __device__ __forceinline__ double operator()(int p, int q) const {
+    const int hi = p > q ? p : q, lo = p > q ? q : p;
+    return Sg[wl_row_off(hi) + lo];
+  }
+};
+
+static_assert(2 * (wl_lds_bytes(WL_MAX_NODES) + BD_EXTRA_BYTES) <= (size_t)kMaxLdsBytes, "two workgroups of the largest graph per CU, with the bad-data block");
+
+// (the second bound: two waves per SIMD, i.e. two workgroups per CU -- the compiler then keeps to 256 registers in all)
+__global__ void __launch_bounds__(WL_T, 2) wls_bad_data_blocked_kernel(const dss2_wls_bad_data_args b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bl_smem[];
+  const dss2_wls_solve_args& a = b.solve;
+  // (the slice and the place of the fixed block are sized by nodes_per_graph -- with a graph_ptr: the bound -- as in wls_blocked_kernel)
+  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wl_graph_doubles(a.nodes_per_graph);
+  const BdLds r = bd_carve(bl_smem + wl_lds_bytes(a.nodes_per_graph));
+  const int slots = b.max_removals > 1 ? b.max_removals : 1;
+  float vlv, vhv;
+  vminmax_fold(a.vminmax, vlv, vhv);
+  const int64_t n_graphs = ws_n_graphs(a);
+  // Two things here are for the register allocator alone (with either one missing the kernel spills).  The graphs
+  // ws_range refuses get their outputs in a loop of their own, so that what bd_refuse needs is not kept alive across the solves; and the
+  // thread's index passes through an empty asm at the head of every graph, so that addresses formed from it are formed where they are
+  // used, not once before the loop and carried through it.
+  int tid = threadIdx.x;
+  if (tid == 0)
+    for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x)
+      if (!ws_range(a, gr).ok) bd_refuse(b, gr, slots);
+  for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
+    asm volatile("" : "+v"(tid));
+    const WsRange rg = ws_range(a, gr);
+    if (!rg.ok) continue;                // uniform over the workgroup (its outputs were written above)
+    const int n = rg.n, ns = 2 * n;
+    const WlLds l = wl_carve(bl_smem, n);
+    const WsGraph g = ws_graph(rg.base, n, vlv, l.u, l.slk);
+    const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
+    ws_load_start<WL_T>(a, g, start, tid);
+    WsTally t = {0, 1, 0.0};
+    int nrem = 0, n_active = 0;          // nrem is uniform; n_active is thread 0's
+    bool removing = true;                // uniform
+    for (int round = 0; round <= b.max_removals; ++round) {
+      if (removing) {
+        const WsRemoved mask = {r.rem, nrem};
+        wl_gauss_newton(a, g, A, l, ns, tid, t, WsNoWeight(), mask);
+        bool failed = l.ctl[0] != 0 && l.ctl[1] == 0;      // (uniform: the words of the last iteration run, behind its barrier)
+        if (!failed) {
+          wl_form(a, g, A, ns, tid, WsNoWeight(), mask);   // (its first barrier: ctl has been read)
+          const bool ok = wl_factor(A, l, ns, tid);
+          if (tid == 0) l.ctl[3] = ok ? 1 : 0;             // (wave 0's answer, made the workgroup's)
+          __syncthreads();
+          if (l.ctl[3] == 0) {
+            failed = true;
+            if (tid == 0) t.status = 2;
+          }
+        }
+        if (!failed) wl_invert(A, l, ns, tid);
+        BdBest best = {-1.0, 0x7fffffff};
+        int cnt = 0;
+        const BdBlockRows Sg = {A};
+        for (int k = tid; k < n; k += WL_T) bd_bus(b, g, Sg, k, mask, failed, best, cnt);
+        for (int q = tid; q < ns; q += WL_T)
+          b.state_std[(g.base + (q >> 1)) * 2 + (q & 1)] = (failed || ((q & 1) && l.slk[q >> 1])) ? 0.0 : sqrt(Sg(q, q));
+        removing = bd_decide<WL_T>(b, r, l.ctl, gr, slots, failed, nrem, tid, best, cnt, n_active);
+        if (removing) ++nrem;
+      }
+    }
+    ws_store_state<WL_T>(a, g, ns, tid);
+    double jb, je;
+    ws_objective<WL_T>(a, g, l.du, tid, WsRemoved{r.rem, nrem}, jb, je);
+    if (tid == 0) bd_finish(b, gr, t, jb, je, n_active, nrem, slots, l.slk, n);
+    __syncthreads();                     // the next graph of this workgroup reuses the LDS (rem and slk included)
+  }
+}
+
 }  // namespace dss2
 
 using namespace dss2;
@@ -123,6 +207,13 @@ extern "C" size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph) {
 
 static int wls_bad_data_launch(const dss2_wls_bad_data_args* bp, void* stream) {
   const dss2_wls_bad_data_args& b = *bp;
+  if (b.workspace) {                     // the blocked form
+    const char* who = "wls_bad_data (blocked)";
+    if (int rc = wl_check_size(b.solve, who)) return rc;
+    if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, who)) return rc;
+    if (int rc = bd_check_params(b, who)) return rc;
+    return wl_launch<wls_bad_data_blocked_kernel>(b, who, as_stream(stream), BD_EXTRA_BYTES);
+  }
   if (int rc = ws_check_args(b.solve, "wls_bad_data", BD_EXTRA_BYTES)) return rc;
   const int n = b.solve.nodes_per_graph;
   if (2 * n > 256) { set_error("wls_bad_data: %d states do not fit the workgroup that owns the covariance's rows", 2 * n); return 2; }

@@ -1,5 +1,5 @@
-// The blocked fp64 WLS solve with the gain matrix in global memory, shared by csrc/dss2_wls_large.hip (the plain estimator) and
-// csrc/dss2_wls_robust.hip (the Huber M-estimator's large form): the workspace layout, the LDS carve, the rows' assembly, the blocked
+// The blocked fp64 WLS solve with the gain matrix in global memory, shared by csrc/dss2_wls_large.hip (the plain estimator),
+// csrc/dss2_wls_robust.hip (the Huber M-estimator's large form) and csrc/dss2_wls_bad_data.hip (the blocked bad-data kernel): the workspace layout, the LDS carve, the rows' assembly, the blocked
 // Cholesky and back substitution, the Gauss-Newton loop (wl_gauss_newton), the ONE kernel body on this layout (wls_blocked_kernel: the
 // two estimators are two instantiations of it), and the host side -- the entries' size check, grid and workspace check, and their
 // launch path (wl_launch).  The layout and every step are described in the header of dss2_wls_large.hip; nothing here depends on which
@@ -48,14 +48,16 @@ __device__ __forceinline__ double wl_lane(double x, int lane) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane), __builtin_amdgcn_readlane(__double2loint(x), lane));
 }
 
-// A <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read A before are done with).
-template <class Wt = WsNoWeight>
-__device__ __forceinline__ void wl_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, int ns, int tid, const Wt& wt = Wt()) {
+// A <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read A before are done with).  `mask` is the
+// removal mask of dss2_wls_core.hpp (WsNoMask, the default, compiles to nothing: the plain and the Huber kernel).
+template <class Wt = WsNoWeight, class Mask = WsNoMask>
+__device__ __forceinline__ void wl_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, int ns, int tid, const Wt& wt = Wt(),
+                                        const Mask& mask = Mask()) {
   const size_t pairs = wl_graph_doubles(g.n) / 2;
   __syncthreads();
   for (size_t p = tid; p < pairs; p += WL_T) reinterpret_cast<wl_d2*>(A)[p] = wl_d2{0.0, 0.0};
   __syncthreads();
-  for (int r = tid; r < ns; r += WL_T) ws_accumulate_row_at(a, g, r, A + wl_row_off(r), A + wl_row_off(ns), WsNoMask(), wt);
+  for (int r = tid; r < ns; r += WL_T) ws_accumulate_row_at(a, g, r, A + wl_row_off(r), A + wl_row_off(ns), mask, wt);
 }
 
 // Wave 0: the diagonal block at (j0, j0), w columns wide, factorised in registers; lane i < w holds row i.  Returns whether every pivot
@@ -224,15 +226,16 @@ __device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A,
 
 // ws_gauss_newton's counterpart on this layout: Gauss-Newton from the state in LDS, at most a.max_iter iterations (the trip count is
 // fixed; a graph that has stopped skips the body, uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status
-// (1, then 0 or 2) and t.last.  wt.at(it) is the weighting of iteration `it`.  Ends with a barrier.
-template <class Wt>
+// (1, then 0 or 2) and t.last.  wt.at(it) is the weighting of iteration `it`, `mask` the removal mask.  Ends with a barrier, after which
+// l.ctl = {stop, apply} of the last iteration run: stop without apply is a failed factorisation.
+template <class Wt, class Mask = WsNoMask>
 __device__ __forceinline__ void wl_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, const WlLds& l, int ns,
-                                                int tid, WsTally& t, const Wt& wt) {
+                                                int tid, WsTally& t, const Wt& wt, const Mask& mask = Mask()) {
   t.status = 1;
   bool active = true;                                  // uniform over the workgroup
   for (int it = 0; it < a.max_iter; ++it) {
     if (active) {
-      wl_form(a, g, A, ns, tid, wt.at(it));
+      wl_form(a, g, A, ns, tid, wt.at(it), mask);
       const bool ok = wl_factor(A, l, ns, tid);
       wl_back_substitute(A, l, ns, tid);
       ws_decide(a, l.du, l.ctl, ns, tid, ok, t);
@@ -314,14 +317,15 @@ inline int wl_check_workspace(const dss2_wls_solve_args& a, const void* workspac
   }
   return ws_check_rest(a, who);
 }
-// The launch of kernel K on this layout, after the entry's checks (ws_launch's counterpart; the flag is K's own here too)
+// The launch of kernel K on this layout, after the entry's checks (ws_launch's counterpart; the flag is K's own here too).  extra_lds:
+// what K keeps behind the carve of the bound.
 template <auto K, class Args>
-inline int wl_launch(const Args& b, const char* who, hipStream_t s) {
+inline int wl_launch(const Args& b, const char* who, hipStream_t s, size_t extra_lds = 0) {
   const dss2_wls_solve_args& a = b.solve;
   static std::atomic<uint32_t> done{0};
   if (int rc = ensure_max_lds(reinterpret_cast<const void*>(K), done, who)) return rc;
   launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
-  hipLaunchKernelGGL(K, dim3((unsigned)wl_grid(a)), dim3(WL_T), wl_lds_bytes(a.nodes_per_graph), s, b);
+  hipLaunchKernelGGL(K, dim3((unsigned)wl_grid(a)), dim3(WL_T), wl_lds_bytes(a.nodes_per_graph) + extra_lds, s, b);
   return check_launch(who);
 }
 

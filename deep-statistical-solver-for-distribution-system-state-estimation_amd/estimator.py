@@ -22,12 +22,17 @@ The rest of the classical estimator on the same solve and in the same single lau
 on J, residual sensitivities and normalized residuals, removal of the largest one followed by a re-solve, the state's standard deviation.
 It inverts the gain matrix in LDS: up to 99 buses per graph.
 
+    wls_bad_data_large(... same arguments ...) -> WLSBadDataResult
+
+The same test for up to ``max_nodes_per_graph_large()`` = 256 buses per graph (ober179), small graphs included: the blocked kernels of
+``wls_estimate_large``, the gain matrix inverted in place on its block rows in the workspace.  Opt-in: ``wls_bad_data`` keeps its limit.
+
     wls_robust(... same inputs ..., gamma=3.0, plain_iters=1, large=None) -> WLSRobustResult
 
 The second classical answer to gross errors, for every bus count up to 256: the Huber M-estimator by iteratively re-weighted
 Gauss-Newton on the kernels of ``wls_estimate`` and ``wls_estimate_large`` (csrc/dss2_wls_robust.hip).  No covariance, one launch.
 
-Batches that mix bus counts: all four take the keyword ``graph_ptr`` (``_public`` at the end of the module adds it: the parameter lists
+Batches that mix bus counts: all five take the keyword ``graph_ptr`` (``_public`` at the end of the module adds it: the parameter lists
 above are pinned by callers and tests, and ``inspect.signature`` goes on reporting them), a contiguous int64 device tensor [G + 1] of row offsets (what
 ``synthetic.make_batch`` returns for a list of grids and ``dataset.MixedDataset`` puts on its batches).  Graph g then owns rows
 [graph_ptr[g], graph_ptr[g + 1]) and ``nodes_per_graph`` is an UPPER BOUND on a graph's bus count, known on the host: the kernel choice,
@@ -286,7 +291,7 @@ def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
                  init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
                  weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
                  confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0,
-                 graph_ptr: Optional[torch.Tensor] = None) -> WLSBadDataResult:
+                 graph_ptr: Optional[torch.Tensor] = None, large: bool = False) -> WLSBadDataResult:
     """``wls_estimate`` followed, inside the same launch, by the chi-square test, the largest-normalized-residual test and up to
     ``max_removals`` removals, each followed by a re-solve from the current state.  A measurement is active if its weight
     c_k R^-1 is above 0 and it has not been removed; S_i = 1 - w_i h_i Sigma h_i^T, rN_i = |z_i - h_i(u)| sqrt(w_i / S_i) where
@@ -294,7 +299,8 @@ def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
     Ids: 4 i + k for bus i (row of x), k in V, theta, P, Q; 4 N + 2 e + k for stored branch e, k in P_from, Q_from.
     With ``max_removals = 0`` the first five fields are ``wls_estimate``'s, bit for bit.
     ``graph_ptr`` as for ``wls_estimate``: ``nodes_per_graph`` is then an upper bound (a bound above 99 is refused as 100 buses are),
-    and the ids -- ``removed`` among them -- stay the global ones above."""
+    and the ids -- ``removed`` among them -- stay the global ones above.
+    ``large`` (``wls_bad_data_large``): the blocked form, up to ``max_nodes_per_graph_large()`` buses, with ``wls_estimate_large``'s workspace."""
     def check_own():
         if not threshold > 0:
             raise ValueError("threshold must be > 0")
@@ -306,7 +312,10 @@ def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
             raise ValueError("s_min must be in (0, 1)")
 
     def refuse_size(n):
-        if _lib.lib().dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
+        if large and n > max_nodes_per_graph_large():
+            raise NotImplementedError(f"wls_bad_data_large keeps a block column's panel of the gain matrix in LDS: at most "
+                                      f"{max_nodes_per_graph_large()} buses per graph, got {n}")
+        if not large and _lib.lib().dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
             raise NotImplementedError(f"wls_bad_data keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
 
     b = _lib.WlsBadDataArgs()
@@ -326,9 +335,29 @@ def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
      b.state_std) = (t.data_ptr() for t in res[5:])
     b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
     b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
-    _lib.check(_lib.lib().dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
+    L = _lib.lib()
+    if large:                    # (a non-null workspace selects the blocked form; kept by (device, bytes) like wls_estimate_large's: a recorded launch replays with its address)
+        need = int(L.dss2_wls_large_workspace_bytes(b.solve.nodes_per_graph, L.dss2_wls_large_groups(C.byref(b.solve))))
+        if (dev, need) not in _WORKSPACES:
+            _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        b.workspace, b.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
+    _lib.check(L.dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
     del keep                     # (held until here: the launch has been issued)
     return res
+
+
+def _wls_bad_data_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                       init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                       weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
+                       confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0,
+                       graph_ptr: Optional[torch.Tensor] = None) -> WLSBadDataResult:
+    """``wls_bad_data`` -- the same inputs, rounds, result and decisions -- for graphs of up to ``max_nodes_per_graph_large()`` buses,
+    small ones included: the solves are ``wls_estimate_large``'s (its five outputs to the bit with ``max_removals = 0``), and the gain
+    matrix is inverted in place on its block rows in ``wls_estimate_large``'s workspace, csrc/dss2_wls_bad_data.hip.  Still one launch,
+    recordable.  Against ``wls_bad_data`` on a graph both serve the sums run in another order: equal to rounding, not to the bit.
+    ``graph_ptr`` as for ``wls_estimate``: with it ``nodes_per_graph`` is an upper bound, and the workspace is sized by the bound."""
+    return _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, threshold,
+                         max_removals, confidence, s_min, max_groups, graph_ptr=graph_ptr, large=True)
 
 
 def _public(impl):
@@ -380,3 +409,12 @@ def wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n
                  confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0) -> WLSBadDataResult:
     return _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, threshold,
                          max_removals, confidence, s_min, max_groups)
+
+
+@_public(_wls_bad_data_large)
+def wls_bad_data_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                       init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                       weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
+                       confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0) -> WLSBadDataResult:
+    return _wls_bad_data_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                               threshold, max_removals, confidence, s_min, max_groups)

@@ -339,8 +339,10 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
     that did not end with status 0).  ``model`` None: a flat start, the baseline a learned estimator is compared with; a model: its
     de-normalised output is the start, the hybrid.  ``solver_kw``: max_iter, tol, weights.  ``bad_data`` = dict(threshold=...,
     max_removals=..., [confidence, s_min]): the solve is ``estimator.wls_bad_data`` with these, and the metrics gain ``wls_suspect``
-    (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed; ``wls_bad_data`` has no large form:
-    above ``estimator.max_nodes_per_graph()`` buses it refuses).  The keyword ``robust`` = dict(gamma=..., [plain_iters]) (taken out of
+    (graphs that fail the chi-square test after the removals) and ``wls_removed`` (measurements removed).  The dict may also carry
+    ``large``, taken off before the call: False or absent -- ``wls_bad_data``, which refuses above ``estimator.max_nodes_per_graph()``
+    buses; True -- ``estimator.wls_bad_data_large``, the blocked form, up to ``estimator.max_nodes_per_graph_large()`` buses; "auto" -- chosen
+    by the batch's bound as the plain solve is (what ``--wls-bad-data`` passes).  The keyword ``robust`` = dict(gamma=..., [plain_iters]) (taken out of
     ``solver_kw``): the solve is ``estimator.wls_robust`` with these, the Huber M-estimator, for every bus count up to
     ``estimator.max_nodes_per_graph_large()``, and the metrics gain ``wls_downweighted`` (measurements with a weight factor below 1 at the
     solution); not together with ``bad_data``.  A batch that carries a ``graph_ptr`` (a dict key or an attribute: ``synthetic.make_batch``,
@@ -351,6 +353,12 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
     robust = solver_kw.pop("robust", None)
     if bad_data is not None and robust is not None:
         raise ValueError("evaluate_wls: bad_data and robust are two answers to gross errors: give one of them")
+    bad_large = False
+    if bad_data is not None:
+        bad_data = dict(bad_data)
+        bad_large = bad_data.pop("large", False)
+        if not (bad_large is True or bad_large is False or bad_large == "auto"):
+            raise ValueError(f"evaluate_wls: bad_data['large'] must be False, True or 'auto', got {bad_large!r}")
     dev = stats[0].device
     acc = torch.zeros(10, dtype=torch.float64, device=dev)
     tally = torch.zeros(5, dtype=torch.float64, device=dev)          # updates, graphs, graphs not converged, suspect graphs, removals (robust: down-weighted measurements)
@@ -379,7 +387,9 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
             res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw)
             suspect, removed = zero, zero
         else:
-            res = estimator.wls_bad_data(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **bad_data)
+            large = bound > estimator.max_nodes_per_graph() if bad_large == "auto" else bad_large
+            solve = estimator.wls_bad_data_large if large else estimator.wls_bad_data
+            res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **bad_data)
             suspect, removed = res.suspect.sum(), res.n_removed.sum()
         dss2_data._eval_state_batch(res.state, y, x, ei, ea, acc)
         tally += torch.stack([res.iterations.sum(), torch.tensor(res.iterations.numel(), device=dev), (res.status != 0).sum(),
@@ -423,7 +433,8 @@ def main(argv=None):
     ap.add_argument("--wls-baseline", action="store_true", help="after training, print the evaluation metrics of the classical WLS "
                     "estimator on the test split, from a flat start and from the trained model's output (evaluate_wls); a data list may mix bus counts")
     ap.add_argument("--wls-bad-data", type=float, default=None, metavar="THRESHOLD", help="the --wls-baseline lines (implied) through "
-                    "estimator.wls_bad_data: up to 5 measurements per graph are removed while the largest normalized residual exceeds THRESHOLD")
+                    "estimator.wls_bad_data (above 99 buses per graph: wls_bad_data_large): up to 5 measurements per graph are removed while the "
+                    "largest normalized residual exceeds THRESHOLD")
     ap.add_argument("--wls-robust", type=float, default=None, metavar="GAMMA", help="the --wls-baseline lines (implied) through "
                     "estimator.wls_robust, the Huber M-estimator with threshold GAMMA (3.0 is the usual choice); any bus count up to 256; "
                     "not together with --wls-bad-data")
@@ -500,7 +511,7 @@ def main(argv=None):
         if n_bus is None:                                            # a data list that mixes bus counts: its batches carry graph_ptr; the bound is the largest part's
             n_bus = max(p.n for p in ds.parts)
         for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
-            bad_data = dict(threshold=a.wls_bad_data, max_removals=5) if a.wls_bad_data is not None else None
+            bad_data = dict(threshold=a.wls_bad_data, max_removals=5, large="auto") if a.wls_bad_data is not None else None
             robust = dict(gamma=a.wls_robust) if a.wls_robust is not None else None
             m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data, robust=robust)
             print(f"wls baseline ({label})  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()), flush=True)

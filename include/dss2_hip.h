@@ -744,7 +744,7 @@ size_t dss2_wls_solve_lds_bytes(int nodes_per_graph);
  *      normalized residuals, removal of the largest one followed by a re-solve, and the state's standard deviation.  Per graph:
  *        1. Gauss-Newton exactly as dss2_wls_solve (`solve` is its argument block, outputs included), from init / the flat start, later
  *           from the current state;
- *        2. at the last iterate G is formed and factorised once more and inverted in place in LDS: Sigma = G^-1;
+ *        2. at the last iterate G is formed and factorised once more and inverted in place: Sigma = G^-1;
  *        3. for every ACTIVE measurement i (effective weight w_i = c_k R^-1 > 0, not removed), with h_i its Jacobian row without the
  *           slack angles' columns:  S_i = 1 - w_i h_i Sigma h_i^T (the residual sensitivity w_i Omega_ii) and
  *           rN_i = |z_i - h_i(u)| sqrt(w_i / S_i) where S_i >= s_min, 0 below it (critical measurements: the residual says nothing);
@@ -755,7 +755,17 @@ size_t dss2_wls_solve_lds_bytes(int nodes_per_graph);
  *      A failed factorisation in any solve or in 2. ends the graph with status 2: the state of the previous iterate (in 2.: the last
  *      one), the removals so far, per-measurement outputs and state_std 0.  Measurement ids (int32): 4 i + k for bus i (global row), k in V, theta, P, Q;
  *      4 N + 2 e + k for stored branch e, k in P_from, Q_from; rc 2 where 4 N + 2 E does not fit.  iterations counts the updates of
- *      all solves; status and last_step are the last solve's.  No atomics, one writer per value, fixed summation orders. */
+ *      all solves; status and last_step are the last solve's.  No atomics, one writer per value, fixed summation orders.
+ *      TWO FORMS behind the one entry, chosen by `workspace`:
+ *        workspace == NULL   the gain matrix, and then Sigma, on the packed triangle in LDS: dss2_wls_solve's kernel geometry and size
+ *                            limit with a fixed block on top (dss2_wls_bad_data_lds_bytes(n) <= 160 KiB: 99 buses; rc 2 above).
+ *        workspace != NULL   the blocked form for 1 to dss2_wls_large_max_nodes() buses (256): dss2_wls_solve_large's layout, geometry
+ *                            (256 threads, dss2_wls_large_groups(&solve) workgroups, max_groups honoured) and workspace --
+ *                            dss2_wls_large_workspace_bytes(nodes_per_graph, dss2_wls_large_groups(&solve)) bytes, 16-byte aligned,
+ *                            contents irrelevant before and after: G is inverted in place on its block rows, as in LDS, so the solve's
+ *                            slice is all it needs.  rc 2 with a message, before any launch, for a misaligned or short workspace, n
+ *                            above the cap, or what the other form refuses of the parameters.  Runs, batch positions and group
+ *                            counts agree to the bit; the two forms agree to rounding (another summation order), not to the bit. */
 typedef struct dss2_wls_bad_data_args {
   dss2_wls_solve_args solve;
   double threshold;                               /* > 0: the largest normalized residual is removed above it                     */
@@ -771,6 +781,7 @@ typedef struct dss2_wls_bad_data_args {
   double* bus_rn; double* bus_sens;               /* [N, 4]  rN and S of the final solve, 0 where inactive                        */
   double* edge_rn; double* edge_sens;             /* [E, 2]  (an edge that leaves its graph is not written)                       */
   double* state_std;                              /* [N, 2]  sqrt(Sigma_jj), 0 at slack angles                                    */
+  void* workspace; uint64_t workspace_bytes;      /* NULL, 0: the LDS form; otherwise the blocked form's workspace (above)       */
 } dss2_wls_bad_data_args;
 int dss2_wls_bad_data(const dss2_wls_bad_data_args* args_host, void* stream);
 /* bytes of LDS a graph of nodes_per_graph buses needs (pure host arithmetic): the solve's plus a fixed block */
