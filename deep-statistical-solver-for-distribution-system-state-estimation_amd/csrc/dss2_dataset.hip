@@ -10,8 +10,11 @@ namespace dss2 {
 // ---- measurement model -----------------------------------------------------------------------
 // numpy evaluates data.py:128-136 in float64 and rounds to float32 once; the same here, with
 // explicit round-to-nearest intrinsics so that no multiply-add is contracted into an fma.
+// A NaN standard deviation stays a NaN weight, as torch.maximum and `cov *= (cov < cap)` leave it (fmaxf would drop the NaN
+// operand, and the cap would then turn 1/floor^2 into a weight of 0).
 __device__ __forceinline__ float inv_var(double std, float floor_, float cap) {
   const float s = fabsf((float)std);
+  if (s != s) return s;
   const float m = fmaxf(s, floor_);
   const float c = __fdiv_rn(1.0f, __fmul_rn(m, m));
   return c < cap ? c : 0.f;
@@ -82,9 +85,13 @@ __global__ void __launch_bounds__(256) masked_stats_kernel(const float* __restri
     for (int c = 0; c < ZS_MAXC; ++c) {
       if (c < ncols) {
         const float v = t[r * ld + c];
-        if (v != 0.f) {
-          if (pass == 0) { s[c] += (double)v; cnt[c] += 1.0; }
-          else { const float d = __fsub_rn(v, mean[c]); s[c] += (double)__fmul_rn(d, d); }
+        if (pass == 0) {
+          if (v != 0.f) { s[c] += (double)v; cnt[c] += 1.0; }
+        } else {
+          // (t - mean)^2 * mask as the reference writes it: an unmeasured entry adds 0 unless its square overflowed (inf * 0 = nan,
+          // so that a column whose mean was clamped to FLT_MAX gets the reference's std of 0 wherever it holds a zero)
+          const float d = __fsub_rn(v, mean[c]);
+          s[c] += (double)__fmul_rn(__fmul_rn(d, d), v != 0.f ? 1.f : 0.f);
         }
       }
     }
@@ -103,6 +110,13 @@ __global__ void __launch_bounds__(256) masked_stats_kernel(const float* __restri
   }
 }
 
+__device__ __forceinline__ float nan_to_num_f(float v) {
+  if (v != v) return 0.f;
+  if (v == INFINITY) return 3.4028234663852886e38f;
+  if (v == -INFINITY) return -3.4028234663852886e38f;
+  return v;
+}
+
 // pass 0 -> mean[c], count kept in cnt[c]; pass 1 -> std[c]
 __global__ void masked_stats_finish_kernel(const double* __restrict__ partials, int nblocks, int ncols, int pass,
                                            float* __restrict__ mean, float* __restrict__ stdv, double* __restrict__ cnt) {
@@ -110,21 +124,15 @@ __global__ void masked_stats_finish_kernel(const double* __restrict__ partials, 
   if (c >= ncols) return;
   double s = 0.0, n = 0.0;
   for (int b = 0; b < nblocks; ++b) { s += partials[(size_t)b * 2 * ZS_MAXC + c]; n += partials[(size_t)b * 2 * ZS_MAXC + ZS_MAXC + c]; }
+  // The quotients are formed in double and rounded ONCE: (float)s / (float)n rounds the sum first, and for a column whose n measured
+  // entries are all the same v, fl(fl(n v) / n) != v for most n that are no power of two -- the mean one ulp off, that ulp the "std",
+  // every z-score +-1 of rounding noise.  (float)(s / n) gives v, hence std 0 and z-scores 0 (the reference's rule for std 0).
   if (pass == 0) {
     cnt[c] = n;
-    const float m = (float)s / (float)n;                      // 0/0 = nan -> nan_to_num -> 0
-    mean[c] = (m != m) ? 0.f : m;
+    mean[c] = nan_to_num_f((float)(s / n));                   // 0/0 = nan -> nan_to_num -> 0; +-inf -> +-FLT_MAX
   } else {
-    const float v = sqrtf((float)s / (float)cnt[c]);
-    stdv[c] = (v != v) ? 0.f : v;
+    stdv[c] = nan_to_num_f(sqrtf((float)(s / cnt[c])));
   }
-}
-
-__device__ __forceinline__ float nan_to_num_f(float v) {
-  if (v != v) return 0.f;
-  if (v == INFINITY) return 3.4028234663852886e38f;
-  if (v == -INFINITY) return -3.4028234663852886e38f;
-  return v;
 }
 
 __global__ void __launch_bounds__(256) masked_normalize_kernel(const float* __restrict__ t, long long rows, int ld, int num_feat,
@@ -208,7 +216,7 @@ __global__ void __launch_bounds__(256) collate_ragged_kernel(const RaggedArgs a)
 __global__ void cursor_advance_kernel(long long* cursor, long long B) {
   long long p = cursor[0] + B;
   const long long n = cursor[1];
-  if (n > 0 && p >= n) p -= n;
+  if (n > 0) p %= n;      // (a batch longer than the epoch passes the end more than once)
   cursor[0] = p;
 }
 
@@ -272,8 +280,10 @@ extern "C" int dss2_masked_zscore(const float* t, int64_t rows, int32_t ld, int3
                                   float* mean, float* stdv, double* scratch, void* stream) {
   DSS2_NOT_IN_PLAN("dss2_masked_zscore");
   if (rows <= 0) return 0;
-  if (num_feat <= 0 || num_feat > ZS_MAXC || num_feat > ld) { set_error("masked_zscore: num_feat %d out of range 1..%d", num_feat, ZS_MAXC); return 2; }
+  if (num_feat <= 0 || num_feat > ZS_MAXC || num_feat > ld) { set_error("masked_zscore: num_feat %d out of range 1..%d (and no more than ld %d)", num_feat, ZS_MAXC, ld); return 2; }
   if (!t || !out || !mean || !stdv || !scratch) { set_error("masked_zscore: null argument"); return 2; }
+  // every row of out takes ld values: a shorter output row would run into the next one, and past the end of out after the last
+  if (ld_out < ld || (out == t && ld_out != ld)) { set_error("masked_zscore: ld_out %d does not hold a row of ld %d%s", ld_out, ld, out == t ? " in place" : ""); return 2; }
   hipStream_t s = as_stream(stream);
   int nb = (int)((rows + 255) / 256);
   if (nb > 256) nb = 256;

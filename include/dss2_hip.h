@@ -853,7 +853,8 @@ int dss2_small_gemm(const dss2_sgemm_desc* descs, int n_desc, int max_tiles, flo
  * bool_slack, bool_zero_inj); meas_v_mask [n_per_sample] bytes (1 = voltage magnitude measured at that bus);
  * z [rows][4] float64 standard-normal draws (the reference's np.random.normal(0, |std|) = z * |std|).
  * x [rows][11] float32 <- (V, 1/var, theta, 1/var, P, 1/var, Q, 1/var, vn_kv, bool_slack, bool_zero_inj),
- * NOT yet normalised.  float64 arithmetic rounded once, like numpy.                                      */
+ * NOT yet normalised.  float64 arithmetic rounded once, like numpy.  A NaN in a raw value gives a NaN
+ * measurement AND a NaN weight (the reference's torch.maximum and cap keep it), never a weight of 0.       */
 int dss2_measure_nodes(const double* nodes, const uint8_t* meas_v_mask, int32_t n_per_sample, const double* z,
                        double v_noise, double pm_noise, double p_noise, double zero_inj_coef, float* x, int64_t rows,
                        void* stream);
@@ -866,7 +867,10 @@ int dss2_measure_edges(const double* edges, const uint8_t* meas_pflow_mask, int3
 
 /* masked z-score (data.py:179-190): for the first num_feat (<= 16) columns, mean / std over the NON-ZERO entries,
  * out = nan_to_num((t - mean) * (t != 0) / std); the other columns are copied.  mean/stdv [num_feat] are written
- * (nan -> 0 like the reference).  In place allowed (out == t, ld_out == ld).  scratch: device doubles,
+ * (nan -> 0, +-inf -> +-FLT_MAX like the reference); both are the exact double sum divided in double and rounded
+ * to float once, so a column of one repeated value has that value as its mean and std 0.  In place allowed
+ * (out == t, ld_out == ld); out of place every output row takes ld values, so ld_out >= ld (cells [ld, ld_out) of a
+ * row are not written); any other ld_out returns 2.  scratch: device doubles,
  * dss2_masked_zscore_scratch_doubles(rows) of them.  Deterministic (fixed-order double partial sums).     */
 int dss2_masked_zscore(const float* t, int64_t rows, int32_t ld, int32_t num_feat, float* out, int32_t ld_out,
                        float* mean, float* stdv, double* scratch, void* stream);
@@ -887,7 +891,8 @@ int dss2_collate(const dss2_collate_desc* descs_host, int32_t n_desc, const int6
 /* The same collation with the batch's position on the DEVICE (host-free epochs: dss2_run.py:131-147's loop as N replays of one
  * recorded step).  cursor: DEVICE int64[2] = {position, epoch length}; slot b reads sample_ids[(cursor[0] + b) mod cursor[1]]
  * (cursor[1] <= 0: no wrap).  advance != 0: a one-thread launch behind the collation moves cursor[0] forward by `batch` (wrapping
- * at cursor[1]), so the identical pair of launches, replayed, walks the epoch -- which is why this entry point is recorded into
+ * at cursor[1]: cursor[0] <- (cursor[0] + batch) mod cursor[1], also when batch exceeds the epoch length), so the identical
+ * pair of launches, replayed, walks the epoch -- which is why this entry point is recorded into
  * launch plans and captured into hipGraphs like every other launch of a step.  The caller re-draws sample_ids (a device
  * permutation) and zeroes cursor[0] between epochs; nothing is read back. */
 int dss2_collate_cursor(const dss2_collate_desc* descs_host, int32_t n_desc, const int64_t* sample_ids, int64_t* cursor,
