@@ -219,7 +219,7 @@ class WlsSolveArgs(C.Structure):
                 ("tol", C.c_double), ("w_v", C.c_double), ("w_p", C.c_double), ("w_pf", C.c_double),
                 ("init", C.c_void_p), ("ld_init", C.c_int64), ("state", C.c_void_p), ("objective", C.c_void_p),
                 ("iterations", C.c_void_p), ("status", C.c_void_p), ("last_step", C.c_void_p), ("vminmax", C.c_void_p),
-                ("max_groups", C.c_int32), ("pad_", C.c_int32), ("graph_ptr", C.c_void_p), ("n_graphs", C.c_int64)]
+                ("max_groups", C.c_int32), ("half_bandwidth", C.c_int32), ("graph_ptr", C.c_void_p), ("n_graphs", C.c_int64)]
 
 
 class WlsBadDataArgs(C.Structure):
@@ -234,6 +234,9 @@ class WlsBadDataArgs(C.Structure):
 class WlsLargeArgs(C.Structure):
     """dss2_wls_large_args (include/dss2_hip.h)."""
     _fields_ = [("solve", WlsSolveArgs), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+WLS_BAND_BLOCK, WLS_BAND_GROUPS, WLS_BAND_LDS_BYTES = 16, 512, 160 * 1024      # the banded form of dss2_wls_solve_large
 
 
 class WlsRobustArgs(C.Structure):

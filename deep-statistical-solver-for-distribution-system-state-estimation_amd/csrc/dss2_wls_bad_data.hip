@@ -166,11 +166,11 @@ __global__ void __launch_bounds__(WL_T, 2) wls_bad_data_blocked_kernel(const dss
     for (int round = 0; round <= b.max_removals; ++round) {
       if (removing) {
         const WsRemoved mask = {r.rem, nrem};
-        wl_gauss_newton(a, g, A, l, ns, tid, t, WsNoWeight(), mask);
+        wl_gauss_newton(a, g, A, WlRows(), l, ns, tid, t, WsNoWeight(), mask);
         bool failed = l.ctl[0] != 0 && l.ctl[1] == 0;      // (uniform: the words of the last iteration run, behind its barrier)
         if (!failed) {
-          wl_form(a, g, A, ns, tid, WsNoWeight(), mask);   // (its first barrier: ctl has been read)
-          const bool ok = wl_factor(A, l, ns, tid);
+          wl_form(a, g, A, WlRows(), ns, tid, WsNoWeight(), mask);   // (its first barrier: ctl has been read)
+          const bool ok = wl_factor(A, WlRows(), l, ns, tid);
           if (tid == 0) l.ctl[3] = ok ? 1 : 0;             // (wave 0's answer, made the workgroup's)
           __syncthreads();
           if (l.ctl[3] == 0) {

@@ -3,7 +3,8 @@
 // Cholesky and back substitution, the Gauss-Newton loop (wl_gauss_newton), the ONE kernel body on this layout (wls_blocked_kernel: the
 // two estimators are two instantiations of it), and the host side -- the entries' size check, grid and workspace check, and their
 // launch path (wl_launch).  The layout and every step are described in the header of dss2_wls_large.hip; nothing here depends on which
-// kernel runs it.
+// kernel runs it.  The steps find a slice's rows through a rows object (WlRows below: this layout), so that dss2_wls_banded.hpp runs
+// them on a band of the gain matrix.
 #pragma once
 #include "dss2_wls_core.hpp"
 
@@ -24,24 +25,51 @@ __host__ __device__ constexpr size_t wl_graph_doubles(int n) {       // block ro
   return (size_t)(WL_NB * WL_NB) * ((size_t)((2 * n + WL_NB) / WL_NB) * ((2 * n + WL_NB) / WL_NB + 1) / 2);
 }
 __host__ __device__ constexpr int wl_pstride(int n) { return (2 * n + 1 + WL_TILE - 1) / WL_TILE * WL_TILE; }
-__host__ __device__ constexpr size_t wl_lds_doubles(int n) { return (size_t)WL_NB * wl_pstride(n) + WL_NB * WL_NB + WL_NB + 4 * (size_t)n; }
-__host__ __device__ constexpr size_t wl_lds_bytes(int n) { return wl_lds_doubles(n) * 8 + 16 + ((size_t)n + 15) / 16 * 16; }
+// (S: the panel's stride.  The dense rows' is wl_pstride(n); a band's is shorter, dss2_wls_banded.hpp)
+__host__ __device__ constexpr size_t wl_lds_doubles(int n, int S) { return (size_t)WL_NB * S + WL_NB * WL_NB + WL_NB + 4 * (size_t)n; }
+__host__ __device__ constexpr size_t wl_lds_bytes(int n, int S) { return wl_lds_doubles(n, S) * 8 + 16 + ((size_t)n + 15) / 16 * 16; }
+__host__ __device__ constexpr size_t wl_lds_doubles(int n) { return wl_lds_doubles(n, wl_pstride(n)); }
+__host__ __device__ constexpr size_t wl_lds_bytes(int n) { return wl_lds_bytes(n, wl_pstride(n)); }
 static_assert(2 * wl_lds_bytes(WL_MAX_NODES) <= (size_t)kMaxLdsBytes, "two workgroups of the largest graph per CU");
 static_assert(WL_NB == 16 && WL_TILE == 8 && WL_NB % WL_TILE == 0, "the unrolled loops and the readlane indices assume 16 and 8");
 
 struct WlLds { double* Pt; double* Ld; double* invd; double* u; double* du; int* ctl; unsigned char* slk; int S; };
-__device__ __forceinline__ WlLds wl_carve(unsigned char* smem, int n) {
+__device__ __forceinline__ WlLds wl_carve(unsigned char* smem, int n, int S) {
   WlLds l;
-  l.S = wl_pstride(n);
+  l.S = S;
   l.Pt = reinterpret_cast<double*>(smem);
   l.Ld = l.Pt + (size_t)WL_NB * l.S;
   l.invd = l.Ld + WL_NB * WL_NB;
   l.u = l.invd + WL_NB;
   l.du = l.u + 2 * n;
-  l.ctl = reinterpret_cast<int*>(smem + wl_lds_doubles(n) * 8);
-  l.slk = smem + wl_lds_doubles(n) * 8 + 16;
+  l.ctl = reinterpret_cast<int*>(smem + wl_lds_doubles(n, S) * 8);
+  l.slk = smem + wl_lds_doubles(n, S) * 8 + 16;
   return l;
 }
+__device__ __forceinline__ WlLds wl_carve(unsigned char* smem, int n) { return wl_carve(smem, n, wl_pstride(n)); }
+
+// Where the steps below find the ROWS of a slice A.  WlRows is the lower triangle of blocks above; WbRows (dss2_wls_banded.hpp) keeps a
+// band of block columns per block row.  Both give
+//   doubles(n)     the slice's length for n buses (wl_form zeroes it)
+//   at(A, r)       row r < ns as a pointer to its column 0: at(A, r)[c] is G[r, c] for every column c the row stores
+//   rhs(A, ns)     the right-hand side b, ns entries
+//   left(j0)       the first column that the rows of the block row at j0 store
+//   below(j0, w, ns)  the PANEL of the block column j0 .. j0 + w: the rows `first` .. `end` - 1 that have entries in these columns, and
+//                  the b row, which counts as row `end`; at(A, i) as above, pt(i) the row's place in a row of Pt
+// The slice travels beside the object as a `double* __restrict__`, and n and ns come in as arguments, so that WlRows has no state: the
+// dense kernels then compile to what they were (the blocked bad-data kernel sits at 256 registers and spilled with n kept in the object).
+struct WlPanelRows {
+  int first, end;
+  __device__ __forceinline__ double* at(double* A, int i) const { return A + wl_row_off(i); }      // (the b row is row ns of the slice)
+  __device__ __forceinline__ int pt(int i) const { return i; }
+};
+struct WlRows {
+  __device__ __forceinline__ size_t doubles(int n) const { return wl_graph_doubles(n); }
+  __device__ __forceinline__ double* at(double* A, int r) const { return A + wl_row_off(r); }
+  __device__ __forceinline__ double* rhs(double* A, int ns) const { return A + wl_row_off(ns); }
+  __device__ __forceinline__ int left(int) const { return 0; }
+  __device__ __forceinline__ WlPanelRows below(int j0, int w, int ns) const { return WlPanelRows{j0 + w, ns}; }
+};
 
 // lane `lane`'s x in every lane (`lane` is a constant after unrolling: two v_readlane_b32)
 __device__ __forceinline__ double wl_lane(double x, int lane) {
@@ -50,21 +78,22 @@ __device__ __forceinline__ double wl_lane(double x, int lane) {
 
 // A <- 0, then every row by its owner.  Starts with a barrier (u, slk and whatever read A before are done with).  `mask` is the
 // removal mask of dss2_wls_core.hpp (WsNoMask, the default, compiles to nothing: the plain and the Huber kernel).
-template <class Wt = WsNoWeight, class Mask = WsNoMask>
-__device__ __forceinline__ void wl_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, int ns, int tid, const Wt& wt = Wt(),
+template <class Rows, class Wt = WsNoWeight, class Mask = WsNoMask>
+__device__ __forceinline__ void wl_form(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, const Rows rows, int ns, int tid, const Wt& wt = Wt(),
                                         const Mask& mask = Mask()) {
-  const size_t pairs = wl_graph_doubles(g.n) / 2;
+  const size_t pairs = rows.doubles(g.n) / 2;
   __syncthreads();
   for (size_t p = tid; p < pairs; p += WL_T) reinterpret_cast<wl_d2*>(A)[p] = wl_d2{0.0, 0.0};
   __syncthreads();
-  for (int r = tid; r < ns; r += WL_T) ws_accumulate_row_at(a, g, r, A + wl_row_off(r), A + wl_row_off(ns), mask, wt);
+  for (int r = tid; r < ns; r += WL_T) ws_accumulate_row_at(a, g, r, rows.at(A, r), rows.rhs(A, ns), mask, wt);
 }
 
 // Wave 0: the diagonal block at (j0, j0), w columns wide, factorised in registers; lane i < w holds row i.  Returns whether every pivot
 // was > 0 and finite (uniform over the wave).
-__device__ __forceinline__ bool wl_factor_diag(double* __restrict__ A, const WlLds& l, int j0, int w, int lane) {
+template <class Rows>
+__device__ __forceinline__ bool wl_factor_diag(double* __restrict__ A, const Rows rows, const WlLds& l, int j0, int w, int lane) {
   const bool mine = lane < w;
-  double* grow = A + wl_row_off(j0 + (mine ? lane : 0)) + j0;
+  double* grow = rows.at(A, j0 + (mine ? lane : 0)) + j0;
   double row[WL_NB];
 #pragma unroll
   for (int k = 0; k < WL_NB; ++k) row[k] = (mine && k <= lane) ? grow[k] : 0.0;
@@ -96,11 +125,12 @@ __device__ __forceinline__ bool wl_factor_diag(double* __restrict__ A, const WlL
   return ok;
 }
 
-// The panel below the diagonal block: thread i solves row i (j1 .. ns, the b row included) against Ld.  Beyond the block's width
+// The panel below the diagonal block: thread i solves row i (p.first .. p.end, the b row included) against Ld.  Beyond the block's width
 // (the last block column only) A holds zeros and Ld is 0: those entries stay 0.
-__device__ __forceinline__ void wl_panel(double* __restrict__ A, const WlLds& l, int j0, int w, int ns, int tid) {
-  for (int i = j0 + w + tid; i <= ns; i += WL_T) {
-    wl_d2* prow = reinterpret_cast<wl_d2*>(A + wl_row_off(i) + j0);
+template <class Panel>
+__device__ __forceinline__ void wl_panel(double* __restrict__ A, const Panel p, const WlLds& l, int j0, int tid) {
+  for (int i = p.first + tid; i <= p.end; i += WL_T) {
+    wl_d2* prow = reinterpret_cast<wl_d2*>(p.at(A, i) + j0);
     double x[WL_NB];
 #pragma unroll
     for (int k = 0; k < WL_NB / 2; ++k) { const wl_d2 v = prow[k]; x[2 * k] = v.x; x[2 * k + 1] = v.y; }
@@ -113,12 +143,15 @@ __device__ __forceinline__ void wl_panel(double* __restrict__ A, const WlLds& l,
 #pragma unroll
     for (int k = 0; k < WL_NB / 2; ++k) prow[k] = wl_d2{x[2 * k], x[2 * k + 1]};
 #pragma unroll
-    for (int k = 0; k < WL_NB; ++k) l.Pt[(size_t)k * l.S + i] = x[k];
+    for (int k = 0; k < WL_NB; ++k) l.Pt[(size_t)k * l.S + p.pt(i)] = x[k];
   }
 }
 
 // A[i, c] -= sum_j Pt[j][i] Pt[j][c] for j1 <= c <= i <= ns, c < ns, on 8 x 8 tiles: tile p = ti (ti + 1) / 2 + tj, tj <= ti
-__device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds& l, int j1, int ns, int tid) {
+// (j1 = rw.first, ns = rw.end: the panel's rows, the b row last)
+template <class Panel>
+__device__ __forceinline__ void wl_trailing(double* __restrict__ A, const Panel rw, const WlLds& l, int tid) {
+  const int j1 = rw.first, ns = rw.end;
   const int ntr = (ns + 1 - j1 + WL_TILE - 1) / WL_TILE, ntiles = ntr * (ntr + 1) / 2;
   for (int p = tid; p < ntiles; p += WL_T) {
     int ti = (int)((sqrtf(8.f * (float)p + 1.f) - 1.f) * 0.5f);
@@ -133,8 +166,8 @@ __device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds&
       for (int c = 0; c < WL_TILE; ++c) acc[q][c] = 0.0;
 #pragma unroll 4
     for (int j = 0; j < WL_NB; ++j) {
-      const wl_d2* pr2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + i0);
-      const wl_d2* pc2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + c0);
+      const wl_d2* pr2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + rw.pt(i0));
+      const wl_d2* pc2 = reinterpret_cast<const wl_d2*>(l.Pt + (size_t)j * l.S + rw.pt(c0));
       double pr[WL_TILE], pc[WL_TILE];
 #pragma unroll
       for (int q = 0; q < WL_TILE / 2; ++q) {
@@ -149,7 +182,7 @@ __device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds&
     if (tj < ti && i0 + WL_TILE - 1 <= ns) {            // a whole tile below the diagonal
 #pragma unroll
       for (int q = 0; q < WL_TILE; ++q) {
-        wl_d2* arow = reinterpret_cast<wl_d2*>(A + wl_row_off(i0 + q) + c0);
+        wl_d2* arow = reinterpret_cast<wl_d2*>(rw.at(A, i0 + q) + c0);
 #pragma unroll
         for (int c = 0; c < WL_TILE / 2; ++c) {
           wl_d2 v = arow[c];
@@ -162,7 +195,7 @@ __device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds&
       for (int q = 0; q < WL_TILE; ++q) {
         const int i = i0 + q;
         if (i > ns) continue;
-        double* arow = A + wl_row_off(i);
+        double* arow = rw.at(A, i);
 #pragma unroll
         for (int c = 0; c < WL_TILE; ++c)
           if (c0 + c <= i && c0 + c < ns) arow[c0 + c] -= acc[q][c];
@@ -172,24 +205,27 @@ __device__ __forceinline__ void wl_trailing(double* __restrict__ A, const WlLds&
 }
 
 // Cholesky of A WITH the b row (row ns), which leaves as y = L^-1 b.  Wave 0's return value says whether every pivot was good.
-__device__ __forceinline__ bool wl_factor(double* __restrict__ A, const WlLds& l, int ns, int tid) {
+template <class Rows>
+__device__ __forceinline__ bool wl_factor(double* __restrict__ A, const Rows rows, const WlLds& l, int ns, int tid) {
   bool ok = true;
   for (int j0 = 0; j0 < ns; j0 += WL_NB) {
     const int w = ns - j0 < WL_NB ? ns - j0 : WL_NB;
     __syncthreads();                                   // the rows' owners, or the previous trailing update, have written the block
-    if (tid < 64) ok = wl_factor_diag(A, l, j0, w, tid) && ok;
+    if (tid < 64) ok = wl_factor_diag(A, rows, l, j0, w, tid) && ok;
     __syncthreads();
-    wl_panel(A, l, j0, w, ns, tid);
+    const auto below = rows.below(j0, w, ns);
+    wl_panel(A, below, l, j0, tid);
     __syncthreads();
-    if (j0 + w < ns) wl_trailing(A, l, j0 + w, ns, tid);
+    if (j0 + w < ns) wl_trailing(A, below, l, tid);
   }
   return ok;
 }
 
 // L^T du = y, block column by block column from the last; starts and ends with a barrier
-__device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A, const WlLds& l, int ns, int tid) {
+template <class Rows>
+__device__ __forceinline__ void wl_back_substitute(double* __restrict__ A, const Rows rows, const WlLds& l, int ns, int tid) {
   __syncthreads();
-  const double* y = A + wl_row_off(ns);
+  const double* y = rows.rhs(A, ns);
   for (int c = tid; c < ns; c += WL_T) l.du[c] = y[c];
   __syncthreads();
   for (int j0 = (ns - 1) / WL_NB * WL_NB; j0 >= 0; j0 -= WL_NB) {
@@ -199,7 +235,7 @@ __device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A,
       double Lc[WL_NB], dg = 1.0;
 #pragma unroll
       for (int j = 0; j < WL_NB; ++j) {
-        Lc[j] = (mine && j >= tid && j < w) ? A[wl_row_off(j0 + j) + j0 + tid] : 0.0;
+        Lc[j] = (mine && j >= tid && j < w) ? rows.at(A, j0 + j)[j0 + tid] : 0.0;
         if (mine && j == tid) dg = Lc[j];
       }
       const double inv = 1.0 / dg;
@@ -215,9 +251,9 @@ __device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A,
       if (mine) l.du[j0 + tid] = yv;
     }
     __syncthreads();
-    for (int c = tid; c < j0; c += WL_T) {             // the columns left of the block: rows of A, coalesced over c
+    for (int c = rows.left(j0) + tid; c < j0; c += WL_T) {   // the columns left of the block: rows of A, coalesced over c
       double s = l.du[c];
-      for (int j = 0; j < w; ++j) s -= A[wl_row_off(j0 + j) + c] * l.du[j0 + j];
+      for (int j = 0; j < w; ++j) s -= rows.at(A, j0 + j)[c] * l.du[j0 + j];
       l.du[c] = s;
     }
     __syncthreads();
@@ -228,16 +264,16 @@ __device__ __forceinline__ void wl_back_substitute(const double* __restrict__ A,
 // fixed; a graph that has stopped skips the body, uniformly over its workgroup).  Adds the updates applied to t.iters, sets t.status
 // (1, then 0 or 2) and t.last.  wt.at(it) is the weighting of iteration `it`, `mask` the removal mask.  Ends with a barrier, after which
 // l.ctl = {stop, apply} of the last iteration run: stop without apply is a failed factorisation.
-template <class Wt, class Mask = WsNoMask>
-__device__ __forceinline__ void wl_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, const WlLds& l, int ns,
+template <class Rows, class Wt, class Mask = WsNoMask>
+__device__ __forceinline__ void wl_gauss_newton(const dss2_wls_solve_args& a, const WsGraph& g, double* __restrict__ A, const Rows rows, const WlLds& l, int ns,
                                                 int tid, WsTally& t, const Wt& wt, const Mask& mask = Mask()) {
   t.status = 1;
   bool active = true;                                  // uniform over the workgroup
   for (int it = 0; it < a.max_iter; ++it) {
     if (active) {
-      wl_form(a, g, A, ns, tid, wt.at(it), mask);
-      const bool ok = wl_factor(A, l, ns, tid);
-      wl_back_substitute(A, l, ns, tid);
+      wl_form(a, g, A, rows, ns, tid, wt.at(it), mask);
+      const bool ok = wl_factor(A, rows, l, ns, tid);
+      wl_back_substitute(A, rows, l, ns, tid);
       ws_decide(a, l.du, l.ctl, ns, tid, ok, t);
       __syncthreads();
       if (l.ctl[1]) for (int r = tid; r < ns; r += WL_T) l.u[r] += l.du[r];
@@ -278,7 +314,7 @@ __global__ void __launch_bounds__(WL_T) wls_blocked_kernel(const Args b) {
     const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
     ws_load_start<WL_T>(a, g, start, tid);
     WsTally t = {0, 1, 0.0};
-    wl_gauss_newton(a, g, A, l, ns, tid, t, wt);
+    wl_gauss_newton(a, g, A, WlRows(), l, ns, tid, t, wt);
     if constexpr (Wt::robust) wt.n_down = b.n_downweighted + gr;
     ws_finish<WL_T>(a, g, gr, l.du, ns, tid, t, wt);   // (the objective's per-bus parts go through du)
   }

@@ -16,6 +16,14 @@ It keeps the gain matrix in LDS and serves up to ``max_nodes_per_graph()`` = 99 
 The same estimator for up to ``max_nodes_per_graph_large()`` = 256 buses per graph (ober179): the gain matrix in a workspace in global
 memory, a blocked Cholesky, csrc/dss2_wls_large.hip.
 
+    band_order(edge_index, nodes_per_graph, half_bandwidth=None, num_nodes=None, identity=False) -> BandOrder
+    wls_estimate_banded(... same arguments ..., order=None) -> WLSResult
+
+The same estimator beyond 256 buses per graph (feeders of 300, 1000 buses): the buses are numbered for a small bandwidth of the gain
+matrix on the host, once per structure (``band_order``: Cuthill-McKee), and the blocked kernel runs on the band alone,
+csrc/dss2_wls_banded.hpp.  ``num_nodes`` counts buses behind the last branch (one-bus graphs at the end of a batch); ``identity`` keeps the
+caller's numbering and only measures its half-bandwidth.  Equal-size graphs; no ``graph_ptr``, no Huber form, no bad-data detection.
+
     wls_bad_data(... same inputs ..., threshold=3.0, max_removals=0, confidence=0.95, s_min=1e-3) -> WLSBadDataResult
 
 The rest of the classical estimator on the same solve and in the same single launch (csrc/dss2_wls_bad_data.hip): the chi-square test
@@ -32,7 +40,7 @@ The same test for up to ``max_nodes_per_graph_large()`` = 256 buses per graph (o
 The second classical answer to gross errors, for every bus count up to 256: the Huber M-estimator by iteratively re-weighted
 Gauss-Newton on the kernels of ``wls_estimate`` and ``wls_estimate_large`` (csrc/dss2_wls_robust.hip).  No covariance, one launch.
 
-Batches that mix bus counts: all five take the keyword ``graph_ptr`` (``_public`` at the end of the module adds it: the parameter lists
+Batches that mix bus counts: the five dense functions take the keyword ``graph_ptr`` (``_public`` at the end of the module adds it: the parameter lists
 above are pinned by callers and tests, and ``inspect.signature`` goes on reporting them), a contiguous int64 device tensor [G + 1] of row offsets (what
 ``synthetic.make_batch`` returns for a list of grids and ``dataset.MixedDataset`` puts on its batches).  Graph g then owns rows
 [graph_ptr[g], graph_ptr[g + 1]) and ``nodes_per_graph`` is an UPPER BOUND on a graph's bus count, known on the host: the kernel choice,
@@ -358,6 +366,219 @@ def _wls_bad_data_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     ``graph_ptr`` as for ``wls_estimate``: with it ``nodes_per_graph`` is an upper bound, and the workspace is sized by the bound."""
     return _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, threshold,
                          max_removals, confidence, s_min, max_groups, graph_ptr=graph_ptr, large=True)
+
+
+# ---- beyond 256 buses: the banded form of the blocked kernel on a reordered grid (csrc/dss2_wls_banded.hpp) -------------------------
+
+class BandOrder(NamedTuple):
+    """What ``band_order`` found for one batch structure; ``wls_estimate_banded(order=...)`` solves the relabelled batch with it."""
+    perm: torch.Tensor           # [N] int32: row k of the relabelled batch is row perm[k] of the caller's (x, init are gathered by it)
+    inverse: torch.Tensor        # [N] int32: the caller's row i is row inverse[i] of the relabelled batch (the state is gathered by it)
+    edge_index: torch.Tensor     # [2, E]: the caller's edge list with both endpoints relabelled; stored order and orientation kept
+    topology: object             # the relabelled edge list's Topology (its incidence CSR is the kernel's); None for a CPU edge list
+    half_bandwidth: int          # hb in states: >= r - c over every non-zero G[r, c] of every graph, relabelled
+    nodes_per_graph: int
+    n_orderings: int             # distinct topologies ordered (graphs with equal relative edge lists share one)
+
+
+def _cuthill_mckee(n, adj):
+    """Reverse Cuthill-McKee of a graph of n buses (adj: sorted neighbour lists): order[k] = the bus numbered k.  Every component is
+    numbered breadth-first from a pseudo-peripheral bus, neighbours by ascending degree; every tie goes to the lower bus index."""
+    deg = [len(a) for a in adj]
+
+    def levels(root):
+        seen, level, out = {root}, [root], []
+        while level:
+            out.append(level)
+            nxt = []
+            for u in level:
+                for v in adj[u]:
+                    if v not in seen:
+                        seen.add(v)
+                        nxt.append(v)
+            level = nxt
+        return out
+
+    done, order = [False] * n, []
+    for seed in sorted(range(n), key=lambda v: (deg[v], v)):
+        if done[seed]:
+            continue
+        root, lv = seed, levels(seed)
+        while True:              # pseudo-peripheral: move to the lowest-degree bus of the last level while that deepens the levels
+            far = min(lv[-1], key=lambda v: (deg[v], v))
+            lv2 = levels(far)
+            if len(lv2) <= len(lv):
+                break
+            root, lv = far, lv2
+        done[root] = True
+        queue, head = [root], 0
+        while head < len(queue):
+            for v in sorted(adj[queue[head]], key=lambda v: (deg[v], v)):
+                if not done[v]:
+                    done[v] = True
+                    queue.append(v)
+            head += 1
+        order.extend(queue)
+    return order[::-1]
+
+
+def _two_hop_bandwidth(adj, label):
+    """max |label[i] - label[j]| over the buses i, j within two branches of each other (the pattern of G), in buses."""
+    bw = 0
+    for i, a in enumerate(adj):
+        reach = set(a)
+        for j in a:
+            reach.update(adj[j])
+        if reach:
+            bw = max(bw, max(abs(label[i] - label[j]) for j in reach))
+    return bw
+
+
+def band_half_bandwidth(bandwidth_buses: int) -> int:
+    """hb in states for a 2-hop bandwidth in buses: bus i has the states 2 i and 2 i + 1."""
+    return 2 * int(bandwidth_buses) + 1
+
+
+def band_blocks(half_bandwidth: int) -> int:
+    """Wb: the block columns a block row keeps left of its diagonal block."""
+    return -(-int(half_bandwidth) // _lib.WLS_BAND_BLOCK)
+
+
+def band_lds_bytes(nodes_per_graph: int, half_bandwidth: int) -> int:
+    """The LDS of a workgroup of the banded kernel: wb_lds_bytes of csrc/dss2_wls_banded.hpp (the C side checks the same formula)."""
+    nb, n = _lib.WLS_BAND_BLOCK, int(nodes_per_graph)
+    return (nb * (nb * band_blocks(half_bandwidth) + 8) + nb * nb + nb + 4 * n) * 8 + 16 + (n + 15) // 16 * 16
+
+
+def band_groups(n_graphs: int, max_groups: int = 0) -> int:
+    g = min(int(n_graphs), _lib.WLS_BAND_GROUPS)
+    return min(g, int(max_groups)) if max_groups > 0 else g
+
+
+def band_workspace_bytes(nodes_per_graph: int, half_bandwidth: int, groups: int) -> int:
+    """One slice per workgroup: ceil(2 n / 16) block rows of 16 rows of 16 (Wb + 1) doubles, and the right-hand side behind them."""
+    nb = _lib.WLS_BAND_BLOCK
+    block_rows = -(-2 * int(nodes_per_graph) // nb)
+    return int(groups) * block_rows * (nb * nb * (band_blocks(half_bandwidth) + 1) + nb) * 8
+
+
+def band_max_half_bandwidth(nodes_per_graph: int) -> int:
+    """The largest hb the banded kernel serves at this bus count (0: the bus count itself is beyond the LDS)."""
+    if band_lds_bytes(nodes_per_graph, 0) > _lib.WLS_BAND_LDS_BYTES:
+        return 0
+    spare = (_lib.WLS_BAND_LDS_BYTES - band_lds_bytes(nodes_per_graph, 0)) // (8 * _lib.WLS_BAND_BLOCK * _lib.WLS_BAND_BLOCK)
+    return max(spare, 0) * _lib.WLS_BAND_BLOCK
+
+
+def band_order(edge_index: torch.Tensor, nodes_per_graph: int, half_bandwidth: Optional[int] = None,
+               num_nodes: Optional[int] = None, identity: bool = False) -> BandOrder:
+    """Numbers the buses of every graph for a small bandwidth of the gain matrix (reverse Cuthill-McKee on the branch graph; G couples the
+    buses within two branches) and returns the ``BandOrder`` that ``wls_estimate_banded`` solves with.  Host work, once per structure:
+    ``edge_index`` is read back ONCE here, and nothing is read back per solve.  Graph g owns the buses [g n, (g + 1) n); graphs with equal
+    relative edge lists share one ordering.  ``half_bandwidth`` may raise hb above what the numbering needs (ValueError below it);
+    ``num_nodes`` counts buses behind the last branch (default: the last bus an edge names, rounded up to whole graphs);
+    ``identity`` keeps the caller's numbering and only measures its hb."""
+    n = int(nodes_per_graph)
+    if n < 1 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError("band_order: edge_index must be [2, E] and nodes_per_graph at least 1")
+    ei = edge_index.detach().cpu().numpy()         # the one read-back
+    E = ei.shape[1]
+    N = int(num_nodes) if num_nodes is not None else (-(-(int(ei.max()) + 1) // n) * n if E else n)
+    if N < 1 or N % n != 0 or (E and (int(ei.min()) < 0 or int(ei.max()) >= N)):
+        raise ValueError(f"band_order: {N} buses are not whole graphs of {n}, or an edge names a bus outside them")
+    G = N // n
+    gid = ei[0] // n
+    if E and (ei[1] // n != gid).any():
+        raise ValueError("band_order: an edge crosses graphs")
+    by_graph = gid.argsort(kind="stable")
+    starts = [0] * (G + 1)
+    for g in gid.tolist():
+        starts[g + 1] += 1
+    for g in range(G):
+        starts[g + 1] += starts[g]
+    new_of_old = [0] * N
+    orderings, bw = {}, 0
+    for g in range(G):
+        rel = ei[:, by_graph[starts[g]:starts[g + 1]]] - g * n
+        key = rel.tobytes()
+        if key not in orderings:
+            adj = [set() for _ in range(n)]
+            for f, t in rel.T.tolist():
+                if f != t:
+                    adj[f].add(t)
+                    adj[t].add(f)
+            adj = [sorted(a) for a in adj]
+            order = list(range(n)) if identity else _cuthill_mckee(n, adj)
+            label = [0] * n
+            for k, old in enumerate(order):
+                label[old] = k
+            orderings[key] = (label, _two_hop_bandwidth(adj, label))
+        label, b = orderings[key]
+        bw = max(bw, b)
+        for i in range(n):
+            new_of_old[g * n + i] = g * n + label[i]
+    hb = band_half_bandwidth(bw)
+    if half_bandwidth is not None:
+        if int(half_bandwidth) < hb:
+            raise ValueError(f"band_order: half_bandwidth = {half_bandwidth} is below the {hb} states this numbering needs")
+        hb = int(half_bandwidth)
+    dev = edge_index.device
+    inverse = torch.tensor(new_of_old, dtype=torch.int64)
+    perm = torch.empty_like(inverse)
+    perm[inverse] = torch.arange(N)
+    relabelled = inverse[torch.from_numpy(ei).long()].to(edge_index.dtype).to(dev)
+    topo = get_topology(relabelled, N) if relabelled.is_cuda and E else None
+    return BandOrder(perm.int().to(dev), inverse.int().to(dev), relabelled, topo, hb, n, len(orderings))
+
+
+def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                        init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                        weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
+                        order: Optional[BandOrder] = None) -> WLSResult:
+    """``wls_estimate_large`` -- the same inputs, iteration, result and decisions -- without its cap of 256 buses, for grids whose gain
+    matrix is a band once the buses are numbered for it (radial feeders, sparse meshes): the blocked kernel on rows that keep a band of
+    G, csrc/dss2_wls_banded.hpp.  ``order``: ``band_order(edge_index, nodes_per_graph, num_nodes=N)`` of this structure; None computes it
+    here, which reads ``edge_index`` back.  With a given ``order`` nothing is read back and every launch is the library's (two or three
+    row gathers around the solve): recordable into a hipGraph or a launch plan.  The kernel solves the relabelled graph; ``x`` and
+    ``init`` rows go in and the state comes out in the caller's bus order, ``edge_attr`` is used as it is.  Equal-size graphs whose
+    topologies may differ.  NotImplementedError where (n, hb) needs more LDS than a workgroup has (``band_max_half_bandwidth(n)``).
+    Not served here: ``graph_ptr`` batches, the Huber form, bad-data detection (it needs the dense covariance)."""
+    from .ops import gather_rows
+    if order is None:
+        _require_gpu(x, edge_index, edge_attr)
+        order = band_order(edge_index, nodes_per_graph, num_nodes=x.size(0))
+    n, hb = int(nodes_per_graph), int(order.half_bandwidth)
+
+    def check_own():
+        if order.nodes_per_graph != n or order.perm.numel() != x.size(0) or order.edge_index.shape != edge_index.shape:
+            raise ValueError(f"order was made for {order.perm.numel()} buses in graphs of {order.nodes_per_graph} and "
+                             f"{order.edge_index.size(1)} edges, not for this batch")
+
+    def refuse_size(n):
+        if band_lds_bytes(n, hb) > _lib.WLS_BAND_LDS_BYTES:
+            raise NotImplementedError(f"wls_estimate_banded keeps a band's panel and the state in LDS: at {n} buses per graph a "
+                                      f"half-bandwidth hb of at most {band_max_half_bandwidth(n)} states, got hb = {hb}")
+
+    args = _lib.WlsLargeArgs()
+    a = args.solve
+    # (the checks run on the caller's tensors; the rows are gathered once they have passed)
+    keep, res, N, E, G = _solve_block(a, x, order.edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n, init, max_iter, tol,
+                                      weights, max_groups, refuse_size, check_own)
+    dev = x.device
+    xp = gather_rows(x, order.perm)
+    a.x, a.ldx = xp.data_ptr(), xp.stride(0)
+    ip = None
+    if init is not None:
+        ip = gather_rows(init.detach(), order.perm)
+        a.init, a.ld_init = ip.data_ptr(), ip.stride(0)
+    need = band_workspace_bytes(n, hb, band_groups(G, max_groups))
+    if (dev, need) not in _WORKSPACES:
+        _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    args.workspace, args.workspace_bytes, a.half_bandwidth = _WORKSPACES[(dev, need)].data_ptr(), need, hb
+    L = _lib.lib()
+    _lib.check(L.dss2_wls_solve_large(C.byref(args), _stream(x)), "dss2_wls_solve_large")
+    del keep, xp, ip             # (held until here: the launch has been issued)
+    return res._replace(state=gather_rows(res.state, order.inverse))
 
 
 def _public(impl):

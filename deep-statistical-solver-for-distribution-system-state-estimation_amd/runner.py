@@ -348,8 +348,16 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
     solution); not together with ``bad_data``.  A batch that carries a ``graph_ptr`` (a dict key or an attribute: ``synthetic.make_batch``,
     ``dataset.MixedDataset`` on parts of different bus counts) is solved with it and with its ``max_nodes`` -- else ``nodes_per_graph``,
     which may be None where every batch says its own -- as the bound on a graph's bus count: a data list may mix grids.  The kernel
-    (LDS or blocked) is chosen by that bound.  One device-to-host copy."""
+    (LDS or blocked) is chosen by that bound.  One device-to-host copy.
+    The keyword ``banded`` (taken out of ``solver_kw`` like ``robust``; default False): True -- the plain solve is ``estimator.wls_estimate_banded`` (no cap of 256 buses; equal-size graphs -- a ``graph_ptr`` that mixes bus counts is
+    refused --, and not with ``bad_data`` or ``robust``, which keep their own solves); "auto" -- only above ``estimator.max_nodes_per_graph_large()`` buses; False, the default --
+    never: above 256 buses the call is refused as before.  The banded solve orders each distinct edge list once (``estimator.band_order``
+    reads it back: one more copy per structure) and keeps the order for the batches that share the tensor."""
     from . import estimator
+    banded = solver_kw.pop("banded", False)
+    if not (banded is True or banded is False or banded == "auto"):
+        raise ValueError(f"evaluate_wls: banded must be False, True or 'auto', got {banded!r}")
+    orders = {}                  # id(edge_index) -> (edge_index, BandOrder): a loader that reuses its structure tensor is ordered once
     robust = solver_kw.pop("robust", None)
     if bad_data is not None and robust is not None:
         raise ValueError("evaluate_wls: bad_data and robust are two answers to gross errors: give one of them")
@@ -382,6 +390,14 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
         if robust is not None:
             res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **robust)
             suspect, removed = zero, res.n_downweighted.sum()
+        elif bad_data is None and (banded is True or (banded == "auto" and bound > estimator.max_nodes_per_graph_large())):
+            # (a graph_ptr whose graphs all reach the bound describes equal-size graphs: known on the host from the two lengths)
+            if graph_ptr is not None and x.size(0) != (graph_ptr.numel() - 1) * bound:
+                raise NotImplementedError("evaluate_wls: the banded solve serves equal-size graphs; this batch's graph_ptr mixes bus counts")
+            if id(ei) not in orders:
+                orders[id(ei)] = (ei, estimator.band_order(ei, bound, num_nodes=x.size(0)))
+            res = estimator.wls_estimate_banded(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, order=orders[id(ei)][1], **solver_kw)
+            suspect, removed = zero, zero
         elif bad_data is None:
             solve = estimator.wls_estimate if bound <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
             res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw)
@@ -438,6 +454,8 @@ def main(argv=None):
     ap.add_argument("--wls-robust", type=float, default=None, metavar="GAMMA", help="the --wls-baseline lines (implied) through "
                     "estimator.wls_robust, the Huber M-estimator with threshold GAMMA (3.0 is the usual choice); any bus count up to 256; "
                     "not together with --wls-bad-data")
+    ap.add_argument("--wls-banded", action="store_true", help="the --wls-baseline lines (implied) on grids above 256 buses per graph through "
+                    "estimator.wls_estimate_banded (the buses are ordered for a small bandwidth once per structure); up to 256 buses as without it")
     a = ap.parse_args(argv)
     if a.wls_robust is not None and a.wls_bad_data is not None:
         ap.error("--wls-robust and --wls-bad-data are exclusive")
@@ -505,7 +523,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(f"epoch {epoch:4d}  train_loss {tl:.6g}  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()) +
               f"  ({time.perf_counter() - t0:.2f} s)", flush=True)
-    if a.wls_baseline or a.wls_bad_data is not None or a.wls_robust is not None:
+    if a.wls_baseline or a.wls_bad_data is not None or a.wls_robust is not None or a.wls_banded:
         ds = getattr(test_loader, "dataset", None)
         n_bus = getattr(ds, "n", None) if ds is not None else synthetic.load_grid(a.case).n
         if n_bus is None:                                            # a data list that mixes bus counts: its batches carry graph_ptr; the bound is the largest part's
@@ -513,7 +531,7 @@ def main(argv=None):
         for label, start in [("flat start", None)] + ([(f"start = {a.model}'s output", model)] if hp["dim_out"] == 2 else []):
             bad_data = dict(threshold=a.wls_bad_data, max_removals=5, large="auto") if a.wls_bad_data is not None else None
             robust = dict(gamma=a.wls_robust) if a.wls_robust is not None else None
-            m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data, robust=robust)
+            m = evaluate_wls(test_loader, stats, n_bus, model=start, bad_data=bad_data, robust=robust, banded="auto" if a.wls_banded else False)
             print(f"wls baseline ({label})  " + "  ".join(f"{k} {v:.4g}" for k, v in m.items()), flush=True)
     if a.save:                                                       # dss2_run.py:240-247
         torch.save({"epoch": a.epochs - 1, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},

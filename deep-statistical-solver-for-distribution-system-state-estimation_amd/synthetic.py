@@ -123,6 +123,18 @@ def load_grid(name: str) -> Grid:
     return g
 
 
+def register_radial(n: int, seed: Optional[int] = None) -> str:
+    """Puts ``_radial_feeder(n, seed)`` (seed None: n, as 'ober179' has it) behind ``load_grid`` and ``make_batch`` and returns its name,
+    'radial<n>' or 'radial<n>_s<seed>'.  Any size: feeders beyond the dense estimators' 256 buses are what ``wls_estimate_banded`` is for."""
+    n = int(n)
+    if n < 4:
+        raise ValueError("a radial feeder has at least 4 buses")
+    name = f"radial{n}" if seed is None else f"radial{n}_s{int(seed)}"
+    if name not in _GRIDS:
+        _GRIDS[name] = _radial_feeder(n, seed=n if seed is None else int(seed))
+    return name
+
+
 def branch_flows(v, th, g: Grid, v_lv: float):
     """AC branch flows, fp64 numpy, same equations as /root/reference/data.py:370-376
     (shift = 0, scaled by V_lv^2).  v, th: [B, n]."""

@@ -726,7 +726,10 @@ typedef struct dss2_wls_solve_args {
   int32_t* status;                                /* [G]     0 converged, 1 max_iter reached, 2 factorisation failed             */
   double* last_step;                              /* [G]     max |du| of the last update applied (0 if none)                      */
   float* vminmax;                                 /* [130] device scratch                                                         */
-  int32_t max_groups; int32_t pad_;               /* > 0: at most this many workgroups (they stride over the graphs); 0: the library's choice */
+  int32_t max_groups;                             /* > 0: at most this many workgroups (they stride over the graphs); 0: the library's choice */
+  int32_t half_bandwidth;                         /* dss2_wls_solve_large alone reads it (0: its dense form, > 0: its banded form, below); every other entry ignores the word.
+                                                   * This word used to be padding (pad_): a caller of dss2_wls_solve_large MUST set it to 0 for the dense form -- a struct
+                                                   * that was never zeroed now selects the banded form, or gets rc 2 for a negative value */
   /* Batches that mix bus counts (every entry that takes this block).  graph_ptr = NULL: the uniform layout above.  Otherwise graph g
    * owns buses [graph_ptr[g], graph_ptr[g + 1]) and nodes_per_graph is an UPPER BOUND on a graph's bus count: LDS, workspace, the
    * workgroup's width, the grid and every size refusal go by it, and n_nodes need not be a multiple of it.  The kernel reads the two
@@ -794,7 +797,21 @@ size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph);
  *      dss2_wls_large_max_nodes() (256: 512 states); above it rc 2.  The workgroups stride over the graphs, each in its own slice of
  *      the workspace: dss2_wls_large_workspace_bytes(nodes_per_graph, dss2_wls_large_groups(&solve)) bytes, 16-byte aligned, contents
  *      irrelevant before and after.  No atomics, fixed summation orders: runs, batch positions and group counts agree to the bit.
- *      rc 2 with a message for a null argument, a null, misaligned or short workspace, N not a multiple of n, n above the cap.  */
+ *      rc 2 with a message for a null argument, a null, misaligned or short workspace, N not a multiple of n, n above the cap.
+ *      THE BANDED FORM (solve.half_bandwidth > 0, csrc/dss2_wls_banded.hpp) lifts the cap for graphs whose buses are numbered so that the gain
+ *      matrix is a band: hb = half_bandwidth >= max (r - c) over the non-zeros G[r, c] (states: bus i has states 2 i and 2 i + 1; G
+ *      couples the buses within two branches of each other).  Same kernel steps, decisions and outputs on another layout: block row R
+ *      (16 states) keeps only the block columns R - Wb .. R, Wb = ceil(hb / 16), the right-hand side is a row of its own, and the
+ *      factorisation, the panel in LDS and the back substitution stay inside the band.  With nb = ceil(2 n / 16):
+ *        workspace   groups * (256 nb (Wb + 1) + 16 nb) * 8 bytes, groups = min(graphs, DSS2_WLS_BAND_GROUPS, max_groups if > 0)
+ *        LDS         (16 (16 Wb + 8) + 16 * 16 + 16 + 4 n) * 8 + 16 + 16 ceil(n / 16) bytes <= DSS2_WLS_BAND_LDS_BYTES: the cap on (n, hb)
+ *      Equal-size graphs only (graph_ptr: rc 2).  A graph with a non-zero outside the declared band is not assembled: status 2,
+ *      0 iterations, its start as its state; nothing is written outside its slice, and the other graphs are solved.  rc 2 with a
+ *      message for half_bandwidth < 0, (n, hb) above the cap, a short workspace and what the dense form refuses of the rest.
+ *      half_bandwidth = 0 is the dense form above, unchanged.  */
+#define DSS2_WLS_BAND_BLOCK 16           /* states of a block row and of a block column */
+#define DSS2_WLS_BAND_GROUPS 512         /* workgroups at most */
+#define DSS2_WLS_BAND_LDS_BYTES 163840   /* the LDS of a workgroup */
 typedef struct dss2_wls_large_args {
   dss2_wls_solve_args solve;                      /* as for dss2_wls_solve                                                        */
   void* workspace; uint64_t workspace_bytes;
