@@ -17,7 +17,11 @@ weights are the oracle model's own initialisation under the case's seed.
 
 STRUCTURE and ROUTE pin what every case is there for as literals.  They were read off the library BEFORE these tests existed (the
 topology oracle for the structure; route.block_route, the whole-stack query, the weight-gradient plan and the edge plan on a stand-in
-topology for the route), not produced by a run of changed code: a case that drifts fails loudly."""
+topology for the route), not produced by a run of changed code: a case that drifts fails loudly.
+
+tests/mpn_width_cases.py builds cases of its own on the graphs of these (other hidden widths, heads, K and depths): ``batch``, ``reference``,
+``topology_oracle``, ``stub_topology`` and ``structure`` take a case object as well as a name of this table, and cases with the same graph
+fields share graphs, features and topology oracle."""
 import dataclasses
 import functools
 import importlib
@@ -186,17 +190,27 @@ def _graph(n, cap, hub, tail, g):
     return edges, hub
 
 
+def case_of(key):
+    """A case given as itself or by its name in BY_NAME (tests/mpn_width_cases.py builds cases of its own on the graphs of these)."""
+    return key if isinstance(key, Case) else BY_NAME[key]
+
+
+def graph_key(key):
+    """What of a case decides its graphs: two cases with the same key share edge list, x and edge_attr (and the topology oracle)."""
+    case = case_of(key)
+    return (case.counts, case.cap, case.tail, case.dup3, case.seed)
+
+
 @functools.lru_cache(maxsize=None)
-def batch(name):
-    """dict(x [N, 8] fp64, edge_index [2, E], edge_attr [E, 6] fp64, gout [N, dim_out] fp64, hubs (global row per graph), start (first row
-    per graph)) of a case.  Built once and shared: nobody writes to it."""
-    case = BY_NAME[name]
-    g = torch.Generator().manual_seed(7000 + case.seed)
+def _graphs(gkey):
+    """(edge_index, x, edge_attr, hubs, start, the generator's state behind them) of a graph key."""
+    counts, cap, tails, dup3, seed = gkey
+    g = torch.Generator().manual_seed(7000 + seed)
     src, dst, hubs, starts, base = [], [], [], [], 0
-    for k, n in enumerate(case.counts):
-        tail = k in case.tail
-        edges, hub = _graph(n, case.cap, n - 1 if tail else n // 2, tail, g)
-        if case.dup3:
+    for k, n in enumerate(counts):
+        tail = k in tails
+        edges, hub = _graph(n, cap, n - 1 if tail else n // 2, tail, g)
+        if dup3:
             edges = [e for j, e in enumerate(edges) for _ in range(2 if j % 3 == 0 else 1)]
         src += [a + base for a, _ in edges]
         dst += [b + base for _, b in edges]
@@ -204,9 +218,26 @@ def batch(name):
         starts.append(base)
         base += n
     ei = torch.tensor([src, dst], dtype=torch.int64)
-    draw = lambda *shape: torch.randn(*shape, generator=g, dtype=torch.float64).float().double()      # noqa: E731  (fp32 values, held in fp64)
-    x, ea, gout = draw(base, 8), draw(ei.size(1), 6), draw(base, case.args[2])
-    return dict(x=x, edge_index=ei, edge_attr=ea, gout=gout, hubs=tuple(hubs), start=tuple(starts))
+    x, ea = _draw(g, base, 8), _draw(g, ei.size(1), 6)
+    return ei, x, ea, tuple(hubs), tuple(starts), g.get_state()
+
+
+def _draw(g, *shape):
+    return torch.randn(*shape, generator=g, dtype=torch.float64).float().double()      # (fp32 values, held in fp64)
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(gkey, dim_out):
+    ei, x, ea, hubs, starts, state = _graphs(gkey)
+    g = torch.Generator()
+    g.set_state(state)                      # gout comes behind x and edge_attr, whatever its width
+    return dict(x=x, edge_index=ei, edge_attr=ea, gout=_draw(g, x.size(0), dim_out), hubs=hubs, start=starts)
+
+
+def batch(key):
+    """dict(x [N, 8] fp64, edge_index [2, E], edge_attr [E, 6] fp64, gout [N, dim_out] fp64, hubs (global row per graph), start (first row
+    per graph)) of a case (or the name of one).  Built once and shared: nobody writes to it."""
+    return _batch(graph_key(key), case_of(key).args[2])
 
 
 def degrees(name):
@@ -226,7 +257,7 @@ def oracle_model(case, dtype=torch.float64):
 
 def oracle_run(case, dtype):
     """The oracle model at dtype on the CPU: dict(out, dx, grads {name: tensor})."""
-    b = batch(case.name)
+    b = batch(case)
     m = oracle_model(case, dtype)
     x = b["x"].to(dtype).clone().requires_grad_(True)
     out = m(x, b["edge_index"], b["edge_attr"].to(dtype))
@@ -235,19 +266,23 @@ def oracle_run(case, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
-    """The fp64 run of a case, computed once."""
-    return oracle_run(BY_NAME[name], torch.float64)
+def reference(key):
+    """The fp64 run of a case (or the name of one), computed once."""
+    return oracle_run(case_of(key), torch.float64)
 
 
 # ------------------------------------------------------------------------------------------
 # structure and route without a device
 # ------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def topology_oracle(name, nrb=None):
-    b = batch(name)
-    o = TopologyOracle(b["edge_index"], b["x"].size(0), nrb=nrb)
+def _topology_oracle(gkey, nrb):
+    ei, x = _graphs(gkey)[:2]
+    o = TopologyOracle(ei, x.size(0), nrb=nrb)
     return o if o.tiled else None
+
+
+def topology_oracle(key, nrb=None):
+    return _topology_oracle(graph_key(key), nrb)
 
 
 def structure(name):
@@ -269,11 +304,15 @@ def _tiling(o):
 
 
 @functools.lru_cache(maxsize=None)
-def stub_topology(name):
-    """What the route predicates, stack.tiles_of and the weight-gradient geometry read of a Topology, from the oracle's numbers."""
-    prim = topology_oracle(name)
+def _stub_topology(gkey):
+    prim = _topology_oracle(gkey, None)
     return types.SimpleNamespace(tiling=_tiling(prim), N=prim.N, hint=None, device=None,
-                                 tiles_for=functools.lru_cache(maxsize=None)(lambda nrb: _tiling(topology_oracle(name, nrb))))
+                                 tiles_for=functools.lru_cache(maxsize=None)(lambda nrb: _tiling(_topology_oracle(gkey, nrb))))
+
+
+def stub_topology(key):
+    """What the route predicates, stack.tiles_of and the weight-gradient geometry read of a Topology, from the oracle's numbers."""
+    return _stub_topology(graph_key(key))
 
 
 def blocks_of(case):
@@ -292,7 +331,7 @@ def stack_supported(case):
     keep = st._cu_count
     st._cu_count = lambda dev: CUS
     try:
-        return st.supported(blocks_of(case), stub_topology(case.name)) is not None
+        return st.supported(blocks_of(case), stub_topology(case)) is not None
     finally:
         st._cu_count = keep
 
@@ -302,19 +341,20 @@ def route_literal(case, need_dx, block_routes=None, topo=None):
     ``topo``: the device Topology (else the stand-in)."""
     P = pkg()
     blocks = blocks_of(case)
-    stub = stub_topology(case.name) if topo is None else topo
+    stub = stub_topology(case) if topo is None else topo
     ts = stub.tiling
     in_stack = len(blocks) > 1
     if block_routes is None:
         block_routes = [P.route.block_route(m, ts, bool(bi > 0 or need_dx), in_stack) for bi, m in enumerate(blocks)]
     rows = tuple(tuple(getattr(r, f) for f in ROUTE_FIELDS) for r in block_routes)
     hid, L, nmat = case.args[3], case.args[4], case.args[5] + 1
-    wts = P.ops._wgrad_tiles(stub, nmat, hid, hid, 1)
+    b16 = int(P.flags.WGRAD_BF16)      # (as ops.wgrad_batched asks)
+    wts = P.ops._wgrad_tiles(stub, nmat, hid, hid, b16)
     keep = torch.cuda.is_current_stream_capturing
     if topo is None:      # (no device to ask: nothing is being captured)
         torch.cuda.is_current_stream_capturing = lambda: False
     try:
-        mode = P.ops._wgrad_mode(wts, nmat, 1)
+        mode = P.ops._wgrad_mode(wts, nmat, b16)
     finally:
         torch.cuda.is_current_stream_capturing = keep
     wp = P.ops._wgrad_shape_plan(wts, nmat, hid, hid, mode, L - 1 if L - 1 >= 2 else 0)
