@@ -225,7 +225,7 @@ class WlsSolveArgs(C.Structure):
 class WlsBadDataArgs(C.Structure):
     """dss2_wls_bad_data_args (include/dss2_hip.h)."""
     _fields_ = [("solve", WlsSolveArgs), ("threshold", C.c_double), ("z_p", C.c_double), ("s_min", C.c_double),
-                ("max_removals", C.c_int32), ("pad_", C.c_int32), ("dof", C.c_void_p), ("chi2_limit", C.c_void_p),
+                ("max_removals", C.c_int32), ("pad_", C.c_int32), ("bus_label", C.c_void_p), ("dof", C.c_void_p), ("chi2_limit", C.c_void_p),
                 ("suspect", C.c_void_p), ("removed", C.c_void_p), ("removed_rn", C.c_void_p), ("n_removed", C.c_void_p),
                 ("bus_rn", C.c_void_p), ("bus_sens", C.c_void_p), ("edge_rn", C.c_void_p), ("edge_sens", C.c_void_p),
                 ("state_std", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
@@ -237,6 +237,7 @@ class WlsLargeArgs(C.Structure):
 
 
 WLS_BAND_BLOCK, WLS_BAND_GROUPS, WLS_BAND_LDS_BYTES = 16, 512, 160 * 1024      # the banded form of dss2_wls_solve_large
+WLS_BAND_BAD_DATA_BYTES = 320                                                  # ... of dss2_wls_bad_data: its fixed LDS block behind the solve's
 
 
 class WlsRobustArgs(C.Structure):

@@ -33,8 +33,13 @@
 // the owner of a COLUMN in place of the owner of a row, since 2 n may exceed the workgroup); then steps 3 and 4 above by the same bd_*
 // functions with Sigma addressed on the block rows (BdBlockRows).  LDS is the large solve's carve of the bound, then the same fixed
 // block (red, rem).  Everything after the rounds is the LDS kernel's; the objective's per-bus parts go through du.
+//
+// THE BANDED FORM (wls_bad_data_banded_kernel; args.workspace != NULL and solve.half_bandwidth > 0): the blocked form's rounds on the band
+// rows of dss2_wls_banded.hpp, beyond 256 buses, with the entries of Sigma inside the band in place of the whole inverse
+// (dss2_wls_banded_invert.hpp).  Described at the kernel, below.
 #include "dss2_wls_bad_data_core.hpp"
 #include "dss2_wls_large_invert.hpp"
+#include "dss2_wls_banded_invert.hpp"
 
 namespace dss2 {
 
@@ -197,6 +202,96 @@ __global__ void __launch_bounds__(WL_T, 2) wls_bad_data_blocked_kernel(const dss
   }
 }
 
+// Sigma on the band rows of dss2_wls_banded.hpp, after wb_selinv: rows.at(A, hi)[lo].  A band row stores its columns from
+// 16 (hi / 16 - Wb) on and nothing left of that, so it must only ever be asked for in-band positions -- and it is: bd_bus asks for the
+// states of bus li and of the buses incident to it, in pairs (bus, bus), (bus, neighbour) and (neighbour, neighbour of the same bus);
+// the two buses of every such pair are within two branches of each other, and wb_fits has checked, before anything of the graph was
+// assembled, that every bus's block row reaches back to the lowest bus within two branches of it (a bus's two states share a block
+// row).  state_std asks for the diagonal.
+struct BdBandRows {
+  double* A; WbRows rows;
+  __device__ __forceinline__ double operator()(int p, int q) const {
+    const int hi = p > q ? p : q, lo = p > q ? q : p;
+    return rows.at(A, hi)[lo];
+  }
+};
+
+static_assert(BD_EXTRA_BYTES == (size_t)DSS2_WLS_BAND_BAD_DATA_BYTES, "the header's constant is the fixed block behind the banded carve");
+
+// THE BANDED FORM (args.workspace != NULL and solve.half_bandwidth > 0): the rounds of wls_bad_data_blocked_kernel on the band rows of
+// dss2_wls_banded.hpp, for graphs beyond 256 buses.  wb_fits once per graph, before anything is assembled: a graph that does not fit
+// gets bd_refuse's outputs and its start as its state, and its slice stays untouched.  Per round: wl_gauss_newton with the removal mask;
+// G at the last iterate formed and factorised once more; wb_selinv (dss2_wls_banded_invert.hpp): the entries of Sigma inside the band,
+// in place -- all that steps 3 and 4 read (BdBandRows above).  LDS is the banded carve, then the fixed block.
+// The kernel works on the relabelled graph (estimator.band_order): the removal list in LDS, the mask and the arg-max -- hence its ties,
+// which go to the smallest RELABELLED id -- keep relabelled ids.  Only `removed`, the caller's list, is translated, by the thread that
+// records it: a bus measurement's id through bus_label (branch ids are the caller's already: band_order keeps the stored edge order).
+__global__ void __launch_bounds__(WL_T) wls_bad_data_banded_kernel(const dss2_wls_bad_data_args b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bb_smem[];
+  const dss2_wls_solve_args& a = b.solve;
+  const int n = a.nodes_per_graph, ns = 2 * n, Wb = wb_blocks(a.half_bandwidth);
+  double* A = static_cast<double*>(b.workspace) + (size_t)blockIdx.x * wb_graph_doubles(n, Wb);
+  const WbRows rows = {WL_NB * (Wb + 1), WL_NB * Wb};
+  const WlLds l = wl_carve(bb_smem, n, wb_pstride(Wb));
+  const BdLds r = bd_carve(bb_smem + wb_lds_bytes(n, Wb));
+  const int slots = b.max_removals > 1 ? b.max_removals : 1;
+  const int tid = threadIdx.x;
+  float vlv, vhv;
+  vminmax_fold(a.vminmax, vlv, vhv);
+  const int64_t n_graphs = a.n_nodes / n;
+  for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
+    const WsGraph g = ws_graph(gr * n, n, vlv, l.u, l.slk);
+    const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
+    ws_load_start<WL_T>(a, g, start, tid);
+    if (!wb_fits(a, g, l.ctl, rows.shift, tid)) {      // uniform over the workgroup (its second barrier: the start is in LDS)
+      ws_store_state<WL_T>(a, g, ns, tid);
+      if (tid == 0) bd_refuse(b, gr, slots);
+      __syncthreads();                                 // the next graph of this workgroup reuses the LDS
+      continue;
+    }
+    WsTally t = {0, 1, 0.0};
+    int nrem = 0, n_active = 0;          // nrem is uniform; n_active is thread 0's
+    bool removing = true;                // uniform
+    for (int round = 0; round <= b.max_removals; ++round) {
+      if (removing) {
+        const WsRemoved mask = {r.rem, nrem};
+        wl_gauss_newton(a, g, A, rows, l, ns, tid, t, WsNoWeight(), mask);
+        bool failed = l.ctl[0] != 0 && l.ctl[1] == 0;      // (uniform: the words of the last iteration run, behind its barrier)
+        if (!failed) {
+          wl_form(a, g, A, rows, ns, tid, WsNoWeight(), mask);   // (its first barrier: ctl has been read)
+          const bool ok = wl_factor(A, rows, l, ns, tid);
+          if (tid == 0) l.ctl[3] = ok ? 1 : 0;             // (wave 0's answer, made the workgroup's)
+          __syncthreads();
+          if (l.ctl[3] == 0) {
+            failed = true;
+            if (tid == 0) t.status = 2;
+          }
+        }
+        if (!failed) wb_selinv(A, rows, l, ns, tid);
+        BdBest best = {-1.0, 0x7fffffff};
+        int cnt = 0;
+        const BdBandRows Sg = {A, rows};
+        for (int k = tid; k < n; k += WL_T) bd_bus(b, g, Sg, k, mask, failed, best, cnt);
+        for (int q = tid; q < ns; q += WL_T)
+          b.state_std[(g.base + (q >> 1)) * 2 + (q & 1)] = (failed || ((q & 1) && l.slk[q >> 1])) ? 0.0 : sqrt(Sg(q, q));
+        removing = bd_decide<WL_T>(b, r, l.ctl, gr, slots, failed, nrem, tid, best, cnt, n_active);
+        if (removing) {
+          if (tid == 0 && b.bus_label) {                   // (thread 0 wrote removed[] in bd_decide: still its one writer)
+            const int id = r.rem[nrem];
+            if ((int64_t)id < 4 * a.n_nodes) b.removed[gr * slots + nrem] = 4 * b.bus_label[id >> 2] + (id & 3);
+          }
+          ++nrem;
+        }
+      }
+    }
+    ws_store_state<WL_T>(a, g, ns, tid);
+    double jb, je;
+    ws_objective<WL_T>(a, g, l.du, tid, WsRemoved{r.rem, nrem}, jb, je);
+    if (tid == 0) bd_finish(b, gr, t, jb, je, n_active, nrem, slots, l.slk, n);
+    __syncthreads();                     // the next graph of this workgroup reuses the LDS (rem and slk included)
+  }
+}
+
 }  // namespace dss2
 
 using namespace dss2;
@@ -207,6 +302,13 @@ extern "C" size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph) {
 
 static int wls_bad_data_launch(const dss2_wls_bad_data_args* bp, void* stream) {
   const dss2_wls_bad_data_args& b = *bp;
+  if (b.workspace && b.solve.half_bandwidth != 0) {      // the banded form, routed as dss2_wls_solve_large routes the banded solve
+    const char* who = "wls_bad_data (banded)";
+    if (int rc = ws_check_batch(b.solve, who)) return rc;
+    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, who, BD_EXTRA_BYTES)) return rc;
+    if (int rc = bd_check_params(b, who)) return rc;
+    return wb_launch<wls_bad_data_banded_kernel>(b, who, as_stream(stream), BD_EXTRA_BYTES);
+  }
   if (b.workspace) {                     // the blocked form
     const char* who = "wls_bad_data (blocked)";
     if (int rc = wl_check_size(b.solve, who)) return rc;

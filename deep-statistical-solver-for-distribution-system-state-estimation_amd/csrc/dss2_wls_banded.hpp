@@ -13,6 +13,10 @@
 //                     row comes last); Ld, invd, u, du, ctl, slk as in the dense form.  wb_lds_bytes(n, Wb) <= the LDS of a
 //                     workgroup is the cap on (n, hb), DSS2_WLS_BAND_LDS_BYTES; the host mirrors the formula (estimator.py).
 //
+// Three kernels run on this layout: wls_banded_kernel<dss2_wls_large_args> (the plain estimator, csrc/dss2_wls_large.hip),
+// wls_banded_kernel<dss2_wls_robust_args> (the Huber one, csrc/dss2_wls_robust.hip) and wls_bad_data_banded_kernel (csrc/dss2_wls_bad_data.hip,
+// with the selected inverse of dss2_wls_banded_invert.hpp); each enters through its dense form's C function when half_bandwidth > 0.
+//
 // THE GUARD.  The row owners write G[r, c] at at(r)[c]; a column left of the band would land in another row.  Which columns a row has is
 // a matter of the graph alone, so it is checked once per graph before anything is assembled (wb_fits: every bus against the lowest
 // bus within two branches of it).  A graph that does not fit is not assembled: status 2, no iteration, its start as its state.
@@ -76,8 +80,12 @@ __device__ __forceinline__ bool wb_fits(const dss2_wls_solve_args& a, const WsGr
 }
 
 // wls_blocked_kernel on the band: one workgroup of WL_T threads per graph and slice, the workgroups stride over the graphs.  Equal-size
-// graphs only (the host refuses a graph_ptr).
-__global__ void __launch_bounds__(WL_T) wls_banded_kernel(const dss2_wls_large_args b) {
+// graphs only (the host refuses a graph_ptr).  Args is dss2_wls_large_args (the plain estimator) or dss2_wls_robust_args (the Huber one:
+// ws_weighting gives its WsHuber), as for wls_blocked_kernel.  The Huber form's per-bus counts of q < 1 cannot pass through the panel as
+// they do there -- 16 (16 Wb + 8) doubles hold fewer than n ints once the band is narrow -- so they pass through the head of the slice,
+// which is idle after the last factorisation (also for a graph that does not fit: the one thing written to its slice).
+template <class Args>
+__global__ void __launch_bounds__(WL_T) wls_banded_kernel(const Args b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wb_smem[];
   const dss2_wls_solve_args& a = b.solve;
   const int n = a.nodes_per_graph, ns = 2 * n, Wb = wb_blocks(a.half_bandwidth);
@@ -86,31 +94,35 @@ __global__ void __launch_bounds__(WL_T) wls_banded_kernel(const dss2_wls_large_a
   const int tid = threadIdx.x;
   float vlv, vhv;
   vminmax_fold(a.vminmax, vlv, vhv);
+  auto wt = ws_weighting(b);
+  using Wt = decltype(wt);
   const WlLds l = wl_carve(wb_smem, n, wb_pstride(Wb));
+  if constexpr (Wt::robust) wt.cnt = reinterpret_cast<int*>(A);
   const int64_t n_graphs = a.n_nodes / n;
   for (int64_t gr = blockIdx.x; gr < n_graphs; gr += gridDim.x) {
     const WsGraph g = ws_graph(gr * n, n, vlv, l.u, l.slk);
     const WsLds start = {nullptr, nullptr, l.u, l.du, l.ctl, l.slk};
     ws_load_start<WL_T>(a, g, start, tid);
     WsTally t = {0, 2, 0.0};
-    if (wb_fits(a, g, l.ctl, rows.shift, tid)) wl_gauss_newton(a, g, A, rows, l, ns, tid, t, WsNoWeight());
-    ws_finish<WL_T>(a, g, gr, l.du, ns, tid, t, WsNoWeight());
+    if (wb_fits(a, g, l.ctl, rows.shift, tid)) wl_gauss_newton(a, g, A, rows, l, ns, tid, t, wt);
+    if constexpr (Wt::robust) wt.n_down = b.n_downweighted + gr;
+    ws_finish<WL_T>(a, g, gr, l.du, ns, tid, t, wt);
   }
 }
 
-// ---- host side: the banded form's own checks (after ws_check_batch) and its launch
+// ---- host side: the banded forms' own checks (after ws_check_batch) and their launch.  extra_lds: what a kernel keeps behind the
+// banded carve (the bad-data form's fixed block); it counts against the cap on (n, hb).
 inline int64_t wb_grid(const dss2_wls_solve_args& a) {
   const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
   int64_t grid = WB_GROUPS;
   if (a.max_groups > 0 && a.max_groups < grid) grid = a.max_groups;
   return n_graphs < grid ? n_graphs : grid;
 }
-inline int wb_check(const dss2_wls_large_args& b, const char* who) {
-  const dss2_wls_solve_args& a = b.solve;
+inline int wb_check(const dss2_wls_solve_args& a, const void* workspace, uint64_t workspace_bytes, const char* who, size_t extra_lds = 0) {
   const int n = a.nodes_per_graph, hb = a.half_bandwidth;
   if (a.graph_ptr) { set_error("%s: the banded form serves equal-size graphs (no graph_ptr)", who); return 2; }
   if (hb < 0) { set_error("%s: half_bandwidth must be >= 0", who); return 2; }
-  if (n > (1 << 20) || hb > (1 << 20) || wb_lds_bytes(n, wb_blocks(hb)) > (size_t)DSS2_WLS_BAND_LDS_BYTES) {
+  if (n > (1 << 20) || hb > (1 << 20) || wb_lds_bytes(n, wb_blocks(hb)) + extra_lds > (size_t)DSS2_WLS_BAND_LDS_BYTES) {
     set_error("%s: %d buses per graph at a half-bandwidth of %d states need more than the %d bytes of LDS a workgroup has", who, n, hb,
               DSS2_WLS_BAND_LDS_BYTES);
     return 2;
@@ -118,20 +130,21 @@ inline int wb_check(const dss2_wls_large_args& b, const char* who) {
   if (a.max_groups < 0) { set_error("%s: bad leading dimension or max_groups", who); return 2; }
   const int64_t grid = wb_grid(a);
   const size_t need = (size_t)grid * wb_graph_doubles(n, wb_blocks(hb)) * 8;
-  if (!b.workspace || (reinterpret_cast<uintptr_t>(b.workspace) & 15) != 0) { set_error("%s: the workspace is null or not 16-byte aligned", who); return 2; }
-  if (b.workspace_bytes < need) {
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) { set_error("%s: the workspace is null or not 16-byte aligned", who); return 2; }
+  if (workspace_bytes < need) {
     set_error("%s: the workspace has %llu bytes, %lld workgroups of %d buses at a half-bandwidth of %d need %llu", who,
-              (unsigned long long)b.workspace_bytes, (long long)grid, n, hb, (unsigned long long)need);
+              (unsigned long long)workspace_bytes, (long long)grid, n, hb, (unsigned long long)need);
     return 2;
   }
   return ws_check_rest(a, who);
 }
-inline int wb_launch(const dss2_wls_large_args& b, const char* who, hipStream_t s) {
+template <auto K, class Args>
+inline int wb_launch(const Args& b, const char* who, hipStream_t s, size_t extra_lds = 0) {
   const dss2_wls_solve_args& a = b.solve;
   static std::atomic<uint32_t> done{0};
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(wls_banded_kernel), done, who)) return rc;
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(K), done, who)) return rc;
   launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
-  hipLaunchKernelGGL(wls_banded_kernel, dim3((unsigned)wb_grid(a)), dim3(WL_T), wb_lds_bytes(a.nodes_per_graph, wb_blocks(a.half_bandwidth)), s, b);
+  hipLaunchKernelGGL(K, dim3((unsigned)wb_grid(a)), dim3(WL_T), wb_lds_bytes(a.nodes_per_graph, wb_blocks(a.half_bandwidth)) + extra_lds, s, b);
   return check_launch(who);
 }
 

@@ -51,8 +51,8 @@ static int wls_solve_large_launch(const dss2_wls_large_args* bp, void* stream) {
   const dss2_wls_large_args& b = *bp;
   if (b.solve.half_bandwidth != 0) {
     if (int rc = ws_check_batch(b.solve, "wls_solve_large (banded)")) return rc;
-    if (int rc = wb_check(b, "wls_solve_large (banded)")) return rc;
-    return wb_launch(b, "wls_solve_large (banded)", as_stream(stream));
+    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large (banded)")) return rc;
+    return wb_launch<wls_banded_kernel<dss2_wls_large_args>>(b, "wls_solve_large (banded)", as_stream(stream));
   }
   if (int rc = wl_check_size(b.solve, "wls_solve_large")) return rc;
   if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;

@@ -13,13 +13,15 @@
 // (ws_weighting in dss2_wls_core.hpp turns them into the WsHuber):
 //   wls_lds_kernel<64 / 256, .>   the gain matrix packed in LDS (dss2_wls_core.hpp; dss2_wls_solve.hip's layout and steps), up to 99 buses
 //   wls_blocked_kernel<.>         the gain matrix in a workspace in global memory, blocked Cholesky (dss2_wls_large_core.hpp), up to 256
+//   wls_banded_kernel<.>          the same on rows that keep a band of G (dss2_wls_banded.hpp; half_bandwidth > 0), beyond 256 buses; it
+//                                 enters through dss2_wls_robust_large as the plain banded solve enters through dss2_wls_solve_large
 //
 // After the last iterate, with weighting on: the objective pass (a bus owns its four measurements and the two flows of every branch it
 // is the from-end of) writes every q, replaces the term of a measurement with q < 1 by rho's tail 2 gamma t - gamma^2, and counts the
 // q < 1; the per-bus counts go through workgroup scratch that is idle by then (the packed array; the panel Pt) and thread 0 adds them.
 // No atomics, one writer per value, fixed summation orders.  Every __syncthreads() sits in control flow that is uniform over the
 // workgroup; no loop's end depends on the iterate.
-#include "dss2_wls_large_core.hpp"
+#include "dss2_wls_banded.hpp"
 
 using namespace dss2;
 
@@ -45,6 +47,13 @@ extern "C" int dss2_wls_robust(const dss2_wls_robust_args* bp, void* stream) { r
 
 static int wls_robust_large_launch(const dss2_wls_robust_args* bp, void* stream) {
   const dss2_wls_robust_args& b = *bp;
+  if (b.solve.half_bandwidth != 0) {     // the banded form, as dss2_wls_solve_large routes it
+    const char* who = "wls_robust_large (banded)";
+    if (int rc = ws_check_batch(b.solve, who)) return rc;
+    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, who)) return rc;
+    if (int rc = wr_check_params(b, who)) return rc;
+    return wb_launch<wls_banded_kernel<dss2_wls_robust_args>>(b, who, as_stream(stream));
+  }
   if (int rc = wl_check_size(b.solve, "wls_robust_large")) return rc;
   if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_robust_large")) return rc;
   if (int rc = wr_check_params(b, "wls_robust_large")) return rc;

@@ -22,7 +22,15 @@ memory, a blocked Cholesky, csrc/dss2_wls_large.hip.
 The same estimator beyond 256 buses per graph (feeders of 300, 1000 buses): the buses are numbered for a small bandwidth of the gain
 matrix on the host, once per structure (``band_order``: Cuthill-McKee), and the blocked kernel runs on the band alone,
 csrc/dss2_wls_banded.hpp.  ``num_nodes`` counts buses behind the last branch (one-bus graphs at the end of a batch); ``identity`` keeps the
-caller's numbering and only measures its half-bandwidth.  Equal-size graphs; no ``graph_ptr``, no Huber form, no bad-data detection.
+caller's numbering and only measures its half-bandwidth.  Equal-size graphs; no ``graph_ptr``.
+
+    wls_bad_data_banded(... wls_bad_data_large's arguments ..., order=None) -> WLSBadDataResult
+    wls_robust_banded(... wls_robust's arguments without ``large`` ..., order=None) -> WLSRobustResult
+
+The two answers to gross errors (below) on the banded kernel, beyond 256 buses.  The bad-data test reads the covariance only at its
+diagonal and between buses within two branches of each other; those entries of the inverse lie inside the band and follow from the banded
+factor by the selected-inverse recurrence, in place (csrc/dss2_wls_banded_invert.hpp) -- no dense inverse.  Results come back in the
+caller's bus order, ``removed`` in the caller's ids.
 
     wls_bad_data(... same inputs ..., threshold=3.0, max_removals=0, confidence=0.95, s_min=1e-3) -> WLSBadDataResult
 
@@ -444,10 +452,12 @@ def band_blocks(half_bandwidth: int) -> int:
     return -(-int(half_bandwidth) // _lib.WLS_BAND_BLOCK)
 
 
-def band_lds_bytes(nodes_per_graph: int, half_bandwidth: int) -> int:
-    """The LDS of a workgroup of the banded kernel: wb_lds_bytes of csrc/dss2_wls_banded.hpp (the C side checks the same formula)."""
+def band_lds_bytes(nodes_per_graph: int, half_bandwidth: int, bad_data: bool = False) -> int:
+    """The LDS of a workgroup of the banded kernel: wb_lds_bytes of csrc/dss2_wls_banded.hpp (the C side checks the same formula).
+    ``bad_data``: of ``wls_bad_data_banded``'s, which keeps its fixed block (the arg-max's per-wave results, the removal list) behind it."""
     nb, n = _lib.WLS_BAND_BLOCK, int(nodes_per_graph)
-    return (nb * (nb * band_blocks(half_bandwidth) + 8) + nb * nb + nb + 4 * n) * 8 + 16 + (n + 15) // 16 * 16
+    solve = (nb * (nb * band_blocks(half_bandwidth) + 8) + nb * nb + nb + 4 * n) * 8 + 16 + (n + 15) // 16 * 16
+    return solve + (_lib.WLS_BAND_BAD_DATA_BYTES if bad_data else 0)
 
 
 def band_groups(n_graphs: int, max_groups: int = 0) -> int:
@@ -462,11 +472,12 @@ def band_workspace_bytes(nodes_per_graph: int, half_bandwidth: int, groups: int)
     return int(groups) * block_rows * (nb * nb * (band_blocks(half_bandwidth) + 1) + nb) * 8
 
 
-def band_max_half_bandwidth(nodes_per_graph: int) -> int:
-    """The largest hb the banded kernel serves at this bus count (0: the bus count itself is beyond the LDS)."""
-    if band_lds_bytes(nodes_per_graph, 0) > _lib.WLS_BAND_LDS_BYTES:
+def band_max_half_bandwidth(nodes_per_graph: int, bad_data: bool = False) -> int:
+    """The largest hb the banded kernel serves at this bus count (0: the bus count itself is beyond the LDS); ``bad_data``: the
+    bad-data form's, whose fixed block in LDS comes off the same cap."""
+    if band_lds_bytes(nodes_per_graph, 0, bad_data) > _lib.WLS_BAND_LDS_BYTES:
         return 0
-    spare = (_lib.WLS_BAND_LDS_BYTES - band_lds_bytes(nodes_per_graph, 0)) // (8 * _lib.WLS_BAND_BLOCK * _lib.WLS_BAND_BLOCK)
+    spare = (_lib.WLS_BAND_LDS_BYTES - band_lds_bytes(nodes_per_graph, 0, bad_data)) // (8 * _lib.WLS_BAND_BLOCK * _lib.WLS_BAND_BLOCK)
     return max(spare, 0) * _lib.WLS_BAND_BLOCK
 
 
@@ -531,18 +542,18 @@ def band_order(edge_index: torch.Tensor, nodes_per_graph: int, half_bandwidth: O
     return BandOrder(perm.int().to(dev), inverse.int().to(dev), relabelled, topo, hb, n, len(orderings))
 
 
-def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
-                        init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
-                        weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
-                        order: Optional[BandOrder] = None) -> WLSResult:
-    """``wls_estimate_large`` -- the same inputs, iteration, result and decisions -- without its cap of 256 buses, for grids whose gain
-    matrix is a band once the buses are numbered for it (radial feeders, sparse meshes): the blocked kernel on rows that keep a band of
-    G, csrc/dss2_wls_banded.hpp.  ``order``: ``band_order(edge_index, nodes_per_graph, num_nodes=N)`` of this structure; None computes it
-    here, which reads ``edge_index`` back.  With a given ``order`` nothing is read back and every launch is the library's (two or three
-    row gathers around the solve): recordable into a hipGraph or a launch plan.  The kernel solves the relabelled graph; ``x`` and
-    ``init`` rows go in and the state comes out in the caller's bus order, ``edge_attr`` is used as it is.  Equal-size graphs whose
-    topologies may differ.  NotImplementedError where (n, hb) needs more LDS than a workgroup has (``band_max_half_bandwidth(n)``).
-    Not served here: ``graph_ptr`` batches, the Huber form, bad-data detection (it needs the dense covariance)."""
+def _gather_f64(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """``gather_rows`` of an fp64 [N, k] tensor: its rows travel as 2 k fp32 words each, which the gather copies as they are."""
+    from .ops import gather_rows
+    return gather_rows(t.view(_F32), idx).view(torch.float64)
+
+
+def _banded(who, args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+            max_groups, order, check_params=None, bad_data=False):
+    """What the three banded functions share in front of their launch: the order (computed here if None, which reads ``edge_index``
+    back), ``_solve_block`` on the caller's tensors with the banded checks at their places, the gathered rows of ``x`` and ``init``, the
+    workspace and hb.  Fills ``args`` (a struct with a ``solve`` block, ``workspace`` and ``workspace_bytes``) and returns
+    (order, keep, out, N, E, G): ``keep`` is held until the launch has been issued, ``out`` is the WLSResult in the KERNEL's bus order."""
     from .ops import gather_rows
     if order is None:
         _require_gpu(x, edge_index, edge_attr)
@@ -550,16 +561,17 @@ def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     n, hb = int(nodes_per_graph), int(order.half_bandwidth)
 
     def check_own():
+        if check_params is not None:
+            check_params()
         if order.nodes_per_graph != n or order.perm.numel() != x.size(0) or order.edge_index.shape != edge_index.shape:
             raise ValueError(f"order was made for {order.perm.numel()} buses in graphs of {order.nodes_per_graph} and "
                              f"{order.edge_index.size(1)} edges, not for this batch")
 
     def refuse_size(n):
-        if band_lds_bytes(n, hb) > _lib.WLS_BAND_LDS_BYTES:
-            raise NotImplementedError(f"wls_estimate_banded keeps a band's panel and the state in LDS: at {n} buses per graph a "
-                                      f"half-bandwidth hb of at most {band_max_half_bandwidth(n)} states, got hb = {hb}")
+        if band_lds_bytes(n, hb, bad_data) > _lib.WLS_BAND_LDS_BYTES:
+            raise NotImplementedError(f"{who} keeps a band's panel and the state in LDS: at {n} buses per graph a "
+                                      f"half-bandwidth hb of at most {band_max_half_bandwidth(n, bad_data)} states, got hb = {hb}")
 
-    args = _lib.WlsLargeArgs()
     a = args.solve
     # (the checks run on the caller's tensors; the rows are gathered once they have passed)
     keep, res, N, E, G = _solve_block(a, x, order.edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n, init, max_iter, tol,
@@ -575,10 +587,106 @@ def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     if (dev, need) not in _WORKSPACES:
         _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     args.workspace, args.workspace_bytes, a.half_bandwidth = _WORKSPACES[(dev, need)].data_ptr(), need, hb
-    L = _lib.lib()
-    _lib.check(L.dss2_wls_solve_large(C.byref(args), _stream(x)), "dss2_wls_solve_large")
-    del keep, xp, ip             # (held until here: the launch has been issued)
+    return order, (keep, xp, ip), res, N, E, G
+
+
+def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                        init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                        weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
+                        order: Optional[BandOrder] = None) -> WLSResult:
+    """``wls_estimate_large`` -- the same inputs, iteration, result and decisions -- without its cap of 256 buses, for grids whose gain
+    matrix is a band once the buses are numbered for it (radial feeders, sparse meshes): the blocked kernel on rows that keep a band of
+    G, csrc/dss2_wls_banded.hpp.  ``order``: ``band_order(edge_index, nodes_per_graph, num_nodes=N)`` of this structure; None computes it
+    here, which reads ``edge_index`` back.  With a given ``order`` nothing is read back and every launch is the library's (two or three
+    row gathers around the solve): recordable into a hipGraph or a launch plan.  The kernel solves the relabelled graph; ``x`` and
+    ``init`` rows go in and the state comes out in the caller's bus order, ``edge_attr`` is used as it is.  Equal-size graphs whose
+    topologies may differ.  NotImplementedError where (n, hb) needs more LDS than a workgroup has (``band_max_half_bandwidth(n)``).
+    Not served here: ``graph_ptr`` batches.  The Huber form is ``wls_robust_banded``, bad-data detection ``wls_bad_data_banded`` (the
+    covariance is wanted between buses within two branches of each other only -- inside the band, where the selected inverse gives it)."""
+    from .ops import gather_rows
+    args = _lib.WlsLargeArgs()
+    order, keep, res, N, E, G = _banded("wls_estimate_banded", args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
+                                        nodes_per_graph, init, max_iter, tol, weights, max_groups, order)
+    _lib.check(_lib.lib().dss2_wls_solve_large(C.byref(args), _stream(x)), "dss2_wls_solve_large")
+    del keep                     # (held until here: the launch has been issued)
     return res._replace(state=gather_rows(res.state, order.inverse))
+
+
+def wls_robust_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                      init: Optional[torch.Tensor] = None, max_iter: int = 20, tol: float = 1e-6,
+                      weights: Sequence[float] = (1.0, 1.0, 1.0), gamma: float = 3.0, plain_iters: int = 1,
+                      max_groups: int = 0, order: Optional[BandOrder] = None) -> WLSRobustResult:
+    """``wls_robust`` -- the same weighting, iteration, result and decisions -- beyond 256 buses per graph: the banded kernel of
+    ``wls_estimate_banded`` with the Huber weighting on the row owners' walk (``gamma = inf`` gives ``wls_estimate_banded``'s five
+    outputs to the bit).  ``order``, the bus order of inputs and outputs (``bus_q`` comes back in the caller's; ``edge_q`` is per stored
+    edge), the cap on (n, hb) and the refusals are ``wls_estimate_banded``'s; with a given ``order`` nothing is read back."""
+    from .ops import gather_rows
+    gamma = float(gamma)
+    if not gamma > 0:
+        raise ValueError("gamma must be > 0")
+    if int(plain_iters) != plain_iters or plain_iters < 0:
+        raise ValueError("plain_iters must be an integer >= 0")
+    args = _lib.WlsRobustArgs()
+    order, keep, res, N, E, G = _banded("wls_robust_banded", args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
+                                        nodes_per_graph, init, max_iter, tol, weights, max_groups, order)
+    dev = x.device
+    res = WLSRobustResult(*res, bus_q=torch.empty(N, 4, dtype=torch.float64, device=dev),
+                          edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
+                          n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
+    args.gamma, args.plain_iters = gamma, int(plain_iters)
+    args.bus_q, args.edge_q, args.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
+    _lib.check(_lib.lib().dss2_wls_robust_large(C.byref(args), _stream(x)), "dss2_wls_robust_large")
+    del keep                     # (held until here: the launch has been issued)
+    return res._replace(state=gather_rows(res.state, order.inverse), bus_q=_gather_f64(res.bus_q, order.inverse))
+
+
+def wls_bad_data_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
+                        init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
+                        weights: Sequence[float] = (1.0, 1.0, 1.0), threshold: float = 3.0, max_removals: int = 0,
+                        confidence: float = 0.95, s_min: float = 1e-3, max_groups: int = 0,
+                        order: Optional[BandOrder] = None) -> WLSBadDataResult:
+    """``wls_bad_data_large`` -- the same rounds, result and decisions -- beyond 256 buses per graph, on the banded kernel of
+    ``wls_estimate_banded`` (its five outputs to the bit with ``max_removals = 0``).  The test reads the covariance at its diagonal and
+    between buses within two branches of each other: positions inside the band, which the selected inverse of the banded factor gives in
+    place (csrc/dss2_wls_banded_invert.hpp) -- no dense inverse.  ``order`` and the bus order of inputs and outputs are
+    ``wls_estimate_banded``'s: ``state``, ``bus_rn``, ``bus_sens`` and ``state_std`` come back in the caller's order, the edge outputs
+    are per stored edge, and ``removed`` holds the caller's ids.  The kernel compares ids as it numbers the buses: a TIE in rN goes to
+    the smallest relabelled id, not to the caller's smallest.  NotImplementedError above ``band_max_half_bandwidth(n, bad_data=True)``.
+    A graph with a non-zero outside the band of ``order``: status 2, 0 iterations, objective 0, its start as its state, dof 0, no removal,
+    per-measurement outputs 0.  With a given ``order`` nothing is read back and every launch is the library's: recordable."""
+    from .ops import gather_rows
+
+    def check_params():
+        if not threshold > 0:
+            raise ValueError("threshold must be > 0")
+        if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
+            raise ValueError("max_removals must be an integer in 0 .. 64")
+        if not 0 < confidence < 1:
+            raise ValueError("confidence must be in (0, 1)")
+        if not 0 < s_min < 1:
+            raise ValueError("s_min must be in (0, 1)")
+
+    b = _lib.WlsBadDataArgs()
+    order, keep, solved, N, E, G = _banded("wls_bad_data_banded", b, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
+                                           nodes_per_graph, init, max_iter, tol, weights, max_groups, order, check_params, bad_data=True)
+    dev, slots = x.device, max(int(max_removals), 1)
+    f64, i32 = torch.float64, torch.int32
+    new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
+    rows = lambda *shape: torch.zeros(*shape, dtype=f64, device=dev)      # (a graph outside its band writes no row)
+    res = WLSBadDataResult(
+        *solved,
+        dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
+        n_removed=new(G, dtype=i32), bus_rn=rows(N, 4), edge_rn=rows(E, 2), bus_sens=rows(N, 4), edge_sens=rows(E, 2), state_std=rows(N, 2))
+    (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
+     b.state_std) = (t.data_ptr() for t in res[5:])
+    b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
+    b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
+    b.bus_label = order.perm.data_ptr()                 # (the caller's row of the kernel's row k: for `removed` alone)
+    _lib.check(_lib.lib().dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
+    del keep                     # (held until here: the launch has been issued)
+    back = lambda t: _gather_f64(t, order.inverse)
+    return res._replace(state=gather_rows(res.state, order.inverse), bus_rn=back(res.bus_rn), bus_sens=back(res.bus_sens),
+                        state_std=back(res.state_std))
 
 
 def _public(impl):

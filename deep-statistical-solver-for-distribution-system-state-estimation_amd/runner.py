@@ -350,8 +350,9 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
     which may be None where every batch says its own -- as the bound on a graph's bus count: a data list may mix grids.  The kernel
     (LDS or blocked) is chosen by that bound.  One device-to-host copy.
     The keyword ``banded`` (taken out of ``solver_kw`` like ``robust``; default False): True -- the plain solve is ``estimator.wls_estimate_banded`` (no cap of 256 buses; equal-size graphs -- a ``graph_ptr`` that mixes bus counts is
-    refused --, and not with ``bad_data`` or ``robust``, which keep their own solves); "auto" -- only above ``estimator.max_nodes_per_graph_large()`` buses; False, the default --
-    never: above 256 buses the call is refused as before.  The banded solve orders each distinct edge list once (``estimator.band_order``
+    refused); "auto" -- only above ``estimator.max_nodes_per_graph_large()`` buses; False, the default --
+    never: above 256 buses the call is refused as before.  With ``bad_data`` or ``robust``, True and "auto" alike: up to 256 buses their dense
+    solves as without it, above 256 ``estimator.wls_bad_data_banded`` / ``estimator.wls_robust_banded`` (``bad_data['large']`` has nothing to choose there).  The banded solve orders each distinct edge list once (``estimator.band_order``
     reads it back: one more copy per structure) and keeps the order for the batches that share the tensor."""
     from . import estimator
     banded = solver_kw.pop("banded", False)
@@ -387,17 +388,27 @@ def evaluate_wls(loader, stats, nodes_per_graph: Optional[int] = None, model=Non
             bound = get("max_nodes") or nodes_per_graph
         if bound is None:
             raise ValueError("evaluate_wls: nodes_per_graph is None and the batch carries no graph_ptr with max_nodes")
-        if robust is not None:
-            res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **robust)
-            suspect, removed = zero, res.n_downweighted.sum()
-        elif bad_data is None and (banded is True or (banded == "auto" and bound > estimator.max_nodes_per_graph_large())):
+        beyond = bound > estimator.max_nodes_per_graph_large()
+        # (banded=True moves the PLAIN solve onto the band at every bus count; bad_data and robust keep their dense solves up to 256 buses)
+        if (banded is True and (beyond or (bad_data is None and robust is None))) or (banded == "auto" and beyond):
             # (a graph_ptr whose graphs all reach the bound describes equal-size graphs: known on the host from the two lengths)
             if graph_ptr is not None and x.size(0) != (graph_ptr.numel() - 1) * bound:
                 raise NotImplementedError("evaluate_wls: the banded solve serves equal-size graphs; this batch's graph_ptr mixes bus counts")
             if id(ei) not in orders:
                 orders[id(ei)] = (ei, estimator.band_order(ei, bound, num_nodes=x.size(0)))
-            res = estimator.wls_estimate_banded(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, order=orders[id(ei)][1], **solver_kw)
+            band_kw = dict(solver_kw, init=init, order=orders[id(ei)][1])
             suspect, removed = zero, zero
+            if robust is not None:
+                res = estimator.wls_robust_banded(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, **band_kw, **robust)
+                removed = res.n_downweighted.sum()
+            elif bad_data is not None:       # (`large` chooses between the two dense forms: nothing to choose here)
+                res = estimator.wls_bad_data_banded(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, **band_kw, **bad_data)
+                suspect, removed = res.suspect.sum(), res.n_removed.sum()
+            else:
+                res = estimator.wls_estimate_banded(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, **band_kw)
+        elif robust is not None:
+            res = estimator.wls_robust(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw, **robust)
+            suspect, removed = zero, res.n_downweighted.sum()
         elif bad_data is None:
             solve = estimator.wls_estimate if bound <= estimator.max_nodes_per_graph() else estimator.wls_estimate_large
             res = solve(x, ei, ea, stats[0], stats[1], stats[2], stats[3], bound, init=init, **kw)
@@ -455,7 +466,8 @@ def main(argv=None):
                     "estimator.wls_robust, the Huber M-estimator with threshold GAMMA (3.0 is the usual choice); any bus count up to 256; "
                     "not together with --wls-bad-data")
     ap.add_argument("--wls-banded", action="store_true", help="the --wls-baseline lines (implied) on grids above 256 buses per graph through "
-                    "estimator.wls_estimate_banded (the buses are ordered for a small bandwidth once per structure); up to 256 buses as without it")
+                    "estimator.wls_estimate_banded (the buses are ordered for a small bandwidth once per structure); up to 256 buses as without it.  "
+                    "Combines with --wls-bad-data and --wls-robust: above 256 buses through wls_bad_data_banded and wls_robust_banded")
     a = ap.parse_args(argv)
     if a.wls_robust is not None and a.wls_bad_data is not None:
         ap.error("--wls-robust and --wls-bad-data are exclusive")

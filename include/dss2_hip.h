@@ -768,13 +768,26 @@ size_t dss2_wls_solve_lds_bytes(int nodes_per_graph);
  *                            contents irrelevant before and after: G is inverted in place on its block rows, as in LDS, so the solve's
  *                            slice is all it needs.  rc 2 with a message, before any launch, for a misaligned or short workspace, n
  *                            above the cap, or what the other form refuses of the parameters.  Runs, batch positions and group
- *                            counts agree to the bit; the two forms agree to rounding (another summation order), not to the bit. */
+ *                            counts agree to the bit; the two forms agree to rounding (another summation order), not to the bit.
+ *        workspace != NULL and solve.half_bandwidth > 0
+ *                            the banded form (csrc/dss2_wls_banded.hpp, dss2_wls_solve_large's banded form below): the same rounds on
+ *                            rows that keep a band of G, beyond 256 buses.  Sigma is wanted only at the diagonal and between buses
+ *                            within two branches of each other -- inside the band -- and the entries of G^-1 inside the band of a
+ *                            banded Cholesky factor follow from L by the selected-inverse recurrence, block column by block column
+ *                            from the last, in place (csrc/dss2_wls_banded_invert.hpp).  Workspace as for the banded solve; LDS is the
+ *                            banded solve's plus the fixed block (320 bytes), which is the cap on (n, hb).  Equal-size graphs only
+ *                            (graph_ptr: rc 2).  A graph with a non-zero outside the declared band: status 2, 0 iterations, objective
+ *                            0, its start as its state, dof 0, no removal, its per-measurement rows and its slice not written.
+ *                            The kernel works on the graph as it is numbered here; bus_label, if given, translates a removed BUS
+ *                            measurement's id for `removed` alone: 4 bus_label[id / 4] + id % 4 (branch ids are the stored order's
+ *                            either way).  The arg-max and its ties (the smallest id) go by the ids as numbered here.  */
 typedef struct dss2_wls_bad_data_args {
   dss2_wls_solve_args solve;
   double threshold;                               /* > 0: the largest normalized residual is removed above it                     */
   double z_p;                                     /* the standard normal quantile of the test's confidence                        */
   double s_min;                                   /* in (0, 1): sensitivities below it give rN = 0                                */
   int32_t max_removals; int32_t pad_;             /* 0 .. 64                                                                      */
+  const int32_t* bus_label;                       /* [N] or NULL; the banded form only: the caller's row of the kernel's row k    */
   int32_t* dof;                                   /* [G]                                                                          */
   double* chi2_limit;                             /* [G]                                                                          */
   int32_t* suspect;                               /* [G]     J > chi2_limit                                                       */
@@ -812,6 +825,7 @@ size_t dss2_wls_bad_data_lds_bytes(int nodes_per_graph);
 #define DSS2_WLS_BAND_BLOCK 16           /* states of a block row and of a block column */
 #define DSS2_WLS_BAND_GROUPS 512         /* workgroups at most */
 #define DSS2_WLS_BAND_LDS_BYTES 163840   /* the LDS of a workgroup */
+#define DSS2_WLS_BAND_BAD_DATA_BYTES 320 /* what dss2_wls_bad_data's banded form keeps in LDS behind the banded solve's */
 typedef struct dss2_wls_large_args {
   dss2_wls_solve_args solve;                      /* as for dss2_wls_solve                                                        */
   void* workspace; uint64_t workspace_bytes;
@@ -834,6 +848,8 @@ size_t dss2_wls_large_lds_bytes(int nodes_per_graph);
  *      gamma and 2 gamma t - gamma^2 above, split into bus part and branch part; q per measurement; the count of q < 1 per graph.
  *      dss2_wls_robust keeps the gain matrix in LDS (dss2_wls_solve's size limit; workspace unused); dss2_wls_robust_large is the
  *      blocked form with dss2_wls_solve_large's workspace (dss2_wls_large_workspace_bytes, dss2_wls_large_groups) and size limit.
+ *      dss2_wls_robust_large with solve.half_bandwidth > 0 is the banded form of dss2_wls_solve_large with this weighting (same
+ *      workspace, LDS, cap and refusals; the per-bus counts of q < 1 pass through the first n ints of the workgroup's slice).
  *      No atomics, fixed summation orders.  rc 2 with a message for what the plain entries refuse, gamma not > 0 (a NaN included),
  *      plain_iters < 0, a null output. */
 typedef struct dss2_wls_robust_args {

@@ -5,7 +5,8 @@ The protocol of tools/wls_large_probe.py -- median of --runs calls after --warmu
 tol = 0 so that every graph runs all eight iterations; the ordering is made once, before the clock.  Where the dense blocked form serves
 the grid too (up to 256 buses) it is timed in the same run, the two arms taking turns call by call.  Default cases: ober179 and radial256
 (synthetic.register_radial(256): a feeder at the dense form's cap, in place of the tests' 256-bus `cap` graph, which is a fixture and no
-grid that make_batch draws samples of) at B = 1024 against the dense form; radial300 and radial1000 at
+grid that make_batch draws samples of) at B = 1024 against the dense form (and wls_bad_data_large against wls_bad_data_banded); beside the
+plain banded solve, in the same turns: wls_bad_data_banded with max_removals = 0 and wls_robust_banded at gamma = 3; radial300 and radial1000 at
 B = 256, banded alone.  A case is grid:graphs[:seed] (seed 1 unless given; radial300 runs with seed 2: at B = 256 the batches of seeds 0
 and 1 hold one injection weight near 4e6 times the typical one, the fp32 normalisation of x then rounds the small weights away, and every
 graph's gain matrix is singular at the flat start -- in the fp64 oracle as in the kernel, status 2 and no iteration).  Per case: hb, the
@@ -74,16 +75,25 @@ def main():
         line = {"case": grid, "graphs": B, "seed": seed, "buses_per_graph": n, "max_iter": 8, "device": torch.cuda.get_device_name(0), "runs": a.runs,
                 "warmup": a.warmup, "half_bandwidth": hb, "block_columns_kept": est.band_blocks(hb) + 1, "orderings": order.n_orderings,
                 "workspace_bytes": est.band_workspace_bytes(n, hb, est.band_groups(B)), "lds_bytes": est.band_lds_bytes(n, hb)}
-        arms = [lambda: run(est.wls_estimate_banded, order=order)]
+        # the plain banded solve, then the two answers to gross errors on the band: bad-data detection without a removal (one solve, one
+        # more factorisation, the selected inverse, the measurement pass) and the Huber form (gamma = 3, the same eight iterations)
+        arms = [lambda: run(est.wls_estimate_banded, order=order), lambda: run(est.wls_bad_data_banded, order=order, max_removals=0),
+                lambda: run(est.wls_robust_banded, order=order, gamma=3.0)]
         dense = n <= est.max_nodes_per_graph_large()
         if dense:
-            arms.append(lambda: run(est.wls_estimate_large))
+            arms += [lambda: run(est.wls_estimate_large), lambda: run(est.wls_bad_data_large, max_removals=0)]
             line["dense_workspace_bytes"] = int(pkg._lib.lib().dss2_wls_large_workspace_bytes(n, min(B, 512)))
         t = timed_in_turns(arms, a.warmup, a.runs)
         line["banded_solve_ms"] = ms(t[0])
+        line["banded_bad_data_ms"], line["banded_robust_ms"] = ms(t[1]), ms(t[2])
+        line["bad_data_over_banded_solve"], line["robust_over_banded_solve"] = t[1][0] / t[0][0], t[2][0] / t[0][0]
+        line["lds_bytes_bad_data"] = est.band_lds_bytes(n, hb, bad_data=True)
         if dense:
-            line["dense_solve_ms"] = ms(t[1])
-            line["dense_over_banded"] = t[1][0] / t[0][0]
+            line["dense_solve_ms"] = ms(t[3])
+            line["dense_over_banded"] = t[3][0] / t[0][0]
+            line["dense_bad_data_ms"] = ms(t[4])
+            line["dense_bad_data_over_dense_solve"] = t[4][0] / t[3][0]
+            line["dense_bad_data_over_banded_bad_data"] = t[4][0] / t[1][0]
         k = min(B, a.check_graphs)
         sub = dict(b, x=b["x"][:k * n], edge_attr=b["edge_attr"][:k * e_of(b, B)], edge_index=b["edge_index"][:, :k * e_of(b, B)])
         cpu = TorchWLS(sub, n, torch.device("cpu")).solve(8)
