@@ -1,8 +1,8 @@
 // What a bad-data kernel needs beyond the solve and the inversion, apart from where the covariance lives: the measurement pass, the arg-max
-// over the wave and the workgroup, the removal decision, the chi-square outputs and the entry's parameter checks.  Both kernels of
-// csrc/dss2_wls_bad_data.hip use it: how Sigma[p, q] is addressed is a template parameter -- a callable Sg(p, q) that accepts the two
-// indices in either order -- BdPacked here (Sigma in place of the packed gain matrix in LDS) and BdBlockRows there (Sigma on
-// csrc/dss2_wls_large.hip's block rows in global memory).
+// over the wave and the workgroup, the removal decision, the chi-square outputs and the entry's parameter checks.  The round body of
+// csrc/dss2_wls_bad_data.hip (bd_round, which all three kernels run) calls them: how Sigma[p, q] is addressed is a template parameter --
+// a callable Sg(p, q) that accepts the two indices in either order -- BdPacked here (Sigma in place of the packed gain matrix in LDS),
+// BdBlockRows and BdBandRows there (Sigma on block rows and on band rows in global memory).
 #pragma once
 #include "dss2_wls_core.hpp"
 

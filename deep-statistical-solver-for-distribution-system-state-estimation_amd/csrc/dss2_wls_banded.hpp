@@ -110,8 +110,9 @@ __global__ void __launch_bounds__(WL_T) wls_banded_kernel(const Args b) {
   }
 }
 
-// ---- host side: the banded forms' own checks (after ws_check_batch) and their launch.  extra_lds: what a kernel keeps behind the
-// banded carve (the bad-data form's fixed block); it counts against the cap on (n, hb).
+// ---- host side: the banded forms' own checks (after ws_check_batch) and their launch, then the one route (wb_route) by which the
+// three entries that serve both the blocked and the banded form reach either.  extra_lds: what a kernel keeps behind the carve (the
+// bad-data form's fixed block); on the band it counts against the cap on (n, hb).
 inline int64_t wb_grid(const dss2_wls_solve_args& a) {
   const int64_t n_graphs = a.n_nodes / a.nodes_per_graph;
   int64_t grid = WB_GROUPS;
@@ -146,6 +147,25 @@ inline int wb_launch(const Args& b, const char* who, hipStream_t s, size_t extra
   launch_vminmax(a.x + 8, a.ldx, a.n_nodes, a.vminmax, s);
   hipLaunchKernelGGL(K, dim3((unsigned)wb_grid(a)), dim3(WL_T), wb_lds_bytes(a.nodes_per_graph, wb_blocks(a.half_bandwidth)) + extra_lds, s, b);
   return check_launch(who);
+}
+
+// The route of an entry that serves both forms on rows: half_bandwidth != 0 selects the banded one.  The form's own checks -- the batch,
+// then the size and the workspace -- then the entry's parameter check (Check(b, who), or none), then the form's launch of its kernel.
+// `who` names the entry and the form in every message; extra_lds as for wb_check and the launches.
+template <auto Blocked, auto Banded, auto Check = nullptr, class Args>
+inline int wb_route(const Args& b, const char* who_blocked, const char* who_banded, hipStream_t s, size_t extra_lds = 0) {
+  const bool banded = b.solve.half_bandwidth != 0;
+  const char* who = banded ? who_banded : who_blocked;
+  if (banded) {
+    if (int rc = ws_check_batch(b.solve, who)) return rc;
+    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, who, extra_lds)) return rc;
+  } else {
+    if (int rc = wl_check_size(b.solve, who)) return rc;             // (ws_check_batch is its first step)
+    if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, who)) return rc;
+  }
+  if constexpr (!std::is_null_pointer_v<decltype(Check)>)
+    if (int rc = Check(b, who)) return rc;
+  return banded ? wb_launch<Banded>(b, who, s, extra_lds) : wl_launch<Blocked>(b, who, s, extra_lds);
 }
 
 }  // namespace dss2

@@ -32,7 +32,8 @@
 // written before they are read; what is read from Pt beyond row ns only reaches tile entries that are not stored).
 // The kernel body (wls_blocked_kernel), its device functions and the launch path live in dss2_wls_large_core.hpp, which
 // csrc/dss2_wls_robust.hip shares; this file instantiates the plain estimator, and its banded form (half_bandwidth > 0: the same steps on
-// rows that keep a band of G, for graphs beyond the cap above; dss2_wls_banded.hpp), which enters through the same function.
+// rows that keep a band of G, for graphs beyond the cap above; dss2_wls_banded.hpp), which enters through the same function: wb_route
+// there is the route of every entry that serves both forms.
 #include "dss2_wls_banded.hpp"
 
 using namespace dss2;
@@ -48,15 +49,8 @@ extern "C" int64_t dss2_wls_large_groups(const dss2_wls_solve_args* ap) {
 }
 
 static int wls_solve_large_launch(const dss2_wls_large_args* bp, void* stream) {
-  const dss2_wls_large_args& b = *bp;
-  if (b.solve.half_bandwidth != 0) {
-    if (int rc = ws_check_batch(b.solve, "wls_solve_large (banded)")) return rc;
-    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large (banded)")) return rc;
-    return wb_launch<wls_banded_kernel<dss2_wls_large_args>>(b, "wls_solve_large (banded)", as_stream(stream));
-  }
-  if (int rc = wl_check_size(b.solve, "wls_solve_large")) return rc;
-  if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_solve_large")) return rc;
-  return wl_launch<wls_blocked_kernel<dss2_wls_large_args>>(b, "wls_solve_large", as_stream(stream));
+  using B = dss2_wls_large_args;
+  return wb_route<wls_blocked_kernel<B>, wls_banded_kernel<B>>(*bp, "wls_solve_large", "wls_solve_large (banded)", as_stream(stream));
 }
 extern "C" int dss2_wls_solve_large(const dss2_wls_large_args* bp, void* stream) {
   return dss2::entry(wls_solve_large_launch, stream, dss2::copied(bp, "dss2_wls_solve_large"));

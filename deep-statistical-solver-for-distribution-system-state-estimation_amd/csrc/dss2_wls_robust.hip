@@ -15,6 +15,7 @@
 //   wls_blocked_kernel<.>         the gain matrix in a workspace in global memory, blocked Cholesky (dss2_wls_large_core.hpp), up to 256
 //   wls_banded_kernel<.>          the same on rows that keep a band of G (dss2_wls_banded.hpp; half_bandwidth > 0), beyond 256 buses; it
 //                                 enters through dss2_wls_robust_large as the plain banded solve enters through dss2_wls_solve_large
+//                                 (wb_route in dss2_wls_banded.hpp, with wr_check_params as the entry's own check)
 //
 // After the last iterate, with weighting on: the objective pass (a bus owns its four measurements and the two flows of every branch it
 // is the from-end of) writes every q, replaces the term of a measurement with q < 1 by rho's tail 2 gamma t - gamma^2, and counts the
@@ -46,18 +47,8 @@ static int wls_robust_launch(const dss2_wls_robust_args* bp, void* stream) {
 extern "C" int dss2_wls_robust(const dss2_wls_robust_args* bp, void* stream) { return dss2::entry(wls_robust_launch, stream, dss2::copied(bp, "dss2_wls_robust")); }
 
 static int wls_robust_large_launch(const dss2_wls_robust_args* bp, void* stream) {
-  const dss2_wls_robust_args& b = *bp;
-  if (b.solve.half_bandwidth != 0) {     // the banded form, as dss2_wls_solve_large routes it
-    const char* who = "wls_robust_large (banded)";
-    if (int rc = ws_check_batch(b.solve, who)) return rc;
-    if (int rc = wb_check(b.solve, b.workspace, b.workspace_bytes, who)) return rc;
-    if (int rc = wr_check_params(b, who)) return rc;
-    return wb_launch<wls_banded_kernel<dss2_wls_robust_args>>(b, who, as_stream(stream));
-  }
-  if (int rc = wl_check_size(b.solve, "wls_robust_large")) return rc;
-  if (int rc = wl_check_workspace(b.solve, b.workspace, b.workspace_bytes, "wls_robust_large")) return rc;
-  if (int rc = wr_check_params(b, "wls_robust_large")) return rc;
-  return wl_launch<wls_blocked_kernel<dss2_wls_robust_args>>(b, "wls_robust_large", as_stream(stream));
+  using B = dss2_wls_robust_args;
+  return wb_route<wls_blocked_kernel<B>, wls_banded_kernel<B>, wr_check_params>(*bp, "wls_robust_large", "wls_robust_large (banded)", as_stream(stream));
 }
 extern "C" int dss2_wls_robust_large(const dss2_wls_robust_args* bp, void* stream) {
   return dss2::entry(wls_robust_large_launch, stream, dss2::copied(bp, "dss2_wls_robust_large"));

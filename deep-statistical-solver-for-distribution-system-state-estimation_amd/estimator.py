@@ -124,8 +124,8 @@ def _wls_estimate(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
     ``tol = 0`` never stops early.  ``max_groups`` > 0 caps the number of workgroups (they stride over the graphs).
     ``graph_ptr`` [G + 1] (int64, device): the batch mixes bus counts, graph g owns rows [graph_ptr[g], graph_ptr[g + 1]) and
     ``nodes_per_graph`` is an upper bound on a graph's bus count (the module docstring: the bound, the ids, V_lv)."""
-    return _estimate(False, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups, graph_ptr=graph_ptr)
+    return _solve(None, _LDS, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                  max_groups, graph_ptr=graph_ptr)
 
 
 def max_nodes_per_graph_large() -> int:
@@ -145,8 +145,8 @@ def _wls_estimate_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     buses, small ones included: the gain matrix lives in a workspace in global memory (one slice per workgroup, allocated once per
     device and size) and is factorised in blocks, csrc/dss2_wls_large.hip.  Still one launch per solve, recordable.
     ``graph_ptr`` as for ``wls_estimate``: with it ``nodes_per_graph`` is an upper bound, and the workspace is sized by the bound."""
-    return _estimate(True, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups, graph_ptr=graph_ptr)
+    return _solve(None, _BLOCKED, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                  max_groups, graph_ptr=graph_ptr)
 
 
 def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
@@ -210,41 +210,145 @@ def _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std
     return (x2, ea2, stats, kept_init, vmm), out, N, E, G
 
 
-def _estimate(large, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-              max_groups, robust=None, graph_ptr=None):
-    """The plain solve (``robust`` None -> WLSResult) or the Huber one (``robust`` = (gamma, plain_iters) -> WLSRobustResult) on the LDS
-    kernel or on the blocked one (``large``)."""
-    who = ("wls_estimate_large" if large else "wls_estimate") if robust is None else f"wls_robust (large={large})"
+class _Huber(NamedTuple):        # the kinds of a solve beside the plain one (None), as the caller passed them: _solve checks them
+    gamma: float
+    plain_iters: int
+
+
+class _BadData(NamedTuple):
+    threshold: float
+    max_removals: int
+    confidence: float
+    s_min: float
+
+
+_LDS, _BLOCKED, _BANDED = "lds", "blocked", "banded"   # the storage forms
+_PUBLIC_SUFFIX = {_LDS: "", _BLOCKED: "_large", _BANDED: "_banded"}     # of the public functions that run on a form (for messages)
+_ENTRY_SUFFIX = {_LDS: "", _BLOCKED: "_large", _BANDED: "_large"}       # of the C entries of the solve and the Huber solve (the banded form enters through the blocked one's)
+
+
+def _workspace(dev, need):
+    """(address, bytes) of the kept workspace of ``need`` bytes on ``dev``."""
+    if (dev, need) not in _WORKSPACES:
+        _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    return _WORKSPACES[(dev, need)].data_ptr(), need
+
+
+def _robust_outputs(args, solved, N, E, G, dev, ones):
+    """The WLSRobustResult around ``solved`` that ``args`` writes.  ``ones``: a graph may write no row (``graph_ptr``)."""
+    f64 = torch.float64
+    res = WLSRobustResult(*solved, bus_q=(torch.ones if ones else torch.empty)(N, 4, dtype=f64, device=dev),
+                          edge_q=torch.ones(E, 2, dtype=f64, device=dev),        # (an edge that leaves its graph is never written)
+                          n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
+    args.bus_q, args.edge_q, args.n_downweighted = (t.data_ptr() for t in res[5:])
+    return res
+
+
+def _bad_data_outputs(args, solved, N, E, G, dev, slots, zeros):
+    """The WLSBadDataResult around ``solved`` that ``args`` writes.  ``zeros``: a graph may write no row (a refused one under
+    ``graph_ptr``, one outside its band)."""
+    f64, i32 = torch.float64, torch.int32
+    new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
+    rows = (lambda *shape: torch.zeros(*shape, dtype=f64, device=dev)) if zeros else new
+    res = WLSBadDataResult(
+        *solved,
+        dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
+        n_removed=new(G, dtype=i32), bus_rn=rows(N, 4),
+        edge_rn=torch.zeros(E, 2, dtype=f64, device=dev),       # (an edge that leaves its graph is never written)
+        bus_sens=rows(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=rows(N, 2))
+    (args.dof, args.chi2_limit, args.suspect, args.removed, args.removed_rn, args.n_removed, args.bus_rn, args.edge_rn, args.bus_sens,
+     args.edge_sens, args.state_std) = (t.data_ptr() for t in res[5:])
+    return res
+
+
+def _solve(kind, storage, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+           max_groups, graph_ptr=None, order=None):
+    """The one road from the public functions to the library.  ``kind``: None (the plain solve -> WLSResult), a ``_Huber``
+    (-> WLSRobustResult) or a ``_BadData`` (-> WLSBadDataResult).  ``storage``: ``_LDS`` (the gain matrix packed in LDS), ``_BLOCKED``
+    (block rows in a workspace) or ``_BANDED`` (band rows in a workspace, on the graph relabelled by ``order``; None computes it here,
+    which reads ``edge_index`` back); None lets the Huber solve choose between the first two by the bus count."""
+    from .ops import gather_rows
+    huber, bad = isinstance(kind, _Huber), isinstance(kind, _BadData)
+    if huber:                    # (refused before anything else is looked at)
+        kind = _Huber(float(kind.gamma), kind.plain_iters)
+        if not kind.gamma > 0:
+            raise ValueError("gamma must be > 0")
+        if int(kind.plain_iters) != kind.plain_iters or kind.plain_iters < 0:
+            raise ValueError("plain_iters must be an integer >= 0")
+        if storage is None:
+            storage = _BLOCKED if int(nodes_per_graph) > max_nodes_per_graph() else _LDS
+    banded = storage == _BANDED
+    who = f"wls_robust (large={storage == _BLOCKED})" if huber and not banded else \
+        ("wls_robust" if huber else "wls_bad_data" if bad else "wls_estimate") + _PUBLIC_SUFFIX[storage]
+    hb = 0
+    if banded:
+        if order is None:
+            _require_gpu(x, edge_index, edge_attr)
+            order = band_order(edge_index, nodes_per_graph, num_nodes=x.size(0))
+        nodes_per_graph, hb = int(nodes_per_graph), int(order.half_bandwidth)
+
+    def check_own():
+        if bad:
+            if not kind.threshold > 0:
+                raise ValueError("threshold must be > 0")
+            if int(kind.max_removals) != kind.max_removals or not 0 <= kind.max_removals <= 64:
+                raise ValueError("max_removals must be an integer in 0 .. 64")
+            if not 0 < kind.confidence < 1:
+                raise ValueError("confidence must be in (0, 1)")
+            if not 0 < kind.s_min < 1:
+                raise ValueError("s_min must be in (0, 1)")
+        if banded and (order.nodes_per_graph != nodes_per_graph or order.perm.numel() != x.size(0) or order.edge_index.shape != edge_index.shape):
+            raise ValueError(f"order was made for {order.perm.numel()} buses in graphs of {order.nodes_per_graph} and "
+                             f"{order.edge_index.size(1)} edges, not for this batch")
 
     def refuse_size(n):
-        if large and n > max_nodes_per_graph_large():
-            raise NotImplementedError(f"{who} keeps a block column's panel of the gain matrix in LDS: at most "
-                                      f"{max_nodes_per_graph_large()} buses per graph, got {n}")
-        if not large and n > max_nodes_per_graph():
-            raise NotImplementedError(f"{who} keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, "
-                                      f"got {n}")
+        if banded:
+            if band_lds_bytes(n, hb, bad) > _lib.WLS_BAND_LDS_BYTES:
+                raise NotImplementedError(f"{who} keeps a band's panel and the state in LDS: at {n} buses per graph a "
+                                          f"half-bandwidth hb of at most {band_max_half_bandwidth(n, bad)} states, got hb = {hb}")
+        elif storage == _BLOCKED:
+            if n > max_nodes_per_graph_large():
+                raise NotImplementedError(f"{who} keeps a block column's panel of the gain matrix in LDS: at most "
+                                          f"{max_nodes_per_graph_large()} buses per graph, got {n}")
+        elif (_lib.lib().dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP) if bad else n > max_nodes_per_graph():
+            raise NotImplementedError(f"{who} keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
 
     # the one place that picks the struct: plain LDS -> the solve block itself; every other form carries it as .solve
-    args = _lib.WlsRobustArgs() if robust is not None else _lib.WlsLargeArgs() if large else _lib.WlsSolveArgs()
+    args = _lib.WlsBadDataArgs() if bad else _lib.WlsRobustArgs() if huber else _lib.WlsSolveArgs() if storage == _LDS else _lib.WlsLargeArgs()
     a = getattr(args, "solve", args)
-    keep, res, N, E, G = _solve_block(a, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter,
-                                      tol, weights, max_groups, refuse_size, graph_ptr=graph_ptr)
+    # (on the band too the checks run on the caller's tensors; the rows are gathered once they have passed)
+    keep, res, N, E, G = _solve_block(a, x, order.edge_index if banded else edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
+                                      nodes_per_graph, init, max_iter, tol, weights, max_groups, refuse_size, check_own, graph_ptr=graph_ptr)
     n, dev = a.nodes_per_graph, x.device
     L = _lib.lib()
-    if robust is not None:
-        res = WLSRobustResult(*res, bus_q=(torch.empty if graph_ptr is None else torch.ones)(N, 4, dtype=torch.float64, device=dev),
-                              edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
-                              n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
-        args.gamma, args.plain_iters = robust
-        args.bus_q, args.edge_q, args.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
-    if large:
-        need = int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a))))
-        if (dev, need) not in _WORKSPACES:
-            _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        args.workspace, args.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
-    name = ("dss2_wls_robust" if robust is not None else "dss2_wls_solve") + ("_large" if large else "")
+    if banded:
+        xp = gather_rows(x, order.perm)
+        a.x, a.ldx, a.half_bandwidth = xp.data_ptr(), xp.stride(0), hb
+        ip = None
+        if init is not None:
+            ip = gather_rows(init.detach(), order.perm)
+            a.init, a.ld_init = ip.data_ptr(), ip.stride(0)
+        keep = (keep, xp, ip)
+        args.workspace, args.workspace_bytes = _workspace(dev, band_workspace_bytes(n, hb, band_groups(G, max_groups)))
+    elif storage == _BLOCKED:    # (kept by (device, bytes): a recorded launch replays with its address; in the bad-data struct a non-null workspace selects the forms on rows)
+        args.workspace, args.workspace_bytes = _workspace(dev, int(L.dss2_wls_large_workspace_bytes(n, L.dss2_wls_large_groups(C.byref(a)))))
+    per_bus = ()                 # the outputs per bus beside the state: on the band they come back in the kernel's order
+    if huber:
+        res = _robust_outputs(args, res, N, E, G, dev, ones=graph_ptr is not None)
+        args.gamma, args.plain_iters = kind.gamma, int(kind.plain_iters)
+        per_bus = ("bus_q",)
+    elif bad:
+        res = _bad_data_outputs(args, res, N, E, G, dev, max(int(kind.max_removals), 1), zeros=banded or graph_ptr is not None)
+        args.threshold, args.max_removals, args.s_min = float(kind.threshold), int(kind.max_removals), float(kind.s_min)
+        args.z_p = float(torch.special.ndtri(torch.tensor(float(kind.confidence), dtype=torch.float64)))   # (a host scalar from a Python float: no read-back)
+        if banded:
+            args.bus_label = order.perm.data_ptr()          # (the caller's row of the kernel's row k: for `removed` alone)
+        per_bus = ("bus_rn", "bus_sens", "state_std")
+    name = "dss2_wls_bad_data" if bad else ("dss2_wls_robust" if huber else "dss2_wls_solve") + _ENTRY_SUFFIX[storage]
     _lib.check(getattr(L, name)(C.byref(args), _stream(x)), name)
     del keep                     # (held until here: the launch has been issued)
+    if banded:
+        res = res._replace(state=gather_rows(res.state, order.inverse), **{f: _gather_f64(getattr(res, f), order.inverse) for f in per_bus})
     return res
 
 
@@ -273,15 +377,8 @@ def _wls_robust(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, no
     ``max_nodes_per_graph_large()``); True / False force one.  gamma = 3 is the default for a reason: at 1.5, on ober179 (condition
     number 2.4e13), three to four measurements per graph are down-weighted and the state is worse than plain WLS.
     ``graph_ptr`` as for ``wls_estimate``: ``nodes_per_graph`` is then an upper bound, and ``large`` None routes by the bound."""
-    gamma = float(gamma)
-    if not gamma > 0:
-        raise ValueError("gamma must be > 0")
-    if int(plain_iters) != plain_iters or plain_iters < 0:
-        raise ValueError("plain_iters must be an integer >= 0")
-    if large is None:
-        large = int(nodes_per_graph) > max_nodes_per_graph()
-    return _estimate(bool(large), x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-                     max_groups, robust=(gamma, int(plain_iters)), graph_ptr=graph_ptr)
+    return _solve(_Huber(gamma, plain_iters), None if large is None else _BLOCKED if large else _LDS, x, edge_index, edge_attr, x_mean, x_std,
+                  edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, max_groups, graph_ptr=graph_ptr)
 
 
 class WLSBadDataResult(NamedTuple):
@@ -317,49 +414,8 @@ def _wls_bad_data(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, 
     ``graph_ptr`` as for ``wls_estimate``: ``nodes_per_graph`` is then an upper bound (a bound above 99 is refused as 100 buses are),
     and the ids -- ``removed`` among them -- stay the global ones above.
     ``large`` (``wls_bad_data_large``): the blocked form, up to ``max_nodes_per_graph_large()`` buses, with ``wls_estimate_large``'s workspace."""
-    def check_own():
-        if not threshold > 0:
-            raise ValueError("threshold must be > 0")
-        if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
-            raise ValueError("max_removals must be an integer in 0 .. 64")
-        if not 0 < confidence < 1:
-            raise ValueError("confidence must be in (0, 1)")
-        if not 0 < s_min < 1:
-            raise ValueError("s_min must be in (0, 1)")
-
-    def refuse_size(n):
-        if large and n > max_nodes_per_graph_large():
-            raise NotImplementedError(f"wls_bad_data_large keeps a block column's panel of the gain matrix in LDS: at most "
-                                      f"{max_nodes_per_graph_large()} buses per graph, got {n}")
-        if not large and _lib.lib().dss2_wls_bad_data_lds_bytes(n) > _LDS_CAP:
-            raise NotImplementedError(f"wls_bad_data keeps a graph's gain matrix in LDS: at most {max_nodes_per_graph()} buses per graph, got {n}")
-
-    b = _lib.WlsBadDataArgs()
-    keep, solved, N, E, G = _solve_block(b.solve, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init,
-                                         max_iter, tol, weights, max_groups, refuse_size, check_own, graph_ptr=graph_ptr)
-    dev, slots = x.device, max(int(max_removals), 1)
-    f64, i32 = torch.float64, torch.int32
-    new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
-    rows = new if graph_ptr is None else lambda *shape: torch.zeros(*shape, dtype=f64, device=dev)   # (a refused graph writes no row)
-    res = WLSBadDataResult(
-        *solved,
-        dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
-        n_removed=new(G, dtype=i32), bus_rn=rows(N, 4),
-        edge_rn=torch.zeros(E, 2, dtype=f64, device=dev),       # (an edge that leaves its graph is never written)
-        bus_sens=rows(N, 4), edge_sens=torch.zeros(E, 2, dtype=f64, device=dev), state_std=rows(N, 2))
-    (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
-     b.state_std) = (t.data_ptr() for t in res[5:])
-    b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
-    b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
-    L = _lib.lib()
-    if large:                    # (a non-null workspace selects the blocked form; kept by (device, bytes) like wls_estimate_large's: a recorded launch replays with its address)
-        need = int(L.dss2_wls_large_workspace_bytes(b.solve.nodes_per_graph, L.dss2_wls_large_groups(C.byref(b.solve))))
-        if (dev, need) not in _WORKSPACES:
-            _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        b.workspace, b.workspace_bytes = _WORKSPACES[(dev, need)].data_ptr(), need
-    _lib.check(L.dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
-    del keep                     # (held until here: the launch has been issued)
-    return res
+    return _solve(_BadData(threshold, max_removals, confidence, s_min), _BLOCKED if large else _LDS, x, edge_index, edge_attr, x_mean, x_std,
+                  edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights, max_groups, graph_ptr=graph_ptr)
 
 
 def _wls_bad_data_large(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
@@ -548,48 +604,6 @@ def _gather_f64(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return gather_rows(t.view(_F32), idx).view(torch.float64)
 
 
-def _banded(who, args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
-            max_groups, order, check_params=None, bad_data=False):
-    """What the three banded functions share in front of their launch: the order (computed here if None, which reads ``edge_index``
-    back), ``_solve_block`` on the caller's tensors with the banded checks at their places, the gathered rows of ``x`` and ``init``, the
-    workspace and hb.  Fills ``args`` (a struct with a ``solve`` block, ``workspace`` and ``workspace_bytes``) and returns
-    (order, keep, out, N, E, G): ``keep`` is held until the launch has been issued, ``out`` is the WLSResult in the KERNEL's bus order."""
-    from .ops import gather_rows
-    if order is None:
-        _require_gpu(x, edge_index, edge_attr)
-        order = band_order(edge_index, nodes_per_graph, num_nodes=x.size(0))
-    n, hb = int(nodes_per_graph), int(order.half_bandwidth)
-
-    def check_own():
-        if check_params is not None:
-            check_params()
-        if order.nodes_per_graph != n or order.perm.numel() != x.size(0) or order.edge_index.shape != edge_index.shape:
-            raise ValueError(f"order was made for {order.perm.numel()} buses in graphs of {order.nodes_per_graph} and "
-                             f"{order.edge_index.size(1)} edges, not for this batch")
-
-    def refuse_size(n):
-        if band_lds_bytes(n, hb, bad_data) > _lib.WLS_BAND_LDS_BYTES:
-            raise NotImplementedError(f"{who} keeps a band's panel and the state in LDS: at {n} buses per graph a "
-                                      f"half-bandwidth hb of at most {band_max_half_bandwidth(n, bad_data)} states, got hb = {hb}")
-
-    a = args.solve
-    # (the checks run on the caller's tensors; the rows are gathered once they have passed)
-    keep, res, N, E, G = _solve_block(a, x, order.edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, n, init, max_iter, tol,
-                                      weights, max_groups, refuse_size, check_own)
-    dev = x.device
-    xp = gather_rows(x, order.perm)
-    a.x, a.ldx = xp.data_ptr(), xp.stride(0)
-    ip = None
-    if init is not None:
-        ip = gather_rows(init.detach(), order.perm)
-        a.init, a.ld_init = ip.data_ptr(), ip.stride(0)
-    need = band_workspace_bytes(n, hb, band_groups(G, max_groups))
-    if (dev, need) not in _WORKSPACES:
-        _WORKSPACES[(dev, need)] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    args.workspace, args.workspace_bytes, a.half_bandwidth = _WORKSPACES[(dev, need)].data_ptr(), need, hb
-    return order, (keep, xp, ip), res, N, E, G
-
-
 def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
                         init: Optional[torch.Tensor] = None, max_iter: int = 10, tol: float = 1e-6,
                         weights: Sequence[float] = (1.0, 1.0, 1.0), max_groups: int = 0,
@@ -603,13 +617,8 @@ def wls_estimate_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     topologies may differ.  NotImplementedError where (n, hb) needs more LDS than a workgroup has (``band_max_half_bandwidth(n)``).
     Not served here: ``graph_ptr`` batches.  The Huber form is ``wls_robust_banded``, bad-data detection ``wls_bad_data_banded`` (the
     covariance is wanted between buses within two branches of each other only -- inside the band, where the selected inverse gives it)."""
-    from .ops import gather_rows
-    args = _lib.WlsLargeArgs()
-    order, keep, res, N, E, G = _banded("wls_estimate_banded", args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
-                                        nodes_per_graph, init, max_iter, tol, weights, max_groups, order)
-    _lib.check(_lib.lib().dss2_wls_solve_large(C.byref(args), _stream(x)), "dss2_wls_solve_large")
-    del keep                     # (held until here: the launch has been issued)
-    return res._replace(state=gather_rows(res.state, order.inverse))
+    return _solve(None, _BANDED, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init, max_iter, tol, weights,
+                  max_groups, order=order)
 
 
 def wls_robust_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
@@ -620,24 +629,8 @@ def wls_robust_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_s
     ``wls_estimate_banded`` with the Huber weighting on the row owners' walk (``gamma = inf`` gives ``wls_estimate_banded``'s five
     outputs to the bit).  ``order``, the bus order of inputs and outputs (``bus_q`` comes back in the caller's; ``edge_q`` is per stored
     edge), the cap on (n, hb) and the refusals are ``wls_estimate_banded``'s; with a given ``order`` nothing is read back."""
-    from .ops import gather_rows
-    gamma = float(gamma)
-    if not gamma > 0:
-        raise ValueError("gamma must be > 0")
-    if int(plain_iters) != plain_iters or plain_iters < 0:
-        raise ValueError("plain_iters must be an integer >= 0")
-    args = _lib.WlsRobustArgs()
-    order, keep, res, N, E, G = _banded("wls_robust_banded", args, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
-                                        nodes_per_graph, init, max_iter, tol, weights, max_groups, order)
-    dev = x.device
-    res = WLSRobustResult(*res, bus_q=torch.empty(N, 4, dtype=torch.float64, device=dev),
-                          edge_q=torch.ones(E, 2, dtype=torch.float64, device=dev),      # (an edge that leaves its graph is never written)
-                          n_downweighted=torch.empty(G, dtype=torch.int32, device=dev))
-    args.gamma, args.plain_iters = gamma, int(plain_iters)
-    args.bus_q, args.edge_q, args.n_downweighted = res.bus_q.data_ptr(), res.edge_q.data_ptr(), res.n_downweighted.data_ptr()
-    _lib.check(_lib.lib().dss2_wls_robust_large(C.byref(args), _stream(x)), "dss2_wls_robust_large")
-    del keep                     # (held until here: the launch has been issued)
-    return res._replace(state=gather_rows(res.state, order.inverse), bus_q=_gather_f64(res.bus_q, order.inverse))
+    return _solve(_Huber(gamma, plain_iters), _BANDED, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph, init,
+                  max_iter, tol, weights, max_groups, order=order)
 
 
 def wls_bad_data_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std, nodes_per_graph: int,
@@ -654,39 +647,8 @@ def wls_bad_data_banded(x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge
     the smallest relabelled id, not to the caller's smallest.  NotImplementedError above ``band_max_half_bandwidth(n, bad_data=True)``.
     A graph with a non-zero outside the band of ``order``: status 2, 0 iterations, objective 0, its start as its state, dof 0, no removal,
     per-measurement outputs 0.  With a given ``order`` nothing is read back and every launch is the library's: recordable."""
-    from .ops import gather_rows
-
-    def check_params():
-        if not threshold > 0:
-            raise ValueError("threshold must be > 0")
-        if int(max_removals) != max_removals or not 0 <= max_removals <= 64:
-            raise ValueError("max_removals must be an integer in 0 .. 64")
-        if not 0 < confidence < 1:
-            raise ValueError("confidence must be in (0, 1)")
-        if not 0 < s_min < 1:
-            raise ValueError("s_min must be in (0, 1)")
-
-    b = _lib.WlsBadDataArgs()
-    order, keep, solved, N, E, G = _banded("wls_bad_data_banded", b, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
-                                           nodes_per_graph, init, max_iter, tol, weights, max_groups, order, check_params, bad_data=True)
-    dev, slots = x.device, max(int(max_removals), 1)
-    f64, i32 = torch.float64, torch.int32
-    new = lambda *shape, dtype=f64: torch.empty(*shape, dtype=dtype, device=dev)
-    rows = lambda *shape: torch.zeros(*shape, dtype=f64, device=dev)      # (a graph outside its band writes no row)
-    res = WLSBadDataResult(
-        *solved,
-        dof=new(G, dtype=i32), chi2_limit=new(G), suspect=new(G, dtype=i32), removed=new(G, slots, dtype=i32), removed_rn=new(G, slots),
-        n_removed=new(G, dtype=i32), bus_rn=rows(N, 4), edge_rn=rows(E, 2), bus_sens=rows(N, 4), edge_sens=rows(E, 2), state_std=rows(N, 2))
-    (b.dof, b.chi2_limit, b.suspect, b.removed, b.removed_rn, b.n_removed, b.bus_rn, b.edge_rn, b.bus_sens, b.edge_sens,
-     b.state_std) = (t.data_ptr() for t in res[5:])
-    b.threshold, b.max_removals, b.s_min = float(threshold), int(max_removals), float(s_min)
-    b.z_p = float(torch.special.ndtri(torch.tensor(float(confidence), dtype=f64)))      # (a host scalar from a Python float: no read-back)
-    b.bus_label = order.perm.data_ptr()                 # (the caller's row of the kernel's row k: for `removed` alone)
-    _lib.check(_lib.lib().dss2_wls_bad_data(C.byref(b), _stream(x)), "dss2_wls_bad_data")
-    del keep                     # (held until here: the launch has been issued)
-    back = lambda t: _gather_f64(t, order.inverse)
-    return res._replace(state=gather_rows(res.state, order.inverse), bus_rn=back(res.bus_rn), bus_sens=back(res.bus_sens),
-                        state_std=back(res.state_std))
+    return _solve(_BadData(threshold, max_removals, confidence, s_min), _BANDED, x, edge_index, edge_attr, x_mean, x_std, edge_mean, edge_std,
+                  nodes_per_graph, init, max_iter, tol, weights, max_groups, order=order)
 
 
 def _public(impl):
